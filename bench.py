@@ -17,6 +17,12 @@ uploaded (H2D) before the timed region; a step re-unpacks the resident records, 
 chunk by chunk; per-pixel ADC results stay in HBM.  N > 1 is weak scaling: every rank owns its own 100k-segment set of
 events (batches are sharded by (event, TPC group), no data-path collective until the final all-gather-v of the compact
 hit rows, which is inside the timed region).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step` and the roofline of the timed
+steps' own kernel timings).  --full adds the side measurements, each of which takes runs of its own after the timed steps:
+the PCIe-inclusive passes, the exact-zero-trim and dense-response passes and the CPU baseline of the oracle.
+--dump-outputs DIR writes what the last timed step computed, as a caller of the chain receives it, to DIR/<name>.npy
+(see dump_outputs()).
 """
 import argparse
 import json
@@ -38,6 +44,14 @@ CHUNK_SEGMENTS = int(os.environ.get("LDSIM_CHUNK_SEGMENTS", "100000"))
 FP64_VALU_PEAK_TFLOPS = 78.6      # MI355X vector FP64 (spec)
 HBM_PEAK_GBS = 8000.0             # MI355X HBM3E (spec), /opt/skills/guides/MI355X_MICROARCH.md
 TRAFFIC_FILE = os.path.join(REPO, "profiles", "r04_traffic.json")   # written by tools/pmc_traffic.py from rocprofv3 --pmc passes
+# --dump-outputs: rows kept per array family (spread over the step's chain launches), and the cap on all files together
+DUMP_SEED = 20241018
+DUMP_INDEX_ROWS = 1 << 18          # unique_pix, batch
+DUMP_PIXEL_ROWS = 3072             # the per-pixel ADC arrays, track_pixel_map and current_fractions (12 KB per row)
+DUMP_SEGMENT_ROWS = 8192           # the resident segments after quench + drift
+DUMP_LIGHT_ROWS = 256              # light incidence rows (segments)
+DUMP_LIGHT_SUM_ELEMS = 1 << 20     # photon sum of the last batch: whole detector rows up to this many values
+DUMP_MAX_BYTES = 64_000_000
 
 
 def host_cpu():
@@ -134,6 +148,67 @@ def profiled_traffic(config, kernel):
         return None, f"no PMC pass for {config}/{kernel} in profiles/{os.path.basename(TRAFFIC_FILE)} (tools/pmc_traffic.py writes it)"
 
 
+def sample_rows(n, k, key):
+    """Sorted row indices: all n rows when n <= k, else a fixed sample of k of them (seeded by DUMP_SEED and `key`)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, *key]).choice(n, size=k, replace=False))
+
+
+def take_pixel_rows(ch, launch, n_launches, row0):
+    """The per-pixel arrays of the chain launch just run (ChargeChain.download(), what the driver exports), sampled:
+    unique_pix / batch on up to DUMP_INDEX_ROWS, the rest on up to DUMP_PIXEL_ROWS rows, both split over the step's
+    launches.  `pixel_rows` holds the sampled rows' indices in the step's rows (launches one after the other, from row0)."""
+    out = ch.download()
+    n = len(out["unique_pix"])
+    wide = sample_rows(n, max(1, DUMP_INDEX_ROWS // n_launches), (launch, 0))
+    rows = sample_rows(n, max(1, DUMP_PIXEL_ROWS // n_launches), (launch, 1))
+    part = {"unique_pix": out["unique_pix"][wide], "batch": out["batch"][wide], "pixel_rows": row0 + rows}
+    for k in ("adc_list", "adc_ticks_list", "adc_digit", "track_pixel_map", "current_fractions"):
+        if k in out:
+            part[k] = out[k][rows]
+    return part, n
+
+
+def dump_outputs(path, ch, pixel_parts, seg, light_on):
+    """Writes the last timed step's results as float64 (float32 where the library's array is f4) .npy files:
+    * unique_pix, batch, pixel_rows, adc_list, adc_ticks_list, adc_digit, track_pixel_map, current_fractions: the per-pixel
+      arrays of every chain launch of the step, on the fixed row samples of take_pixel_rows();
+    * segments: the resident segments after quench + drift (download_segments), columns in larndsim_amd.layout.FIELDS
+      order, segment_rows: which segments;
+    * with the light leg: light_n_photons_det (+ light_t0_det in trigger mode 0), light_voxel, light_rows: light incidence
+      of a fixed sample of segments; light_sum, light_sum_rows: the photon sum of the step's last batch (without truth
+      slots), whole detector rows up to DUMP_LIGHT_SUM_ELEMS values."""
+    from larndsim_amd import consts, layout
+    ch.synchronize()
+    arrays = {k: np.concatenate([p[k] for p in pixel_parts]) for k in pixel_parts[0]}
+    srows = sample_rows(len(seg), DUMP_SEGMENT_ROWS, (0, 2))
+    dev = ch.download_segments(seg.copy())[srows]
+    fields = [f for f in layout.FIELDS if f in dev.dtype.names]
+    arrays["segments"] = np.stack([dev[f].astype(np.float64) for f in fields], axis=1)
+    arrays["segment_rows"] = srows
+    if light_on:
+        lrows = sample_rows(len(seg), DUMP_LIGHT_ROWS, (0, 3))
+        inc = [ch.download_light_incidence(int(r), int(r) + 1) for r in lrows]
+        arrays["light_n_photons_det"] = np.concatenate([i["n_photons_det"] for i, _ in inc])
+        if consts.light.LIGHT_TRIG_MODE == 0:
+            arrays["light_t0_det"] = np.concatenate([i["t0_det"] for i, _ in inc])
+        arrays["light_voxel"] = np.concatenate([v for _, v in inc])
+        arrays["light_rows"] = lrows
+        lsum = ch.download_light(truth=False)[0]
+        drows = sample_rows(lsum.shape[0], max(1, DUMP_LIGHT_SUM_ELEMS // max(lsum.shape[1], 1)), (0, 4))
+        arrays["light_sum"] = lsum[drows]
+        arrays["light_sum_rows"] = drows
+    arrays = {k: (v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte cap")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    sys.stderr.write(f"bench.py: {len(arrays)} arrays ({total / 1e6:.1f} MB) written to {path}\n")
+
+
 def self_launch(n):
     """--gpus N without a launcher: N fresh child processes, one rank each (never an exec of a process that has touched the
     GPU: this parent imports nothing that does).  Rank 0's stdout is relayed; the exit code is the worst child's."""
@@ -181,8 +256,16 @@ def main():
     ap.add_argument("--light", default="auto", choices=["auto", "on", "off"],
                     help="time the light leg (incidence + per-batch photon sum) with the charge chain; auto = ndlar only "
                          "(BASELINE configs[4], synthetic light set-up of SURVEY 8d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the dense-response and PCIe-inclusive side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements (PCIe-inclusive, exact-zero trim and dense-response "
+                         "passes; the CPU baseline of the oracle); a plain run only sets up, warms up, times the steps and prints "
+                         "the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64 / float32, fixed seeded row "
+                         "samples, at most 64 MB); with more than one chain launch per step the earlier launches' results are "
+                         "copied to the host inside the last step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the dense-response and PCIe-inclusive side measurements")
     ap.add_argument("--fractions", type=int, default=1, help="compute backtracking fractions (reference always does)")
     ap.add_argument("--force-dist", action="store_true", help="run the RCCL all-gather path even with one rank")
     ap.add_argument("--weights-mode", type=int, default=2, choices=[0, 1, 2],
@@ -194,6 +277,8 @@ def main():
 
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a.gpus)                      # (does not return)
     rank = int(os.environ.get("RANK", "0"))
@@ -301,7 +386,9 @@ def main():
     acc = new_acc()
     gathered = {"rows": 0, "per_rank": []}
 
-    def step(record, download=False):
+    def step(record, download=False, capture=None):
+        # capture: a list that receives the sampled per-pixel results of every chain launch but the last (--dump-outputs;
+        # the last launch's results are still resident after the step)
         ch.reset()
         ch.quench_drift()
         if light_on:
@@ -344,6 +431,10 @@ def main():
                 ch.download_async()
             elif download:
                 ch.download(pinned=True)
+            if capture is not None and i < len(ranges) - 1:
+                row0 = capture[-1][1] if capture else 0          # (part, rows of the step so far) per launch
+                part, n = take_pixel_rows(ch, i, len(ranges), row0)
+                capture.append((part, row0 + n))
         if download == "overlapped":
             ch.wait_download()
         if cm is not None:
@@ -360,9 +451,11 @@ def main():
     for _ in range(a.warmup):
         step(False)
     barrier()
+    dump = a.dump_outputs is not None and rank == 0
+    captured = []
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step(True)
+    for k in range(a.steps):
+        step(True, capture=captured if dump and k == a.steps - 1 else None)
     barrier()
     elapsed = time.perf_counter() - t0
     n_job = float(len(seg))
@@ -374,9 +467,13 @@ def main():
         if n_ranks_rccl != a.gpus:
             raise SystemExit(f"--gpus {a.gpus} but the RCCL communicator holds {n_ranks_rccl} ranks: no result line")
 
-    # ---- side measurements (one GPU only; never part of `value`) ------------------------------------------------------------
+    if dump:        # before the side measurements, which run the chain again
+        last, _ = take_pixel_rows(ch, len(ranges) - 1, len(ranges), captured[-1][1] if captured else 0)
+        dump_outputs(a.dump_outputs, ch, [p for p, _ in captured] + [last], seg, light_on)
+
+    # ---- side measurements (--full; one GPU only; never part of `value`) -----------------------------------------------------
     extras = {}
-    if rank == 0 and world == 1 and not a.no_extras:
+    if rank == 0 and world == 1 and a.full and not a.no_extras:
         main_acc, acc = acc, new_acc()
         # (a) host buffers in, host results out: H2D of the records + the step + D2H of every per-pixel array
         def timed_pass(download):            # median of three passes: upload + step + downloads (one pass alone varies by 2x)
@@ -596,11 +693,11 @@ def main():
                                     if light_own_stream else
                                     "wall time of a step's photon-sum loop over its batches (host calls included) / batches")}
         out.update(extras)
-        if world > 1:
+        if a.full and world > 1:
             # timed on rank 0 of the single-GPU run only: at N > 1 it would keep the other ranks waiting at the barrier
             out["cpu_baseline"] = {"value": None, "unit": "segments/s", "cores": 0, "kind": "port",
                                    "sample": "timed in the 1-GPU run only"}
-        elif not a.no_cpu_baseline:
+        elif a.full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(response)
             except Exception as e:      # the baseline is reported, never required for the GPU number

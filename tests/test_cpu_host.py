@@ -3,6 +3,7 @@ import ctypes as C
 import json
 import os
 import re
+import tarfile
 
 import numpy as np
 import pytest
@@ -11,7 +12,16 @@ import helpers as H
 from larndsim_amd import abi, batching, consts, layout, lib, synth
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/larndsim"
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    """larndsim/ of a larnd-sim tree's settings files (config.yaml, the YAML files it names for module0, 2x2, 2x2_no_modvar and
+    ndlar, the SiPM impulse file they point to), unpacked from tests/golden/larndsim_tree.tar.gz (tests/golden/larndsim_tree.md)"""
+    root = tmp_path_factory.mktemp("larndsim_tree")
+    with tarfile.open(os.path.join(REPO, "tests", "golden", "larndsim_tree.tar.gz")) as t:
+        t.extractall(root, **({"filter": "data"} if hasattr(tarfile, "data_filter") else {}))
+    return str(root / "larndsim")
 
 
 def test_library_loads_and_exports_every_declared_symbol():
@@ -74,11 +84,9 @@ def test_segments_dtype_is_the_edep_sim_schema():
                        "simulation_properties/2x2_NuMI_sim_no_modvar.yaml")),
     ("ndlar", ("detector_properties/ndlar-module.yaml", "pixel_layouts/multi_tile_layout-3.0.40.yaml",
                "simulation_properties/NDLAr_LBNF_sim.yaml"))])
-def test_yaml_loader_reproduces_reference_constants(cfg, files):
+def test_yaml_loader_reproduces_reference_constants(cfg, files, ref):
     """Own YAML loader == snapshot written from the reference's loader (bit-identical floats)."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference YAML files not present on this box")
-    consts.load_properties(*(os.path.join(REF, f) for f in files))
+    consts.load_properties(*(os.path.join(ref, f) for f in files))
     mine = json.loads(json.dumps(consts.snapshot_dict()))
     snap = json.load(open(os.path.join(REPO, "larnd-sim_amd", "larndsim_amd", "snapshots", cfg + ".json")))
     assert mine == snap
@@ -482,7 +490,7 @@ def test_packets_writer_golden(cfg):
             assert (as2["event_ids"] == -1).all() and (as2["segment_ids"] == -1).all() and (as2["fraction"] == 0).all()
 
 
-def test_config_keyword_resolution():
+def test_config_keyword_resolution(ref):
     """config.get_config follows larndsim/config/config.py:40-69: bare names joined to their family's directory, names with
     '/' kept, lists element by element, other keys passed through; the module-variation decision and the per-module file
     lists follow cli/simulate_pixels.py:106-122, 355-372."""
@@ -504,18 +512,16 @@ def test_config_keyword_resolution():
     assert config.single_file(["x"]) == "x" and config.single_file("x") == "x"
     with pytest.raises(KeyError, match="more than one"):
         config.single_file(["x", "y"], "response file")
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present on this box")
-    keys = set(config.list_config_keys(REF))
+    keys = set(config.list_config_keys(ref))
     assert {"module0", "2x2", "2x2_no_modvar", "2x2_mpvmpr", "ndlar"} <= keys
-    c = config.get_config("2x2_no_modvar", REF)
-    assert c["DET_PROPERTIES"] == os.path.join(REF, "detector_properties", "2x2_no_modvar.yaml")
-    assert c["PIXEL_LAYOUT"] == os.path.join(REF, "pixel_layouts", "multi_tile_layout-2.4.16.yaml")
-    assert c["RESPONSE"] == os.path.join(REF, "bin", "response_44.npy")
+    c = config.get_config("2x2_no_modvar", ref)
+    assert c["DET_PROPERTIES"] == os.path.join(ref, "detector_properties", "2x2_no_modvar.yaml")
+    assert c["PIXEL_LAYOUT"] == os.path.join(ref, "pixel_layouts", "multi_tile_layout-2.4.16.yaml")
+    assert c["RESPONSE"] == os.path.join(ref, "bin", "response_44.npy")
     assert c["LIGHT_LUT"].startswith("/global/cfs/")                   # has a '/': kept as written
     assert c["MOD2MOD_VARIATION"] is False and c["LIGHT_SIMULATED"] is True
-    m = config.get_config("2x2", REF)
-    assert m["PIXEL_LAYOUT"] == [os.path.join(REF, "pixel_layouts", f) for f in
+    m = config.get_config("2x2", ref)
+    assert m["PIXEL_LAYOUT"] == [os.path.join(ref, "pixel_layouts", f) for f in
                                  ("multi_tile_layout-2.4.16.yaml", "multi_tile_layout-2.5.16.yaml")]
     assert m["PIXEL_LAYOUT_ID"] == [0, 0, 1, 0] and m["MOD2MOD_VARIATION"] is True
     # per-module loading through the package's own YAML loader == the per-module snapshots written from the reference's
@@ -528,7 +534,7 @@ def test_config_keyword_resolution():
         assert mine == snap, i_mod
     assert consts.detector.RESPONSE_SAMPLING == 0.05 and consts.sim.MAX_MC_TRUTH_IDS == 50
     with pytest.raises(KeyError):
-        config.get_config("2x2_mod2mod_variation", REF)               # the reference CLI's default keyword is not in its own map
+        config.get_config("2x2_mod2mod_variation", ref)               # the reference CLI's default keyword is not in its own map
     # the resolved files load through the package's own YAML loader
     consts.load_properties(c["DET_PROPERTIES"], c["PIXEL_LAYOUT"], c["SIM_PROPERTIES"])
     assert consts.detector.TPC_BORDERS.shape == (8, 3, 2) and len(consts.detector.PIXEL_CONNECTION_DICT) == 4900

@@ -24,10 +24,10 @@ echo "sq" >> $O/progress; timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WA
 (cd $R && python3 tools/pmc_sq.py $O/sq gtables gcorr pixel_adc > $O/r04_sq_counters_module0.txt)
 rm -rf $O/pmc_fetch $O/pmc_write $O/kt $O/kt2 $O/sq
 cd $R
-echo "bench module0" >> $O/progress; python3 bench.py > $O/bench_module0.log 2>&1 || exit 1
-echo "bench 2x2" >> $O/progress; python3 bench.py --config 2x2_no_modvar --no-cpu-baseline > $O/bench_2x2.log 2>&1 || exit 1
+echo "bench module0" >> $O/progress; python3 bench.py --full > $O/bench_module0.log 2>&1 || exit 1
+echo "bench 2x2" >> $O/progress; python3 bench.py --full --config 2x2_no_modvar --no-cpu-baseline > $O/bench_2x2.log 2>&1 || exit 1
 echo "bench 2x2 light" >> $O/progress; python3 bench.py --config 2x2_no_modvar --light on --no-cpu-baseline --no-extras > $O/bench_2x2_light.log 2>&1 || exit 1
-echo "bench ndlar" >> $O/progress; python3 bench.py --config ndlar --light on --no-cpu-baseline > $O/bench_ndlar_light.log 2>&1 || exit 1
+echo "bench ndlar" >> $O/progress; python3 bench.py --full --config ndlar --light on --no-cpu-baseline > $O/bench_ndlar_light.log 2>&1 || exit 1
 echo "phases" >> $O/progress
 timeout -k 10 200 python3 tools/gform_phases.py module0 survey 50000 tables > $O/phases_tables.log 2>&1
 timeout -k 10 200 python3 tools/gform_phases.py module0 survey 50000 corr > $O/phases_corr.log 2>&1
