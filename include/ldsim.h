@@ -463,6 +463,28 @@ int ldsim_hits_accumulate(ldsim_ctx* ctx, int32_t reset);
 int ldsim_comm_allgather_hits(ldsim_ctx* ctx, void** gathered, int64_t* total_rows, int64_t* counts);
 int ldsim_comm_gathered_download(ldsim_ctx* ctx, void* rows, int64_t n);
 
+/* ---- the drop-in driver's exchange (cli/simulate_pixels.py --n_gpus): every rank's results to one writer ---------------------
+ * ldsim_compact_accumulate: after ldsim_chain_compact_build, append the launch's five compact parts to this rank's stream in HBM
+ * (device-to-device on the ctx stream; a launch is appended once).  reset != 0 only empties the stream: call it before the first
+ * launch of a pass.  Parts, in this order: hit-pixel rows [5] i32, track segments i64, hit rows (24 B), charges f64, fractions f64.
+ * ldsim_comm_gather_compact: collective, one source rank per call.  All-gather of the five element counts of every rank
+ * (sizes[world][5], may be NULL), then root receives rank src_rank's parts (ncclSend / ncclRecv, one call per part; a
+ * device-to-device copy when src_rank is root) into buffers sized for that rank alone, so root never holds more than one
+ * rank's stream: loop src_rank over the ranks and export each before receiving the next.
+ * ldsim_comm_gathered_compact_download (root only): the parts of the last gather, from rank src_rank, in the layout of
+ * ldsim_chain_compact_download (buffers sized from sizes[src_rank]; any pointer may be NULL).
+ * ldsim_comm_gatherv_bytes: collective gather-v of n host bytes per rank to root through device staging (counts[world] = bytes
+ * per rank, may be NULL); ldsim_comm_gathered_bytes_download (root only): rank src_rank's bytes.
+ * LDSIM_EINVAL: no communicator, root / source rank out of range, an all-gathered size of this rank that differs from the local
+ * one; LDSIM_ESTATE: accumulate without a compact build of the last launch, a download of a rank this rank has not gathered as
+ * root by the last call. */
+int ldsim_compact_accumulate(ldsim_ctx* ctx, int32_t reset);
+int ldsim_comm_gather_compact(ldsim_ctx* ctx, int32_t root, int32_t src_rank, int64_t* sizes);
+int ldsim_comm_gathered_compact_download(ldsim_ctx* ctx, int32_t src_rank, int32_t* hit_pixels, int64_t* track_segments,
+                                         void* hit_rows, double* hit_charge, double* fractions);
+int ldsim_comm_gatherv_bytes(ldsim_ctx* ctx, int32_t root, const void* host, int64_t n, int64_t* counts);
+int ldsim_comm_gathered_bytes_download(ldsim_ctx* ctx, int32_t src_rank, void* out);
+
 /* ---- fee.export_to_hdf5's hit loop on compact rows (larndsim/fee.py:143-344) -- host code, no ctx, no GPU ---------------------------
  * The LArPix `packets` rows (larpix-control's HDF5 format 2.4: 36-byte packed rows, ldsim_packets_row_bytes) and the
  * `mc_packets_assn` rows (event_ids (1,) i8 | segment_ids (n,) i8 | fraction (n,) f8 | file_traj_ids (n,) i8 | fraction_traj (n,) f8,

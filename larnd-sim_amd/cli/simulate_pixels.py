@@ -16,28 +16,100 @@ per-module constants, pixel layout, response, light LUT, thresholds and gains; p
 The per-module pointer lists (--pixel_layout_id, --response_id, --light_lut_id, --pixel_thresholds_id, --pixel_gains_id: module m
 uses file ids[m] of the corresponding file list) default to the keyword's <X>_ID entries.
 
+Several GPUs (--n_gpus N): whole events sharded over N processes, one per GPU; rank 0 gathers the others' results and writes
+the one output file ("Multi-GPU driver").
+
 Not built (the flag is accepted and reported): memory logging (--save_memory).
 """
 import argparse
 import os
+import pickle
 from math import ceil
 import sys
 import warnings
 from time import time
 
-import numpy as np
-import numpy.lib.recfunctions as rfn
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
+from larndsim_amd import launch  # noqa: E402  (standard library only)
+
+IGNORED = ("save_memory",)
+ID_FLAGS = ("pixel_layout_id", "response_id", "light_lut_id", "pixel_thresholds_id", "pixel_gains_id")
+
+
+def _parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--input_filename", required=True)
+    ap.add_argument("--output_filename", required=True)
+    ap.add_argument("--config", default="module0")
+    ap.add_argument("--config_root", default=None, help="larnd-sim tree holding config/config.yaml and the YAML families "
+                                                        "(default: $LARNDSIM_ROOT, else the built-in snapshot keywords)")
+    tf = lambda s: s.lower() in ("1", "true", "yes")                # noqa: E731
+    ap.add_argument("--mod2mod_variation", type=tf, default=None,
+                    help="per-module pixel layouts / responses / light LUTs / thresholds / gains (comma-separated lists), "
+                         "default: the keyword's MOD2MOD_VARIATION")
+    ap.add_argument("--light_simulated", type=tf, default=None)
+    for k in ("pixel_layout", "detector_properties", "simulation_properties", "response_file", "light_lut_filename",
+              "light_det_noise_filename", "bad_channels", "pixel_thresholds_file", "pixel_gains_file", *IGNORED):
+        ap.add_argument("--" + k, default=None)
+    for k in ID_FLAGS:
+        ap.add_argument("--" + k, default=None, help="module variation: per-module index into the corresponding file list, "
+                                                      "e.g. 0,0,1,0 (default: the keyword's entry)")
+    ap.add_argument("--n_events", type=int, default=None)
+    ap.add_argument("--rand_seed", type=int, default=None)
+    ap.add_argument("--tracks_current_mc", action="store_true",
+                    help="induced currents from tracks_current_mc like the reference driver (default: tracks_current)")
+    ap.add_argument("--raw_arrays", action="store_true", help="also store the per-pixel arrays (raw/...) and light_sample_inc")
+    ap.add_argument("--numba_f32", default="auto", choices=["auto", "0", "1"],
+                    help="evaluate the sub-expressions Numba types as float32 for f4 record fields in single precision like the "
+                         "reference (1), all in double (0), or by the input records' dtype (auto, default); unpinned restatement")
+    ap.add_argument("--n_gpus", type=int, default=None,
+                    help="shard the events over N GPUs, one process each (started here, or by a launcher that sets WORLD_SIZE=N); "
+                         "rank 0 writes the one output file.  Deterministic stages give the one-GPU result at any N; the random "
+                         "stages (FEE noise, light fluctuations and noise) depend on N: rank r seeds its table with rand_seed + r, "
+                         "and the reference's history-dependent RNG chain is not replayed across ranks")
+    ap.add_argument("--force_dist", action="store_true", help="with --n_gpus 1: run the multi-GPU (RCCL) path with one rank")
+    ap.add_argument("--chunk_segments", type=int, default=50000,
+                    help="segments per chain launch (whole batches, at least this many; default 50000)")
+    return ap
+
+
+def launch_ranks_if_asked(argv=None):
+    """--n_gpus N (or --n_gpus 1 --force_dist) without a launcher: N fresh child processes, one rank each, and exit with the
+    worst child's code.  Runs before the simulation modules are imported: this parent loads neither numpy nor the HIP
+    library, touches no GPU and is never replaced by exec.  Returns (without doing anything) in every other case."""
+    a = vars(_parser().parse_args(argv))
+    try:
+        _, world = launch.dist_mode(a["n_gpus"], a["force_dist"])  # (refuses a WORLD_SIZE that contradicts --n_gpus)
+    except ValueError as e:
+        raise SystemExit(f"simulate_pixels.py: {e}")
+    if world is not None and world > 1 and a["raw_arrays"]:
+        raise SystemExit("simulate_pixels.py: --raw_arrays is not available with --n_gpus > 1 (the compact path is the "
+                         "production one)")
+    if world is None or "WORLD_SIZE" in os.environ:
+        return
+    if os.path.exists(a["output_filename"]):
+        raise SystemExit(f"Output file {a['output_filename']} already exists.")
+    code, bad = launch.launch_ranks([sys.executable, os.path.abspath(__file__)] + list(sys.argv[1:] if argv is None else argv),
+                                    world)
+    if code:
+        sys.stderr.write(f"simulate_pixels.py --n_gpus {world}: ranks failed (rank, exit code): {bad}\n")
+    raise SystemExit(code)
+
+
+if __name__ == "__main__":
+    launch_ranks_if_asked()
+
+import numpy as np  # noqa: E402
+import numpy.lib.recfunctions as rfn  # noqa: E402
+
 from larndsim_amd import batching, consts, fee, light_sim, packets, synth  # noqa: E402
 from larndsim_amd import config as cfgmod  # noqa: E402
+from larndsim_amd import dist as ldist  # noqa: E402
 from larndsim_amd.chain import ChargeChain  # noqa: E402
 
 SEED = int(time())
-IGNORED = ("save_memory",)
-ID_FLAGS = ("pixel_layout_id", "response_id", "light_lut_id", "pixel_thresholds_id", "pixel_gains_id")
 TRUTH_DATASETS = ("trajectories", "vertices", "mc_hdr", "mc_stack")
 
 
@@ -159,6 +231,17 @@ class _Output:
                         z.write(k, v)
 
 
+class _Collect:
+    """what a rank > 0 of a sharded run would write: kept in memory for rank 0"""
+
+    def __init__(self):
+        self.parts = {}
+
+    def append(self, name, data):
+        if data.shape[0]:
+            self.parts.setdefault(name, []).append(data)
+
+
 def _prepend_t_event(arr):
     """The dataset with an f4 ``t_event`` field in front (aligned dtype, cli/simulate_pixels.py:618-625, 632-639)."""
     if "t_event" in arr.dtype.names:
@@ -224,15 +307,24 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    pixel_thresholds_file=None, pixel_gains_file=None, rand_seed=None, config_root=None,
                    tracks_current_mc=False, chunk_segments=50000, raw_arrays=False, overlap_downloads=None,
                    pixel_layout_id=None, response_id=None, light_lut_id=None, pixel_thresholds_id=None, pixel_gains_id=None,
-                   numba_f32="auto", **ignored):
+                   numba_f32="auto", n_gpus=None, force_dist=False, **ignored):
+    rank, world = launch.dist_mode(n_gpus, force_dist)
+    if world is not None and "WORLD_SIZE" not in os.environ:
+        raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
+                           "--n_gpus N starts them itself) or a launcher that sets WORLD_SIZE")
+    if world is not None and world > 1 and raw_arrays:
+        raise ValueError("--raw_arrays is not available with --n_gpus > 1: the per-pixel arrays stay on the rank that made them "
+                         "(the compact path is the production one)")
     if not os.path.exists(input_filename):
         raise Exception(f"Input file {input_filename} does not exist.")
-    if os.path.exists(output_filename):
+    if rank == 0 and os.path.exists(output_filename):             # (only rank 0 writes)
         raise Exception(f"Output file {output_filename} already exists.")
     for k, v in ignored.items():
         if v is not None:
             print(f"[simulate_pixels] --{k} concerns a stage that is not built and is ignored")
     from larndsim_amd import lib
+    if world is not None and n_gpus > lib.device_count():
+        raise RuntimeError(f"--n_gpus {n_gpus} but only {lib.device_count()} GPU(s) are visible")
 
     # ---- configuration (cli/simulate_pixels.py:269-384) ------------------------------------------------------------------
     cfg = cfgmod.get_config(config, config_root)
@@ -336,8 +428,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     traj_field = "file_traj_id" if "file_traj_id" in all_tracks.dtype.names else "traj_id"
     mod_ids = list(det.MOD_IDS) if m2m else [-1]
 
-    out = _Output(output_filename)
+    out = _Output(output_filename) if rank == 0 else _Collect()    # (ranks > 0 write nothing: their results travel to rank 0)
     totals = dict(n_segments=0, n_batches=0, n_hits=0, n_packets=0, n_light_triggers=0)
+    rows_per_rank = np.zeros(world or 1, dtype=np.int64)
     kept_tracks, light_dat = [], {}
     rng_seeded = False
     lib.set_option("mc_current", 1 if tracks_current_mc else 0)
@@ -348,6 +441,13 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     f32_mode = numba_f32_mode(numba_f32, all_tracks.dtype)
     print("Numba f32 typing mode:", "on" if f32_mode else "off", f"(--numba_f32 {numba_f32})")
     lib.set_option("numba_f32", f32_mode)
+    dist = None
+    if world is not None:
+        from larndsim_amd import comm as lcomm
+        dist = lcomm.Communicator(lib.context(refresh_consts=False), rank, world)
+        n_rccl, r_rccl = dist.count()
+        if (n_rccl, r_rccl) != (world, rank):
+            raise RuntimeError(f"rank {rank} of {world}: the RCCL communicator reports rank {r_rccl} of {n_rccl}")
     try:
         for i_mod in mod_ids:                                       # convention: module ids count from 1 (:676-715)
             if m2m:
@@ -369,7 +469,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             chain = ChargeChain(response)
             chain.clear_pixel_tables()
             if not rng_seeded:
-                chain.seed_rng(rand_seed)                           # create_xoroshiro128p_states(1024*256, seed) (:396), once
+                # create_xoroshiro128p_states(1024*256, seed) (:396), once; rank r of a sharded run seeds rand_seed + r
+                chain.seed_rng(rand_seed + rank)
                 rng_seeded = True
             thr_file, gain_file = per_module(pixel_thresholds_file, i_mod), per_module(pixel_gains_file, i_mod)
             if thr_file is not None:                                # :439-443, 698-706, 1079-1084
@@ -380,12 +481,17 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                 chain.set_pixel_gains(*fee.load_pixel_table(gain_file))
             res = _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field,
                                    per_module(light_lut_filename, i_mod) if light_simulated else None, light_det_noise_filename,
-                                   cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads)
+                                   cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist)
             for k in totals:
                 totals[k] += res[k]
+            rows_per_rank += res["rows_per_rank"]
             kept_tracks.append(res["tracks"])
             if res["light_dat"] is not None:
                 light_dat[i_mod] = res["light_dat"]
+        if dist is not None:
+            dist.destroy()
+        if rank > 0:
+            return None                                             # (rank 0 writes the file and the summary)
         # ---- end of file (:1226-1297) --------------------------------------------------------------------------------------------------
         out_tracks = np.concatenate(kept_tracks) if len(kept_tracks) > 1 else kept_tracks[0].copy()
         if sim.IS_SPILL_SIM:
@@ -415,14 +521,23 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     print(f"simulated {totals['n_segments']} segments in {totals['n_batches']} batches -> {totals['n_hits']} hits, "
           f"{totals['n_packets']} packets" + (f", {totals['n_light_triggers']} light triggers" if light_simulated else ""))
     print("Output saved in:", output_filename)
+    totals["n_ranks"] = world or 1
+    totals["rows_per_rank"] = [int(v) for v in rows_per_rank]
     return totals
 
 
 def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field, light_lut,
-                     light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None):
+                     light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None,
+                     dist=None):
     """One pass of the driver's module loop body (cli/simulate_pixels.py:717-1232) on the device-resident chain: quench + drift,
     light leg, charge chain, packets.  ``tracks``: the module's active segments (all active segments without module
-    variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out)."""
+    variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out).
+
+    ``dist`` (a larndsim_amd.comm.Communicator, --n_gpus): quench + drift and light incidence stay whole-input on every rank;
+    the per-batch work -- photon sums, light response, triggers, waveforms, charge chain launches -- runs over the rank's
+    contiguous run of whole events (dist.shard_events).  Ranks > 0 keep their light results on the host and their compact
+    charge results in HBM; at the end of the module rank 0 receives them rank by rank and exports them after its own, so
+    the file's rows come in the one-rank order."""
     det, sim, light = consts.detector, consts.sim, consts.light
     one = lambda v: v[0] if isinstance(v, (list, tuple)) else v          # noqa: E731
     bid, order, table = batching.assign_batches(tracks, tpc_borders=det_borders)
@@ -440,6 +555,21 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
     res["tracks"] = file_rows
     edges = np.flatnonzero(np.r_[True, bid[1:nsim] != bid[:nsim - 1], True]) if nsim else np.array([0])
     n_groups = int(np.ceil(np.asarray(det_borders).shape[0] / sim.EVENT_BATCH_SIZE))
+    rank, world = (dist.rank, dist.world) if dist is not None else (0, 1)
+    res["rows_per_rank"] = np.zeros(world, dtype=np.int64)
+    own_edges = edges                                               # segment boundaries of the batches this rank simulates
+    owner = lambda ev: 0                                            # noqa: E731  (rank that simulates an event)
+    if dist is not None:
+        brank = ldist.shard_events(table, world)
+        mine = np.flatnonzero(brank == rank)
+        own_edges = edges[mine[0]:mine[-1] + 2] if len(mine) else np.array([0])
+        ev_of_b = np.array([t[0] for t in table])
+
+        def owner(ev):
+            # an event without a batch in this module (its light leg still reads out) goes with the next event that has one
+            if not len(table):
+                return 0
+            return int(brank[min(int(np.searchsorted(ev_of_b, ev, side="left")), len(table) - 1)])
     batch_of = {}
     for ib, (ev, grp, sub, _n) in enumerate(table):
         batch_of.setdefault((int(ev), int(grp)), []).append(ib)
@@ -471,6 +601,8 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
         light_rows, i_trig = [], 0
         null_wvfm = None
         for ev in all_events:                                       # the reference's loop order: events, TPC groups (:864)
+            if owner(ev) != rank:
+                continue
             ev_time = np.array([event_times[int(ev) % sim.MAX_EVENTS_PER_FILE]])
             for grp in range(n_groups):
                 acc = dict(start=[], idx=[], typ=[], opc=[], wv=[], tid=[], tph=[])
@@ -530,6 +662,24 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
             nt_max = max(r.shape[1] for r in light_rows)           # the tick count follows each batch's arrival times
             out.put("light_sample_inc" + (f"_mod{i_mod - 1}" if m2m else ""),
                     np.stack([np.pad(r, ((0, 0), (0, nt_max - r.shape[1]))) for r in light_rows]))
+        if dist is not None:
+            # the ranks' light results to rank 0 (small: trigger rows, waveforms, truth rows, the trigger tuples of the packet
+            # stream), appended after its own in rank order; truth rows carry the rank's running trigger index from 0
+            payload = pickle.dumps((out.parts, light_trig_of, i_trig, res["n_light_triggers"]), protocol=5) if rank else b""
+            counts = dist.gatherv_bytes(payload)
+            if rank > 0:
+                out.parts.clear()
+            else:
+                for r in range(1, world):
+                    parts, trig_of, n_calls, n_trig = pickle.loads(dist.gathered_bytes(r, counts))
+                    for name, arrs in parts.items():
+                        data = np.concatenate(arrs)
+                        if name == "light_wvfm_mc_assn":
+                            data["trigger_id"] += i_trig
+                        out.append(name, data)
+                    light_trig_of.update(trig_of)
+                    i_trig += n_calls
+                    res["n_light_triggers"] += n_trig
 
     # ---- sync / timestamp / trigger packets at every new event (:866-890), then the event's charge packets ------------------
     period = det.CLOCK_RESET_PERIOD * det.CLOCK_CYCLE
@@ -684,7 +834,18 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
     overlapped = raw_arrays and ((nsim >= 8 * chunk_segments) if overlap_downloads is None else bool(overlap_downloads))
     b = 0
     in_flight = None
-    launches = [(int(b0), int(e0)) for b0, e0 in _launch_ranges(edges, nsim, chunk_segments)]
+    launches = [(int(b0), int(e0)) for b0, e0 in _launch_ranges(own_edges, int(own_edges[-1]), chunk_segments)]
+    if dist is not None:
+        dist.accumulate_compact(reset=True)
+    if rank > 0:
+        # a rank > 0 exports nothing: its launches' compact results stay in HBM until rank 0 gathers them
+        for b0, e0 in launches:
+            chain.run(b0, e0, want_fractions=True)
+            chain.build_compact()
+            dist.accumulate_compact()
+        for r in range(1, world):                                   # (collective: every rank takes part in each rank's turn)
+            dist.gather_compact(r)
+        return res
     if not raw_arrays:
         # Default path.  Launch k runs on a worker thread (ChargeChain.run_async: the C call blocks on its size read-backs but
         # releases the interpreter) while launch k - 1's packets are built here from its compact download -- host work that never
@@ -711,6 +872,17 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
     if in_flight is not None:
         chain.wait_download()
         export_chunk(in_flight)
+    res["rows_per_rank"][0] = res["n_hits"]
+    if dist is not None:
+        # rank 0's own launches were exported as they came; the others' streams arrive one rank at a time (rank 0 holds one
+        # of them, in HBM and on the host), each exported through the same pending / WRITE_BATCH_SIZE bookkeeping as if it had
+        # come from rank 0's own launches before the next rank's is received
+        for r in range(1, world):
+            sizes = dist.gather_compact(r)
+            c = dist.gathered_compact(r, sizes)
+            res["rows_per_rank"][r] = len(c["hit_rows"])
+            export_chunk_compact(c)
+            del c
     if len(all_events):
         announce_until(all_events[-1])
     flush_pending()                                  # (what is left after the event loop, :1219-1222)
@@ -721,8 +893,9 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
 
 
 def _launch_ranges(edges, nsim, chunk_segments):
-    """segment ranges of the chain launches: whole batches, at least chunk_segments each (the last one: what is left)"""
-    b = 0
+    """segment ranges of the chain launches over the batches of ``edges`` (batch boundaries, ending at ``nsim``): whole batches,
+    at least chunk_segments each (the last one: what is left)"""
+    b = edges[0]
     for e in edges[1:]:
         if e - b >= chunk_segments or e == nsim:
             yield b, e
@@ -730,32 +903,21 @@ def _launch_ranges(edges, nsim, chunk_segments):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--input_filename", required=True)
-    ap.add_argument("--output_filename", required=True)
-    ap.add_argument("--config", default="module0")
-    ap.add_argument("--config_root", default=None, help="larnd-sim tree holding config/config.yaml and the YAML families "
-                                                        "(default: $LARNDSIM_ROOT, else the built-in snapshot keywords)")
-    tf = lambda s: s.lower() in ("1", "true", "yes")                # noqa: E731
-    ap.add_argument("--mod2mod_variation", type=tf, default=None,
-                    help="per-module pixel layouts / responses / light LUTs / thresholds / gains (comma-separated lists), "
-                         "default: the keyword's MOD2MOD_VARIATION")
-    ap.add_argument("--light_simulated", type=tf, default=None)
-    for k in ("pixel_layout", "detector_properties", "simulation_properties", "response_file", "light_lut_filename",
-              "light_det_noise_filename", "bad_channels", "pixel_thresholds_file", "pixel_gains_file", *IGNORED):
-        ap.add_argument("--" + k, default=None)
-    for k in ID_FLAGS:
-        ap.add_argument("--" + k, default=None, help="module variation: per-module index into the corresponding file list, "
-                                                      "e.g. 0,0,1,0 (default: the keyword's entry)")
-    ap.add_argument("--n_events", type=int, default=None)
-    ap.add_argument("--rand_seed", type=int, default=None)
-    ap.add_argument("--tracks_current_mc", action="store_true",
-                    help="induced currents from tracks_current_mc like the reference driver (default: tracks_current)")
-    ap.add_argument("--raw_arrays", action="store_true", help="also store the per-pixel arrays (raw/...) and light_sample_inc")
-    ap.add_argument("--numba_f32", default="auto", choices=["auto", "0", "1"],
-                    help="evaluate the sub-expressions Numba types as float32 for f4 record fields in single precision like the "
-                         "reference (1), all in double (0), or by the input records' dtype (auto, default); unpinned restatement")
-    a = vars(ap.parse_args(argv))
+    launch_ranks_if_asked(argv)                                     # (does not return when it started the ranks)
+    a = vars(_parser().parse_args(argv))
+    rank, world = launch.dist_mode(a["n_gpus"], a["force_dist"])
+    if world is not None and os.environ.get("LDSIM_CLI_REHEARSAL"):
+        # CPU rehearsal of the launch path (tests/test_cpu_multirank.py): the ranks meet over the ncclUniqueId hand-out and stop
+        # before anything touches a GPU; LDSIM_CLI_REHEARSAL_FAIL_RANK=r makes rank r exit non-zero before the rendezvous
+        from larndsim_amd import comm as lcomm
+        print(f"rehearsal: rank {rank} of {world} started (pid {os.getpid()})", flush=True)
+        if os.environ.get("LDSIM_CLI_REHEARSAL_FAIL_RANK") == str(rank):
+            raise SystemExit(f"rank {rank}: asked to fail (test of the launcher's error path)")
+        got = lcomm.exchange_id(bytes(range(128)) if rank == 0 else b"", rank, world, timeout=120.0)
+        if got != bytes(range(128)):
+            raise SystemExit(f"rank {rank}: rendezvous payload differs")
+        print(f"rehearsal: rank {rank} of {world} met", flush=True)
+        return
     run_simulation(**a)
 
 

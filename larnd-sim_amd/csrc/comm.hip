@@ -68,6 +68,7 @@ extern "C" int ldsim_comm_destroy(ldsim_ctx* ctx) {
   NCCLCHK(ncclCommDestroy((ncclComm_t)ctx->comm));
   ctx->comm = nullptr;
   ctx->comm_world = 0;
+  ctx->cpt_all_root = ctx->cpt_all_src = ctx->gv_all_root = -1;
   return 0;
 }
 
@@ -161,5 +162,206 @@ extern "C" int ldsim_comm_gathered_download(ldsim_ctx* ctx, void* rows, int64_t 
   if (n == 0) return 0;
   NEEDC((size_t)n * 24 <= ctx->hits_all.bytes, "more rows requested than gathered");
   HIPCHK(hipMemcpy(rows, ctx->hits_all.p, (size_t)n * 24, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- the drop-in driver's exchange (cli/simulate_pixels.py --n_gpus): every rank's compact results to one writer ------------
+// A rank keeps the five parts of ldsim_chain_compact_build of each of its launches in HBM, one growing buffer per part; at the
+// end of a module root receives them, one source rank at a time.  Every part of a rank is one contiguous run, so a rank sends it in place with one ncclSend
+// per part (no pack kernel).  Element bytes and, per part, which of cpt_n[] counts it:
+//   0 hit-pixel rows [5] i32 (cpt_n[0]) | 1 track segments i64 (cpt_n[2]) | 2 hit rows 24 B (cpt_n[1]) | 3 charges f64 (cpt_n[1])
+//   4 fractions f64 (cpt_n[3])
+static const size_t CPT_ELEM[5] = {20, 8, 24, 8, 8};
+
+// grow b (keeping its first `keep` bytes) to hold at least `need` bytes
+static int grow_keep(ldsim_ctx* ctx, DevBuf* b, size_t keep, size_t need) {
+  if (need <= b->bytes && b->p) return 0;
+  DevBuf nb;
+  int rc = ldsim_ensure_buf(ctx, &nb, need * 2);
+  if (rc) return rc;
+  if (keep) HIPCHK(hipMemcpyAsync(nb.p, b->p, keep, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (b->p) (void)hipFree(b->p);
+  *b = nb;
+  return 0;
+}
+
+extern "C" int ldsim_compact_accumulate(ldsim_ctx* ctx, int32_t reset) {
+  LDSIM_ENTER(ctx);
+  NEEDC(ctx, "null ctx");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (reset) {                               // (empties the stream and appends nothing)
+    for (int k = 0; k < 5; k++) ctx->cpt_acc_n[k] = 0;
+    return 0;
+  }
+  if (ctx->cpt_gen != ctx->out_gen) {
+    ldsim_set_error("ldsim_chain_compact_build has not run for the last chain launch");
+    return LDSIM_ESTATE;
+  }
+  if (ctx->cpt_acc_gen == ctx->cpt_gen) {
+    ldsim_set_error("the last chain launch's compact results are already in the stream");
+    return LDSIM_ESTATE;
+  }
+  ctx->cpt_acc_gen = ctx->cpt_gen;
+  const int64_t n_hp = ctx->cpt_n[0], n_hits = ctx->cpt_n[1], n_trk = ctx->cpt_n[2], n_frac = ctx->cpt_n[3];
+  const size_t b_hp = ((size_t)n_hp * 20 + 7) & ~(size_t)7, b_trk = (size_t)n_trk * 8, b_chg = (size_t)n_hits * 8;
+  const char* base = (const char*)ctx->scratch[SB_CPO].p;
+  const void* src[5] = {base, base + b_hp, ctx->scratch[SB_HITS].p, base + b_hp + b_trk, base + b_hp + b_trk + b_chg};
+  const int64_t cnt[5] = {n_hp, n_trk, n_hits, n_hits, n_frac};
+  for (int k = 0; k < 5; k++) {
+    if (cnt[k] == 0) continue;
+    const size_t have = (size_t)ctx->cpt_acc_n[k] * CPT_ELEM[k], add = (size_t)cnt[k] * CPT_ELEM[k];
+    int rc = grow_keep(ctx, &ctx->cpt_acc[k], have, have + add);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync((char*)ctx->cpt_acc[k].p + have, src[k], add, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->cpt_acc_n[k] += cnt[k];
+  }
+  return 0;
+}
+
+// One source rank per call: root never holds more than one rank's stream (its buffers are sized for that rank alone), and
+// downloads and exports it before it receives the next.
+extern "C" int ldsim_comm_gather_compact(ldsim_ctx* ctx, int32_t root, int32_t src_rank, int64_t* sizes) {
+  LDSIM_ENTER(ctx);
+  NEEDC(ctx && ctx->comm, "no communicator");
+  const int W = ctx->comm_world, me = ctx->comm_rank;
+  NEEDC(root >= 0 && root < W, "root out of range");
+  NEEDC(src_rank >= 0 && src_rank < W, "source rank out of range");
+  HIPCHK(hipSetDevice(ctx->device));
+  ncclComm_t comm = (ncclComm_t)ctx->comm;
+  hipStream_t st = ctx->stream;
+  ctx->cpt_all_root = ctx->cpt_all_src = -1;
+  int rc = ldsim_ensure_buf(ctx, &ctx->comm_tmp, 64 + 40 * (size_t)W);
+  if (rc) return rc;
+  int64_t* d_mine = (int64_t*)ctx->comm_tmp.p;
+  int64_t* d_all = (int64_t*)((char*)ctx->comm_tmp.p + 64);
+  HIPCHK(hipMemcpyAsync(d_mine, ctx->cpt_acc_n, 40, hipMemcpyHostToDevice, st));
+  NCCLCHK(ncclAllGather(d_mine, d_all, 5, ncclInt64, comm, st));
+  std::vector<int64_t> h((size_t)W * 5);
+  HIPCHK(hipMemcpyAsync(h.data(), d_all, 40 * (size_t)W, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t i = 0; i < h.size(); i++) NEEDC(h[i] >= 0, "negative size received");
+  for (int k = 0; k < 5; k++)
+    if (h[(size_t)me * 5 + k] != ctx->cpt_acc_n[k]) {
+      ldsim_set_error("gather_compact: the all-gathered size of part %d of rank %d (%lld) differs from the local one (%lld)", k,
+                      me, (long long)h[(size_t)me * 5 + k], (long long)ctx->cpt_acc_n[k]);
+      return LDSIM_EINVAL;
+    }
+  const int64_t* n = &h[(size_t)src_rank * 5];
+  if (me == root)
+    for (int k = 0; k < 5; k++)
+      if ((rc = ldsim_ensure_buf(ctx, &ctx->cpt_all[k], (size_t)(n[k] > 0 ? n[k] : 1) * CPT_ELEM[k]))) return rc;
+  if (src_rank == root) {
+    if (me == root)                                    // root's own stream: a device-to-device copy
+      for (int k = 0; k < 5; k++)
+        if (n[k]) HIPCHK(hipMemcpyAsync(ctx->cpt_all[k].p, ctx->cpt_acc[k].p, (size_t)n[k] * CPT_ELEM[k], hipMemcpyDeviceToDevice, st));
+  } else if (me == root || me == src_rank) {
+    NCCLCHK(ncclGroupStart());
+    for (int k = 0; k < 5; k++) {
+      if (n[k] == 0) continue;
+      const size_t bytes = (size_t)n[k] * CPT_ELEM[k];
+      if (me == root) NCCLCHK(ncclRecv(ctx->cpt_all[k].p, bytes, ncclChar, src_rank, comm, st));
+      else NCCLCHK(ncclSend(ctx->cpt_acc[k].p, bytes, ncclChar, root, comm, st));
+    }
+    NCCLCHK(ncclGroupEnd());
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (me == root) {
+    for (int k = 0; k < 5; k++) ctx->cpt_all_n[k] = n[k];
+    ctx->cpt_all_root = root;
+    ctx->cpt_all_src = src_rank;
+  }
+  if (sizes) memcpy(sizes, h.data(), 40 * (size_t)W);
+  return 0;
+}
+
+extern "C" int ldsim_comm_gathered_compact_download(ldsim_ctx* ctx, int32_t src_rank, int32_t* hit_pixels, int64_t* track_segments,
+                                                    void* hit_rows, double* hit_charge, double* fractions) {
+  LDSIM_ENTER(ctx);
+  NEEDC(ctx && ctx->comm, "no communicator");
+  NEEDC(src_rank >= 0 && src_rank < ctx->comm_world, "source rank out of range");
+  if (ctx->cpt_all_root != ctx->comm_rank || ctx->cpt_all_src != src_rank) {
+    ldsim_set_error("this rank holds no gathered compact results of rank %d (not the root of the last ldsim_comm_gather_compact "
+                    "from that rank)", src_rank);
+    return LDSIM_ESTATE;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  void* dst[5] = {hit_pixels, track_segments, hit_rows, hit_charge, fractions};
+  for (int k = 0; k < 5; k++)
+    if (dst[k] && ctx->cpt_all_n[k])
+      HIPCHK(hipMemcpyAsync(dst[k], ctx->cpt_all[k].p, (size_t)ctx->cpt_all_n[k] * CPT_ELEM[k], hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+extern "C" int ldsim_comm_gatherv_bytes(ldsim_ctx* ctx, int32_t root, const void* host, int64_t n, int64_t* counts) {
+  LDSIM_ENTER(ctx);
+  NEEDC(ctx && ctx->comm, "no communicator");
+  const int W = ctx->comm_world, me = ctx->comm_rank;
+  NEEDC(root >= 0 && root < W, "root out of range");
+  NEEDC(n >= 0 && (host || n == 0), "null host buffer / negative length");
+  HIPCHK(hipSetDevice(ctx->device));
+  ncclComm_t comm = (ncclComm_t)ctx->comm;
+  hipStream_t st = ctx->stream;
+  ctx->gv_all_root = -1;
+  int rc = ldsim_ensure_buf(ctx, &ctx->comm_tmp, 64 + 8 * (size_t)W);
+  if (rc) return rc;
+  int64_t* d_mine = (int64_t*)ctx->comm_tmp.p;
+  int64_t* d_all = (int64_t*)((char*)ctx->comm_tmp.p + 64);
+  HIPCHK(hipMemcpyAsync(d_mine, &n, 8, hipMemcpyHostToDevice, st));
+  NCCLCHK(ncclAllGather(d_mine, d_all, 1, ncclInt64, comm, st));
+  std::vector<int64_t> h((size_t)W);
+  HIPCHK(hipMemcpyAsync(h.data(), d_all, 8 * (size_t)W, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  int64_t total = 0, mine_off = 0;
+  for (int r = 0; r < W; r++) {
+    NEEDC(h[r] >= 0, "negative length received");
+    if (r < me) mine_off += h[r];
+    total += h[r];
+  }
+  if (h[me] != n) {
+    ldsim_set_error("gatherv_bytes: the all-gathered length of rank %d (%lld) differs from the local one (%lld)", me,
+                    (long long)h[me], (long long)n);
+    return LDSIM_EINVAL;
+  }
+  if (me == root) {
+    if ((rc = ldsim_ensure_buf(ctx, &ctx->gv_all, (size_t)(total > 0 ? total : 1)))) return rc;
+    if (n) HIPCHK(hipMemcpyAsync((char*)ctx->gv_all.p + mine_off, host, (size_t)n, hipMemcpyHostToDevice, st));
+  } else if (n) {
+    if ((rc = ldsim_ensure_buf(ctx, &ctx->gv_send, (size_t)n))) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->gv_send.p, host, (size_t)n, hipMemcpyHostToDevice, st));
+  }
+  NCCLCHK(ncclGroupStart());
+  int64_t off = 0;
+  for (int r = 0; r < W; r++) {
+    if (h[r] > 0 && r != root) {
+      if (me == root) NCCLCHK(ncclRecv((char*)ctx->gv_all.p + off, (size_t)h[r], ncclChar, r, comm, st));
+      else if (me == r) NCCLCHK(ncclSend(ctx->gv_send.p, (size_t)h[r], ncclChar, root, comm, st));
+    }
+    off += h[r];
+  }
+  NCCLCHK(ncclGroupEnd());
+  HIPCHK(hipStreamSynchronize(st));
+  ctx->gv_all_n = h;
+  ctx->gv_all_root = root;
+  if (counts) memcpy(counts, h.data(), 8 * (size_t)W);
+  return 0;
+}
+
+extern "C" int ldsim_comm_gathered_bytes_download(ldsim_ctx* ctx, int32_t src_rank, void* out) {
+  LDSIM_ENTER(ctx);
+  NEEDC(ctx && ctx->comm, "no communicator");
+  NEEDC(src_rank >= 0 && src_rank < ctx->comm_world, "source rank out of range");
+  if (ctx->gv_all_root != ctx->comm_rank) {
+    ldsim_set_error("this rank holds no gathered bytes (not the root of the last ldsim_comm_gatherv_bytes)");
+    return LDSIM_ESTATE;
+  }
+  const int64_t n = ctx->gv_all_n[src_rank];
+  NEEDC(out || n == 0, "null output buffer");
+  if (n == 0) return 0;
+  int64_t off = 0;
+  for (int r = 0; r < src_rank; r++) off += ctx->gv_all_n[r];
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpy(out, (const char*)ctx->gv_all.p + off, (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }

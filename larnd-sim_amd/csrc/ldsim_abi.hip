@@ -275,8 +275,11 @@ extern "C" int ldsim_ctx_destroy(ldsim_ctx* ctx) {
     if (b.p) (void)hipFree(b.p);
   (void)ldsim_comm_destroy(ctx);
   if (ctx->d_rng.p) (void)hipFree(ctx->d_rng.p);
-  for (DevBuf* b : {&ctx->comm_tmp, &ctx->hits_acc, &ctx->hits_all})
+  for (DevBuf* b : {&ctx->comm_tmp, &ctx->hits_acc, &ctx->hits_all, &ctx->gv_send, &ctx->gv_all})
     if (b->p) (void)hipFree(b->p);
+  for (int k = 0; k < 5; k++)
+    for (DevBuf* b : {&ctx->cpt_acc[k], &ctx->cpt_all[k]})
+      if (b->p) (void)hipFree(b->p);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return 0;

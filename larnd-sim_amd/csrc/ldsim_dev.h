@@ -229,6 +229,14 @@ struct ldsim_ctx {
   int comm_rank = 0, comm_world = 0;
   DevBuf comm_tmp, hits_acc, hits_all;
   int64_t hits_acc_rows = 0;
+  // compact results of a rank's launches (ldsim_compact_accumulate) and root's gather of them; gather-v of host bytes
+  DevBuf cpt_acc[5], cpt_all[5], gv_send, gv_all;
+  int64_t cpt_acc_n[5] = {0, 0, 0, 0, 0};
+  int64_t cpt_acc_gen = -1;                   // chain launch whose compact parts were appended last
+  int64_t cpt_all_n[5] = {0, 0, 0, 0, 0};     // element counts of the one rank's stream root holds
+  std::vector<int64_t> gv_all_n;              // [world] bytes of the last gather-v
+  int cpt_all_root = -1, cpt_all_src = -1;    // root and source rank of the last compact gather (-1: none)
+  int gv_all_root = -1;                       // root of the last gather-v (-1: none)
   // chain results
   LdsimChainStats stats{};
   LdsimChainStats stage_stats{};   // counters of the last ldsim_tracks_current stage call (ldsim_tracks_current_stats)

@@ -181,14 +181,18 @@ class ChargeChain:
                                                   lib.ptr(out['track_pixel_map']), lib.ptr(fr)))
         return out
 
+    def build_compact(self):
+        """``ldsim_chain_compact_build`` of the last run() in HBM: (hit pixels, hits, track entries, fraction entries)"""
+        sizes = (C.c_int64 * 4)()
+        lib.check(lib.load().ldsim_chain_compact_build(self.ctx, sizes))
+        return tuple(int(v) for v in sizes)
+
     def download_compact(self):
         """The last run()'s results in compact form (``ldsim_chain_compact_build`` / ``_download``): what the exporter reads --
         hit pixels, their hits and the fractions of the track slots they have -- gathered on the device first: a few MB over
         PCIe instead of 13 KB per unique pixel.  ``expand_compact`` turns it into the dense rows of the hit pixels."""
         from .comm import HIT_ROW
-        sizes = (C.c_int64 * 4)()
-        lib.check(lib.load().ldsim_chain_compact_build(self.ctx, sizes))
-        n_hp, n_hits, n_trk, n_frac = (int(v) for v in sizes)
+        n_hp, n_hits, n_trk, n_frac = self.build_compact()
         out = dict(hit_pixels=np.zeros((n_hp, 5), dtype=np.int32), track_segments=np.zeros(n_trk, dtype=np.int64),
                    hit_rows=np.zeros(n_hits, dtype=HIT_ROW), hit_charge=np.zeros(n_hits), fractions=np.zeros(n_frac),
                    has_fractions=bool(self._want_fractions))

@@ -5,7 +5,9 @@ LOCAL_RANK / MASTER_ADDR / MASTER_PORT) only starts the processes; the communica
 rank 0 draws the ncclUniqueId and serves its 128 bytes over a TCP socket on MASTER_ADDR : MASTER_PORT + 1 + offset.
 
 The path shards by batch (event x TPC group) with no data-path collective; the one exchange reassembles the compact
-hit rows on every rank: ``allgather_hits``.
+hit rows on every rank: ``allgather_hits``.  The drop-in driver (cli/simulate_pixels.py --n_gpus) gathers every
+rank's compact results and light results to one writer instead: ``accumulate_compact`` / ``gather_compact`` /
+``gathered_compact`` and ``gatherv_bytes`` / ``gathered_bytes``; ``launch.launch_ranks`` starts its ranks.
 """
 import ctypes as C
 import os
@@ -170,5 +172,45 @@ class Communicator:
         lib.check(lib.load().ldsim_comm_gathered_download(self.ctx, lib.ptr(rows), C.c_int64(n.value)))
         return n.value, cnt, rows
 
+    # ---- the drop-in driver's exchange (cli/simulate_pixels.py --n_gpus) ----------------------------------------------------
+
+    def accumulate_compact(self, reset=False):
+        """append the last launch's compact parts (after ``ldsim_chain_compact_build``) to this rank's stream in HBM;
+        ``reset=True`` only empties the stream (before a pass's first launch)"""
+        lib.check(lib.load().ldsim_compact_accumulate(self.ctx, C.c_int32(int(reset))))
+
+    def gather_compact(self, src_rank, root=0):
+        """collective: rank ``src_rank``'s accumulated compact parts to ``root`` (one rank per call: root holds that rank's stream
+        only); returns every rank's element counts int64[world][5] (hit-pixel rows, track segments, hit rows, charges, fractions)"""
+        sizes = np.zeros((self.world, 5), dtype=np.int64)
+        lib.check(lib.load().ldsim_comm_gather_compact(self.ctx, C.c_int32(root), C.c_int32(src_rank), lib.ptr(sizes)))
+        return sizes
+
+    def gathered_compact(self, src_rank, sizes, has_fractions=True):
+        """(root) the parts of the last ``gather_compact(src_rank)`` as ``ChargeChain.download_compact()`` returns a launch's"""
+        n_hp, n_trk, n_hits, _, n_frac = (int(v) for v in sizes[src_rank])
+        out = dict(hit_pixels=np.zeros((n_hp, 5), dtype=np.int32), track_segments=np.zeros(n_trk, dtype=np.int64),
+                   hit_rows=np.zeros(n_hits, dtype=HIT_ROW), hit_charge=np.zeros(n_hits), fractions=np.zeros(n_frac),
+                   has_fractions=bool(has_fractions))
+        lib.check(lib.load().ldsim_comm_gathered_compact_download(
+            self.ctx, C.c_int32(src_rank), lib.ptr(out["hit_pixels"]), lib.ptr(out["track_segments"]), lib.ptr(out["hit_rows"]),
+            lib.ptr(out["hit_charge"]), lib.ptr(out["fractions"])))
+        return out
+
+    def gatherv_bytes(self, data, root=0):
+        """collective gather-v of ``data`` (bytes) to ``root`` through device staging; returns the byte counts per rank"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        counts = np.zeros(self.world, dtype=np.int64)
+        lib.check(lib.load().ldsim_comm_gatherv_bytes(self.ctx, C.c_int32(root), lib.ptr(buf) if len(buf) else None,
+                                                      C.c_int64(len(buf)), lib.ptr(counts)))
+        return counts
+
+    def gathered_bytes(self, src_rank, counts):
+        """(root) rank ``src_rank``'s bytes of the last ``gatherv_bytes``"""
+        out = np.zeros(int(counts[src_rank]), dtype=np.uint8)
+        lib.check(lib.load().ldsim_comm_gathered_bytes_download(self.ctx, C.c_int32(src_rank), lib.ptr(out) if len(out) else None))
+        return out.tobytes()
+
     def destroy(self):
         lib.check(lib.load().ldsim_comm_destroy(self.ctx))
+

@@ -42,6 +42,8 @@ EXPORTS = [
     "ldsim_dev_light_response", "ldsim_dev_light_response_download", "ldsim_light_response_ms",
     "ldsim_comm_unique_id", "ldsim_comm_init", "ldsim_comm_destroy", "ldsim_comm_count", "ldsim_comm_allreduce_f64", "ldsim_hits_accumulate",
     "ldsim_comm_allgather_hits", "ldsim_comm_gathered_download",
+    "ldsim_compact_accumulate", "ldsim_comm_gather_compact", "ldsim_comm_gathered_compact_download", "ldsim_comm_gatherv_bytes",
+    "ldsim_comm_gathered_bytes_download",
     "ldsim_packets_build", "ldsim_packets_row_bytes", "ldsim_packets_assn_row_bytes", "ldsim_crc32_parts",
 ]
 

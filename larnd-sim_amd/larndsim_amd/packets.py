@@ -512,10 +512,14 @@ def compact_to_rows(c, event_of_batch, first_segment_of_batch, segment_ids, traj
     pixels, default all): events from the rows' batch ids, track slots mapped to segment / trajectory ids (a batch's track slots
     count its segments from its first one, cli/simulate_pixels.py:1019-1026)."""
     hp = c["hit_pixels"]
-    nh_all, nt_all = hp[:, 3].astype(np.int64), (hp[:, 4] & 255).astype(np.int64)
-    h0 = np.r_[0, np.cumsum(nh_all)]
-    t0 = np.r_[0, np.cumsum(nt_all)]
-    f0 = np.r_[0, np.cumsum(nh_all * nt_all)]
+    # the part offsets of every row, computed once per result and kept in it: an export calls this once per batch, and a
+    # gathered rank's stream holds all of that rank's launches
+    cached = c.get("_row_offsets")
+    if cached is None or cached[0] is not hp:
+        nh_all, nt_all = hp[:, 3].astype(np.int64), (hp[:, 4] & 255).astype(np.int64)
+        cached = (hp, nh_all, nt_all, np.r_[0, np.cumsum(nh_all)], np.r_[0, np.cumsum(nt_all)], np.r_[0, np.cumsum(nh_all * nt_all)])
+        c["_row_offsets"] = cached
+    _, nh_all, nt_all, h0, t0, f0 = cached
     a, b = (0, len(hp)) if rows is None else rows
     batch = hp[a:b, 2].astype(np.int64)
     seg_idx = np.repeat(np.asarray(first_segment_of_batch, dtype=np.int64)[batch], nt_all[a:b]) + c["track_segments"][t0[a]:t0[b]]
