@@ -199,6 +199,25 @@ int ldsim_rng_clear(ldsim_ctx* ctx);
  * table -> create_xoroshiro128p_states(n - len, seed) appended; otherwise untouched.  ldsim_rng_count: states held, -1 none. */
 int ldsim_rng_extend(ldsim_ctx* ctx, int64_t n_states, uint64_t seed);
 int64_t ldsim_rng_count(ldsim_ctx* ctx);
+/* Keyed random streams (opt-in; csrc/rng.h states the generator): every draw is Philox4x32-10 keyed by the 64-bit run seed,
+ * counter (draw block, stream key lo, stream key hi, stage tag), with stream keys folded from what is simulated -- FEE row:
+ * key_mix(batch key, pixel id); tracks_current_mc (pair, tick): key_mix(key_mix(key_mix(batch key, segment index within its
+ * batch), pixel id), tick); light fluctuation of (det, tick): key_mix(key_mix(call key, det), tick); light noise phases:
+ * seeded by the call key.  Results then do not depend on chunking, rank count or call history.
+ *   ldsim_rng_keyed_seed       switches the ctx to keyed mode (drops the table); ldsim_rng_seed / ldsim_rng_clear switch back.
+ *   ldsim_chain_set_batch_keys one key per batch id of the upload; a keyed chain launch whose batches have none: LDSIM_ESTATE.
+ *   ldsim_rng_set_call_key     identity of the light response / trigger / noise calls that follow.
+ *   ldsim_rng_keyed_normals / _uniforms: out[s*nd + j] = draw d0 + j of stream (tag, stream_keys[s]) (tests).
+ * The host-array stage calls that draw (ldsim_get_adc_values with noise, ldsim_tracks_current_mc, ldsim_stat_fluctuations)
+ * carry no identity for their rows and return LDSIM_ESTATE in keyed mode. */
+int ldsim_rng_keyed_seed(ldsim_ctx* ctx, uint64_t seed);
+int ldsim_rng_is_keyed(ldsim_ctx* ctx);
+int ldsim_chain_set_batch_keys(ldsim_ctx* ctx, const uint64_t* keys, int64_t n_batches);
+int ldsim_rng_set_call_key(ldsim_ctx* ctx, uint64_t key);
+int ldsim_rng_keyed_normals(ldsim_ctx* ctx, uint32_t tag, const uint64_t* stream_keys, int64_t n, uint32_t d0, int32_t nd,
+                            float* out);
+int ldsim_rng_keyed_uniforms(ldsim_ctx* ctx, uint32_t tag, const uint64_t* stream_keys, int64_t n, uint32_t d0, int32_t nd,
+                             float* out);
 
 /* ---- (1) stage-by-stage, host buffers ---------------------------------------------------------- */
 /* quenching.quench[bpg,tpb](tracks, mode)            -- reference larndsim/quenching.py:11-44 */

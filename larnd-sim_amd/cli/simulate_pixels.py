@@ -66,10 +66,15 @@ def _parser():
                          "reference (1), all in double (0), or by the input records' dtype (auto, default); unpinned restatement")
     ap.add_argument("--n_gpus", type=int, default=None,
                     help="shard the events over N GPUs, one process each (started here, or by a launcher that sets WORLD_SIZE=N); "
-                         "rank 0 writes the one output file.  Deterministic stages give the one-GPU result at any N; the random "
-                         "stages (FEE noise, light fluctuations and noise) depend on N: rank r seeds its table with rand_seed + r, "
-                         "and the reference's history-dependent RNG chain is not replayed across ranks")
+                         "rank 0 writes the one output file.  Deterministic stages give the one-GPU result at any N.  With --rng "
+                         "table the random stages (FEE noise, light fluctuations and noise) depend on N: rank r seeds its table with "
+                         "rand_seed + r, and the reference's history-dependent RNG chain is not replayed across ranks; with --rng "
+                         "keyed they do not depend on N")
     ap.add_argument("--force_dist", action="store_true", help="with --n_gpus 1: run the multi-GPU (RCCL) path with one rank")
+    ap.add_argument("--rng", default="table", choices=["table", "keyed"],
+                    help="random streams: table (default; the restated numba xoroshiro128p table, advanced in place) or keyed "
+                         "(every draw a function of the seed and the identity of what is simulated: the same file at any "
+                         "--n_gpus, --chunk_segments or event subset)")
     ap.add_argument("--chunk_segments", type=int, default=50000,
                     help="segments per chain launch (whole batches, at least this many; default 50000)")
     return ap
@@ -107,6 +112,7 @@ import numpy.lib.recfunctions as rfn  # noqa: E402
 from larndsim_amd import batching, consts, fee, light_sim, packets, synth  # noqa: E402
 from larndsim_amd import config as cfgmod  # noqa: E402
 from larndsim_amd import dist as ldist  # noqa: E402
+from larndsim_amd import rng as lrng  # noqa: E402
 from larndsim_amd.chain import ChargeChain  # noqa: E402
 
 SEED = int(time())
@@ -307,7 +313,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    pixel_thresholds_file=None, pixel_gains_file=None, rand_seed=None, config_root=None,
                    tracks_current_mc=False, chunk_segments=50000, raw_arrays=False, overlap_downloads=None,
                    pixel_layout_id=None, response_id=None, light_lut_id=None, pixel_thresholds_id=None, pixel_gains_id=None,
-                   numba_f32="auto", n_gpus=None, force_dist=False, **ignored):
+                   numba_f32="auto", n_gpus=None, force_dist=False, rng="table", **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -440,6 +446,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     # INTEGRATION.md); it differs from all-f64 by up to 5e-5 of a waveform's peak.
     f32_mode = numba_f32_mode(numba_f32, all_tracks.dtype)
     print("Numba f32 typing mode:", "on" if f32_mode else "off", f"(--numba_f32 {numba_f32})")
+    if rng not in ("table", "keyed"):
+        raise ValueError(f"--rng must be table or keyed, not {rng!r}")
+    print("Random streams:", rng, f"(--rng {rng})")
     lib.set_option("numba_f32", f32_mode)
     dist = None
     if world is not None:
@@ -469,8 +478,12 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             chain = ChargeChain(response)
             chain.clear_pixel_tables()
             if not rng_seeded:
-                # create_xoroshiro128p_states(1024*256, seed) (:396), once; rank r of a sharded run seeds rand_seed + r
-                chain.seed_rng(rand_seed + rank)
+                # create_xoroshiro128p_states(1024*256, seed) (:396), once; rank r of a sharded run seeds rand_seed + r.
+                # Keyed mode: every rank seeds rand_seed (the streams follow the identity of what is simulated)
+                if rng == "keyed":
+                    chain.seed_keyed(rank_seed(rand_seed, rank, rng))
+                else:
+                    chain.seed_rng(rank_seed(rand_seed, rank, rng))
                 rng_seeded = True
             thr_file, gain_file = per_module(pixel_thresholds_file, i_mod), per_module(pixel_gains_file, i_mod)
             if thr_file is not None:                                # :439-443, 698-706, 1079-1084
@@ -481,7 +494,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                 chain.set_pixel_gains(*fee.load_pixel_table(gain_file))
             res = _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field,
                                    per_module(light_lut_filename, i_mod) if light_simulated else None, light_det_noise_filename,
-                                   cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist)
+                                   cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist,
+                                   keyed=rng == "keyed")
             for k in totals:
                 totals[k] += res[k]
             rows_per_rank += res["rows_per_rank"]
@@ -528,7 +542,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
 
 def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field, light_lut,
                      light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None,
-                     dist=None):
+                     dist=None, keyed=False):
     """One pass of the driver's module loop body (cli/simulate_pixels.py:717-1232) on the device-resident chain: quench + drift,
     light leg, charge chain, packets.  ``tracks``: the module's active segments (all active segments without module
     variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out).
@@ -546,6 +560,8 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
     res = dict(n_segments=nsim, n_batches=len(table), n_hits=0, n_packets=0, n_light_triggers=0, light_dat=None)
     if len(tracks):                                                 # a module may hold no segment at all: it still reads out
         chain.upload(tracks, bid)
+        if keyed:
+            chain.set_batch_keys(table, i_mod)
         chain.quench_drift(consts.physics.BIRKS)
         chain.download_segments(tracks)
     # the batch-sorted copy is the device's; the file gets the module's segments in input order, like the reference's
@@ -609,7 +625,10 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
                 ibs = batch_of.get((int(ev), grp), [])
                 if not ibs:
                     # nothing to simulate in this module group: waveforms of an empty response (:805-841, 894-899)
-                    if null_wvfm is None:
+                    if null_wvfm is None or keyed:
+                        # (keyed: the noise of an empty group's waveforms belongs to that (event, group), so no cache)
+                        if keyed:
+                            chain.set_rng_key(lrng.call_key(i_mod, int(ev), grp, -1))
                         nt0 = int((light.LIGHT_WINDOW[1] + light.LIGHT_WINDOW[0]) / light.LIGHT_TICK_SIZE)
                         zero = np.zeros((n_det, nt0), dtype=np.float32)
                         mt = sim.MAX_MC_TRUTH_IDS
@@ -626,7 +645,10 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
                                                        segment_track_id=tracks["segment_id"][b0:b1].astype(np.int64))
                     if raw_arrays:
                         light_rows.append(chain.download_light(truth=False)[0])
-                    chain.extend_rng(n_det * (-(-int(n_ticks) // 64)) * 64, rand_seed + int(ev) + table[ib][2] * sim.BATCH_SIZE)
+                    if keyed:
+                        chain.set_rng_key(lrng.call_key(i_mod, int(ev), grp, int(table[ib][2])))
+                    else:
+                        chain.extend_rng(n_det * (-(-int(n_ticks) // 64)) * 64, rand_seed + int(ev) + table[ib][2] * sim.BATCH_SIZE)
                     chain.light_response(fluctuate=True)
                     t_idx, t_opc, t_type = light_sim.get_triggers(None, thr, op_channel, table[ib][2])
                     wv = light_sim.sim_triggers(None, None, None, op_channel, None, None, t_idx, t_opc, digit_samples,
@@ -890,6 +912,11 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
         for k in parts[0]:
             out.put(("raw/" if not m2m else f"raw_mod{i_mod - 1}/") + k, np.concatenate([p[k] for p in parts]))
     return res
+
+
+def rank_seed(rand_seed, rank, rng="table"):
+    """the seed rank `rank` gives its random streams: rand_seed + rank in table mode, rand_seed itself in keyed mode"""
+    return int(rand_seed) if rng == "keyed" else int(rand_seed) + int(rank)
 
 
 def _launch_ranges(edges, nsim, chunk_segments):

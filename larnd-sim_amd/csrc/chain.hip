@@ -244,6 +244,11 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
       return LDSIM_EINVAL;
     }
   }
+  if (ctx->rng_keyed && (int64_t)b_last >= ctx->rng_batch_keys_n) {
+    ldsim_set_error("keyed random mode: no key for batch id %d (ldsim_chain_set_batch_keys holds %lld): set the batch keys "
+                    "after every upload", b_last, (long long)ctx->rng_batch_keys_n);
+    return LDSIM_ESTATE;
+  }
   const int32_t batch0 = b_first;
   const int64_t n_batches = (int64_t)b_last - b_first + 1;
   ctx->stats.n_batches = n_batches;
@@ -374,6 +379,7 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   a.T = T;
   a.tmax_batch = d_tmax_b;
   a.batch0 = batch0;
+  a.batch_first = d_first_b;
   a.counters = counters;
   a.only_flagged = nullptr;
   a.flag_stride = 0;
@@ -418,9 +424,23 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   F.counters = counters;
   F.hit_count = d_hitcnt;
   F.debug = ctx->debug_phases;
-  // FEE noise (fee.py:557,583-584,616-617,621,649): row u of this launch draws from state u of the numba-style table
+  // FEE noise (fee.py:557,583-584,616-617,621,649): row u of this launch draws from state u of the numba-style table, or
+  // (keyed mode) from the stream of its (batch, pixel) identity, inline in the scan: no draws table, no advance pass
   const bool noisy = h.reset_noise_charge != 0 || h.uncorrelated_noise_charge != 0 || h.discriminator_noise != 0;
-  if (noisy) {
+  const bool keyed_inline = noisy && ctx->rng_keyed && !ctx->debug_rng_materialize;
+  if (keyed_inline) {
+    F.batch_keys = (const uint64_t*)ctx->d_batch_keys.p;
+    F.rng_seed = ctx->rng_seed;
+  } else if (noisy && ctx->rng_keyed) {
+    // debug_rng_materialize: the keyed normals written into the table layout and read by the table scan (tests)
+    const int nd = rng_fee_draws_per_pixel(h, h.n_time_ticks);
+    CK(ldsim_ensure(ctx, SB_NOISE, (size_t)U * nd * 4));
+    CK(ldsim_ensure(ctx, SB_NDRAWS, (size_t)U * 4 + 4));
+    CK(rng_launch_fee_keyed_fill(ctx, d_ubatch, d_upix, U, nd, (float*)ctx->scratch[SB_NOISE].p));
+    F.noise_z = (const float*)ctx->scratch[SB_NOISE].p;
+    F.noise_nd = nd;
+    F.n_draws = (int32_t*)ctx->scratch[SB_NDRAWS].p;
+  } else if (noisy) {
     CK(rng_ensure_states(ctx, U));
     const int nd = rng_fee_draws_per_pixel(h, h.n_time_ticks);
     CK(ldsim_ensure(ctx, SB_NOISE, (size_t)U * nd * 4));
@@ -431,7 +451,7 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
     F.n_draws = (int32_t*)ctx->scratch[SB_NDRAWS].p;
   }
   CK(fee_launch_chain(ctx, F));
-  if (noisy) CK(rng_launch_advance(ctx, U, F.n_draws));
+  if (noisy && !ctx->rng_keyed) CK(rng_launch_advance(ctx, U, F.n_draws));
   HIPCHK(hipEventRecord(ctx->ev[3], st));
 
   // ---- compact hit rows (payload of the multi-GPU all-gather) -----------------------------------------------------------------------------

@@ -9,6 +9,7 @@
 // 64-tick chunks, and the per-hit backtracking fractions are wave reductions over the hit spans.
 #include <algorithm>
 #include "ldsim_args.h"
+#include "rng.h"
 
 #define FEE_THREADS 256
 #define FEE_SPAN 512     // ticks of LDS of the one-wave instantiation of pixel_adc_kernel
@@ -78,16 +79,31 @@ struct HitRec {
   double tick;    // adc_ticks_list value
 };
 
-// z: this pixel's normal draws in stream order (fee_noise_kernel), or NULL when every noise charge is 0.  The reference
+// The noise source of the scan: draw i of the pixel's stream.  TableNoise reads what fee_noise_kernel drew ahead (z NULL: every
+// noise charge is 0); KeyedNoise computes it where it is consumed (rng.h: draw i of stream `key`, FEE tag).  get2(i) = draws i, i+1.
+struct TableNoise {
+  const float* z;
+  __device__ bool on() const { return z != nullptr; }
+  __device__ float get(int i) const { return z[i]; }
+  __device__ void get2(int i, float& a, float& b) const { a = z[i]; b = z[i + 1]; }
+};
+struct KeyedNoise {
+  uint64_t seed, key;
+  __device__ bool on() const { return true; }
+  __device__ float get(int i) const { return keyed_normal(seed, RNG_TAG_FEE, key, (uint32_t)i); }
+  __device__ void get2(int i, float& a, float& b) const { keyed_normal2(seed, RNG_TAG_FEE, key, (uint32_t)i, a, b); }
+};
+
+// z: this pixel's normal draws in stream order (the noise source above).  The reference
 // draws one normal before the loop (reset noise, fee.py:557), two at every pass of the loop (uncorrelated + discriminator
 // noise, :583-584, also on busy ticks), two after an integration (:616-617) and one at every reset (:621,649); *n_draws
 // returns how many were consumed.  t_stop = time_ticks[-1] of linspace(0, t_stop, NT + 1) (cli/simulate_pixels.py:1072).
 // [t_first, t_end): the ticks where S can be non-zero.  Without noise and with a positive threshold the scan's state does not
 // change on ticks whose charge is zero while the ADC is idle and the sum below threshold, so it starts at t_first and stops
 // once past t_end + ntap with the ADC idle (with noise every tick draws its normals and may trigger: all ticks are walked).
-template <class K>
+template <class K, class Z>
 __device__ int adc_scan(const K* c, const double* S, int NT, double t_stop, double thr, double time_padding,
-                        int lane, HitRec* hits /* LDS, [A] */, const double* wtap, int ntap, const float* __restrict__ z,
+                        int lane, HitRec* hits /* LDS, [A] */, const double* wtap, int ntap, const Z zs,
                         int* n_draws, int t_first = 0, int t_end = 1 << 30, int s_lo = 0, int s_hi = 1 << 30) {
   const double dt = c->time_sampling;
   const bool has_rt = c->buffer_risetime > 0;
@@ -100,7 +116,8 @@ __device__ int adc_scan(const K* c, const double* S, int NT, double t_stop, doub
   const double s_reset = c->reset_noise_charge, s_unc = c->uncorrelated_noise_charge, s_disc = c->discriminator_noise;
   int ic = 0, iadc = 0, adc_busy = 0, last_reset = 0, cur = 0;
   double q_sum = 0, true_q = 0;
-  if (z) q_sum = (double)z[cur++] * s_reset;
+  const bool z = zs.on();
+  if (z) q_sum = (double)zs.get(cur++) * s_reset;
   const bool skip_idle = !z && thr > 0;
   if (skip_idle && t_first > 0) ic = t_first < NT ? t_first : NT;
   const int t_quiet = t_end + ntap;            // from here on q(ic) = 0
@@ -117,8 +134,10 @@ __device__ int adc_scan(const K* c, const double* S, int NT, double t_stop, doub
     double qs = q_sum + incl;
     double q_noise = 0.0, disc_noise = 0.0;
     if (z && lane < n_live) {
-      q_noise = (double)z[cur + 2 * lane] * s_unc;
-      disc_noise = (double)z[cur + 2 * lane + 1] * s_disc;
+      float za, zb;
+      zs.get2(cur + 2 * lane, za, zb);
+      q_noise = (double)za * s_unc;
+      disc_noise = (double)zb * s_disc;
     }
     int busy_after = busy_before > 0 ? busy_before - 1 : 0;
     bool trig = (lane < n_live) && (qs + q_noise >= thr + disc_noise) && (busy_after == 0);
@@ -151,13 +170,15 @@ __device__ int adc_scan(const K* c, const double* S, int NT, double t_stop, doub
     ic = integrate_end + 1;
     double adc = q_sum, disc2 = 0.0;
     if (z) {
-      adc = q_sum + (double)z[cur] * s_unc;
-      disc2 = (double)z[cur + 1] * s_disc;
+      float za, zb;
+      zs.get2(cur, za, zb);
+      adc = q_sum + (double)za * s_unc;
+      disc2 = (double)zb * s_disc;
       cur += 2;
     }
     if (adc < thr + disc2) {  // fee.py:619-628
       ic += reset_ticks;
-      q_sum = z ? (double)z[cur++] * s_reset : 0.0;
+      q_sum = z ? (double)zs.get(cur++) * s_reset : 0.0;
       true_q = 0;
       last_reset = ic;
       adc_busy = 0;
@@ -176,7 +197,7 @@ __device__ int adc_scan(const K* c, const double* S, int NT, double t_stop, doub
     ic += reset_ticks;
     last_reset = ic;
     adc_busy = busy_ticks;
-    q_sum = z ? (double)z[cur++] * s_reset : 0.0;
+    q_sum = z ? (double)zs.get(cur++) * s_reset : 0.0;
     true_q = 0;
     iadc++;
   }
@@ -190,7 +211,7 @@ __device__ int adc_scan(const K* c, const double* S, int NT, double t_stop, doub
 // pixel, FEE_SPAN ticks of LDS starting at the pixel's first written tick -- for the others, over a list (fee_span_kernel): the
 // kernel is a chain of dependent trips to memory per pixel (pair range -> keys -> slots' starts and windows -> rows), so what
 // counts is pixels in flight, and a CU holds 2048 threads: 8 pixels of 256 threads, 19 of 64 at 8.4 KB each.
-template <int THREADS>
+template <int THREADS, bool KEYED = false>
 __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const int64_t u, const int32_t* __restrict__ span /* [U][2] or NULL */,
                                                const int s_cap) {
   const FeeK* c = &F.k;          // (kernel arguments: scalar registers, no loads)
@@ -275,8 +296,17 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const int64_t u
   if (wv == 0) {
     const double thr = F.thr_table ? F.thr_table[F.upix[u]] : F.threshold;
     int nd = 0;
-    int nh = (F.debug & 0x20000) ? 0 : adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap,
-                      F.noise_z ? F.noise_z + u * (int64_t)F.noise_nd : nullptr, &nd, s_trange[0], s_trange[1], s_lo, s_hi);
+    int nh = 0;
+    if (F.debug & 0x20000) {
+    } else if (KEYED) {
+      const KeyedNoise zs{F.rng_seed, key_mix(F.batch_keys[ubatch], (uint64_t)(int64_t)F.upix[u])};
+      nh = adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap, zs, &nd, s_trange[0],
+                    s_trange[1], s_lo, s_hi);
+    } else {
+      const TableNoise zs{F.noise_z ? F.noise_z + u * (int64_t)F.noise_nd : nullptr};
+      nh = adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap, zs, &nd, s_trange[0],
+                    s_trange[1], s_lo, s_hi);
+    }
     if (lane == 0) {
       s_nh = nh;
       if (F.n_draws) F.n_draws[u] = nd;
@@ -321,19 +351,20 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const int64_t u
   }
 }
 
-// one workgroup per unique pixel
-template <int THREADS>
+// one workgroup per unique pixel.  KEYED: the FEE noise is drawn inline from the row's keyed stream (a separate instance, no
+// runtime branch in the scan)
+template <int THREADS, bool KEYED = false>
 __global__ void __launch_bounds__(THREADS) pixel_adc_kernel(FeeArgs F) {
-  if ((int64_t)blockIdx.x < F.U) pixel_adc_body<THREADS>(F, (int64_t)blockIdx.x, nullptr, 0);
+  if ((int64_t)blockIdx.x < F.U) pixel_adc_body<THREADS, KEYED>(F, (int64_t)blockIdx.x, nullptr, 0);
 }
 // a fixed grid walks a device-built list of pixels (its length stays on the device: no host round trip to size the launch)
-template <int THREADS>
+template <int THREADS, bool KEYED = false>
 __global__ void __launch_bounds__(THREADS) pixel_adc_list_kernel(FeeArgs F, const int32_t* __restrict__ list,
                                                                 const unsigned long long* __restrict__ count,
                                                                 const int32_t* __restrict__ span, int s_cap) {
   const int64_t n = (int64_t)*count;
   for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
-    pixel_adc_body<THREADS>(F, (int64_t)list[i], span, s_cap);
+    pixel_adc_body<THREADS, KEYED>(F, (int64_t)list[i], span, s_cap);
     __syncthreads();          // (the next pixel reuses the workgroup's LDS)
   }
 }
@@ -414,6 +445,12 @@ extern "C++" int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F) {
   // fee_clear_unwritten_fractions has run: the dense downloads call it -- clearing 12 KB per pixel in every launch cost 0.45 ms per
   // 100 k segments, and the compact download reads the written entries only)
   const size_t full = (size_t)((h.n_time_ticks + 1) & ~1) * 8;
+  if (F.batch_keys) {
+    // keyed noise: every tick is walked (no idle skipping), so the whole tick axis goes in LDS like the noisy table case
+    hipLaunchKernelGGL((pixel_adc_kernel<FEE_THREADS, true>), dim3((unsigned)F.U), dim3(FEE_THREADS), full, ctx->stream, F);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   const bool skip_idle = !F.noise_z && ((F.thr_table != nullptr) || F.threshold > 0);
   if (!skip_idle || !F.win || ctx->fee_one_class || h.n_time_ticks <= FEE_SPAN) {
     // (noise: every tick is walked; a threshold table may hold non-positive entries -- the scan decides per pixel, so the table
@@ -523,7 +560,7 @@ __global__ void __launch_bounds__(FEE_THREADS) adc_dense_kernel(const LdsimConst
   if (wv == 0) {
     int nd = 0;
     int nh = adc_scan(c, S, NT, t_stop, thresholds[u], time_padding, lane, hits, wtap, ntap,
-                      noise_z ? noise_z + u * (int64_t)noise_nd : nullptr, &nd);
+                      TableNoise{noise_z ? noise_z + u * (int64_t)noise_nd : nullptr}, &nd);
     if (lane == 0) {
       s_nh = nh;
       if (n_draws) n_draws[u] = nd;

@@ -21,8 +21,13 @@ struct McArgs {
   CurArgs c;
   const RngState* states;
   int64_t n_seg;           // ntrk of the state index  itrk + ntrk * ipix
+  // keyed mode (chain launches only): pair key = key_mix(key_mix(batch key, segment index within its batch), pixel id),
+  // stream of tick it = key_mix(pair key, it)
+  const uint64_t* batch_keys;
+  uint64_t seed;
 };
 
+template <bool KEYED>
 __global__ void __launch_bounds__(256) current_mc_kernel(McArgs Mc) {
   const CurArgs& A = Mc.c;
   const LdsimConsts* c = A.c;
@@ -116,7 +121,14 @@ __global__ void __launch_bounds__(256) current_mc_kernel(McArgs Mc) {
   const double step = g[8], charge = g[9], sT = g[10], sL = g[11], t_start = g[12], z_anode = g[13];
   const int nstep = gi[1], mult = c->mc_sample_multiplier;
   const double dt = c->time_sampling, dtr = c->response_sampling, TW = c->time_window, bin = c->response_bin_size;
-  const RngState base = Mc.states[r + Mc.n_seg * ipix];
+  RngState base{0, 0};
+  uint64_t pair_key = 0;
+  if (KEYED) {
+    const int32_t b = A.s.batch[seg] - A.batch0;
+    pair_key = key_mix(key_mix(Mc.batch_keys[A.s.batch[seg]], (uint64_t)(r - A.batch_first[b])), (uint64_t)pID);
+  } else {
+    base = Mc.states[r + Mc.n_seg * ipix];
+  }
   for (int it = tid; it < A.T; it += 256) {
     const double time_tick = t_start + it * dt;
     if (it >= T || time_tick < 0) {      // beyond this batch's max_length / detsim.py:297-298: the signal stays 0
@@ -124,18 +136,19 @@ __global__ void __launch_bounds__(256) current_mc_kernel(McArgs Mc) {
       continue;
     }
     RngState rs;
-    mc_stream_words(base.s0, base.s1, (uint32_t)it, rs.s0, rs.s1);
+    KeyedStream ks(Mc.seed, RNG_TAG_MC, key_mix(pair_key, (uint64_t)it));
+    if (!KEYED) mc_stream_words(base.s0, base.s1, (uint32_t)it, rs.s0, rs.s1);
     double total = 0;
     for (int istep = 0; istep < nstep; istep++)
       for (int m = 0; m < mult; m++) {
         double x = sx0 + step * (istep + 0.5) * dirx;
         double y = sy0 + step * (istep + 0.5) * diry;
         double z = sz0 + step * (istep + 0.5) * dirz;
-        z += (double)rng_normal_f32(rs) * sL;
+        z += (double)(KEYED ? ks.normal() : rng_normal_f32(rs)) * sL;
         const double t0 = fabs(z - z_anode) / c->v_drift - TW;
         if (!(t0 < time_tick && time_tick < t0 + TW)) continue;
-        x += (double)rng_normal_f32(rs) * sT;
-        y += (double)rng_normal_f32(rs) * sT;
+        x += (double)(KEYED ? ks.normal() : rng_normal_f32(rs)) * sT;
+        y += (double)(KEYED ? ks.normal() : rng_normal_f32(rs)) * sT;
         const double xd = fabs(x_p - x), yd = fabs(y_p - y);
         if (xd > bin * A.ni) continue;
         if (yd > bin * A.nj) continue;
@@ -178,14 +191,27 @@ extern "C++" int current_mc_launch(ldsim_ctx* ctx, const CurArgs& args, int64_t 
     ldsim_set_error("too many pairs for one launch");
     return LDSIM_EINVAL;
   }
+  if (ctx->rng_keyed) {
+    if (!args.pair_val || !args.batch_first) {
+      ldsim_set_error("tracks_current_mc in keyed random mode runs in chain launches only");
+      return LDSIM_ESTATE;
+    }
+    McArgs M{};
+    M.c = args;
+    M.batch_keys = (const uint64_t*)ctx->d_batch_keys.p;
+    M.seed = ctx->rng_seed;
+    hipLaunchKernelGGL(current_mc_kernel<true>, dim3((unsigned)args.n_pairs), dim3(256), 0, ctx->stream, M);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   const int64_t n_states = n_seg * (int64_t)args.P;
   int rc = rng_ensure_states(ctx, n_states);
   if (rc) return rc;
-  McArgs M;
+  McArgs M{};
   M.c = args;
   M.states = (const RngState*)ctx->d_rng.p;
   M.n_seg = n_seg;
-  hipLaunchKernelGGL(current_mc_kernel, dim3((unsigned)args.n_pairs), dim3(256), 0, ctx->stream, M);
+  hipLaunchKernelGGL(current_mc_kernel<false>, dim3((unsigned)args.n_pairs), dim3(256), 0, ctx->stream, M);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(rng_step_kernel, dim3((unsigned)((n_states + 255) / 256)), dim3(256), 0, ctx->stream,
                      (RngState*)ctx->d_rng.p, n_states);

@@ -39,7 +39,43 @@ __global__ void __launch_bounds__(256) rng_advance_kernel(RngState* __restrict__
   states[u] = st;
 }
 
+// keyed FEE rows (debug_rng_materialize): row u's first nd normals of stream key_mix(batch key, pixel id), in the layout of
+// fee_noise_kernel, for the table-reading scan
+__global__ void __launch_bounds__(256) fee_keyed_fill_kernel(uint64_t seed, const uint64_t* __restrict__ batch_keys,
+                                                             const int32_t* __restrict__ ubatch, const int32_t* __restrict__ upix,
+                                                             int64_t U, int nd, float* __restrict__ z) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int nb = nd / 4;
+  if (i >= U * nb) return;
+  const int64_t u = i / nb;
+  const int m = (int)(i - u * nb);
+  const uint64_t key = key_mix(batch_keys[ubatch[u]], (uint64_t)(int64_t)upix[u]);
+  float4 v;
+  keyed_normal2(seed, RNG_TAG_FEE, key, 4 * m, v.x, v.y);
+  keyed_normal2(seed, RNG_TAG_FEE, key, 4 * m + 2, v.z, v.w);
+  ((float4*)(z + u * (int64_t)nd))[m] = v;
+}
+
+// test exports: n streams, nd draws each from index d0
+__global__ void __launch_bounds__(256) rng_keyed_draw_kernel(uint64_t seed, uint32_t tag, const uint64_t* __restrict__ keys,
+                                                             int64_t n, uint32_t d0, int nd, int normal, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * nd) return;
+  const int64_t s = i / nd;
+  const uint32_t d = d0 + (uint32_t)(i - s * nd);
+  out[i] = normal ? keyed_normal(seed, tag, keys[s], d) : keyed_uniform(seed, tag, keys[s], d);
+}
+
 extern "C++" {
+int rng_launch_fee_keyed_fill(ldsim_ctx* ctx, const int32_t* ubatch, const int32_t* upix, int64_t U, int nd, float* z) {
+  if (U == 0) return 0;
+  const int64_t n = U * (nd / 4);
+  hipLaunchKernelGGL(fee_keyed_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rng_seed,
+                     (const uint64_t*)ctx->d_batch_keys.p, ubatch, upix, U, nd, z);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 static void rng_jump_host(RngState& st) {
   static const uint64_t JUMP[2] = {0xbeac0467eba5facbULL, 0xd86b048b86aa9922ULL};
   uint64_t s0 = 0, s1 = 0;
@@ -93,6 +129,10 @@ static int rng_append(ldsim_ctx* ctx, int64_t n, const uint64_t* fresh_seed) {
 }
 
 int rng_ensure_states(ldsim_ctx* ctx, int64_t n) {
+  if (ctx->rng_keyed) {        // (every drawing stage has a keyed form: reaching the table in keyed mode is a bug)
+    ldsim_set_error("internal: a table-mode random stream was requested in keyed mode");
+    return LDSIM_ESTATE;
+  }
   if (!ctx->rng_seeded) {
     ldsim_set_error("this stage draws random numbers but no random state exists: call ldsim_rng_seed first");
     return LDSIM_ESTATE;
@@ -139,6 +179,7 @@ extern "C" int ldsim_rng_seed(ldsim_ctx* ctx, uint64_t seed, int64_t n_states) {
   ctx->rng_n = 0;
   ctx->rng_seed = seed;
   ctx->rng_seeded = 1;
+  ctx->rng_keyed = 0;
   ctx->light_noise_calls = 0;
   ctx->rng_last_init[0] = ctx->rng_last_init[1] = 0;
   try {
@@ -178,6 +219,7 @@ extern "C" int ldsim_rng_clear(ldsim_ctx* ctx) {
   ctx->d_rng = DevBuf{};
   ctx->rng_n = 0;
   ctx->rng_seeded = 0;
+  ctx->rng_keyed = 0;
   return 0;
 }
 
@@ -191,4 +233,96 @@ extern "C" int ldsim_rng_states_download(ldsim_ctx* ctx, uint64_t* states, int64
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (n) HIPCHK(hipMemcpy(states, ctx->d_rng.p, (size_t)n * sizeof(RngState), hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- keyed mode -----------------------------------------------------------------------------------------------------------
+// drop the table; every later draw is Philox of (seed, stage tag, identity key, index) -- rng.h
+extern "C" int ldsim_rng_keyed_seed(ldsim_ctx* ctx, uint64_t seed) {
+  LDSIM_ENTER(ctx);
+  if (!ctx) {
+    ldsim_set_error("bad argument");
+    return LDSIM_EINVAL;
+  }
+  int rc = ldsim_rng_clear(ctx);
+  if (rc) return rc;
+  ctx->rng_seed = seed;
+  ctx->rng_seeded = 1;
+  ctx->rng_keyed = 1;
+  ctx->rng_call_key = 0;
+  ctx->rng_batch_keys_n = 0;
+  return 0;
+}
+
+extern "C" int ldsim_rng_is_keyed(ldsim_ctx* ctx) { return ctx && ctx->rng_keyed ? 1 : 0; }
+
+extern "C" int ldsim_chain_set_batch_keys(ldsim_ctx* ctx, const uint64_t* keys, int64_t n_batches) {
+  LDSIM_ENTER(ctx);
+  if (!ctx || n_batches < 0 || (n_batches && !keys)) {
+    ldsim_set_error("bad argument");
+    return LDSIM_EINVAL;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));      // (a launch in flight may still read the old keys)
+  int rc = ldsim_ensure_buf(ctx, &ctx->d_batch_keys, (size_t)(n_batches ? n_batches : 1) * 8);
+  if (rc) return rc;
+  if (n_batches) HIPCHK(hipMemcpy(ctx->d_batch_keys.p, keys, (size_t)n_batches * 8, hipMemcpyHostToDevice));
+  ctx->rng_batch_keys_n = n_batches;
+  return 0;
+}
+
+extern "C" int ldsim_rng_set_call_key(ldsim_ctx* ctx, uint64_t key) {
+  LDSIM_ENTER(ctx);
+  if (!ctx) {
+    ldsim_set_error("bad argument");
+    return LDSIM_EINVAL;
+  }
+  ctx->rng_call_key = key;
+  return 0;
+}
+
+static int rng_keyed_draws(ldsim_ctx* ctx, uint32_t tag, const uint64_t* stream_keys, int64_t n, uint32_t d0, int32_t nd,
+                           float* out, int normal) {
+  if (!ctx || n < 0 || nd < 0 || (n && nd && (!stream_keys || !out))) {
+    ldsim_set_error("bad argument");
+    return LDSIM_EINVAL;
+  }
+  if (!ctx->rng_keyed) {
+    ldsim_set_error("keyed draws need keyed mode: call ldsim_rng_keyed_seed first");
+    return LDSIM_ESTATE;
+  }
+  if (n == 0 || nd == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t total = n * (int64_t)nd;
+  void *dk = nullptr, *dout = nullptr;
+  HIPCHK(hipMalloc(&dk, (size_t)n * 8));
+  if (hipMalloc(&dout, (size_t)total * 4) != hipSuccess) {
+    (void)hipFree(dk);
+    ldsim_set_error("out of device memory");
+    return LDSIM_EINVAL;
+  }
+  int rc = 0;
+  if (hipMemcpy(dk, stream_keys, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) rc = LDSIM_EINVAL;
+  if (!rc) {
+    hipLaunchKernelGGL(rng_keyed_draw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rng_seed,
+                       tag, (const uint64_t*)dk, n, d0, nd, normal, (float*)dout);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        hipMemcpy(out, dout, (size_t)total * 4, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = LDSIM_EINVAL;
+  }
+  (void)hipFree(dk);
+  (void)hipFree(dout);
+  if (rc) ldsim_set_error("keyed draws: a HIP call failed");
+  return rc;
+}
+
+// out[s * nd + j] = draw d0 + j of stream (tag, stream_keys[s])
+extern "C" int ldsim_rng_keyed_normals(ldsim_ctx* ctx, uint32_t tag, const uint64_t* stream_keys, int64_t n, uint32_t d0,
+                                       int32_t nd, float* out) {
+  LDSIM_ENTER(ctx);
+  return rng_keyed_draws(ctx, tag, stream_keys, n, d0, nd, out, 1);
+}
+extern "C" int ldsim_rng_keyed_uniforms(ldsim_ctx* ctx, uint32_t tag, const uint64_t* stream_keys, int64_t n, uint32_t d0,
+                                        int32_t nd, float* out) {
+  LDSIM_ENTER(ctx);
+  return rng_keyed_draws(ctx, tag, stream_keys, n, d0, nd, out, 0);
 }

@@ -275,6 +275,7 @@ extern "C" int ldsim_ctx_destroy(ldsim_ctx* ctx) {
     if (b.p) (void)hipFree(b.p);
   (void)ldsim_comm_destroy(ctx);
   if (ctx->d_rng.p) (void)hipFree(ctx->d_rng.p);
+  if (ctx->d_batch_keys.p) (void)hipFree(ctx->d_batch_keys.p);
   for (DevBuf* b : {&ctx->comm_tmp, &ctx->hits_acc, &ctx->hits_all, &ctx->gv_send, &ctx->gv_all})
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < 5; k++)
@@ -341,6 +342,7 @@ extern "C" int ldsim_set_option(ldsim_ctx* ctx, const char* name, double value) 
   }
   else if (!strcmp(name, "numba_f32")) ctx->numba_f32 = value != 0;
   else if (!strcmp(name, "mc_current")) ctx->mc_current = value != 0;
+  else if (!strcmp(name, "debug_rng_materialize")) ctx->debug_rng_materialize = value != 0;
   else if (!strcmp(name, "quad_accuracy_log10")) {
     // relative quadrature error of the tables / weights stage as a power of ten of the peak weight (fits of tools/quad_nodes.py,
     // upper envelopes: N = ceil(n0 + slope r) nodes for a segment r Gaussian widths long)
@@ -742,6 +744,10 @@ extern "C" int ldsim_tracks_current_mc(ldsim_ctx* ctx, const void* tracks, int64
   LDSIM_ENTER(ctx);
   NEED(pixels && signals && P >= 0 && T >= 0, "bad tracks_current_mc arguments");
   NEED(ctx && ctx->d_resp, "no response table set (ldsim_set_response)");
+  if (ctx->rng_keyed) {
+    ldsim_set_error(LDSIM_KEYED_STAGE_MSG, "ldsim_tracks_current_mc");
+    return LDSIM_ESTATE;
+  }
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
   size_t bp = (size_t)n * P * 4, bs = (size_t)n * P * T * 4;
   if (bs == 0) return 0;
@@ -813,6 +819,10 @@ extern "C" int ldsim_get_adc_values(ldsim_ctx* ctx, const double* ps, const doub
   HIPCHK(hipSetDevice(ctx->device));
   const LdsimConsts& h = ctx->h_consts;
   const bool noisy = h.reset_noise_charge != 0 || h.uncorrelated_noise_charge != 0 || h.discriminator_noise != 0;
+  if (noisy && ctx->rng_keyed) {
+    ldsim_set_error(LDSIM_KEYED_STAGE_MSG, "ldsim_get_adc_values");
+    return LDSIM_ESTATE;
+  }
   const int A = h.max_adc_values;
   Tmp dps, dpts, dthr, dadc, dtk, dfr, dz, dnd;
   CK(dps.alloc((size_t)U * NT * 8)); CK(dthr.alloc(U * 8)); CK(dadc.alloc((size_t)U * A * 8)); CK(dtk.alloc((size_t)U * A * 8));
@@ -1329,7 +1339,7 @@ extern "C" int ldsim_light_detector_response(ldsim_ctx* ctx, const float* light_
 
 // light_sim.calc_scintillation_effect -> calc_stat_fluctuations -> calc_light_detector_response on the resident photon sum
 // (cli/simulate_pixels.py:1159-1180), everything staying in HBM
-int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n);      // light_wvfm.hip
+int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick);      // light_wvfm.hip
 
 extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain, const double* impulse_model,
                                         int32_t n_impulse, int32_t fluctuate) {
@@ -1387,7 +1397,7 @@ extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain
   HIPCHK(hipEventRecord(ev[1], st));
   const float* disc = (const float*)ctx->light_scint.p;
   if (fluctuate) {
-    CK(light_launch_stat_fluct(ctx, (const float*)ctx->light_scint.p, (float*)ctx->light_disc.p, (int64_t)bo));
+    CK(light_launch_stat_fluct(ctx, (const float*)ctx->light_scint.p, (float*)ctx->light_disc.p, (int64_t)bo, T));
     disc = (const float*)ctx->light_disc.p;
   }
   HIPCHK(hipEventRecord(ev[2], st));

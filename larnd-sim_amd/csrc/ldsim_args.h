@@ -38,6 +38,7 @@ struct CurArgs {
   int32_t T;                     // row stride == max ticks
   const int32_t* tmax_batch;     // per-batch max_length (chain) or NULL -> T
   int32_t batch0;
+  const int32_t* batch_first;    // per-batch first relative segment index (chain) or NULL
   double prune_log;
   double tail_log;        // split path: samples below exp(-tail_log) of the peak density are evaluated in f32 (0 = off)
   int32_t debug_phases;
@@ -101,6 +102,9 @@ struct FeeArgs {
   const float* noise_z;       // [U][noise_nd]
   int32_t noise_nd;
   int32_t* n_draws;           // [U] normals the scan consumed
+  // keyed mode (rng.h): row u draws stream key_mix(batch_keys[ubatch[u]], upix[u]) inline, no table (noise_z NULL)
+  const uint64_t* batch_keys; // [batch ids of the upload] or NULL = table mode
+  uint64_t rng_seed;
   int32_t debug;              // timing tools (debug_phases bits 0x10000 / 0x20000 / 0x40000: no waveform sum / scan / fractions)
 };
 
@@ -110,6 +114,7 @@ int rng_ensure_states(ldsim_ctx* ctx, int64_t n);
 int rng_fee_draws_per_pixel(const LdsimConsts& h, int NT);
 int rng_launch_fee_noise(ldsim_ctx* ctx, int64_t U, int nd, float* z);
 int rng_launch_advance(ldsim_ctx* ctx, int64_t U, const int32_t* n_draws);
+int rng_launch_fee_keyed_fill(ldsim_ctx* ctx, const int32_t* ubatch, const int32_t* upix, int64_t U, int nd, float* z);
 int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F);
 int split_launch_weights(ldsim_ctx* ctx, const CurArgs& args, void* items, void* hdr, void* corr, double* wbuf,
                          unsigned long long wbuf_cap, unsigned long long* cursor);

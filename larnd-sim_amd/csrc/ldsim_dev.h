@@ -224,6 +224,13 @@ struct ldsim_ctx {
   int64_t rng_n = 0;
   uint64_t rng_seed = 0, rng_last_init[2] = {0, 0};
   int rng_seeded = 0;
+  // keyed mode (ldsim_rng_keyed_seed, rng.h): no table; every draw is Philox of (rng_seed, stage, identity key, index).
+  // rng_batch_keys: one key per batch id of the upload (ldsim_chain_set_batch_keys); rng_call_key: identity of the light calls
+  int rng_keyed = 0;
+  uint64_t rng_call_key = 0;
+  DevBuf d_batch_keys;
+  int64_t rng_batch_keys_n = 0;
+  int debug_rng_materialize = 0;     // option: keyed FEE normals written to the noise table and read by the table scan (tests)
   // multi-GPU exchange (comm.hip): RCCL communicator, rows accumulated over the chain calls of a pass, gathered rows
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 0;
@@ -259,6 +266,11 @@ enum {
 void ldsim_set_error(const char* fmt, ...);
 int ldsim_ensure(ldsim_ctx* ctx, int slot, size_t bytes);
 int ldsim_ensure_buf(ldsim_ctx* ctx, DevBuf* b, size_t bytes);
+// refusal of a host-array stage call that draws random numbers while the ctx is in keyed mode (its rows have no identity)
+#define LDSIM_KEYED_STAGE_MSG \
+  "%s draws random numbers, but the context is in keyed mode and this stage call carries no identity for its rows: " \
+  "call ldsim_rng_seed for table mode"
+
 
 // Claims the ctx for the calling thread for the duration of an extern "C" entry point.
 struct CtxEnter {

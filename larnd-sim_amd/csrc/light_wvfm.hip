@@ -50,7 +50,14 @@ struct LTmp {                       // temporary device buffer
 
 // ---- calc_stat_fluctuations ----------------------------------------------------------------------------------------------
 // xoroshiro128p_poisson_int32 (:186-216): inversion with one float32 uniform below a mean of 30, else a normal truncated at 0
-__device__ inline int poisson_int32(double mean, RngState& st) {
+// (st: an RngState, or a KeyedPoisson in keyed mode)
+struct KeyedPoisson {
+  uint64_t seed, key;
+};
+__device__ inline float rng_uniform_f32(const KeyedPoisson& k) { return keyed_uniform(k.seed, RNG_TAG_LIGHT_FLUCT, k.key, 0); }
+__device__ inline float rng_normal_f32(const KeyedPoisson& k) { return keyed_normal(k.seed, RNG_TAG_LIGHT_FLUCT, k.key, 0); }
+template <class St>
+__device__ inline int poisson_int32(double mean, St& st) {
   if (mean <= 0) return 0;
   if (mean < 30) {
     const double u = (double)rng_uniform_f32(st);
@@ -85,8 +92,30 @@ __global__ void __launch_bounds__(256) light_stat_fluct_kernel(const float* __re
   }
 }
 
-extern "C++" int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n) {
+// keyed mode: element (idet, itick) draws uniform / normal 0 of stream key_mix(key_mix(call key, idet), itick)
+__global__ void __launch_bounds__(256) light_stat_fluct_keyed_kernel(const float* __restrict__ inc, float* __restrict__ out,
+                                                                     uint64_t seed, uint64_t call_key, int64_t n, int64_t ntick,
+                                                                     double tick) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const float x = inc[e];
+  if (x > 0) {
+    const int64_t idet = e / ntick, itick = e - idet * ntick;
+    KeyedPoisson src{seed, key_mix(key_mix(call_key, (uint64_t)idet), (uint64_t)itick)};
+    out[e] = (float)(1. / tick * (double)poisson_int32((double)x * tick, src));
+  } else {
+    out[e] = 0.f;
+  }
+}
+
+extern "C++" int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick) {
   if (n == 0) return 0;
+  if (ctx->rng_keyed) {
+    hipLaunchKernelGGL(light_stat_fluct_keyed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, inc, out,
+                       ctx->rng_seed, ctx->rng_call_key, n, ntick, ctx->h_consts.light_tick_size);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   LW_CK(rng_ensure_states(ctx, n));
   hipLaunchKernelGGL(light_stat_fluct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, inc, out,
                      (RngState*)ctx->d_rng.p, n, ctx->h_consts.light_tick_size);
@@ -222,6 +251,12 @@ __host__ __device__ inline uint64_t lw_hash(uint64_t x) {      // SplitMix64 fin
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
   return x ^ (x >> 31);
+}
+// seed of one detector-noise call: the n-th call of the process (table mode), or the light call key (keyed mode,
+// ldsim_rng_set_call_key) -- the same phases for the same (module, event, TPC group, sub-batch) whatever ran before
+static uint64_t light_noise_seed(ldsim_ctx* ctx) {
+  if (ctx->rng_keyed) return lw_hash(ctx->rng_seed ^ ctx->rng_call_key);
+  return lw_hash(ctx->rng_seed ^ lw_hash(0x6c69676874ULL + ctx->light_noise_calls++));
 }
 
 // spectrum row r, frequency bin k: np.interp of the channel's noise spectrum at the FFT frequency (j, dx, dxp and `exact`
@@ -626,7 +661,7 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
       return LDSIM_ESTATE;
     }
     LW_CK(d_noise.alloc((size_t)Rp * nn * 8));
-    const uint64_t seed = lw_hash(ctx->rng_seed ^ lw_hash(0x6c69676874ULL + ctx->light_noise_calls++));
+    const uint64_t seed = light_noise_seed(ctx);
     LW_CK(light_noise_run(ctx, noise_tab, n_ch, nbins, chan, Tp, ticks, ph.empty() ? nullptr : ph.data(), seed,
                           d_noise.as<double>()));
   }
@@ -685,6 +720,10 @@ extern "C" int ldsim_stat_fluctuations(ldsim_ctx* ctx, const float* light_sample
   LDSIM_ENTER(ctx);
   LW_NEED(ctx && light_sample_inc && light_sample_inc_disc && n_det >= 0 && n_ticks >= 0, "bad argument");
   LW_NEED(ctx->h_consts.light_tick_size > 0, "light constants not set");
+  if (ctx->rng_keyed) {
+    ldsim_set_error(LDSIM_KEYED_STAGE_MSG, "ldsim_stat_fluctuations");
+    return LDSIM_ESTATE;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n = (size_t)n_det * n_ticks;
   if (n == 0) return 0;
@@ -692,7 +731,7 @@ extern "C" int ldsim_stat_fluctuations(ldsim_ctx* ctx, const float* light_sample
   LW_CK(din.alloc(n * 4));
   LW_CK(dout.alloc(n * 4));
   HIPCHK(hipMemcpyAsync(din.p, light_sample_inc, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  LW_CK(light_launch_stat_fluct(ctx, din.as<float>(), dout.as<float>(), (int64_t)n));
+  LW_CK(light_launch_stat_fluct(ctx, din.as<float>(), dout.as<float>(), (int64_t)n, n_ticks));
   HIPCHK(hipMemcpyAsync(light_sample_inc_disc, dout.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -735,7 +774,7 @@ extern "C" int ldsim_light_detector_noise(ldsim_ctx* ctx, int32_t n_rows, int32_
   for (int i = 0; i < n_samples; i++) ticks[(size_t)i] = i;
   LTmp dout;
   LW_CK(dout.alloc((size_t)n_rows * n_samples * 8));
-  const uint64_t seed = lw_hash(ctx->rng_seed ^ lw_hash(0x6c69676874ULL + ctx->light_noise_calls++));
+  const uint64_t seed = light_noise_seed(ctx);
   LW_CK(light_noise_run(ctx, spectrum, n_rows, nbins, chan, n_samples, ticks, phases, seed, dout.as<double>()));
   HIPCHK(hipMemcpy(noise, dout.p, (size_t)n_rows * n_samples * 8, hipMemcpyDeviceToHost));
   return 0;

@@ -34,6 +34,22 @@ class ChargeChain:
         """``maybe_create_rng_states(n, seed, rng_states)`` (cli/simulate_pixels.py:92-104) on the ctx's table."""
         lib.check(lib.load().ldsim_rng_extend(self.ctx, C.c_int64(int(n_states)), C.c_uint64(int(seed) & (2 ** 64 - 1))))
 
+    def seed_keyed(self, seed):
+        """Keyed random mode (csrc/rng.h): drop the table; every draw becomes a function of (seed, stage, identity of what is
+        simulated, draw index).  A run then needs ``set_batch_keys`` after each ``upload`` and ``set_rng_key`` before the light
+        calls of a sub-batch.  ``seed_rng`` switches back to table mode."""
+        lib.check(lib.load().ldsim_rng_keyed_seed(self.ctx, C.c_uint64(int(seed) & (2 ** 64 - 1))))
+
+    def set_batch_keys(self, table, i_mod):
+        """keyed mode: the keys of the uploaded batches, from their identities in ``batching.assign_batches``' table"""
+        from . import rng
+        keys = np.ascontiguousarray(rng.batch_keys(table, i_mod), dtype=np.uint64)
+        lib.check(lib.load().ldsim_chain_set_batch_keys(self.ctx, lib.ptr(keys), C.c_int64(len(keys))))
+
+    def set_rng_key(self, key):
+        """keyed mode: identity key (rng.call_key) of the light response / trigger / noise calls that follow"""
+        lib.check(lib.load().ldsim_rng_set_call_key(self.ctx, C.c_uint64(int(key) & (2 ** 64 - 1))))
+
     def _check_constants(self):
         """The ctx is process-wide and this object froze its constants at construction: refuse to compute once anything
         (another ChargeChain, a stage call after ``consts`` was reloaded) has frozen different ones."""
