@@ -367,6 +367,27 @@ int ldsim_segments_reset(ldsim_ctx* ctx);
 /* quench + drift over the resident segments (cli/simulate_pixels.py:732,742) */
 int ldsim_dev_quench_drift(ldsim_ctx* ctx, int32_t mode);
 
+/* ---- drift-field maps ------------------------------------------------------------------------
+ * A regular grid per TPC in the simulation frame (TPC_BORDERS after swap_coordinates, cm; z = drift coordinate), keyed by
+ * the global TPC index so it survives ldsim_set_consts.  Channels, each C-order [nx][ny][nz] and each may be NULL:
+ *   E       local field (kV/cm, finite, > 0) replacing e_field in the recombination (NULL: the constants' e_field);
+ *   dx, dy  displacement of the charge that starts at a node where it reaches the anode (cm, finite; NULL: 0);
+ *   dz      shift of the equivalent drift coordinate: arrival time |z + dz - z_anode| / v_drift (cm, finite; NULL: 0).
+ * Node (i, j, k) sits at origin + (i, j, k) * spacing; the map is interpolated trilinearly, clamped to the edge nodes.
+ * While any map is set, ldsim_dev_quench_drift quenches with E at the true midpoint and drifts the anode view -- start, end
+ * and midpoint moved by the offsets at themselves, clamped into the TPC's box (never further out than the true point) and
+ * rounded to the record's dtype; every charge stage of ldsim_charge_chain reads that view, the light leg and
+ * ldsim_segments_download keep the true positions.  ldsim_charge_chain refuses (LDSIM_ESTATE) when the maps changed since
+ * the last quench_drift; the host-array stage calls that take records (ldsim_quench, ldsim_drift, ldsim_get_pixels,
+ * ldsim_tracks_current, ...) refuse while a map is set.  Validation failures: LDSIM_EINVAL (tpc outside [0, n_tpc), a
+ * dimension < 2, spacing not finite and > 0, E not finite and > 0, an offset not finite). */
+int ldsim_set_field_map(ldsim_ctx* ctx, int32_t tpc, const int64_t shape[3], const double origin[3], const double spacing[3],
+                        const double* E, const double* dx, const double* dy, const double* dz);
+int ldsim_clear_field_maps(ldsim_ctx* ctx);
+/* test export: the anode view of the resident segments after a mapped quench_drift, out[k * n + i] for k = the nine
+ * position fields in enum order (x_start, y_start, z_start, x_end, y_end, z_end, x, y, z) */
+int ldsim_dev_anode_view_download(ldsim_ctx* ctx, double* out);
+
 typedef struct {
   int64_t n_segments;      /* segments simulated in this call */
   int64_t n_pairs;         /* (segment, pixel) pairs with a valid pixel id */

@@ -75,6 +75,9 @@ def _parser():
                     help="random streams: table (default; the restated numba xoroshiro128p table, advanced in place) or keyed "
                          "(every draw a function of the seed and the identity of what is simulated: the same file at any "
                          "--n_gpus, --chunk_segments or event subset)")
+    ap.add_argument("--field_map", default=None,
+                    help="drift-field maps (.npz, larndsim_amd/field_map.py): per TPC the local field of the recombination and "
+                         "the displacement / drift-time shift of the charge on its way to the anode (default: uniform field)")
     ap.add_argument("--chunk_segments", type=int, default=50000,
                     help="segments per chain launch (whole batches, at least this many; default 50000)")
     return ap
@@ -112,6 +115,7 @@ import numpy.lib.recfunctions as rfn  # noqa: E402
 from larndsim_amd import batching, consts, fee, light_sim, packets, synth  # noqa: E402
 from larndsim_amd import config as cfgmod  # noqa: E402
 from larndsim_amd import dist as ldist  # noqa: E402
+from larndsim_amd import field_map as lfmap  # noqa: E402
 from larndsim_amd import rng as lrng  # noqa: E402
 from larndsim_amd.chain import ChargeChain  # noqa: E402
 
@@ -313,7 +317,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    pixel_thresholds_file=None, pixel_gains_file=None, rand_seed=None, config_root=None,
                    tracks_current_mc=False, chunk_segments=50000, raw_arrays=False, overlap_downloads=None,
                    pixel_layout_id=None, response_id=None, light_lut_id=None, pixel_thresholds_id=None, pixel_gains_id=None,
-                   numba_f32="auto", n_gpus=None, force_dist=False, rng="table", **ignored):
+                   numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -449,6 +453,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     if rng not in ("table", "keyed"):
         raise ValueError(f"--rng must be table or keyed, not {rng!r}")
     print("Random streams:", rng, f"(--rng {rng})")
+    field_maps = lfmap.load(field_map, len(det.TPC_BORDERS)) if field_map is not None else None
+    print("Drift-field map:", f"{field_map} (TPCs {sorted(field_maps)})" if field_maps else "none (uniform field)")
     lib.set_option("numba_f32", f32_mode)
     dist = None
     if world is not None:
@@ -477,6 +483,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                 response = synth.make_response("survey", response_sampling=det.RESPONSE_SAMPLING)
             chain = ChargeChain(response)
             chain.clear_pixel_tables()
+            if field_maps:
+                chain.set_field_map(field_maps)
             if not rng_seeded:
                 # create_xoroshiro128p_states(1024*256, seed) (:396), once; rank r of a sharded run seeds rand_seed + r.
                 # Keyed mode: every rank seeds rand_seed (the streams follow the identity of what is simulated)
@@ -938,6 +946,8 @@ def main(argv=None):
         # before anything touches a GPU; LDSIM_CLI_REHEARSAL_FAIL_RANK=r makes rank r exit non-zero before the rendezvous
         from larndsim_amd import comm as lcomm
         print(f"rehearsal: rank {rank} of {world} started (pid {os.getpid()})", flush=True)
+        if a["field_map"] is not None:
+            print(f"rehearsal: rank {rank} field_map {a['field_map']}", flush=True)
         if os.environ.get("LDSIM_CLI_REHEARSAL_FAIL_RANK") == str(rank):
             raise SystemExit(f"rank {rank}: asked to fail (test of the launcher's error path)")
         got = lcomm.exchange_id(bytes(range(128)) if rank == 0 else b"", rank, world, timeout=120.0)

@@ -36,7 +36,7 @@ int sort_compact_hits(ldsim_ctx*, const int32_t*, const int32_t*, const int32_t*
   } while (0)
 
 static void fill_cur_common(ldsim_ctx* ctx, CurArgs& a) {
-  a.s = ctx->seg;
+  a.s = charge_store(ctx);   // (the anode view after a mapped quench_drift)
   a.c = ctx->d_consts;
   a.resp = ctx->d_resp;
   a.ni = ctx->ni; a.nj = ctx->nj; a.nk = ctx->nk;

@@ -55,6 +55,60 @@ __global__ void __launch_bounds__(256) repack_kernel(unsigned char* __restrict__
 }
 
 // ---- a2 quench (quenching.py:11-44) + a3 drift (drifting.py:11-58) -------------------------------------------
+// quench_drift_kernel's arithmetic, operation for operation, as helpers of quench_drift_map_kernel (that kernel keeps its
+// own text so the path without a map compiles exactly as before).
+// Recombination at field e_field (kV/cm): 0 = n_electrons / n_photons written, 1 = unknown mode, 2 = NaN (nothing written)
+__device__ __forceinline__ int quench_at(SegStore& s, const LdsimConsts* __restrict__ c, int mode, double e_field, int64_t i,
+                                         double& n_e) {
+  double dEdx = s.f[LDSIM_DEDX][i], dE = s.f[LDSIM_DE][i];
+  double recomb = 0;
+  if (mode == 1) {  // BOX
+    double csi = c->box_beta * dEdx / (e_field * c->lar_density);
+    double r = log(c->box_alpha + csi) / csi;
+    recomb = (r > 0) ? r : 0;  // Python max(0, r): NaN -> 0
+  } else if (mode == 2) {  // BIRKS
+    recomb = c->birks_ab / (1 + c->birks_kb * dEdx / (e_field * c->lar_density));
+  } else {
+    return 1;
+  }
+  if (isnan(recomb)) return 2;
+  n_e = narrow_store(recomb * dE / c->w_ion, s.store_code[LDSIM_N_ELECTRONS]);
+  s.f[LDSIM_N_ELECTRONS][i] = n_e;
+  s.f[LDSIM_N_PHOTONS][i] = narrow_store((dE / c->w_ph - n_e) * c->scint_prescale, s.store_code[LDSIM_N_PHOTONS]);
+  return 0;
+}
+
+// the TPC of a midpoint: the first whose borders (2e-2 cm of slack) hold it, else default_plane_index
+__device__ __forceinline__ int32_t tpc_of(const LdsimConsts* __restrict__ c, double x, double y, double z) {
+  for (int ip = 0; ip < c->n_tpc; ip++) {
+    const double(*p)[2] = c->tpc_borders[ip];
+    double zlo = fmin(p[2][1] - 2e-2, p[2][0] - 2e-2), zhi = fmax(p[2][1] + 2e-2, p[2][0] + 2e-2);
+    if (p[0][0] - 2e-2 <= x && x <= p[0][1] + 2e-2 && p[1][0] - 2e-2 <= y && y <= p[1][1] + 2e-2 && zlo <= z && z <= zhi)
+      return ip;
+  }
+  return c->default_plane_index;
+}
+
+// drift of a segment in TPC `plane` whose charge starts at drift coordinates z (midpoint), zs, ze
+__device__ __forceinline__ void drift_at(SegStore& s, const LdsimConsts* __restrict__ c, int32_t plane, int64_t i, double n_e,
+                                         double z, double zs, double ze) {
+  double z_anode = c->tpc_borders[plane][2][0];
+  double t0 = s.f[LDSIM_T0][i];
+  double drift_distance = fabs(z - z_anode);
+  double drift_start = fabs(fmin(zs, ze) - z_anode);
+  double drift_end = fabs(fmax(zs, ze) - z_anode);
+  double drift_time = drift_distance / c->v_drift;
+  double lifetime_red = exp(-drift_time / c->electron_lifetime);
+  s.f[LDSIM_N_ELECTRONS][i] = narrow_store(n_e * lifetime_red, s.store_code[LDSIM_N_ELECTRONS]);
+  s.f[LDSIM_LONG_DIFF][i] = narrow_store(sqrt(drift_time * 2 * c->long_diff), s.store_code[LDSIM_LONG_DIFF]);
+  s.f[LDSIM_TRAN_DIFF][i] = narrow_store(sqrt(drift_time * 2 * c->tran_diff), s.store_code[LDSIM_TRAN_DIFF]);
+  s.f[LDSIM_T][i] = narrow_store(s.f[LDSIM_T][i] + (drift_time + t0), s.store_code[LDSIM_T]);
+  s.f[LDSIM_T_START][i] = narrow_store(s.f[LDSIM_T_START][i] + (fmin(drift_start, drift_end) / c->v_drift + t0),
+                                       s.store_code[LDSIM_T_START]);
+  s.f[LDSIM_T_END][i] = narrow_store(s.f[LDSIM_T_END][i] + (fmax(drift_start, drift_end) / c->v_drift + t0),
+                                     s.store_code[LDSIM_T_END]);
+}
+
 // do_quench / do_drift select the stage(s); the chain runs both in one pass over the columns.
 __global__ void __launch_bounds__(256) quench_drift_kernel(SegStore s, const LdsimConsts* __restrict__ c, int mode,
                                                            int do_quench, int do_drift, int* __restrict__ err) {
@@ -114,6 +168,86 @@ __global__ void __launch_bounds__(256) quench_drift_kernel(SegStore s, const Lds
                                          s.store_code[LDSIM_T_END]);
     }
   }
+}
+
+// ---- drift-field map: quench at the local field, then drift the anode view ------------------------
+// Trilinear interpolation of the map at p, clamped to the edge nodes; a + f * (b - a) per axis (z, then y, then x), so a
+// constant map returns its constant exactly.  with_e = 0 leaves v[0] unset.
+__device__ __forceinline__ void fmap_eval(const FieldMapDesc& m, const double p[3], bool with_e, double v[4]) {
+  int64_t i0[3];
+  double f[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    double u = (p[a] - m.origin[a]) * m.inv_spacing[a];
+    u = fmin(fmax(u, 0.0), (double)(m.n[a] - 1));   // (fmax(NaN, 0) = 0: every index stays inside the grid)
+    const int k = min((int)u, m.n[a] - 2);
+    i0[a] = k;
+    f[a] = u - (double)k;
+  }
+  const int64_t sz = m.n[2], sy = (int64_t)m.n[1] * m.n[2];
+  const FieldMapNode* b = m.node + i0[0] * sy + i0[1] * sz + i0[2];
+  FieldMapNode q[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) q[k] = b[((k >> 2) & 1) * sy + ((k >> 1) & 1) * sz + (k & 1)];
+  auto lerp = [](double a0, double a1, double t) { return a0 + t * (a1 - a0); };
+  auto tri = [&](double FieldMapNode::*ch) {
+    const double c00 = lerp(q[0].*ch, q[1].*ch, f[2]), c01 = lerp(q[2].*ch, q[3].*ch, f[2]);
+    const double c10 = lerp(q[4].*ch, q[5].*ch, f[2]), c11 = lerp(q[6].*ch, q[7].*ch, f[2]);
+    return lerp(lerp(c00, c01, f[1]), lerp(c10, c11, f[1]), f[0]);
+  };
+  if (with_e) v[0] = tri(&FieldMapNode::e);
+  v[1] = tri(&FieldMapNode::dx);
+  v[2] = tri(&FieldMapNode::dy);
+  v[3] = tri(&FieldMapNode::dz);
+}
+
+// One thread per segment.  The TPC comes from the true midpoint; E at the midpoint replaces e_field in the recombination;
+// the start, end and midpoint move by (dx, dy, dz) at themselves, clamped into the TPC's box (never further out than the
+// true point already was) and rounded like the record's field; the drift reads the moved z.  The nine moved positions go
+// to the anode view `view` ([LDSIM_NVIEW][cap]), the true ones stay in the store for the light leg and the output.
+__global__ void __launch_bounds__(256) quench_drift_map_kernel(SegStore s, const LdsimConsts* __restrict__ c, int mode,
+                                                               const FieldMapDesc* __restrict__ maps,
+                                                               double* __restrict__ view, int64_t cap,
+                                                               int* __restrict__ err) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= s.n) return;
+  double pos[LDSIM_NVIEW];   // start (x, y, z), end (x, y, z), midpoint (x, y, z): the order of enum ldsim_field
+#pragma unroll
+  for (int k = 0; k < LDSIM_NVIEW; k++) pos[k] = s.f[k][i];
+  const int32_t plane = tpc_of(c, pos[LDSIM_X], pos[LDSIM_Y], pos[LDSIM_Z]);
+  const bool in_tpc = plane != c->default_plane_index;
+  const FieldMapDesc* m = (in_tpc && maps[plane].node) ? &maps[plane] : nullptr;
+  double e_field = c->e_field;
+  if (m) {
+    double v[4];
+    fmap_eval(*m, &pos[LDSIM_X], m->has_e != 0, v);
+    if (m->has_e) e_field = v[0];
+    double d[LDSIM_NVIEW] = {0, 0, 0, 0, 0, 0, v[1], v[2], v[3]};
+    for (int p = 0; p < 2; p++) {
+      fmap_eval(*m, &pos[3 * p], false, v);
+      d[3 * p] = v[1];
+      d[3 * p + 1] = v[2];
+      d[3 * p + 2] = v[3];
+    }
+    const double(*b)[2] = c->tpc_borders[plane];
+#pragma unroll
+    for (int k = 0; k < LDSIM_NVIEW; k++) {
+      const int a = k % 3;
+      const double lo = fmin(fmin(b[a][0], b[a][1]), pos[k]), hi = fmax(fmax(b[a][0], b[a][1]), pos[k]);
+      pos[k] = narrow_store(fmin(fmax(pos[k] + d[k], lo), hi), s.store_code[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < LDSIM_NVIEW; k++) view[k * cap + i] = pos[k];
+  double n_e = s.f[LDSIM_N_ELECTRONS][i];
+  const int q = quench_at(s, c, mode, e_field, i, n_e);
+  if (q == 1) {
+    *err = 1;
+    return;
+  }
+  if (q == 2) *err = 2;
+  s.pixel_plane[i] = plane;
+  if (in_tpc) drift_at(s, c, plane, i, n_e, pos[LDSIM_Z], pos[LDSIM_Z_START], pos[LDSIM_Z_END]);
 }
 
 // ---- pixel walk (pixels_from_track.py:43-65, 111-199) ----------------------------------------------------------
@@ -290,10 +424,18 @@ int seg_launch_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, int* d
   HIPCHK(hipGetLastError());
   return 0;
 }
+int seg_launch_quench_drift_map(ldsim_ctx* ctx, int mode, int* d_err) {
+  if (ctx->seg.n == 0) return 0;
+  hipLaunchKernelGGL(quench_drift_map_kernel, dim3(nblk(ctx->seg.n, 256)), dim3(256), 0, ctx->stream, ctx->seg,
+                     ctx->d_consts, mode, (const FieldMapDesc*)ctx->d_fmap, (double*)ctx->fmap_view.p, ctx->fmap_view_cap,
+                     d_err);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 int seg_launch_max_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int32_t* d_nmax, unsigned long long* d_tranbits) {
   if (e <= b) return 0;
-  hipLaunchKernelGGL(max_pixels_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, ctx->seg, ctx->d_consts, b,
-                     e, d_nmax, d_tranbits);
+  hipLaunchKernelGGL(max_pixels_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, charge_store(ctx), ctx->d_consts,
+                     b, e, d_nmax, d_tranbits);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -301,14 +443,14 @@ int seg_launch_get_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int radius, int3
                           int32_t* neigh, int32_t* nrad, int P, double* n_list, const int32_t* radius_b,
                           int32_t batch0) {
   if (e <= b) return 0;
-  hipLaunchKernelGGL(get_pixels_kernel, dim3(nblk(e - b, 128)), dim3(128), 0, ctx->stream, ctx->seg, ctx->d_consts, b,
-                     e, radius, active, max_active, neigh, nrad, P, n_list, radius_b, batch0);
+  hipLaunchKernelGGL(get_pixels_kernel, dim3(nblk(e - b, 128)), dim3(128), 0, ctx->stream, charge_store(ctx), ctx->d_consts,
+                     b, e, radius, active, max_active, neigh, nrad, P, n_list, radius_b, batch0);
   HIPCHK(hipGetLastError());
   return 0;
 }
 int seg_launch_time_intervals(ldsim_ctx* ctx, int64_t b, int64_t e, double* starts, int32_t* tmax) {
   if (e <= b) return 0;
-  hipLaunchKernelGGL(time_intervals_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, ctx->seg,
+  hipLaunchKernelGGL(time_intervals_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, charge_store(ctx),
                      ctx->d_consts, b, e, starts, tmax);
   HIPCHK(hipGetLastError());
   return 0;

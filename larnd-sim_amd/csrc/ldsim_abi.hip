@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -17,6 +18,7 @@ struct FeeArgs;
 int seg_launch_unpack(ldsim_ctx*, const LdsimTrackLayout*, int64_t);
 int seg_launch_repack(ldsim_ctx*, const LdsimTrackLayout*, int64_t);
 int seg_launch_quench_drift(ldsim_ctx*, int, int, int, int*);
+int seg_launch_quench_drift_map(ldsim_ctx*, int, int*);
 int seg_launch_max_pixels(ldsim_ctx*, int64_t, int64_t, int32_t*, unsigned long long*);
 int seg_launch_get_pixels(ldsim_ctx*, int64_t, int64_t, int, int32_t*, int, int32_t*, int32_t*, int, double*, const int32_t*,
                           int32_t);
@@ -276,6 +278,10 @@ extern "C" int ldsim_ctx_destroy(ldsim_ctx* ctx) {
   (void)ldsim_comm_destroy(ctx);
   if (ctx->d_rng.p) (void)hipFree(ctx->d_rng.p);
   if (ctx->d_batch_keys.p) (void)hipFree(ctx->d_batch_keys.p);
+  for (DevBuf& b : ctx->fmap_nodes)
+    if (b.p) (void)hipFree(b.p);
+  if (ctx->fmap_view.p) (void)hipFree(ctx->fmap_view.p);
+  if (ctx->d_fmap) (void)hipFree(ctx->d_fmap);
   for (DevBuf* b : {&ctx->comm_tmp, &ctx->hits_acc, &ctx->hits_all, &ctx->gv_send, &ctx->gv_all})
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < 5; k++)
@@ -526,10 +532,16 @@ static int upload_tracks(ldsim_ctx* ctx, const void* tracks, int64_t n, const Ld
                          const int32_t* batch_id, bool batch_id_is_resident = false) {
   NEED(ctx && lay && n >= 0 && (tracks || n == 0), "bad tracks argument");
   NEED(lay->itemsize > 0, "bad layout");
+  if (!batch_id_is_resident && ctx->n_fmap > 0) {
+    ldsim_set_error("a drift-field map is set: the host-array stage calls keep the reference's uniform field; "
+                    "ldsim_clear_field_maps first, or run the resident chain");
+    return LDSIM_ESTATE;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
   CK(seg_reserve(ctx, n));
   ctx->seg.n = n;
+  ctx->drift_map_gen = -1;
   ctx->seg_owner = batch_id_is_resident ? 1 : 2;
   ctx->light_n = -1;
   ctx->seg_layout = *lay;
@@ -611,14 +623,25 @@ extern "C" int ldsim_segments_reset(ldsim_ctx* ctx) {
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
   ctx->light_n = -1;
+  ctx->drift_map_gen = -1;
   return seg_launch_unpack(ctx, &ctx->seg_layout, ctx->seg.n);
 }
 
-static int run_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d) {
+// map = true (the resident chain while a drift-field map is set): quench_drift_map_kernel, which also writes the anode view
+static int run_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, bool map = false) {
   CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
   int* d_err = (int*)ctx->scratch[SB_MISC].p;
   HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
-  CK(seg_launch_quench_drift(ctx, mode, do_q, do_d, d_err));
+  ctx->drift_map_gen = -1;
+  if (map) {
+    if (ctx->fmap_view_cap < ctx->seg.cap) {
+      CK(ldsim_ensure_buf(ctx, &ctx->fmap_view, (size_t)ctx->seg.cap * LDSIM_NVIEW * sizeof(double)));
+      ctx->fmap_view_cap = ctx->seg.cap;
+    }
+    CK(seg_launch_quench_drift_map(ctx, mode, d_err));
+  } else {
+    CK(seg_launch_quench_drift(ctx, mode, do_q, do_d, d_err));
+  }
   int h_err = 0;
   HIPCHK(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -630,6 +653,7 @@ static int run_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d) {
     ldsim_set_error("Invalid recombination value");
     return LDSIM_EINVAL;
   }
+  if (map) ctx->drift_map_gen = ctx->fmap_gen;
   return 0;
 }
 
@@ -638,7 +662,119 @@ extern "C" int ldsim_dev_quench_drift(ldsim_ctx* ctx, int32_t mode) {
   NEED(ctx, "null ctx");
   NEED_RESIDENT(ctx);
   CK(light_join(ctx));
-  return run_quench_drift(ctx, mode, 1, 1);
+  return run_quench_drift(ctx, mode, 1, 1, ctx->n_fmap > 0);
+}
+
+// ---- drift-field maps ----------------------------------------------------------------------------------------------------
+static int fmap_upload_desc(ldsim_ctx* ctx) {
+  if (!ctx->d_fmap) HIPCHK(hipMalloc((void**)&ctx->d_fmap, sizeof(ctx->h_fmap)));
+  HIPCHK(hipMemcpyAsync(ctx->d_fmap, ctx->h_fmap, sizeof(ctx->h_fmap), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+static int fmap_check(const double* a, int64_t n, bool positive, const char* name, int tpc) {
+  if (!a) return 0;
+  for (int64_t i = 0; i < n; i++)
+    if (!std::isfinite(a[i]) || (positive && !(a[i] > 0))) {
+      ldsim_set_error("field map of TPC %d: %s[%lld] = %g is not %s", tpc, name, (long long)i, a[i],
+                      positive ? "finite and > 0" : "finite");
+      return LDSIM_EINVAL;
+    }
+  return 0;
+}
+
+extern "C" int ldsim_set_field_map(ldsim_ctx* ctx, int32_t tpc, const int64_t shape[3], const double origin[3],
+                                   const double spacing[3], const double* E, const double* dx, const double* dy,
+                                   const double* dz) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && shape && origin && spacing, "null argument");
+  if (tpc < 0 || tpc >= ctx->h_consts.n_tpc) {
+    ldsim_set_error("field map: TPC %d outside [0, %d)", tpc, ctx->h_consts.n_tpc);
+    return LDSIM_EINVAL;
+  }
+  int64_t nn = 1;
+  for (int a = 0; a < 3; a++) {
+    if (shape[a] < 2 || shape[a] > (1 << 20)) {
+      ldsim_set_error("field map of TPC %d: dimension %d has %lld nodes (2 .. 2^20)", tpc, a, (long long)shape[a]);
+      return LDSIM_EINVAL;
+    }
+    if (!std::isfinite(origin[a]) || !std::isfinite(spacing[a]) || !(spacing[a] > 0)) {
+      ldsim_set_error("field map of TPC %d: origin %g / spacing %g of axis %d must be finite, the spacing > 0", tpc, origin[a],
+                      spacing[a], a);
+      return LDSIM_EINVAL;
+    }
+    nn *= shape[a];
+    NEED(nn <= (int64_t)1 << 26, "field map larger than 2^26 nodes");
+  }
+  CK(fmap_check(E, nn, true, "E", tpc));
+  CK(fmap_check(dx, nn, false, "dx", tpc));
+  CK(fmap_check(dy, nn, false, "dy", tpc));
+  CK(fmap_check(dz, nn, false, "dz", tpc));
+  std::vector<FieldMapNode> node;
+  try {
+    node.resize((size_t)nn);
+  } catch (const std::exception&) {
+    ldsim_set_error("out of host memory for a field map of %lld nodes", (long long)nn);
+    return LDSIM_EINVAL;
+  }
+  for (int64_t i = 0; i < nn; i++)
+    node[(size_t)i] = FieldMapNode{E ? E[i] : 0.0, dx ? dx[i] : 0.0, dy ? dy[i] : 0.0, dz ? dz[i] : 0.0};
+  HIPCHK(hipSetDevice(ctx->device));
+  CK(light_join(ctx));
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // (a launch in flight may still read the old nodes)
+  DevBuf& b = ctx->fmap_nodes[tpc];
+  CK(ldsim_ensure_buf(ctx, &b, (size_t)nn * sizeof(FieldMapNode)));
+  HIPCHK(hipMemcpy(b.p, node.data(), (size_t)nn * sizeof(FieldMapNode), hipMemcpyHostToDevice));
+  FieldMapDesc& d = ctx->h_fmap[tpc];
+  if (!d.node) ctx->n_fmap++;
+  d.node = (const FieldMapNode*)b.p;
+  for (int a = 0; a < 3; a++) {
+    d.n[a] = (int32_t)shape[a];
+    d.origin[a] = origin[a];
+    d.inv_spacing[a] = 1.0 / spacing[a];
+  }
+  d.has_e = E != nullptr;
+  ctx->fmap_gen++;
+  return fmap_upload_desc(ctx);
+}
+
+extern "C" int ldsim_clear_field_maps(ldsim_ctx* ctx) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  ctx->fmap_gen++;
+  if (ctx->n_fmap == 0 && !ctx->fmap_view.p) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  CK(light_join(ctx));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (int t = 0; t < LDSIM_MAX_TPC; t++) {
+    ctx->h_fmap[t] = FieldMapDesc{};
+    if (ctx->fmap_nodes[t].p) HIPCHK(hipFree(ctx->fmap_nodes[t].p));
+    ctx->fmap_nodes[t] = DevBuf{};
+  }
+  ctx->n_fmap = 0;
+  if (ctx->fmap_view.p) HIPCHK(hipFree(ctx->fmap_view.p));
+  ctx->fmap_view = DevBuf{};
+  ctx->fmap_view_cap = 0;
+  if (ctx->drift_map_gen >= 0) ctx->drift_map_gen = -2;     // the store's drift came from a map that is gone
+  return fmap_upload_desc(ctx);
+}
+
+extern "C" int ldsim_dev_anode_view_download(ldsim_ctx* ctx, double* out) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && (out || ctx->seg.n == 0), "null argument");
+  NEED_RESIDENT(ctx);
+  if (ctx->drift_map_gen < 0 || ctx->drift_map_gen != ctx->fmap_gen) {
+    ldsim_set_error("no anode view of the resident segments: ldsim_dev_quench_drift with a field map set first");
+    return LDSIM_ESTATE;
+  }
+  const int64_t n = ctx->seg.n;
+  HIPCHK(hipSetDevice(ctx->device));
+  for (int k = 0; k < LDSIM_NVIEW && n; k++)
+    HIPCHK(hipMemcpyAsync(out + k * n, (double*)ctx->fmap_view.p + k * ctx->fmap_view_cap, n * sizeof(double),
+                          hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 // ---- (1) stage-by-stage host-buffer API ---------------------------------------------------------------------------
@@ -1450,6 +1586,14 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
   NEED(ctx->d_resp, "no response table set (ldsim_set_response)");
   NEED_RESIDENT(ctx);
   NEED(seg_begin >= 0 && seg_end >= seg_begin && seg_end <= ctx->seg.n, "segment range outside the resident store");
+  if (ctx->drift_map_gen != -1 || ctx->n_fmap > 0) {
+    // with drift-field maps the chain reads the anode view of the last quench_drift: it must have been made by the maps set now
+    if (ctx->drift_map_gen != ctx->fmap_gen) {
+      ldsim_set_error("the drift-field maps changed since the last ldsim_dev_quench_drift: upload (or reset) and quench_drift "
+                      "again");
+      return LDSIM_ESTATE;
+    }
+  }
   HIPCHK(hipSetDevice(ctx->device));
   int rc;
   try {

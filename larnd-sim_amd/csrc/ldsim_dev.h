@@ -26,6 +26,20 @@ struct SegStore {
   int64_t cap;
 };
 
+// ---- drift-field map of one TPC (ldsim_set_field_map) ----------------------------------------------------
+// A regular grid in the simulation frame; every node holds (E, dx, dy, dz) so that one corner is one 32-byte read.
+struct alignas(32) FieldMapNode {
+  double e, dx, dy, dz;
+};
+struct FieldMapDesc {
+  const FieldMapNode* node;      // [n[0]][n[1]][n[2]]; nullptr: this TPC has no map
+  int32_t n[3];
+  int32_t has_e;                 // 0: the map carries no E channel (E = the constants' e_field, whatever module is loaded)
+  double origin[3], inv_spacing[3];
+};
+// The anode view: the nine positions (LDSIM_X_START .. LDSIM_Z) where the drifted charge arrives, one column each
+#define LDSIM_NVIEW 9
+
 // ---- Python / Numba scalar semantics on device -----------------------------------------------------
 __device__ __forceinline__ double py_round(double x) { return rint(x); }  // half-to-even (v_rndne_f64)
 
@@ -231,6 +245,15 @@ struct ldsim_ctx {
   DevBuf d_batch_keys;
   int64_t rng_batch_keys_n = 0;
   int debug_rng_materialize = 0;     // option: keyed FEE normals written to the noise table and read by the table scan (tests)
+  // drift-field maps (ldsim_set_field_map), keyed by the global TPC index: they outlive ldsim_set_consts
+  FieldMapDesc h_fmap[LDSIM_MAX_TPC] = {};
+  DevBuf fmap_nodes[LDSIM_MAX_TPC];
+  FieldMapDesc* d_fmap = nullptr;        // device copy of h_fmap
+  int n_fmap = 0;                        // TPCs with a map
+  int64_t fmap_gen = 0;                  // advances on every set / clear
+  int64_t drift_map_gen = -1;            // fmap_gen of the mapped quench_drift whose results the store holds (-1: none)
+  DevBuf fmap_view;                      // [LDSIM_NVIEW][fmap_view_cap] anode-view columns (allocated while a map is set)
+  int64_t fmap_view_cap = 0;
   // multi-GPU exchange (comm.hip): RCCL communicator, rows accumulated over the chain calls of a pass, gathered rows
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 0;
@@ -264,6 +287,13 @@ enum {
 };
 
 void ldsim_set_error(const char* fmt, ...);
+// the segment store the charge kernels read: after a mapped quench_drift its nine position columns are the anode view
+static inline SegStore charge_store(const ldsim_ctx* ctx) {
+  SegStore s = ctx->seg;
+  if (ctx->drift_map_gen >= 0)
+    for (int k = 0; k < LDSIM_NVIEW; k++) s.f[k] = (double*)ctx->fmap_view.p + (size_t)k * ctx->fmap_view_cap;
+  return s;
+}
 int ldsim_ensure(ldsim_ctx* ctx, int slot, size_t bytes);
 int ldsim_ensure_buf(ldsim_ctx* ctx, DevBuf* b, size_t bytes);
 // refusal of a host-array stage call that draws random numbers while the ctx is in keyed mode (its rows have no identity)

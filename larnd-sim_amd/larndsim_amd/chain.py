@@ -22,6 +22,35 @@ class ChargeChain:
         self.n = 0
         if response is not None:
             lib.set_response(response, self.ctx)
+        self.clear_field_map()          # the ctx is process-wide: a fresh chain starts with the uniform field
+
+    def set_field_map(self, maps):
+        """Drift-field maps (``field_map``: {tpc: {"origin", "spacing", "E" / "dx" / "dy" / "dz"}}, or the path of an .npz),
+        replacing any set before.  Takes effect at the next ``quench_drift``; the charge chain then reads the anode view,
+        the light leg and ``download_segments`` the true positions."""
+        from . import field_map
+        n_tpc = len(consts.detector.TPC_BORDERS)
+        maps = field_map.load(maps, n_tpc) if isinstance(maps, (str, bytes)) or hasattr(maps, "__fspath__") \
+            else field_map.validate(maps, n_tpc)
+        L = lib.load()
+        lib.check(L.ldsim_clear_field_maps(self.ctx))
+        for tpc, m in sorted(maps.items()):
+            shape = np.array(next(m[ch] for ch in field_map.CHANNELS if ch in m).shape, dtype=np.int64)
+            lib.check(L.ldsim_set_field_map(self.ctx, C.c_int32(tpc), lib.ptr(shape), lib.ptr(m["origin"]),
+                                            lib.ptr(m["spacing"]), *(lib.ptr(m.get(ch)) for ch in field_map.CHANNELS)))
+        self.field_maps = maps
+
+    def clear_field_map(self):
+        """back to the uniform field (upload or reset, then quench_drift, before the next run)"""
+        lib.check(lib.load().ldsim_clear_field_maps(self.ctx))
+        self.field_maps = {}
+
+    def download_anode_view(self):
+        """[9][n] f64: the positions the charge stages read after a mapped ``quench_drift`` (x_start, y_start, z_start,
+        x_end, y_end, z_end, x, y, z)"""
+        out = np.empty((9, self.n), dtype=np.float64)
+        lib.check(lib.load().ldsim_dev_anode_view_download(self.ctx, lib.ptr(out)))
+        return out
 
     def seed_rng(self, seed, n_states=1024 * 256):
         """``create_xoroshiro128p_states(1024*256, seed=rand_seed)`` of the driver (cli/simulate_pixels.py:396): needed before
