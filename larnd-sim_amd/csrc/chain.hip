@@ -405,6 +405,7 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   F.U = U;
   F.upix = d_upix; F.ubatch = d_ubatch; F.uoff = d_uoff;
   F.pair_val = d_vals2; F.pair_key = d_keys2;
+  F.n_pairs = n_valid;
   F.P = P;
   F.track_starts = d_starts;
   F.waves = d_waves;

@@ -206,13 +206,76 @@ __device__ int adc_scan(const K* c, const double* S, int NT, double t_stop, doub
 }
 
 // ---- chain kernel ----------------------------------------------------------------------------------------------------
+// Timing switches (tools/adc_phases.py): read only by a library built with make DEBUG_FEE=1; loop-invariant tests otherwise gone
+#ifdef LDSIM_FEE_DEBUG
+#define FEEDBG(bit) ((F.debug & (bit)) != 0)
+#else
+#define FEEDBG(bit) false
+#endif
+
+// Launch constants of the kernel: wtap[d] = exp(-d dt/rt) (1 - exp(-dt/rt)), the buffer's taps (fee.py:569), and
+// G[n] = dt * sum_{d=0..n} w(d), the weight of a tick n ticks before the end of a hit span, in this summation order.  One wave,
+// once per (time_sampling, buffer_risetime): tab = wtap[64] | G[64].  (Every pixel used to compute both: two f64 exp per thread and
+// a serial prefix on one lane between barriers.)  The device's exp and the prefix order decide the scan's taps and the fractions,
+// so the tables are built here with the expressions the pixel kernel had, not on the host.
+__global__ void __launch_bounds__(64) fee_tables_kernel(double dt, double rt, double* __restrict__ tab) {
+  __shared__ double wtap[64];
+  const int tid = threadIdx.x;
+  const int ntap = rt > 0 ? (int)ceil(10 * rt / dt) : 0;  // floor(ic - 10*rt/dt) == ic - ceil(10*rt/dt)
+  wtap[tid] = 0;
+  if (tid <= ntap && rt > 0) wtap[tid] = exp((-tid) * dt / rt) * (1 - exp(-dt / rt));
+  __syncthreads();
+  tab[tid] = wtap[tid];
+  tab[64 + tid] = 0;
+  __syncthreads();
+  if (tid == 0) {
+    double acc = 0;
+    for (int d = 0; d <= ntap; d++) {
+      acc += (rt > 0 ? wtap[d] : 1.0) * dt;
+      tab[64 + d] = acc;
+    }
+  }
+}
+
+// What the set-up pass (fee_setup_kernel) leaves per pixel: a header, and one row per slot in a pool indexed like the sorted pair
+// list (slot k of the pixel whose pairs start at p0: row p0 + k), so the record is sized by the slots that exist, not by M.
+struct __attribute__((aligned(32))) FeeHdr {
+  int32_t u;            // the unique pixel
+  int32_t n_slots;      // valid pairs, at most M
+  int32_t overflow;     // the pixel has pairs beyond its slots
+  int32_t t_lo, t_hi;   // the ticks the slots' windows cover (t_lo = NT, t_hi = 0: none)
+  int32_t s_lo;         // first tick held in LDS by the one-wave form
+  int32_t bfirst;       // first relative segment index of the pixel's batch
+  int32_t ubatch;
+  int64_t p0;           // first pair
+  int64_t pad;
+};
+struct __attribute__((aligned(16))) FeeSlot {
+  int32_t start;        // tick of the row's element 0 on the pixel's time axis (detsim.py:506)
+  int32_t w0, w1;       // the ticks of the row tracks_current wrote
+  int32_t track;        // segment index in the batch (track_pixel_map)
+};
+
+template <int THREADS>
+__device__ __forceinline__ void fee_sync() {
+  // a workgroup of one wave: LDS traffic is in order, nothing to wait for but the compiler's own reordering
+  if (THREADS == 64) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    __syncthreads();
+  }
+}
+
 // Two instantiations.  THREADS = 256, the whole tick axis in LDS (16-26 KB: eight pixels per CU), for every pixel when noise is on
 // (the scan then walks every tick) and for pixels whose slots' windows span more than FEE_SPAN ticks.  THREADS = 64 -- a wave per
-// pixel, FEE_SPAN ticks of LDS starting at the pixel's first written tick -- for the others, over a list (fee_span_kernel): the
-// kernel is a chain of dependent trips to memory per pixel (pair range -> keys -> slots' starts and windows -> rows), so what
-// counts is pixels in flight, and a CU holds 2048 threads: 8 pixels of 256 threads, 19 of 64 at 8.4 KB each.
+// pixel, FEE_SPAN ticks of LDS starting at the pixel's first written tick -- for the others, over a list (fee_setup_kernel).  The
+// kernel is a chain of dependent trips to memory per pixel, so what counts is pixels in flight -- a CU holds 2048 threads: 8
+// pixels of 256 threads, 19 of 64 at 8.4 KB each -- and the length of the chain: header (scalar loads; the list form fetches the
+// next pixel's while this one is worked on) -> slot rows and launch constants, one trip -> waveform rows.  Counting the keys,
+// the slots' starts and windows, the tick range and the batch are the set-up pass's work, done once per pixel there.
 template <int THREADS, bool KEYED = false>
-__device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const int64_t u, const int32_t* __restrict__ span /* [U][2] or NULL */,
+__device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const FeeHdr& H, const FeeSlot* __restrict__ slots, const bool windowed,
                                                const int s_cap) {
   const FeeK* c = &F.k;          // (kernel arguments: scalar registers, no loads)
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -223,97 +286,60 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const int64_t u
   extern __shared__ double S[];          // [n_time_ticks]: sized at launch, so LDS (not VGPRs) stops at 8 pixels per CU
   __shared__ HitRec hits[A_MAX];
   __shared__ int s_start[M_MAX], s_w0[M_MAX], s_w1[M_MAX];
-  __shared__ int64_t s_row[M_MAX];
   __shared__ double wtap[64], G[64];
-  __shared__ int s_nh, s_trange[2];
+  __shared__ int s_nh;
 
-  const int64_t p0 = F.uoff[u], p1 = F.uoff[u + 1];
-  // slots: pairs whose ring code is valid (key low nibble != 15), at most M (detsim.py:582-607).  Keys are sorted, the
-  // invalid-distance pairs (nibble 15) sit at the end of the group: their count by one pass of parallel loads (a bisection
-  // was four dependent round trips to memory per pixel)
-  __shared__ int s_nvalid;
-  if (tid == 0) s_nvalid = 0;
-  __syncthreads();
-  {
-    int cnt = 0;
-    for (int64_t p = p0 + tid; p < p1; p += THREADS) cnt += (F.pair_key[p] & 15ull) != 15ull;
-    if (cnt) atomicAdd(&s_nvalid, cnt);
-  }
-  __syncthreads();
-  const int n_valid = s_nvalid;
-  const int n_slots = n_valid < M ? n_valid : M;
-  const bool overflow = (p1 - p0) > n_slots;
-  const int ubatch = F.ubatch[u];
-  const int bfirst = F.batch_first[ubatch - F.batch0];
+  const int64_t u = H.u, p0 = H.p0;
+  const int n_slots = H.n_slots;
+  const int ntap = rt > 0 ? (int)ceil(10 * rt / dt) : 0;  // floor(ic - 10*rt/dt) == ic - ceil(10*rt/dt)
+  // slots: pairs whose ring code is valid, at most M (detsim.py:582-607), in the order of the sorted pair list
   if (tid < n_slots) {
-    int32_t v = F.pair_val[p0 + tid];
-    int r = v / F.P;
-    s_start[tid] = (int)py_round(F.track_starts[r] / dt);   // detsim.py:506
-    s_row[tid] = p0 + tid;
-    s_w0[tid] = F.win ? F.win[2 * (p0 + tid)] : 0;         // the ticks of the row tracks_current wrote
-    s_w1[tid] = F.win ? F.win[2 * (p0 + tid) + 1] : F.T;
-    F.tpm[u * M + tid] = r - bfirst;
+    const FeeSlot sl = slots[p0 + tid];
+    s_start[tid] = sl.start;
+    s_w0[tid] = sl.w0;
+    s_w1[tid] = sl.w1;
+    F.tpm[u * M + tid] = sl.track;
   } else if (tid < M) {
     F.tpm[u * M + tid] = -1;
   }
-  const int ntap = rt > 0 ? (int)ceil(10 * rt / dt) : 0;  // floor(ic - 10*rt/dt) == ic - ceil(10*rt/dt)
-  if (tid <= ntap && rt > 0) {
-    // w(d) = exp(-d*dt/rt) * (1 - exp(-dt/rt))   (fee.py:569)
-    wtap[tid] = exp((-tid) * dt / rt) * (1 - exp(-dt / rt));
-  }
-  __syncthreads();
-  if (tid == 0) {
-    // G[n] = dt * sum_{d=0..n} w(d): weight of a tick n ticks before the end of a hit span
-    double acc = 0;
-    for (int d = 0; d <= ntap; d++) {
-      acc += (rt > 0 ? wtap[d] : 1.0) * dt;
-      G[d] = acc;
-    }
+  if (tid <= ntap) {
+    wtap[tid] = F.tab[tid];
+    G[tid] = F.tab[64 + tid];
   }
   // ---- summed waveform: each thread owns ticks tid, tid+256, ... and adds the slots' rows in slot order, each over the ticks
   // its window puts on the pixel's time axis (detsim.py:516-520) ------------------------------------------------------------
   // the ticks S holds: all of them, or the pixel's window from the set-up pass (every slot's ticks lie inside it)
-  const int s_lo = span ? span[2 * u] : 0;
-  const int s_hi = span ? min(s_lo + s_cap, NT) : NT;
+  const int s_lo = windowed ? H.s_lo : 0;
+  const int s_hi = windowed ? min(s_lo + s_cap, NT) : NT;
   for (int t = tid; t < s_hi - s_lo; t += THREADS) S[t] = 0;
-  if (tid == 0) {          // the ticks the slots' windows cover
-    int t_lo = NT, t_hi = 0;
-    for (int k = 0; k < n_slots; k++) {
-      const int lo = max(s_start[k] + s_w0[k], 0), hi = min(s_start[k] + s_w1[k], NT);
-      if (hi > lo) { t_lo = min(t_lo, lo); t_hi = max(t_hi, hi); }
-    }
-    s_trange[0] = t_lo;
-    s_trange[1] = t_hi;
-  }
-  for (int k = 0; k < n_slots && !(F.debug & 0x10000); k++) {
+  fee_sync<THREADS>();
+  for (int k = 0; k < n_slots && !FEEDBG(0x10000); k++) {
     const int st = s_start[k];
     const int lo = max(st + s_w0[k], 0), hi = min(st + s_w1[k], NT);
-    const float* wf = F.waves + s_row[k] * (int64_t)F.T - st;
+    const float* wf = F.waves + (p0 + k) * (int64_t)F.T - st;
     for (int t = lo + ((tid - lo) & (THREADS - 1)); t < hi; t += THREADS) S[t - s_lo] += (double)wf[t];
   }
-  __syncthreads();
+  fee_sync<THREADS>();
   // ---- trigger scan on wave 0 ----------------------------------------------------------------------------------------
+  int nh = 0;
   if (wv == 0) {
     const double thr = F.thr_table ? F.thr_table[F.upix[u]] : F.threshold;
     int nd = 0;
-    int nh = 0;
-    if (F.debug & 0x20000) {
+    if (FEEDBG(0x20000)) {
     } else if (KEYED) {
-      const KeyedNoise zs{F.rng_seed, key_mix(F.batch_keys[ubatch], (uint64_t)(int64_t)F.upix[u])};
-      nh = adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap, zs, &nd, s_trange[0],
-                    s_trange[1], s_lo, s_hi);
+      const KeyedNoise zs{F.rng_seed, key_mix(F.batch_keys[H.ubatch], (uint64_t)(int64_t)F.upix[u])};
+      nh = adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap, zs, &nd, H.t_lo, H.t_hi, s_lo, s_hi);
     } else {
       const TableNoise zs{F.noise_z ? F.noise_z + u * (int64_t)F.noise_nd : nullptr};
-      nh = adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap, zs, &nd, s_trange[0],
-                    s_trange[1], s_lo, s_hi);
+      nh = adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap, zs, &nd, H.t_lo, H.t_hi, s_lo, s_hi);
     }
     if (lane == 0) {
-      s_nh = nh;
+      if (THREADS != 64) s_nh = nh;
       if (F.n_draws) F.n_draws[u] = nd;
     }
   }
-  __syncthreads();
-  const int nh = s_nh;
+  fee_sync<THREADS>();
+  if (THREADS != 64) nh = s_nh;
   const double gain = F.gain_table ? F.gain_table[F.upix[u]] : c->gain * (1e-3 * (1e-6 * 1.0)) / 1.0;   // GAIN * mV / e
   for (int h = tid; h < A; h += THREADS) {
     double q = h < nh ? hits[h].q : 0.0;
@@ -323,14 +349,14 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const int64_t u
   }
   if (tid == 0) {
     F.hit_count[u] = nh;
-    if (overflow) stat_add(F.counters, 2, 1ull);
+    if (H.overflow) stat_add(F.counters, 2, 1ull);
     if (nh) stat_add(F.counters, 3, (unsigned long long)nh);
   }
   // ---- backtracking fractions (fee.py:572-573, 633-635): sum_jc sig_k[jc]*G[min(ntap, b-jc)] / true_q ------------
-  if (F.fractions && !(F.debug & 0x40000)) {
+  if (F.fractions && !FEEDBG(0x40000)) {
     double* fr = F.fractions + u * (int64_t)A * M;       // zero on entry (one memset of the whole array by the launcher)
     for (int k = wv; k < n_slots; k += THREADS / 64) {      // (a wave per slot)
-      const float* wf = F.waves + s_row[k] * (int64_t)F.T;
+      const float* wf = F.waves + (p0 + k) * (int64_t)F.T;
       const int st = s_start[k];
       for (int h = 0; h < nh; h++) {
         int lr = hits[h].lr, b = hits[h].b;
@@ -351,21 +377,30 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const int64_t u
   }
 }
 
-// one workgroup per unique pixel.  KEYED: the FEE noise is drawn inline from the row's keyed stream (a separate instance, no
-// runtime branch in the scan)
+// one workgroup per unique pixel, header u of the set-up pass.  KEYED: the FEE noise is drawn inline from the row's keyed stream
+// (a separate instance, no runtime branch in the scan)
 template <int THREADS, bool KEYED = false>
-__global__ void __launch_bounds__(THREADS) pixel_adc_kernel(FeeArgs F) {
-  if ((int64_t)blockIdx.x < F.U) pixel_adc_body<THREADS, KEYED>(F, (int64_t)blockIdx.x, nullptr, 0);
+__global__ void __launch_bounds__(THREADS) pixel_adc_kernel(FeeArgs F, const FeeHdr* __restrict__ hdr, const FeeSlot* __restrict__ slots) {
+  if ((int64_t)blockIdx.x < F.U) pixel_adc_body<THREADS, KEYED>(F, hdr[blockIdx.x], slots, false, 0);
 }
-// a fixed grid walks a device-built list of pixels (its length stays on the device: no host round trip to size the launch)
+// a fixed grid walks a device-built list of pixels' headers (its length stays on the device: no host round trip to size the
+// launch); the next pixel's header is on its way while this one is worked on
 template <int THREADS, bool KEYED = false>
-__global__ void __launch_bounds__(THREADS) pixel_adc_list_kernel(FeeArgs F, const int32_t* __restrict__ list,
+__global__ void __launch_bounds__(THREADS) pixel_adc_list_kernel(FeeArgs F, const FeeHdr* __restrict__ list,
                                                                 const unsigned long long* __restrict__ count,
-                                                                const int32_t* __restrict__ span, int s_cap) {
+                                                                const FeeSlot* __restrict__ slots, bool windowed, int s_cap) {
   const int64_t n = (int64_t)*count;
-  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
-    pixel_adc_body<THREADS, KEYED>(F, (int64_t)list[i], span, s_cap);
-    __syncthreads();          // (the next pixel reuses the workgroup's LDS)
+  int64_t i = blockIdx.x;
+  if (i >= n) return;
+  FeeHdr H = list[i];
+  while (true) {
+    const int64_t nx = i + gridDim.x;
+    const FeeHdr Hn = list[nx < n ? nx : i];
+    pixel_adc_body<THREADS, KEYED>(F, H, slots, windowed, s_cap);
+    if (nx >= n) break;
+    fee_sync<THREADS>();          // (the next pixel reuses the workgroup's LDS)
+    H = Hn;
+    i = nx;
   }
 }
 
@@ -395,33 +430,47 @@ extern "C++" int fee_clear_unwritten_fractions(ldsim_ctx* ctx, int64_t U, const 
   return 0;
 }
 
-// The ticks a pixel's slots write, [t_lo, t_hi), from the same expressions as pixel_adc_kernel; the pixels whose window fits
-// FEE_SPAN ticks go to list 0, the others to list 1 (one atomic per wave and list).
-__global__ void __launch_bounds__(256) fee_span_kernel(FeeArgs F, int32_t* __restrict__ span, int32_t* __restrict__ lists /* [2][U] */,
-                                                       unsigned long long* __restrict__ counts /* [2] */) {
+// The set-up pass, a thread per unique pixel: counts the pixel's slots (valid keys come first in its group), resolves each slot's
+// start tick, window and track index into the slot pool, the batch and the ticks the slots write, [t_lo, t_hi), into the header.
+// With lists: the pixels whose window fits FEE_SPAN ticks go to list 0, the others to list 1 (one atomic per wave and list), each
+// list holding its pixels' headers; without: header u at index u.
+__global__ void __launch_bounds__(256) fee_setup_kernel(FeeArgs F, FeeSlot* __restrict__ slots, FeeHdr* __restrict__ hdr /* [2][U] or [U] */,
+                                                        unsigned long long* __restrict__ counts /* [2] or NULL */) {
   const FeeK* c = &F.k;
   const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
   int cls = -1;
+  FeeHdr H{};
   if (u < F.U) {
     const int NT = c->n_time_ticks, M = c->max_tracks_per_pixel;
     const double dt = c->time_sampling;
     const int64_t p0 = F.uoff[u], p1 = F.uoff[u + 1];
+    const int ubatch = F.ubatch[u];
+    const int bfirst = F.batch_first[ubatch - F.batch0];
     int n_slots = 0;
     for (int64_t p = p0; p < p1 && n_slots < M; p++) n_slots += (F.pair_key[p] & 15ull) != 15ull;      // (valid ones come first)
     int t_lo = NT, t_hi = 0;
     for (int k = 0; k < n_slots; k++) {
       const int r = F.pair_val[p0 + k] / F.P;
-      const int st = (int)py_round(F.track_starts[r] / dt);
+      const int st = (int)py_round(F.track_starts[r] / dt);   // detsim.py:506
       const int w0 = F.win ? F.win[2 * (p0 + k)] : 0, w1 = F.win ? F.win[2 * (p0 + k) + 1] : F.T;
       const int lo = max(st + w0, 0), hi = min(st + w1, NT);
       if (hi > lo) { t_lo = min(t_lo, lo); t_hi = max(t_hi, hi); }
+      slots[p0 + k] = FeeSlot{st, w0, w1, r - bfirst};
     }
-    if (t_hi <= t_lo) { t_lo = 0; t_hi = 0; }
-    span[2 * u] = t_lo;
-    span[2 * u + 1] = t_hi;
-    cls = (t_hi - t_lo <= FEE_SPAN) ? 0 : 1;
+    H.u = (int32_t)u;
+    H.n_slots = n_slots;
+    H.overflow = (p1 - p0) > n_slots;
+    H.t_lo = t_lo;
+    H.t_hi = t_hi;
+    H.s_lo = t_hi <= t_lo ? 0 : t_lo;
+    H.bfirst = bfirst;
+    H.ubatch = ubatch;
+    H.p0 = p0;
+    if (!counts) hdr[u] = H;
+    else cls = (t_hi <= t_lo || t_hi - t_lo <= FEE_SPAN) ? 0 : 1;
   }
+  if (!counts) return;
   for (int cc = 0; cc < 2; cc++) {
     const unsigned long long m = __ballot(cls == cc);
     if (!m) continue;
@@ -429,52 +478,63 @@ __global__ void __launch_bounds__(256) fee_span_kernel(FeeArgs F, int32_t* __res
     if (lane == 0) base = atomicAdd(&counts[cc], (unsigned long long)__popcll(m));
     base = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
            (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-    if (cls == cc) lists[(int64_t)cc * F.U + (int64_t)base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)u;
+    if (cls == cc) hdr[(int64_t)cc * F.U + (int64_t)base + __popcll(m & ((1ull << lane) - 1ull))] = H;
   }
 }
 
-extern "C++" int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F) {
-  if (F.U == 0) return 0;
+extern "C++" int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0) {
+  if (F0.U == 0) return 0;
   const LdsimConsts& h = ctx->h_consts;
   if (h.n_time_ticks > NT_MAX || h.max_adc_values > A_MAX || h.max_tracks_per_pixel > M_MAX ||
       (h.buffer_risetime > 0 && 10 * h.buffer_risetime / h.time_sampling > 62)) {
     ldsim_set_error("FEE constants exceed the kernel's static tiles");
     return LDSIM_EINVAL;
   }
+  // the launch constants: built when the two constants they depend on change, not per launch
+  if (!ctx->d_fee_tab) HIPCHK(hipMalloc((void**)&ctx->d_fee_tab, 128 * sizeof(double)));
+  if (ctx->fee_tab_dt != h.time_sampling || ctx->fee_tab_rt != h.buffer_risetime) {
+    hipLaunchKernelGGL(fee_tables_kernel, dim3(1), dim3(64), 0, ctx->stream, h.time_sampling, h.buffer_risetime, ctx->d_fee_tab);
+    HIPCHK(hipGetLastError());
+    ctx->fee_tab_dt = h.time_sampling;
+    ctx->fee_tab_rt = h.buffer_risetime;
+  }
+  FeeArgs F = F0;
+  F.tab = ctx->d_fee_tab;
   // (the kernel writes the (hit, slot) entries that exist; everything else of `fractions` reads 0 like the reference's array once
   // fee_clear_unwritten_fractions has run: the dense downloads call it -- clearing 12 KB per pixel in every launch cost 0.45 ms per
   // 100 k segments, and the compact download reads the written entries only)
   const size_t full = (size_t)((h.n_time_ticks + 1) & ~1) * 8;
-  if (F.batch_keys) {
-    // keyed noise: every tick is walked (no idle skipping), so the whole tick axis goes in LDS like the noisy table case
-    hipLaunchKernelGGL((pixel_adc_kernel<FEE_THREADS, true>), dim3((unsigned)F.U), dim3(FEE_THREADS), full, ctx->stream, F);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  const bool skip_idle = !F.noise_z && ((F.thr_table != nullptr) || F.threshold > 0);
-  if (!skip_idle || !F.win || ctx->fee_one_class || h.n_time_ticks <= FEE_SPAN) {
-    // (noise: every tick is walked; a threshold table may hold non-positive entries -- the scan decides per pixel, so the table
-    // case keeps the windows only when the constant path would; complete rows: no windows to go by)
-    hipLaunchKernelGGL(pixel_adc_kernel<FEE_THREADS>, dim3((unsigned)F.U), dim3(FEE_THREADS), full, ctx->stream, F);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
+  // noise: every tick is walked (no idle skipping), so the whole tick axis goes in LDS; a threshold table may hold non-positive
+  // entries -- the scan decides per pixel, so the table case keeps the windows only when the constant path would; complete rows: no
+  // windows to go by
+  const bool skip_idle = !F.batch_keys && !F.noise_z && ((F.thr_table != nullptr) || F.threshold > 0);
+  const bool one_class = !skip_idle || !F.win || ctx->fee_one_class || h.n_time_ticks <= FEE_SPAN;
   int rc;
-  if ((rc = ldsim_ensure(ctx, SB_SPAN, (size_t)F.U * 16 + 64))) return rc;      // span [U][2] | lists [2][U] | counts [2]
-  int32_t* d_span = (int32_t*)ctx->scratch[SB_SPAN].p;
-  int32_t* d_lists = d_span + 2 * F.U;
-  unsigned long long* d_counts = (unsigned long long*)((char*)ctx->scratch[SB_SPAN].p + (((size_t)F.U * 16 + 15) & ~(size_t)15));
-  HIPCHK(hipMemsetAsync(d_counts, 0, 16, ctx->stream));
-  hipLaunchKernelGGL(fee_span_kernel, dim3((unsigned)((F.U + 255) / 256)), dim3(256), 0, ctx->stream, F, d_span, d_lists, d_counts);
+  const size_t hdr_bytes = (size_t)F.U * sizeof(FeeHdr) * (one_class ? 1 : 2);      // headers [U] or lists [2][U] | counts [2]
+  if ((rc = ldsim_ensure(ctx, SB_SPAN, hdr_bytes + 64))) return rc;
+  if ((rc = ldsim_ensure(ctx, SB_FEESLOT, (size_t)F.n_pairs * sizeof(FeeSlot) + 16))) return rc;
+  FeeHdr* d_hdr = (FeeHdr*)ctx->scratch[SB_SPAN].p;
+  FeeSlot* d_slots = (FeeSlot*)ctx->scratch[SB_FEESLOT].p;
+  unsigned long long* d_counts = one_class ? nullptr : (unsigned long long*)((char*)ctx->scratch[SB_SPAN].p + hdr_bytes);
+  if (d_counts) HIPCHK(hipMemsetAsync(d_counts, 0, 16, ctx->stream));
+  hipLaunchKernelGGL(fee_setup_kernel, dim3((unsigned)((F.U + 255) / 256)), dim3(256), 0, ctx->stream, F, d_slots, d_hdr, d_counts);
   HIPCHK(hipGetLastError());
+  if (one_class) {
+    if (F.batch_keys)
+      hipLaunchKernelGGL((pixel_adc_kernel<FEE_THREADS, true>), dim3((unsigned)F.U), dim3(FEE_THREADS), full, ctx->stream, F, d_hdr, d_slots);
+    else
+      hipLaunchKernelGGL(pixel_adc_kernel<FEE_THREADS>, dim3((unsigned)F.U), dim3(FEE_THREADS), full, ctx->stream, F, d_hdr, d_slots);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   // both launches over the whole grid: a workgroup past its list's count leaves at once (the counts stay on the device: no
   // host round trip); the one-wave launch first
   const unsigned g_small = (unsigned)std::min<int64_t>(F.U, 256 * 24), g_big = (unsigned)std::min<int64_t>(F.U, 256 * 8);
-  hipLaunchKernelGGL(pixel_adc_list_kernel<64>, dim3(g_small), dim3(64), (size_t)FEE_SPAN * 8, ctx->stream, F, d_lists,
-                     d_counts, d_span, FEE_SPAN);
+  hipLaunchKernelGGL(pixel_adc_list_kernel<64>, dim3(g_small), dim3(64), (size_t)FEE_SPAN * 8, ctx->stream, F, d_hdr,
+                     d_counts, d_slots, true, FEE_SPAN);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(pixel_adc_list_kernel<FEE_THREADS>, dim3(g_big), dim3(FEE_THREADS), full, ctx->stream, F,
-                     d_lists + F.U, d_counts + 1, (const int32_t*)nullptr, 0);
+                     d_hdr + F.U, d_counts + 1, d_slots, false, 0);
   HIPCHK(hipGetLastError());
   return 0;
 }

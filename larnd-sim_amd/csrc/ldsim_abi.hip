@@ -241,7 +241,7 @@ extern "C" int ldsim_ctx_destroy(ldsim_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   void* ptrs[] = {ctx->d_consts, ctx->d_resp,      ctx->d_eff,    ctx->d_ch2tpc, ctx->d_lut_vis, ctx->d_lut_t0,
                   ctx->d_lut_t0avg, ctx->d_lut_td, ctx->seg_block.p, ctx->raw.p,  ctx->d_pix_thr, ctx->d_pix_gain,
-                  ctx->d_glx, ctx->d_glw, ctx->light_flag_dev};
+                  ctx->d_glx, ctx->d_glw, ctx->light_flag_dev, ctx->d_fee_tab};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (ctx->copy_stream) {

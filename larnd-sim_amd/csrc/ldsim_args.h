@@ -79,6 +79,7 @@ struct FeeArgs {
   // sorted pairs
   const int32_t* pair_val;    // r*P + ipix
   const unsigned long long* pair_key;
+  int64_t n_pairs;            // length of the sorted pair list (sizes the set-up pass's slot pool)
   int32_t P;
   const double* track_starts; // [n_seg] relative index r
   const float* waves;         // [n_pairs][T]
@@ -105,7 +106,9 @@ struct FeeArgs {
   // keyed mode (rng.h): row u draws stream key_mix(batch_keys[ubatch[u]], upix[u]) inline, no table (noise_z NULL)
   const uint64_t* batch_keys; // [batch ids of the upload] or NULL = table mode
   uint64_t rng_seed;
-  int32_t debug;              // timing tools (debug_phases bits 0x10000 / 0x20000 / 0x40000: no waveform sum / scan / fractions)
+  int32_t debug;              // timing tools (debug_phases bits 0x10000 / 0x20000 / 0x40000: no waveform sum / scan / fractions;
+                              // read only by a library built with make DEBUG_FEE=1)
+  const double* tab;          // launch constants wtap[64] | G[64] (fee_launch_chain sets it: ctx->d_fee_tab)
 };
 
 int current_launch(ldsim_ctx* ctx, const CurArgs& args);

@@ -167,6 +167,9 @@ struct ldsim_ctx {
   int debug_lds_b1_kb = 0;                   // timing tools: LDS budget of gcorr_kernel's second class in KB (0 = 32)
   int debug_lds_pad_kb = 0;                  // timing tools: KB taken off the LDS budget of gcorr_kernel's small class
   long long frac_clean_gen = -1;             // out_gen of the output set whose dense fractions array has been completed with zeros
+  // launch constants of the FEE kernels (kernels_fee.hip fee_tables_kernel): wtap[64] | G[64], built for (fee_tab_dt, fee_tab_rt)
+  double* d_fee_tab = nullptr;
+  double fee_tab_dt = 0, fee_tab_rt = -1;
   int fee_one_class = 0;                     // option: 1 = pixel_adc_kernel with 256 threads and the whole tick axis for every pixel (A/B checks)
   int gform_chunks = 1;                      // tables and correlation of the node-separable form in this many pair ranges, the tables of range c + 1 on a second stream beside the correlation of range c (1: one after the other)
   hipStream_t tab_stream = nullptr;          // that second stream, and its per-range events
@@ -283,7 +286,7 @@ struct ldsim_ctx {
 enum {
   SB_ACTIVE = 0, SB_NEIGH, SB_NRAD, SB_NLIST, SB_STARTS, SB_MISC, SB_KEYS, SB_KEYS2, SB_VALS, SB_VALS2,
   SB_SORTTMP, SB_PAIRSEG, SB_PAIRPIX, SB_HEADS, SB_UOFF, SB_UPIX, SB_UBATCH, SB_WAVES, SB_ADC, SB_TICKS,
-  SB_DIGIT, SB_TPM, SB_FRAC, SB_HITS, SB_ITEMS, SB_HDR, SB_CORR, SB_WBUF, SB_NOISE, SB_NDRAWS, SB_PPAR, SB_CPT, SB_CPO, SB_WIN, SB_SPAN, SB_GMAPS
+  SB_DIGIT, SB_TPM, SB_FRAC, SB_HITS, SB_ITEMS, SB_HDR, SB_CORR, SB_WBUF, SB_NOISE, SB_NDRAWS, SB_PPAR, SB_CPT, SB_CPO, SB_WIN, SB_SPAN, SB_GMAPS, SB_FEESLOT
 };
 
 void ldsim_set_error(const char* fmt, ...);

@@ -1,5 +1,6 @@
 """pixel_adc_kernel with parts switched off (debug_phases bits 0x10000 no waveform sum, 0x20000 no trigger scan, 0x40000 no
-backtracking fractions; results are wrong in those runs by construction).  python tools/adc_phases.py [cfg]"""
+backtracking fractions; results are wrong in those runs by construction).  The kernels read the switches only in a library built
+with `make -C larnd-sim_amd/csrc DEBUG_FEE=1`.  python tools/adc_phases.py [cfg]"""
 import os
 import sys
 
