@@ -19,7 +19,7 @@ Faithfulness rules (Numba types arithmetic as f64; NumPy-2 scalars do not):
   * between stages the mutated float fields are rounded through f4 (the HDF5 schema);
   * FEE noise constants are 0 (the Numba RNG stream is third-party and unpinned).
 
-Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,chain,sampled,light,light_response] [--jobs 8]
+Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,chain,sampled,light,light_response,fee] [--jobs 8]
 """
 import argparse
 import importlib
@@ -84,7 +84,8 @@ class _Kernel:
         return launch
 
 
-def _install_standins():
+def _install_standins(normal=None):
+    """normal: the stand-in for numba.cuda.random.xoroshiro128p_normal_float32 (None: every normal is 0.0)"""
     numba = types.ModuleType("numba")
     cuda = types.ModuleType("numba.cuda")
     crandom = types.ModuleType("numba.cuda.random")
@@ -125,7 +126,7 @@ def _install_standins():
     cuda.random = crandom
     cuda.to_device = lambda a: a
     cuda.device_array = lambda n, dtype=None: np.zeros(n, dtype=dtype)
-    crandom.xoroshiro128p_normal_float32 = lambda states, i: 0.0
+    crandom.xoroshiro128p_normal_float32 = normal if normal is not None else (lambda states, i: 0.0)
     crandom.xoroshiro128p_uniform_float32 = lambda states, i: 0.5
     crandom.create_xoroshiro128p_states = lambda n, seed=0: np.zeros(n)
     nerrors.NumbaPerformanceWarning = Warning
@@ -157,8 +158,8 @@ def _install_standins():
 class Ref:
     """The reference package loaded for one configuration."""
 
-    def __init__(self, cfgname, noise_zero=True):
-        _install_standins()
+    def __init__(self, cfgname, noise_zero=True, normal=None):
+        _install_standins(normal)
         if REF not in sys.path:
             sys.path.insert(0, REF)
         for m in [m for m in sys.modules if m == "larndsim" or m.startswith("larndsim.")]:
@@ -1058,6 +1059,231 @@ def gen_packets():
         print("packets", cfg, "trig mode", ref.light.LIGHT_TRIG_MODE, "packets", len(pk), kinds)
 
 
+# --------------------------------------------------------------------------
+# fee: the self-trigger scan on hand-made dense waveforms
+# --------------------------------------------------------------------------
+FEE_CONST_NAMES = ("BUFFER_RISETIME", "ADC_HOLD_DELAY", "ADC_BUSY_DELAY", "RESET_CYCLES", "MAX_ADC_VALUES",
+                   "RESET_NOISE_CHARGE", "UNCORRELATED_NOISE_CHARGE", "DISCRIMINATOR_NOISE")
+# what a variant sets on the reference's detector / sim modules (MAX_ADC_VALUES lives in sim); `noisy` keeps the shipped noise
+FEE_VARIANTS = (("default", {}), ("no_risetime", {"BUFFER_RISETIME": 0}),
+                ("long", {"ADC_HOLD_DELAY": 70, "ADC_BUSY_DELAY": 80, "RESET_CYCLES": 3}),
+                ("cap", {"MAX_ADC_VALUES": 3}), ("noisy", {}))
+FEE_SEED = 20261018
+FEE_M = 3
+
+
+def _fee_owner(ref, name):
+    return ref.sim if name == "MAX_ADC_VALUES" else ref.detector
+
+
+def _fee_prefix_charge(cur, dt, rt):
+    """running sum of the buffer-convolved charge from tick 0 with no reset in between (fee.py:566-581 before any trigger),
+    in plain numpy: where the generator expects the first threshold crossing of a row"""
+    if rt > 0:
+        ntap = int(np.ceil(10 * rt / dt))
+        w = np.exp(-np.arange(ntap + 1) * dt / rt) * (1 - np.exp(-dt / rt))
+        q = np.convolve(cur * dt, w)[:cur.shape[0]]
+    else:
+        q = cur * dt
+    return np.cumsum(q)
+
+
+def _fee_rows(NT, dt, rt, interval, busy_ticks, reset_ticks, thr0):
+    """The rows of one variant: (name, threshold, components); a component is (per-tick charge [NT] in electrons, the three
+    tracks' shares of it).  Spikes sit on single ticks so that the tick of every threshold crossing is known by construction."""
+    def spike(t, q):
+        a = np.zeros(NT)
+        a[t] = q
+        return a
+
+    def plateau(t0, t1, q):
+        a = np.zeros(NT)
+        a[t0:t1] = q
+        return a
+
+    def gauss(c, sigma, q):
+        t = np.arange(NT)
+        a = np.where(np.abs(t - c) <= 4 * sigma, np.exp(-0.5 * ((t - c) / sigma) ** 2), 0.0)
+        return a * (q / np.exp(-0.5 * (np.arange(-4 * sigma, 4 * sigma + 1) / sigma) ** 2).sum())
+
+    one = ((1, 0, 0), (0, 1, 0), (0, 0, 1))
+    rows = []
+    rows.append(("a_plain", thr0, [(spike(700, 20000.0), (0.7, 0.3, 0))]))
+    rows.append(("a_gauss", thr0, [(gauss(1200, 6, 15000.0), one[0]), (gauss(1204, 5, 9000.0), one[1]),
+                                   (gauss(1195, 8, 6000.0), one[2])]))
+    rows.append(("b_start", thr0, [(spike(0, 4000.0), one[0]), (spike(1, 4000.0), one[1]), (spike(2, 4000.0), one[2])]))
+    for name, t in (("c_lane63", 63), ("c_lane0", 64), ("c_lane63_second", 127), ("c_lane0_third", 128)):
+        rows.append((name, thr0, [(spike(t - 3, 5000.0), one[0]), (spike(t, 5000.0), one[1])]))
+    # d: +9000 crosses, -4000 inside the integration pulls the sum below the threshold: failed trigger.  3000 electrons on the
+    # tick just before the moved last_reset (a tick the scan never visits) must not reach the clean pulse that follows.
+    lead = spike(400, 9000.0)
+    c = int(np.flatnonzero(_fee_prefix_charge(lead / dt, dt, rt) >= thr0)[0])
+    moved = c + interval + 1 + reset_ticks
+    rows.append(("d_failed", thr0, [(lead, one[0]), (spike(405, -4000.0), one[1]), (spike(moved - 1, 3000.0), one[2]),
+                                    (spike(moved + 30, 20000.0), (0.6, 0.4, 0))]))
+    rows.append(("e_plateau", thr0, [(plateau(300, 700, 1000.0), one[0]), (plateau(300, 500, 500.0), one[1]),
+                                     (plateau(500, 700, 500.0), one[2])]))
+    # second pulse three ticks after the reset of the first hit: crosses while the ADC is busy and has to wait
+    rows.append(("e_busy_cross", thr0, [(spike(1000, 20000.0), one[0]),
+                                        (spike(1000 + interval + 1 + reset_ticks + 3, 12000.0), one[1])]))
+    rows.append(("f_end_interval", thr0, [(spike(NT - interval + 2, 20000.0), (0.5, 0.25, 0.25))]))
+    rows.append(("f_end_ntap", thr0, [(spike(NT - 2, 20000.0), (0.5, 0.5, 0))]))
+    rows.append(("f_end_gauss", thr0, [(gauss(NT - 4, 3, 30000.0), (0.2, 0.3, 0.5))]))
+    rows.append(("g_cap", thr0, [(plateau(100, 1900, 1500.0), (0.6, 0.4, 0))]))
+    rows.append(("h_cancel", thr0, [(spike(900, 40000.0), one[0]), (spike(900, -20000.0), one[1])]))
+    # threshold below zero: triggers at tick 0 on no charge; the negative lobe makes true_q <= 0 at the hit
+    rows.append(("h_negq", -3000.0, [(spike(5, -3000.0), one[0]), (spike(5, 1000.0), one[1]), (spike(1000, 15000.0), one[2])]))
+    rows.append(("i_zero", thr0, []))
+    rows.append(("i_below", thr0, [(spike(1000, 6800.0), (0.5, 0.5, 0))]))
+    for name, thr in (("j_thr_low", 3000.0), ("j_thr_mid", 9000.0), ("j_thr_high", 12000.0), ("j_thr_zero", 0.0)):
+        rows.append((name, thr, [(spike(500, 10000.0), (0.25, 0.25, 0.5))]))
+    rows.append(("k_two_far", thr0, [(spike(200, 20000.0), one[0]), (spike(1500, 20000.0), one[1])]))
+    rows.append(("l_negative", thr0, [(spike(800, -5000.0), one[2])]))
+    rows.append(("m_wide", thr0, [(gauss(1000, 40, 60000.0), (0.5, 0.3, 0.2))]))
+    return rows
+
+
+def gen_fee():
+    """fee.get_adc_values (fee.py:517-655) and fee.digitize on dense hand-made waveforms, one pixel per row, under five sets of
+    constants -> tests/golden/fee_scan_<variant>.npz (inputs, the constants used, the reference's outputs, expect_* counts).
+    The generator itself proves which branch each row reached (asserts + one printed line per row) and, for the noiseless
+    variants, that no decision sits on the threshold (same hits and stamps with every threshold scaled by 1 +- 1e-9).
+    `noisy`: the normals are the draws of the oracle's restated xoroshiro128p stream, so the reference's control flow
+    consumes the numbers the HIP table path produces; the seed, the states after the call and the draw counts are recorded."""
+    import contextlib
+    import io
+    import time
+    try:
+        from oracle import oracle as ORC
+    except ImportError:
+        import oracle as ORC
+    for variant, over in FEE_VARIANTS:
+        t_begin = time.time()
+        noisy = variant == "noisy"
+        draws = []
+
+        def normal(states, ip):
+            # a Python float: Numba types f32 * f64 as f64 (a NumPy f32 scalar would keep the products in f32)
+            draws[ip] += 1
+            return float(ORC.rng_normals(states, ip, 1)[0])
+        ref = Ref("module0", noise_zero=not noisy, normal=normal if noisy else None)
+        det, sim = ref.detector, ref.sim
+        for k, v in over.items():
+            setattr(_fee_owner(ref, k), k, v)
+        dt, rt = det.TIME_SAMPLING, det.BUFFER_RISETIME
+        # the reference's own expressions (fee.py:590,620,647)
+        interval = round((3 * det.CLOCK_CYCLE + det.ADC_HOLD_DELAY * det.CLOCK_CYCLE) / det.TIME_SAMPLING)
+        busy_ticks = round(det.ADC_BUSY_DELAY * det.CLOCK_CYCLE / det.TIME_SAMPLING)
+        reset_ticks = round(det.RESET_CYCLES * det.CLOCK_CYCLE / det.TIME_SAMPLING)
+        if variant == "long":
+            assert interval > 64 and busy_ticks > 64 and reset_ticks > 1, (interval, busy_ticks, reset_ticks)
+        NT = len(det.TIME_TICKS)
+        A, M = sim.MAX_ADC_VALUES, FEE_M
+        thr0 = det.DISCRIMINATION_THRESHOLD * ref.consts.units.e
+        rows = _fee_rows(NT, dt, rt, interval, busy_ticks, reset_ticks, thr0)
+        U = len(rows)
+        names = [r[0] for r in rows]
+        thresholds = np.array([r[1] for r in rows], dtype=np.float64)
+        pts = np.zeros((U, NT, M))
+        for u, (_, _, comps) in enumerate(rows):
+            for charge, share in comps:
+                for m in range(M):
+                    pts[u, :, m] += charge / dt * share[m]          # e-/us
+        ps = pts[:, :, 0] + pts[:, :, 1] + pts[:, :, 2]
+        time_ticks = np.linspace(0, 1 * det.TIME_INTERVAL[1], NT + 1)
+
+        def run(thr, states):
+            adc = np.zeros((U, A)); ticks = np.zeros((U, A)); frac = np.zeros((U, A, M))
+            del draws[:]
+            draws.extend([0] * U)
+            sink = io.StringIO()
+            with contextlib.redirect_stdout(sink):       # (the reference prints a line per pixel that reaches the cap)
+                ref.fee.get_adc_values[max(1, -(-U // 128)), 128](ps, pts, time_ticks, adc, ticks, 0, states, frac, thr)
+            return adc, ticks, frac, sink.getvalue().count("More ADC values than possible")
+
+        states = ORC.rng_create_states(U, FEE_SEED) if noisy else np.zeros(1)
+        adc, ticks, frac, n_cap = run(thresholds, states)
+        n_draws = np.array(draws, dtype=np.int64)
+        digit = ref.fee.digitize(adc)
+        # ---- margin: no decision on the threshold (device exp and libm differ in the last bit) ----
+        # (with noise: the f32 normals differ in the last bit between device and host, 6e-8 of a few thousand electrons, so
+        # the same check at 2e-7, the stream restarted: a flipped decision would also shift every later draw)
+        for s in (1 + 1e-9, 1 - 1e-9) if not noisy else (1 + 2e-7, 1 - 2e-7):
+            adc_s, ticks_s, _, _ = run(thresholds * s, ORC.rng_create_states(U, FEE_SEED) if noisy else np.zeros(1))
+            for u in range(U):
+                assert np.array_equal(adc_s[u] != 0, adc[u] != 0) and np.array_equal(ticks_s[u], ticks[u]), \
+                    f"fee {variant} row {names[u]}: a decision sits on the threshold (scale {s!r}): reshape the row"
+        # ---- coverage: what each row reached, from the reference's outputs ----
+        hits = (adc != 0).sum(axis=1)
+        slots = (ticks != 0).sum(axis=1)
+        beyond = (ticks > time_ticks[-1]).sum(axis=1)
+        first_cross = np.full(U, -1, dtype=np.int64)
+        for u in range(U):
+            above = np.flatnonzero(_fee_prefix_charge(ps[u], dt, rt) >= thresholds[u])
+            first_cross[u] = above[0] if len(above) else -1
+
+        def stamp(c):
+            ic = c + interval + 1
+            return time_ticks[min(ic, NT)] - 2 + max(ic - NT, 0)
+        row = {n: u for u, n in enumerate(names)}
+        if not noisy:
+            for u, n in enumerate(names):
+                if first_cross[u] < 0:
+                    assert slots[u] == 0, (variant, n, "a hit without a crossing")
+                elif n == "d_failed":
+                    # the only hit is the clean pulse, 30 ticks after the reset that followed the failed trigger
+                    assert hits[u] == 1 and ticks[u, 0] == stamp(first_cross[u] + interval + 1 + reset_ticks + 30), \
+                        (variant, n, ticks[u, :3])
+                    assert not np.any(ticks[u] == stamp(first_cross[u])), (variant, n, "the failed trigger left a hit")
+                else:
+                    assert ticks[u, 0] == stamp(first_cross[u]), (variant, n, first_cross[u], ticks[u, 0])
+            for n, lane in (("c_lane63", 63), ("c_lane0", 64), ("c_lane63_second", 127), ("c_lane0_third", 128)):
+                assert first_cross[row[n]] == lane, (variant, n, first_cross[row[n]])
+            assert first_cross[row["b_start"]] <= 2 and hits[row["b_start"]] == 1
+            assert hits[row["a_plain"]] == 1 and hits[row["h_cancel"]] == 1
+            assert hits[row["e_plateau"]] >= 2 and hits[row["k_two_far"]] == 2
+            # e_busy_cross: the second pulse crossed 3 ticks after the reset; its hit waited for the busy counter to run out
+            u = row["e_busy_cross"]
+            assert hits[u] == 2 and ticks[u, 1] == stamp(1000 + interval + 1 + reset_ticks + max(busy_ticks - 1, 3)), ticks[u, :3]
+            for n in ("f_end_interval", "f_end_ntap", "f_end_gauss"):
+                assert hits[row[n]] == 1 and beyond[row[n]] == 1, (variant, n, ticks[row[n], :2])
+            # (with `long`'s 150-tick cycle the waveform ends before MAX_ADC_VALUES hits)
+            full = A if variant != "long" else 10
+            assert hits[row["g_cap"]] >= full and (n_cap >= 1 or variant == "long"), (variant, hits[row["g_cap"]], n_cap)
+            if variant == "cap":
+                assert A == 3 and hits[row["g_cap"]] == 3 and hits[row["e_plateau"]] == 3
+            # h_cancel: normalised fractions of opposite sign; h_negq: true_q <= 0 at the first hit, fractions left as charges
+            np.testing.assert_allclose(frac[row["h_cancel"], 0], (2.0, -1.0, 0.0), rtol=1e-12, atol=1e-12)
+            u = row["h_negq"]
+            assert adc[u, 0] < 0 and frac[u, 0, 0] < -1000 and frac[u, 0, 1] > 300, (adc[u, 0], frac[u, 0])
+            assert slots[row["j_thr_zero"]] >= full and slots[u] >= full and ticks[row["j_thr_zero"], 0] == stamp(0)
+            assert hits[row["j_thr_low"]] == 1 and hits[row["j_thr_mid"]] == 1 and hits[row["j_thr_high"]] == 0
+            for n in ("i_zero", "i_below", "l_negative"):
+                assert slots[row[n]] == 0, (variant, n)
+        else:
+            # every tick of the empty row drew its two normals, plus the one before the loop (fee.py:557,583-584)
+            assert n_draws[row["i_zero"]] >= 1 + 2 * NT
+            assert not np.array_equal(states.view("u8"), ORC.rng_create_states(U, FEE_SEED).view("u8"))
+        for u, n in enumerate(names):
+            print(f"fee {variant:11s} row {n:16s} thr {thresholds[u]:8.1f} hits {hits[u]:2d} slots {slots[u]:2d} "
+                  f"first crossing {first_cross[u]:5d} first stamp {ticks[u, 0]:9.4f} beyond end {beyond[u]}"
+                  + (f" draws {n_draws[u]}" if noisy else ""))
+        out = dict(rows=np.array(names), pixels_signals=ps, pixels_signals_tracks=pts, thresholds=thresholds,
+                   time_ticks_stop=np.float64(time_ticks[-1]), const_names=np.array(FEE_CONST_NAMES),
+                   const_values=np.array([float(getattr(_fee_owner(ref, k), k)) for k in FEE_CONST_NAMES]),
+                   interval=np.int64(interval), busy_ticks=np.int64(busy_ticks), reset_ticks=np.int64(reset_ticks),
+                   adc_list=adc, adc_ticks_list=ticks, current_fractions=frac, adc_digit=digit,
+                   expect_hits=hits, expect_slots=slots, expect_beyond_end=beyond, expect_first_crossing=first_cross,
+                   expect_cap_breaks=np.int64(n_cap))
+        if noisy:
+            out.update(rng_seed=np.int64(FEE_SEED), rng_states_after=states.view("u8").reshape(-1, 2).copy(), n_draws=n_draws)
+        path = os.path.join(GOLD, f"fee_scan_{variant}.npz")
+        np.savez_compressed(path, **out)
+        print(f"fee {variant}: interval {interval} busy_ticks {busy_ticks} reset_ticks {reset_ticks} rows {U} hits {int(hits.sum())} "
+              f"slots {int(slots.sum())} cap breaks {n_cap} margin check passed "
+              f"{os.path.getsize(path)} bytes {time.time() - t_begin:.1f} s")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="consts,qd,pixels,light,sampled,chain")
@@ -1069,7 +1295,7 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     for s in a.sets.split(","):
         {"consts": gen_consts, "qd": gen_qd, "pixels": gen_pixels, "light": gen_light, "light_response": gen_light_response,
-         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_export": gen_light_export}[s]()
+         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_export": gen_light_export, "fee": gen_fee}[s]()
     return 0
 
 

@@ -106,6 +106,42 @@ def load_light_wvfm_case(name):
     return g
 
 
+FEE_SCAN_VARIANTS = ("default", "no_risetime", "long", "cap", "noisy")
+
+
+def load_fee_scan_case(variant):
+    """Constants of a tests/golden/fee_scan_<variant>.npz case (oracle/gen_golden.py gen_fee): module0 with the FEE constants
+    and noise charges the reference ran with, set on ``consts`` the way the generator set them on the reference's modules.
+    Undo with ``load_cfg("module0")``.  Returns (fixture, time_ticks)."""
+    load_cfg("module0", noise_zero=False)
+    g = gold(f"fee_scan_{variant}.npz")
+    for name, value in zip(g["const_names"], g["const_values"]):
+        owner = consts.sim if str(name) == "MAX_ADC_VALUES" else consts.detector
+        was = getattr(owner, str(name))
+        setattr(owner, str(name), int(value) if isinstance(was, (int, np.integer)) and float(value).is_integer() else float(value))
+    NT = g["pixels_signals"].shape[1]
+    assert NT == len(consts.detector.TIME_TICKS) and float(g["time_ticks_stop"]) == consts.detector.TIME_INTERVAL[1]
+    return g, np.linspace(0, consts.detector.TIME_INTERVAL[1], NT + 1)
+
+
+def assert_fee_scan_matches(g, adc, ticks, frac, digit, noisy):
+    """The assertions the oracle and the HIP kernel share against a fee_scan fixture: hit pattern and tick stamps exact, charges
+    to rtol 1e-9 (with noise: 1e-6 / 1e-2, the f32 normals' last bit), fractions at hit slots, digitised codes, expect_* counts."""
+    ref = g["adc_list"]
+    assert np.array_equal(adc != 0, ref != 0)
+    assert np.array_equal(ticks, g["adc_ticks_list"])
+    if noisy:
+        np.testing.assert_allclose(adc, ref, rtol=1e-6, atol=1e-2)
+    else:
+        np.testing.assert_allclose(adc, ref, rtol=1e-9)
+    hit = ref != 0
+    np.testing.assert_allclose(frac[hit], g["current_fractions"][hit], rtol=1e-9, atol=1e-12)
+    assert np.array_equal(digit, g["adc_digit"])
+    assert np.array_equal((adc != 0).sum(axis=1), g["expect_hits"])
+    assert np.array_equal((ticks != 0).sum(axis=1), g["expect_slots"])
+    assert np.array_equal((ticks > float(g["time_ticks_stop"])).sum(axis=1), g["expect_beyond_end"])
+
+
 def det_phases(shape, seed):
     """The golden generator's stand-in for cp.random.uniform(size=shape) (oracle/gen_golden.py det_phases): a
     multiplicative hash of (row, column, seed) in [0, 1), so the fixtures need not store the phases."""

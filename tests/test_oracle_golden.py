@@ -112,6 +112,25 @@ def test_chain_downstream_stages():
     assert (g["adc_integral_low"] != 0).sum() >= 10
 
 
+@pytest.mark.parametrize("variant", H.FEE_SCAN_VARIANTS)
+def test_fee_scan_golden(variant):
+    """The oracle's get_adc_values / digitize against the reference's own (fee.py:499-655) on the hand-made waveforms of
+    oracle/gen_golden.py gen_fee: failed triggers, hits past the end of the waveform, the MAX_ADC_VALUES cap, true_q <= 0,
+    no buffer rise time, interval / busy delay / reset longer than 64 ticks, thresholds <= 0 and, in `noisy`, the order in which
+    the scan consumes its normals (the reference ran on the oracle's restated stream: same states afterwards)."""
+    try:
+        g, tt = H.load_fee_scan_case(variant)
+        noisy = variant == "noisy"
+        states = O.rng_create_states(len(g["thresholds"]), int(g["rng_seed"])) if noisy else None
+        adc, ticks, frac = O.get_adc_values(g["pixels_signals"], g["pixels_signals_tracks"], tt, g["thresholds"],
+                                            rng_states=states)
+        H.assert_fee_scan_matches(g, adc, ticks, frac, O.digitize(adc), noisy)
+        if noisy:
+            assert np.array_equal(states.view("u8").reshape(-1, 2), g["rng_states_after"])
+    finally:
+        H.load_cfg("module0")
+
+
 def test_numba_f32_typing_effect_is_recorded():
     """DESIGN.md §2 typing caveat: Numba keeps f32 (op) f32 in single precision for f4 record fields.  The oracle can
     emulate those spots; the induced current then moves by ~2e-7 of the waveform peak (median), <1e-3 worst case."""
