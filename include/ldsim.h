@@ -114,6 +114,9 @@ int ldsim_ctx_destroy(ldsim_ctx* ctx);
 /* page-locked host memory for the download / upload buffers of a caller that wants PCIe-rate copies (hipHostMalloc) */
 int ldsim_host_alloc(void** p, size_t bytes);
 int ldsim_host_free(void* p);
+/* test seam: device buffers, streams and events the library holds in this process, over all contexts (page-locked host memory
+ * is not counted).  All three are 0 once every context is destroyed. */
+int ldsim_debug_live_objects(int64_t counts[3]);
 int ldsim_set_consts(ldsim_ctx* ctx, const LdsimConsts* consts);
 /* cp.load(response_file) (cli/simulate_pixels.py:436): f64 table [ni][nj][nk], host pointer */
 int ldsim_set_response(ldsim_ctx* ctx, const double* response, int32_t ni, int32_t nj, int32_t nk);

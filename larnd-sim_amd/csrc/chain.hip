@@ -29,16 +29,10 @@ int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters,
 int sort_compact_hits(ldsim_ctx*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const double*,
                       const double*, int, int64_t, int32_t*);
 
-#define CK(x)            \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-
 static void fill_cur_common(ldsim_ctx* ctx, CurArgs& a) {
   a.s = charge_store(ctx);   // (the anode view after a mapped quench_drift)
-  a.c = ctx->d_consts;
-  a.resp = ctx->d_resp;
+  a.c = ctx->d_consts.as<LdsimConsts>();
+  a.resp = ctx->d_resp.as<double>();
   a.ni = ctx->ni; a.nj = ctx->nj; a.nk = ctx->nk;
   if (ctx->trim_response && ctx->resp_k_last >= ctx->resp_k_first) {
     a.k_first = ctx->resp_k_first;
@@ -209,7 +203,7 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   ctx->ms_current = ctx->ms_adc = ctx->ms_total = 0;
   // per-pixel threshold / gain tables are dense over one pixel geometry: refuse another one before any work is launched
   const bool tables_fit = ctx->pix_table_n == (int64_t)h.n_pixels[0] * h.n_pixels[1] * h.n_tpc;
-  if (!tables_fit && (ctx->d_pix_thr || ctx->d_pix_gain)) {
+  if (!tables_fit && (ctx->d_pix_thr.p || ctx->d_pix_gain.p)) {
     ldsim_set_error("pixel threshold/gain tables were set for another pixel geometry: set them again after set_consts");
     return LDSIM_ESTATE;
   }
@@ -400,7 +394,7 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   int32_t* d_hitcnt = (int32_t*)ctx->scratch[SB_PAIRPIX].p;
   int32_t* d_hitoff = d_hitcnt + U;
   FeeArgs F{};
-  F.c = ctx->d_consts;
+  F.c = ctx->d_consts.as<LdsimConsts>();
   F.k = FEEK_FROM(h);
   F.U = U;
   F.upix = d_upix; F.ubatch = d_ubatch; F.uoff = d_uoff;
@@ -414,8 +408,8 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   F.batch_first = d_first_b;
   F.batch0 = batch0;
   F.threshold = h.discrimination_threshold * 1.0;   // DISCRIMINATION_THRESHOLD * units.e
-  F.thr_table = tables_fit ? ctx->d_pix_thr : nullptr;
-  F.gain_table = tables_fit ? ctx->d_pix_gain : nullptr;
+  F.thr_table = tables_fit ? ctx->d_pix_thr.as<double>() : nullptr;
+  F.gain_table = tables_fit ? ctx->d_pix_gain.as<double>() : nullptr;
   F.time_padding = 0.0;                             // cli/simulate_pixels.py:1092
   F.adc_list = (double*)ctx->scratch[SB_ADC].p;
   F.adc_ticks = (double*)ctx->scratch[SB_TICKS].p;

@@ -15,18 +15,11 @@
       return LDSIM_EHIP;                                                                               \
     }                                                                                                  \
   } while (0)
-#define NEEDC(cond, msg)           \
-  do {                             \
-    if (!(cond)) {                 \
-      ldsim_set_error("%s", msg);  \
-      return LDSIM_EINVAL;         \
-    }                              \
-  } while (0)
 
 static_assert(sizeof(ncclUniqueId) == LDSIM_COMM_ID_BYTES, "LDSIM_COMM_ID_BYTES must be sizeof(ncclUniqueId)");
 
 extern "C" int ldsim_comm_unique_id(void* id) {
-  NEEDC(id, "null id");
+  NEED(id, "null id");
   ncclUniqueId u;
   NCCLCHK(ncclGetUniqueId(&u));
   memcpy(id, &u, sizeof(u));
@@ -35,8 +28,8 @@ extern "C" int ldsim_comm_unique_id(void* id) {
 
 extern "C" int ldsim_comm_init(ldsim_ctx* ctx, const void* id, int32_t rank, int32_t world) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && id && world >= 1 && rank >= 0 && rank < world, "bad communicator arguments");
-  NEEDC(!ctx->comm, "communicator already initialised");
+  NEED(ctx && id && world >= 1 && rank >= 0 && rank < world, "bad communicator arguments");
+  NEED(!ctx->comm, "communicator already initialised");
   HIPCHK(hipSetDevice(ctx->device));
   ncclUniqueId u;
   memcpy(&u, id, sizeof(u));
@@ -52,7 +45,7 @@ extern "C" int ldsim_comm_init(ldsim_ctx* ctx, const void* id, int32_t rank, int
 // launch really joined, instead of trusting the environment it was started with
 extern "C" int ldsim_comm_count(ldsim_ctx* ctx, int32_t* n_ranks, int32_t* rank) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && ctx->comm && n_ranks, "no communicator / null argument");
+  NEED(ctx && ctx->comm && n_ranks, "no communicator / null argument");
   int n = 0, r = 0;
   NCCLCHK(ncclCommCount((ncclComm_t)ctx->comm, &n));
   NCCLCHK(ncclCommUserRank((ncclComm_t)ctx->comm, &r));
@@ -75,7 +68,7 @@ extern "C" int ldsim_comm_destroy(ldsim_ctx* ctx) {
 // value (host, in/out) reduced over the ranks: op 0 = sum, 1 = max.  Doubles as the barrier (every rank leaves after all entered).
 extern "C" int ldsim_comm_allreduce_f64(ldsim_ctx* ctx, double* value, int32_t op) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && value && ctx->comm, "no communicator");
+  NEED(ctx && value && ctx->comm, "no communicator");
   HIPCHK(hipSetDevice(ctx->device));
   int rc = ldsim_ensure_buf(ctx, &ctx->comm_tmp, 64 + 8 * (size_t)ctx->comm_world);
   if (rc) return rc;
@@ -91,22 +84,13 @@ extern "C" int ldsim_comm_allreduce_f64(ldsim_ctx* ctx, double* value, int32_t o
 // are appended (device-to-device, on the ctx stream, before the next chain call reuses its buffer).
 extern "C" int ldsim_hits_accumulate(ldsim_ctx* ctx, int32_t reset) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx, "null ctx");
+  NEED(ctx, "null ctx");
   HIPCHK(hipSetDevice(ctx->device));
   if (reset) ctx->hits_acc_rows = 0;
   const int64_t n = ctx->chain_hits;
   if (n == 0) return 0;
   const size_t need = (size_t)(ctx->hits_acc_rows + n) * 24;
-  if (need > ctx->hits_acc.bytes) {
-    DevBuf nb;
-    int rc = ldsim_ensure_buf(ctx, &nb, need * 2);
-    if (rc) return rc;
-    if (ctx->hits_acc_rows)
-      HIPCHK(hipMemcpyAsync(nb.p, ctx->hits_acc.p, (size_t)ctx->hits_acc_rows * 24, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (ctx->hits_acc.p) (void)hipFree(ctx->hits_acc.p);
-    ctx->hits_acc = nb;
-  }
+  CK(ctx->hits_acc.grow_keep(ctx->stream, (size_t)ctx->hits_acc_rows * 24, need));
   HIPCHK(hipMemcpyAsync((char*)ctx->hits_acc.p + (size_t)ctx->hits_acc_rows * 24, ctx->scratch[SB_HITS].p, (size_t)n * 24,
                         hipMemcpyDeviceToDevice, ctx->stream));
   ctx->hits_acc_rows += n;
@@ -117,7 +101,7 @@ extern "C" int ldsim_hits_accumulate(ldsim_ctx* ctx, int32_t reset) {
 // device pointer owned by the ctx (valid until the next call) holding the rows of rank 0, 1, .. back to back.
 extern "C" int ldsim_comm_allgather_hits(ldsim_ctx* ctx, void** gathered, int64_t* total_rows, int64_t* counts) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && gathered && total_rows && ctx->comm, "no communicator / null argument");
+  NEED(ctx && gathered && total_rows && ctx->comm, "no communicator / null argument");
   HIPCHK(hipSetDevice(ctx->device));
   const int W = ctx->comm_world;
   ncclComm_t comm = (ncclComm_t)ctx->comm;
@@ -133,7 +117,7 @@ extern "C" int ldsim_comm_allgather_hits(ldsim_ctx* ctx, void** gathered, int64_
   HIPCHK(hipStreamSynchronize(ctx->stream));
   int64_t total = 0;
   for (int r = 0; r < W; r++) {
-    NEEDC(h[r] >= 0, "negative row count received");
+    NEED(h[r] >= 0, "negative row count received");
     total += h[r];
   }
   if ((rc = ldsim_ensure_buf(ctx, &ctx->hits_all, (size_t)(total > 0 ? total : 1) * 24))) return rc;
@@ -158,9 +142,9 @@ extern "C" int ldsim_comm_allgather_hits(ldsim_ctx* ctx, void** gathered, int64_
 // rows [0, n) of the gathered buffer to host (tests / the driver's output writer)
 extern "C" int ldsim_comm_gathered_download(ldsim_ctx* ctx, void* rows, int64_t n) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && (rows || n == 0), "null argument");
+  NEED(ctx && (rows || n == 0), "null argument");
   if (n == 0) return 0;
-  NEEDC((size_t)n * 24 <= ctx->hits_all.bytes, "more rows requested than gathered");
+  NEED((size_t)n * 24 <= ctx->hits_all.bytes, "more rows requested than gathered");
   HIPCHK(hipMemcpy(rows, ctx->hits_all.p, (size_t)n * 24, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -173,22 +157,9 @@ extern "C" int ldsim_comm_gathered_download(ldsim_ctx* ctx, void* rows, int64_t 
 //   4 fractions f64 (cpt_n[3])
 static const size_t CPT_ELEM[5] = {20, 8, 24, 8, 8};
 
-// grow b (keeping its first `keep` bytes) to hold at least `need` bytes
-static int grow_keep(ldsim_ctx* ctx, DevBuf* b, size_t keep, size_t need) {
-  if (need <= b->bytes && b->p) return 0;
-  DevBuf nb;
-  int rc = ldsim_ensure_buf(ctx, &nb, need * 2);
-  if (rc) return rc;
-  if (keep) HIPCHK(hipMemcpyAsync(nb.p, b->p, keep, hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (b->p) (void)hipFree(b->p);
-  *b = nb;
-  return 0;
-}
-
 extern "C" int ldsim_compact_accumulate(ldsim_ctx* ctx, int32_t reset) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx, "null ctx");
+  NEED(ctx, "null ctx");
   HIPCHK(hipSetDevice(ctx->device));
   if (reset) {                               // (empties the stream and appends nothing)
     for (int k = 0; k < 5; k++) ctx->cpt_acc_n[k] = 0;
@@ -211,8 +182,7 @@ extern "C" int ldsim_compact_accumulate(ldsim_ctx* ctx, int32_t reset) {
   for (int k = 0; k < 5; k++) {
     if (cnt[k] == 0) continue;
     const size_t have = (size_t)ctx->cpt_acc_n[k] * CPT_ELEM[k], add = (size_t)cnt[k] * CPT_ELEM[k];
-    int rc = grow_keep(ctx, &ctx->cpt_acc[k], have, have + add);
-    if (rc) return rc;
+    CK(ctx->cpt_acc[k].grow_keep(ctx->stream, have, have + add));
     HIPCHK(hipMemcpyAsync((char*)ctx->cpt_acc[k].p + have, src[k], add, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->cpt_acc_n[k] += cnt[k];
   }
@@ -223,10 +193,10 @@ extern "C" int ldsim_compact_accumulate(ldsim_ctx* ctx, int32_t reset) {
 // downloads and exports it before it receives the next.
 extern "C" int ldsim_comm_gather_compact(ldsim_ctx* ctx, int32_t root, int32_t src_rank, int64_t* sizes) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && ctx->comm, "no communicator");
+  NEED(ctx && ctx->comm, "no communicator");
   const int W = ctx->comm_world, me = ctx->comm_rank;
-  NEEDC(root >= 0 && root < W, "root out of range");
-  NEEDC(src_rank >= 0 && src_rank < W, "source rank out of range");
+  NEED(root >= 0 && root < W, "root out of range");
+  NEED(src_rank >= 0 && src_rank < W, "source rank out of range");
   HIPCHK(hipSetDevice(ctx->device));
   ncclComm_t comm = (ncclComm_t)ctx->comm;
   hipStream_t st = ctx->stream;
@@ -240,7 +210,7 @@ extern "C" int ldsim_comm_gather_compact(ldsim_ctx* ctx, int32_t root, int32_t s
   std::vector<int64_t> h((size_t)W * 5);
   HIPCHK(hipMemcpyAsync(h.data(), d_all, 40 * (size_t)W, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  for (size_t i = 0; i < h.size(); i++) NEEDC(h[i] >= 0, "negative size received");
+  for (size_t i = 0; i < h.size(); i++) NEED(h[i] >= 0, "negative size received");
   for (int k = 0; k < 5; k++)
     if (h[(size_t)me * 5 + k] != ctx->cpt_acc_n[k]) {
       ldsim_set_error("gather_compact: the all-gathered size of part %d of rank %d (%lld) differs from the local one (%lld)", k,
@@ -278,8 +248,8 @@ extern "C" int ldsim_comm_gather_compact(ldsim_ctx* ctx, int32_t root, int32_t s
 extern "C" int ldsim_comm_gathered_compact_download(ldsim_ctx* ctx, int32_t src_rank, int32_t* hit_pixels, int64_t* track_segments,
                                                     void* hit_rows, double* hit_charge, double* fractions) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && ctx->comm, "no communicator");
-  NEEDC(src_rank >= 0 && src_rank < ctx->comm_world, "source rank out of range");
+  NEED(ctx && ctx->comm, "no communicator");
+  NEED(src_rank >= 0 && src_rank < ctx->comm_world, "source rank out of range");
   if (ctx->cpt_all_root != ctx->comm_rank || ctx->cpt_all_src != src_rank) {
     ldsim_set_error("this rank holds no gathered compact results of rank %d (not the root of the last ldsim_comm_gather_compact "
                     "from that rank)", src_rank);
@@ -296,10 +266,10 @@ extern "C" int ldsim_comm_gathered_compact_download(ldsim_ctx* ctx, int32_t src_
 
 extern "C" int ldsim_comm_gatherv_bytes(ldsim_ctx* ctx, int32_t root, const void* host, int64_t n, int64_t* counts) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && ctx->comm, "no communicator");
+  NEED(ctx && ctx->comm, "no communicator");
   const int W = ctx->comm_world, me = ctx->comm_rank;
-  NEEDC(root >= 0 && root < W, "root out of range");
-  NEEDC(n >= 0 && (host || n == 0), "null host buffer / negative length");
+  NEED(root >= 0 && root < W, "root out of range");
+  NEED(n >= 0 && (host || n == 0), "null host buffer / negative length");
   HIPCHK(hipSetDevice(ctx->device));
   ncclComm_t comm = (ncclComm_t)ctx->comm;
   hipStream_t st = ctx->stream;
@@ -315,7 +285,7 @@ extern "C" int ldsim_comm_gatherv_bytes(ldsim_ctx* ctx, int32_t root, const void
   HIPCHK(hipStreamSynchronize(st));
   int64_t total = 0, mine_off = 0;
   for (int r = 0; r < W; r++) {
-    NEEDC(h[r] >= 0, "negative length received");
+    NEED(h[r] >= 0, "negative length received");
     if (r < me) mine_off += h[r];
     total += h[r];
   }
@@ -350,14 +320,14 @@ extern "C" int ldsim_comm_gatherv_bytes(ldsim_ctx* ctx, int32_t root, const void
 
 extern "C" int ldsim_comm_gathered_bytes_download(ldsim_ctx* ctx, int32_t src_rank, void* out) {
   LDSIM_ENTER(ctx);
-  NEEDC(ctx && ctx->comm, "no communicator");
-  NEEDC(src_rank >= 0 && src_rank < ctx->comm_world, "source rank out of range");
+  NEED(ctx && ctx->comm, "no communicator");
+  NEED(src_rank >= 0 && src_rank < ctx->comm_world, "source rank out of range");
   if (ctx->gv_all_root != ctx->comm_rank) {
     ldsim_set_error("this rank holds no gathered bytes (not the root of the last ldsim_comm_gatherv_bytes)");
     return LDSIM_ESTATE;
   }
   const int64_t n = ctx->gv_all_n[src_rank];
-  NEEDC(out || n == 0, "null output buffer");
+  NEED(out || n == 0, "null output buffer");
   if (n == 0) return 0;
   int64_t off = 0;
   for (int r = 0; r < src_rank; r++) off += ctx->gv_all_n[r];

@@ -491,15 +491,15 @@ extern "C++" int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0) {
     return LDSIM_EINVAL;
   }
   // the launch constants: built when the two constants they depend on change, not per launch
-  if (!ctx->d_fee_tab) HIPCHK(hipMalloc((void**)&ctx->d_fee_tab, 128 * sizeof(double)));
+  CK(ctx->d_fee_tab.ensure(128 * sizeof(double)));
   if (ctx->fee_tab_dt != h.time_sampling || ctx->fee_tab_rt != h.buffer_risetime) {
-    hipLaunchKernelGGL(fee_tables_kernel, dim3(1), dim3(64), 0, ctx->stream, h.time_sampling, h.buffer_risetime, ctx->d_fee_tab);
+    hipLaunchKernelGGL(fee_tables_kernel, dim3(1), dim3(64), 0, ctx->stream, h.time_sampling, h.buffer_risetime, ctx->d_fee_tab.as<double>());
     HIPCHK(hipGetLastError());
     ctx->fee_tab_dt = h.time_sampling;
     ctx->fee_tab_rt = h.buffer_risetime;
   }
   FeeArgs F = F0;
-  F.tab = ctx->d_fee_tab;
+  F.tab = ctx->d_fee_tab.as<double>();
   // (the kernel writes the (hit, slot) entries that exist; everything else of `fractions` reads 0 like the reference's array once
   // fee_clear_unwritten_fractions has run: the dense downloads call it -- clearing 12 KB per pixel in every launch cost 0.45 ms per
   // 100 k segments, and the compact download reads the written entries only)
@@ -685,14 +685,14 @@ int fee_launch_adc_dense(ldsim_ctx* ctx, const double* ps, const double* pts, in
     ldsim_set_error("FEE constants exceed the kernel's static tiles");
     return LDSIM_EINVAL;
   }
-  hipLaunchKernelGGL(adc_dense_kernel, dim3((unsigned)U), dim3(FEE_THREADS), 0, ctx->stream, ctx->d_consts, ps, pts, U,
+  hipLaunchKernelGGL(adc_dense_kernel, dim3((unsigned)U), dim3(FEE_THREADS), 0, ctx->stream, ctx->d_consts.as<LdsimConsts>(), ps, pts, U,
                      NT, M, thr, time_padding, t_stop, noise_z, noise_nd, n_draws, adc, ticks, frac);
   HIPCHK(hipGetLastError());
   return 0;
 }
 int fee_launch_digitize(ldsim_ctx* ctx, const double* q, const double* gain, double* out, int64_t n) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(digitize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_consts, q,
+  hipLaunchKernelGGL(digitize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_consts.as<LdsimConsts>(), q,
                      gain, out, n);
   HIPCHK(hipGetLastError());
   return 0;

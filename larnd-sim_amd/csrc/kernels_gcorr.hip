@@ -816,8 +816,8 @@ extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long lo
   GA.maps = (const unsigned char*)ctx->scratch[SB_GMAPS].p;
   GA.rec = (double*)ctx->scratch[SB_WBUF].p;
   GA.flags = (int32_t*)ctx->scratch[SB_ITEMS].p;
-  GA.glx = ctx->d_glx;
-  GA.glw = ctx->d_glw;
+  GA.glx = ctx->d_glx.as<double>();
+  GA.glw = ctx->d_glw.as<double>();
   GA.resp_pad = (const double*)ctx->resp_pad.p;
   auto corr = [&](int cls, int64_t pair0, int64_t count) -> int {
     if (count <= 0) return 0;
@@ -845,9 +845,8 @@ extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long lo
     // VALU-bound kernel beside one that waits on memory and the matrix pipe -- and a range's records (tens of MB) are read back
     // while they are still in the Infinity Cache.  Order: the tables of the listed pairs (wide wave kernel, workgroup kernel) first,
     // then range after range; the correlation's listed launches (larger LDS classes) after the last range.
-    if (!ctx->tab_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->tab_stream, hipStreamNonBlocking));
-    for (int c = 0; c <= K; c++)
-      if (!ctx->tab_ev[c]) HIPCHK(hipEventCreateWithFlags(&ctx->tab_ev[c], hipEventDisableTiming));
+    CK(ctx->tab_stream.ensure(hipStreamNonBlocking));
+    for (int c = 0; c <= K; c++) CK(ctx->tab_ev[c].ensure(hipEventDisableTiming));
     hipStream_t ts = ctx->tab_stream;
     HIPCHK(hipEventRecord(ctx->tab_ev[K], st));                  // (everything the tables need is queued on st before this)
     HIPCHK(hipStreamWaitEvent(ts, ctx->tab_ev[K], 0));

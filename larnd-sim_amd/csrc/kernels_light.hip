@@ -786,7 +786,7 @@ int light_check_emit_overflow(ldsim_ctx* ctx) {
   HIPCHK(hipMemcpy(&f, ctx->light_emit_flag, 4, hipMemcpyDeviceToHost));
   ctx->light_emit_flag = nullptr;
   if (f) {
-    HIPCHK(hipMemset(ctx->light_flag_dev, 0, 4));
+    HIPCHK(hipMemset(ctx->light_flag_dev.as<unsigned>(), 0, 4));
     ldsim_set_error("photon sum with truth slots: a (detector, segment) pair deposited into more ticks than its record slots hold "
                     "(profile bins + 2); the arrays of that sum are incomplete");
     return LDSIM_ESTATE;
@@ -812,19 +812,19 @@ int light_launch_incidence(ldsim_ctx* ctx, int64_t seg0, int64_t n, int n_out, f
   if (n_out % 4 == 0 && ctx->lut_ndet % 4 == 0 && ctx->light_eff_plain && !ctx->light_incidence_scalar) {
     const dim3 grid((unsigned)((n + LI_SEGS - 1) / LI_SEGS));
     if (n_out < ctx->h_consts.n_op_channel)
-      hipLaunchKernelGGL(light_incidence4_kernel<false>, grid, dim3(256), 0, ctx->stream, ctx->seg, ctx->d_consts, seg0, n,
-                         ctx->d_lut_vis, ctx->d_lut_t0, ctx->lut_nx, ctx->lut_ny, ctx->lut_nz, ctx->lut_ndet, ctx->d_eff,
-                         ctx->d_ch2tpc, n_out, nph, t0det, voxel, fill);
+      hipLaunchKernelGGL(light_incidence4_kernel<false>, grid, dim3(256), 0, ctx->stream, ctx->seg, ctx->d_consts.as<LdsimConsts>(), seg0, n,
+                         ctx->d_lut_vis.as<float>(), ctx->d_lut_t0.as<float>(), ctx->lut_nx, ctx->lut_ny, ctx->lut_nz, ctx->lut_ndet, ctx->d_eff.as<double>(),
+                         ctx->d_ch2tpc.as<int32_t>(), n_out, nph, t0det, voxel, fill);
     else
-      hipLaunchKernelGGL(light_incidence4_kernel<true>, grid, dim3(256), 0, ctx->stream, ctx->seg, ctx->d_consts, seg0, n,
-                         ctx->d_lut_vis, ctx->d_lut_t0, ctx->lut_nx, ctx->lut_ny, ctx->lut_nz, ctx->lut_ndet, ctx->d_eff,
-                         ctx->d_ch2tpc, n_out, nph, t0det, voxel, fill);
+      hipLaunchKernelGGL(light_incidence4_kernel<true>, grid, dim3(256), 0, ctx->stream, ctx->seg, ctx->d_consts.as<LdsimConsts>(), seg0, n,
+                         ctx->d_lut_vis.as<float>(), ctx->d_lut_t0.as<float>(), ctx->lut_nx, ctx->lut_ny, ctx->lut_nz, ctx->lut_ndet, ctx->d_eff.as<double>(),
+                         ctx->d_ch2tpc.as<int32_t>(), n_out, nph, t0det, voxel, fill);
     HIPCHK(hipGetLastError());
     return 0;
   }
   hipLaunchKernelGGL(light_incidence_kernel, dim3((unsigned)((n + LI_SEGS - 1) / LI_SEGS)), dim3(256), 0, ctx->stream,
-                     ctx->seg, ctx->d_consts, seg0, n, ctx->d_lut_vis, ctx->d_lut_t0, ctx->lut_nx, ctx->lut_ny,
-                     ctx->lut_nz, ctx->lut_ndet, ctx->d_eff, ctx->d_ch2tpc, n_out, nph, t0det, voxel, fill);
+                     ctx->seg, ctx->d_consts.as<LdsimConsts>(), seg0, n, ctx->d_lut_vis.as<float>(), ctx->d_lut_t0.as<float>(), ctx->lut_nx, ctx->lut_ny,
+                     ctx->lut_nz, ctx->lut_ndet, ctx->d_eff.as<double>(), ctx->d_ch2tpc.as<int32_t>(), n_out, nph, t0det, voxel, fill);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -853,8 +853,8 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
     return 0;
   }
   LightSum L;
-  L.s = ctx->seg; L.c = ctx->d_consts; L.seg0 = seg0; L.n = n; L.voxel = voxel; L.nph = nph; L.n_inc = n_inc;
-  L.op_channel = op_channel; L.n_det = n_det; L.t0_avg = ctx->d_lut_t0avg; L.time_dist = ctx->d_lut_td;
+  L.s = ctx->seg; L.c = ctx->d_consts.as<LdsimConsts>(); L.seg0 = seg0; L.n = n; L.voxel = voxel; L.nph = nph; L.n_inc = n_inc;
+  L.op_channel = op_channel; L.n_det = n_det; L.t0_avg = ctx->d_lut_t0avg.as<float>(); L.time_dist = ctx->d_lut_td.as<float>();
   L.ny = ctx->lut_ny; L.nz = ctx->lut_nz; L.ndet_lut = ctx->lut_ndet; L.nprof = ctx->lut_nprof;
   L.start_time = start_time; L.n_ticks = n_ticks;
   hipStream_t st = ctx->stream;
@@ -890,9 +890,9 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
     // ---- resident sum, compact form (kernels above): pairs with photons -> visiting order -> records by wave -> cells -> replay ----
     const int cap = (ctx->h_consts.enable_lut_smearing ? ctx->lut_nprof : 1) + LIGHT_SPARE;
     if ((rc = ldsim_ensure_buf(ctx, &T[1], 64))) return rc;                        // [0] pairs with photons
-    if (!ctx->light_flag_dev) {                                                       // record slot overflow: sticky until read
-      HIPCHK(hipMalloc((void**)&ctx->light_flag_dev, 8));
-      HIPCHK(hipMemsetAsync(ctx->light_flag_dev, 0, 8, st));
+    if (!ctx->light_flag_dev.p) {                                                     // record slot overflow: sticky until read
+      CK(ctx->light_flag_dev.ensure(8));
+      HIPCHK(hipMemsetAsync(ctx->light_flag_dev.as<unsigned>(), 0, 8, st));
     }
     if ((rc = ldsim_ensure_buf(ctx, &T[3], (size_t)np * 8))) return rc;
     if ((rc = ldsim_ensure_buf(ctx, &T[0], (size_t)np * 8))) return rc;
@@ -925,7 +925,7 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
     unsigned *k0 = (unsigned*)T[3].p, *k1 = (unsigned*)T[4].p;
     unsigned long long *v0 = (unsigned long long*)T[7].p, *v1 = (unsigned long long*)T[8].p;
     hipLaunchKernelGGL(light_emit_wave_kernel, dim3(nblk(n_act, 4)), dim3(256), 0, st, L, (const int32_t*)T[6].p, n_act, cap, tick_bits,
-                       k0, v0, ctx->light_flag_dev);
+                       k0, v0, ctx->light_flag_dev.as<unsigned>());
     HIPCHK(hipGetLastError());
     // The records leave the emit kernel detector after detector: a STABLE sort on the tick bits alone puts a (detector, tick) cell's
     // records side by side -- tick-major, detectors ascending inside a tick -- in their order of emission, in two radix passes for up
@@ -936,7 +936,7 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
                        track_id, n_ticks, ctx->h_consts.mc_truth_threshold, out, true_id, true_ph, max_truth, 1);
     HIPCHK(hipGetLastError());
     *n_rec_out = n_slots;
-    ctx->light_emit_flag = ctx->light_flag_dev;  // (read at the next synchronising call: light_check_emit_overflow)
+    ctx->light_emit_flag = ctx->light_flag_dev.as<unsigned>();  // (read at the next synchronising call: light_check_emit_overflow)
     return 0;
   }
   if ((rc = ldsim_ensure_buf(ctx, &T[1], (size_t)np * 4 + 16))) return rc;     // count, then offsets in T[2]

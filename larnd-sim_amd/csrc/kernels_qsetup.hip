@@ -279,7 +279,7 @@ extern "C++" size_t qpair_params_bytes(int64_t n_pairs) { return (size_t)n_pairs
 // the per-pair records of both quadrature weight kernels
 extern "C++" int qpair_setup_launch(ldsim_ctx* ctx, const SplitArgs& S, int M, void* params, void* ginfo, void* maps) {
   if (S.c.n_pairs == 0) return 0;
-  if (!ctx->d_glx || !ctx->d_glw || !params) {
+  if (!ctx->d_glx.p || !ctx->d_glw.p || !params) {
     ldsim_set_error("Gauss-Legendre tables / pair parameter buffer missing");
     return LDSIM_ESTATE;
   }

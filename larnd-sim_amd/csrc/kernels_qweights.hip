@@ -577,11 +577,11 @@ extern "C++" int qweights_launch(ldsim_ctx* ctx, const SplitArgs& S, int M, void
   if (rc) return rc;
   const PairParams* pp = (const PairParams*)params;
   if (M == 1)
-    hipLaunchKernelGGL(qweights_kernel<1>, dim3((unsigned)S.c.n_pairs), dim3(CUR_THREADS), 0, ctx->stream, S, pp, ctx->d_glx,
-                       ctx->d_glw);
+    hipLaunchKernelGGL(qweights_kernel<1>, dim3((unsigned)S.c.n_pairs), dim3(CUR_THREADS), 0, ctx->stream, S, pp, ctx->d_glx.as<double>(),
+                       ctx->d_glw.as<double>());
   else
-    hipLaunchKernelGGL(qweights_kernel<2>, dim3((unsigned)S.c.n_pairs), dim3(CUR_THREADS), 0, ctx->stream, S, pp, ctx->d_glx,
-                       ctx->d_glw);
+    hipLaunchKernelGGL(qweights_kernel<2>, dim3((unsigned)S.c.n_pairs), dim3(CUR_THREADS), 0, ctx->stream, S, pp, ctx->d_glx.as<double>(),
+                       ctx->d_glw.as<double>());
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -111,15 +111,7 @@ static int rng_append(ldsim_ctx* ctx, int64_t n, const uint64_t* fresh_seed) {
     fresh[i] = cur;
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if ((size_t)n * sizeof(RngState) > ctx->d_rng.bytes) {
-    const int64_t cap = n + n / 4 + 1024;
-    DevBuf nb;
-    int rc = ldsim_ensure_buf(ctx, &nb, (size_t)cap * sizeof(RngState));
-    if (rc) return rc;
-    if (ctx->rng_n) HIPCHK(hipMemcpy(nb.p, ctx->d_rng.p, (size_t)ctx->rng_n * sizeof(RngState), hipMemcpyDeviceToDevice));
-    if (ctx->d_rng.p) (void)hipFree(ctx->d_rng.p);
-    ctx->d_rng = nb;
-  }
+  CK(ctx->d_rng.grow_keep(ctx->stream, (size_t)ctx->rng_n * sizeof(RngState), (size_t)n * sizeof(RngState)));
   HIPCHK(hipMemcpy((char*)ctx->d_rng.p + (size_t)ctx->rng_n * sizeof(RngState), fresh.data(), fresh.size() * sizeof(RngState),
                    hipMemcpyHostToDevice));
   ctx->rng_n = n;
@@ -174,8 +166,7 @@ extern "C" int ldsim_rng_seed(ldsim_ctx* ctx, uint64_t seed, int64_t n_states) {
   }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_rng.p) (void)hipFree(ctx->d_rng.p);
-  ctx->d_rng = DevBuf{};
+  ctx->d_rng.reset();
   ctx->rng_n = 0;
   ctx->rng_seed = seed;
   ctx->rng_seeded = 1;
@@ -215,8 +206,7 @@ extern "C" int ldsim_rng_clear(ldsim_ctx* ctx) {
   LDSIM_ENTER(ctx);
   if (!ctx) return 0;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_rng.p) (void)hipFree(ctx->d_rng.p);
-  ctx->d_rng = DevBuf{};
+  ctx->d_rng.reset();
   ctx->rng_n = 0;
   ctx->rng_seeded = 0;
   ctx->rng_keyed = 0;
@@ -293,24 +283,18 @@ static int rng_keyed_draws(ldsim_ctx* ctx, uint32_t tag, const uint64_t* stream_
   if (n == 0 || nd == 0) return 0;
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t total = n * (int64_t)nd;
-  void *dk = nullptr, *dout = nullptr;
-  HIPCHK(hipMalloc(&dk, (size_t)n * 8));
-  if (hipMalloc(&dout, (size_t)total * 4) != hipSuccess) {
-    (void)hipFree(dk);
-    ldsim_set_error("out of device memory");
-    return LDSIM_EINVAL;
-  }
+  DevBuf dk, dout;
+  CK(dk.ensure((size_t)n * 8));
+  CK(dout.ensure((size_t)total * 4));
   int rc = 0;
-  if (hipMemcpy(dk, stream_keys, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) rc = LDSIM_EINVAL;
+  if (hipMemcpy(dk.p, stream_keys, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) rc = LDSIM_EINVAL;
   if (!rc) {
     hipLaunchKernelGGL(rng_keyed_draw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rng_seed,
-                       tag, (const uint64_t*)dk, n, d0, nd, normal, (float*)dout);
+                       tag, dk.as<uint64_t>(), n, d0, nd, normal, dout.as<float>());
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(out, dout, (size_t)total * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(out, dout.p, (size_t)total * 4, hipMemcpyDeviceToHost) != hipSuccess)
       rc = LDSIM_EINVAL;
   }
-  (void)hipFree(dk);
-  (void)hipFree(dout);
   if (rc) ldsim_set_error("keyed draws: a HIP call failed");
   return rc;
 }

@@ -420,21 +420,21 @@ int seg_launch_repack(ldsim_ctx* ctx, const LdsimTrackLayout* lay, int64_t n) {
 int seg_launch_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, int* d_err) {
   if (ctx->seg.n == 0) return 0;
   hipLaunchKernelGGL(quench_drift_kernel, dim3(nblk(ctx->seg.n, 256)), dim3(256), 0, ctx->stream, ctx->seg,
-                     ctx->d_consts, mode, do_q, do_d, d_err);
+                     ctx->d_consts.as<LdsimConsts>(), mode, do_q, do_d, d_err);
   HIPCHK(hipGetLastError());
   return 0;
 }
 int seg_launch_quench_drift_map(ldsim_ctx* ctx, int mode, int* d_err) {
   if (ctx->seg.n == 0) return 0;
   hipLaunchKernelGGL(quench_drift_map_kernel, dim3(nblk(ctx->seg.n, 256)), dim3(256), 0, ctx->stream, ctx->seg,
-                     ctx->d_consts, mode, (const FieldMapDesc*)ctx->d_fmap, (double*)ctx->fmap_view.p, ctx->fmap_view_cap,
+                     ctx->d_consts.as<LdsimConsts>(), mode, (const FieldMapDesc*)ctx->d_fmap.as<FieldMapDesc>(), (double*)ctx->fmap_view.p, ctx->fmap_view_cap,
                      d_err);
   HIPCHK(hipGetLastError());
   return 0;
 }
 int seg_launch_max_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int32_t* d_nmax, unsigned long long* d_tranbits) {
   if (e <= b) return 0;
-  hipLaunchKernelGGL(max_pixels_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, charge_store(ctx), ctx->d_consts,
+  hipLaunchKernelGGL(max_pixels_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, charge_store(ctx), ctx->d_consts.as<LdsimConsts>(),
                      b, e, d_nmax, d_tranbits);
   HIPCHK(hipGetLastError());
   return 0;
@@ -443,7 +443,7 @@ int seg_launch_get_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int radius, int3
                           int32_t* neigh, int32_t* nrad, int P, double* n_list, const int32_t* radius_b,
                           int32_t batch0) {
   if (e <= b) return 0;
-  hipLaunchKernelGGL(get_pixels_kernel, dim3(nblk(e - b, 128)), dim3(128), 0, ctx->stream, charge_store(ctx), ctx->d_consts,
+  hipLaunchKernelGGL(get_pixels_kernel, dim3(nblk(e - b, 128)), dim3(128), 0, ctx->stream, charge_store(ctx), ctx->d_consts.as<LdsimConsts>(),
                      b, e, radius, active, max_active, neigh, nrad, P, n_list, radius_b, batch0);
   HIPCHK(hipGetLastError());
   return 0;
@@ -451,7 +451,7 @@ int seg_launch_get_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int radius, int3
 int seg_launch_time_intervals(ldsim_ctx* ctx, int64_t b, int64_t e, double* starts, int32_t* tmax) {
   if (e <= b) return 0;
   hipLaunchKernelGGL(time_intervals_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, charge_store(ctx),
-                     ctx->d_consts, b, e, starts, tmax);
+                     ctx->d_consts.as<LdsimConsts>(), b, e, starts, tmax);
   HIPCHK(hipGetLastError());
   return 0;
 }

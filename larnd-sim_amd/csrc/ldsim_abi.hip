@@ -81,45 +81,13 @@ extern "C" int ldsim_device_count(void) {
   return n;
 }
 
-int ldsim_ensure_buf(ldsim_ctx* ctx, DevBuf* b, size_t bytes) {
-  (void)ctx;
-  if (bytes <= b->bytes && b->p) return 0;
-  if (b->p) HIPCHK(hipFree(b->p));
-  b->p = nullptr;
-  b->bytes = 0;
-  size_t want = bytes + bytes / 8 + 256;
-  HIPCHK(hipMalloc(&b->p, want));
-  b->bytes = want;
+// device buffers, streams and events the library holds in this process (the owner types of ldsim_dev.h count them)
+std::atomic<int64_t> ldsim_live[3];
+extern "C" int ldsim_debug_live_objects(int64_t counts[3]) {
+  NEED(counts, "null argument");
+  for (int k = 0; k < 3; k++) counts[k] = ldsim_live[k].load();
   return 0;
 }
-int ldsim_ensure(ldsim_ctx* ctx, int slot, size_t bytes) { return ldsim_ensure_buf(ctx, &ctx->scratch[slot], bytes); }
-
-// temporary device buffer for the host-buffer API
-struct Tmp {
-  void* p = nullptr;
-  ~Tmp() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    HIPCHK(hipMalloc(&p, bytes ? bytes : 8));
-    return 0;
-  }
-  template <class T>
-  T* as() { return (T*)p; }
-};
-
-#define CK(x)                \
-  do {                       \
-    int rc_ = (x);           \
-    if (rc_) return rc_;     \
-  } while (0)
-#define NEED(cond, msg)            \
-  do {                             \
-    if (!(cond)) {                 \
-      ldsim_set_error("%s", msg);  \
-      return LDSIM_EINVAL;         \
-    }                              \
-  } while (0)
 
 // Photon sums issued on the light stream (option light_sum_async) read the segment store, the incidence arrays, the LUT and the
 // constants, and write the resident photon-sum array: every entry point that writes one of the former or reads the latter makes
@@ -172,20 +140,21 @@ static int make_gl_tables(ldsim_ctx* ctx, int nmax) {
       w[off + k] = w[off + n - 1 - k] = (double)wt;
     }
   }
-  HIPCHK(hipMalloc((void**)&ctx->d_glx, total * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&ctx->d_glw, total * sizeof(double)));
-  HIPCHK(hipMemcpy(ctx->d_glx, x.data(), total * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_glw, w.data(), total * sizeof(double), hipMemcpyHostToDevice));
+  CK(ctx->d_glx.ensure(total * sizeof(double)));
+  CK(ctx->d_glw.ensure(total * sizeof(double)));
+  HIPCHK(hipMemcpy(ctx->d_glx.p, x.data(), total * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->d_glw.p, w.data(), total * sizeof(double), hipMemcpyHostToDevice));
   ctx->gl_nmax = nmax;
   return 0;
 }
 
 // ---- context ------------------------------------------------------------------------------------------------------
 static int ctx_init(ldsim_ctx* ctx, const LdsimConsts* consts) {
-  HIPCHK(hipStreamCreate(&ctx->stream));
-  HIPCHK(hipMalloc((void**)&ctx->d_consts, sizeof(LdsimConsts)));
-  for (int i = 0; i < 8; i++) HIPCHK(hipEventCreate(&ctx->ev[i]));
-  for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&ctx->evl[i]));
+  CK(ctx->main_stream.ensure());
+  ctx->stream = ctx->main_stream;
+  CK(ctx->d_consts.ensure(sizeof(LdsimConsts)));
+  for (Event& e : ctx->ev) CK(e.ensure());
+  for (Event& e : ctx->evl) CK(e.ensure());
   CK(make_gl_tables(ctx, 256));
   return ldsim_set_consts(ctx, consts);
 }
@@ -221,7 +190,7 @@ extern "C" int ldsim_set_consts(ldsim_ctx* ctx, const LdsimConsts* consts) {
   // instead of keeping the high-water mark of everything this process has ever run
   if (memcmp(&ctx->h_consts, consts, sizeof(LdsimConsts)) != 0) ctx->wbuf_learned = 0;
   ctx->h_consts = *consts;
-  HIPCHK(hipMemcpyAsync(ctx->d_consts, &ctx->h_consts, sizeof(LdsimConsts), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->d_consts.p, &ctx->h_consts, sizeof(LdsimConsts), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -238,56 +207,9 @@ extern "C" int ldsim_ctx_destroy(ldsim_ctx* ctx) {
     }
   }
   (void)hipSetDevice(ctx->device);
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  void* ptrs[] = {ctx->d_consts, ctx->d_resp,      ctx->d_eff,    ctx->d_ch2tpc, ctx->d_lut_vis, ctx->d_lut_t0,
-                  ctx->d_lut_t0avg, ctx->d_lut_td, ctx->seg_block.p, ctx->raw.p,  ctx->d_pix_thr, ctx->d_pix_gain,
-                  ctx->d_glx, ctx->d_glw, ctx->light_flag_dev, ctx->d_fee_tab};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (ctx->copy_stream) {
-    (void)hipStreamSynchronize(ctx->copy_stream);
-    (void)hipStreamDestroy(ctx->copy_stream);
-  }
-  if (ctx->light_stream) {
-    (void)hipStreamSynchronize(ctx->light_stream);
-    (void)hipStreamDestroy(ctx->light_stream);
-  }
-  if (ctx->tab_stream) {
-    (void)hipStreamSynchronize(ctx->tab_stream);
-    (void)hipStreamDestroy(ctx->tab_stream);
-  }
-  for (auto& e : ctx->tab_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->ev_light_in) (void)hipEventDestroy(ctx->ev_light_in);
-  if (ctx->ev_light_done) (void)hipEventDestroy(ctx->ev_light_done);
-  for (auto& b : ctx->scratch)
-    if (b.p) (void)hipFree(b.p);
-  for (auto& b : ctx->out_alt)
-    if (b.p) (void)hipFree(b.p);
-  for (int i = 0; i < 8; i++)
-    if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-  for (int i = 0; i < 4; i++)
-    if (ctx->evl[i]) (void)hipEventDestroy(ctx->evl[i]);
-  for (DevBuf* b : {&ctx->light_nph, &ctx->light_t0, &ctx->light_vox, &ctx->light_out, &ctx->light_tid, &ctx->light_tph,
-                    &ctx->light_opc, &ctx->light_trk, &ctx->light_scint, &ctx->light_scint_tid, &ctx->light_scint_tph,
-                    &ctx->light_disc, &ctx->light_resp, &ctx->light_resp_tid, &ctx->light_resp_tph, &ctx->light_w[0],
-                    &ctx->light_w[1], &ctx->light_gain, &ctx->resp_pad, &ctx->light_tmax, &ctx->light_env, &ctx->light_xd, &ctx->light_wtid, &ctx->light_wtph, &ctx->light_wtid2})
-    if (b->p) (void)hipFree(b->p);
-  for (auto& b : ctx->light_tmp)
-    if (b.p) (void)hipFree(b.p);
+  for (Stream* st : {&ctx->main_stream, &ctx->copy_stream, &ctx->light_stream, &ctx->tab_stream})
+    if (st->s) (void)hipStreamSynchronize(st->s);
   (void)ldsim_comm_destroy(ctx);
-  if (ctx->d_rng.p) (void)hipFree(ctx->d_rng.p);
-  if (ctx->d_batch_keys.p) (void)hipFree(ctx->d_batch_keys.p);
-  for (DevBuf& b : ctx->fmap_nodes)
-    if (b.p) (void)hipFree(b.p);
-  if (ctx->fmap_view.p) (void)hipFree(ctx->fmap_view.p);
-  if (ctx->d_fmap) (void)hipFree(ctx->d_fmap);
-  for (DevBuf* b : {&ctx->comm_tmp, &ctx->hits_acc, &ctx->hits_all, &ctx->gv_send, &ctx->gv_all})
-    if (b->p) (void)hipFree(b->p);
-  for (int k = 0; k < 5; k++)
-    for (DevBuf* b : {&ctx->cpt_acc[k], &ctx->cpt_all[k]})
-      if (b->p) (void)hipFree(b->p);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return 0;
 }
@@ -371,7 +293,7 @@ extern "C" int ldsim_set_option(ldsim_ctx* ctx, const char* name, double value) 
 }
 
 // dense table over all pixel ids of the current geometry: the reference's CudaDict lookup with its default
-static int set_pixel_table(ldsim_ctx* ctx, double** slot, const int32_t* keys, const double* values, int64_t n,
+static int set_pixel_table(ldsim_ctx* ctx, DevBuf* slot, const int32_t* keys, const double* values, int64_t n,
                            double default_value) {
   NEED(ctx && n >= 0 && (n == 0 || (keys && values)), "bad pixel table");
   HIPCHK(hipSetDevice(ctx->device));
@@ -379,17 +301,16 @@ static int set_pixel_table(ldsim_ctx* ctx, double** slot, const int32_t* keys, c
   const int64_t n_ids = (int64_t)h.n_pixels[0] * h.n_pixels[1] * h.n_tpc;
   NEED(n_ids > 0, "pixel geometry not set");
   if (ctx->pix_table_n != n_ids) {        // tables of another geometry cannot be mixed with this one
-    if (ctx->d_pix_thr) (void)hipFree(ctx->d_pix_thr);
-    if (ctx->d_pix_gain) (void)hipFree(ctx->d_pix_gain);
-    ctx->d_pix_thr = ctx->d_pix_gain = nullptr;
+    ctx->d_pix_thr.reset();
+    ctx->d_pix_gain.reset();
     ctx->pix_table_n = n_ids;
   }
   std::vector<double> tab((size_t)n_ids, default_value);
   for (int64_t i = 0; i < n; i++)
     if (keys[i] >= 0 && keys[i] < n_ids) tab[(size_t)keys[i]] = values[i];   // other keys can never be looked up
-  if (!*slot) HIPCHK(hipMalloc((void**)slot, (size_t)n_ids * sizeof(double)));
+  CK(slot->ensure((size_t)n_ids * sizeof(double)));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(*slot, tab.data(), (size_t)n_ids * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(slot->p, tab.data(), (size_t)n_ids * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -412,9 +333,8 @@ extern "C" int ldsim_clear_pixel_tables(ldsim_ctx* ctx) {
   NEED(ctx, "null ctx");
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_pix_thr) (void)hipFree(ctx->d_pix_thr);
-  if (ctx->d_pix_gain) (void)hipFree(ctx->d_pix_gain);
-  ctx->d_pix_thr = ctx->d_pix_gain = nullptr;
+  ctx->d_pix_thr.reset();
+  ctx->d_pix_gain.reset();
   ctx->pix_table_n = 0;
   return 0;
 }
@@ -439,10 +359,11 @@ extern "C" int ldsim_set_response(ldsim_ctx* ctx, const double* response, int32_
   LDSIM_ENTER(ctx);
   NEED(ctx && response && ni > 0 && nj > 0 && nk > 0, "bad response table");
   HIPCHK(hipSetDevice(ctx->device));
-  if (ctx->d_resp) HIPCHK(hipFree(ctx->d_resp));
   size_t bytes = (size_t)ni * nj * nk * sizeof(double);
-  HIPCHK(hipMalloc((void**)&ctx->d_resp, bytes));
-  HIPCHK(hipMemcpy(ctx->d_resp, response, bytes, hipMemcpyHostToDevice));
+  DevBuf nb;                                 // (a failed replacement leaves the old table in place)
+  CK(nb.ensure(bytes));
+  HIPCHK(hipMemcpy(nb.p, response, bytes, hipMemcpyHostToDevice));
+  ctx->d_resp = std::move(nb);
   ctx->ni = ni; ctx->nj = nj; ctx->nk = nk;
   // largest |entry| of every tick over all cells: the support of the table along k follows from it for any trim threshold
   ctx->h_resp_kmax.assign((size_t)nk, 0.0);
@@ -462,17 +383,19 @@ extern "C" int ldsim_set_light_channels(ldsim_ctx* ctx, const double* eff, const
   LDSIM_ENTER(ctx);
   NEED(ctx && n >= 0, "bad light channels");
   CK(light_join(ctx));
-  if (ctx->d_eff) HIPCHK(hipFree(ctx->d_eff));
-  if (ctx->d_ch2tpc) HIPCHK(hipFree(ctx->d_ch2tpc));
-  ctx->d_eff = nullptr; ctx->d_ch2tpc = nullptr; ctx->n_light_ch = n;
-  if (n == 0) return 0;
-  HIPCHK(hipMalloc((void**)&ctx->d_eff, n * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&ctx->d_ch2tpc, n * sizeof(int32_t)));
-  HIPCHK(hipMemcpy(ctx->d_eff, eff, n * sizeof(double), hipMemcpyHostToDevice));
-  ctx->light_eff_plain = 1;             // finite, non-negative efficiencies: what light_incidence4_kernel's zero fill assumes
-  for (int32_t i = 0; i < n; i++)
-    if (!(eff[i] >= 0.0 && eff[i] <= 1.7e308)) ctx->light_eff_plain = 0;
-  HIPCHK(hipMemcpy(ctx->d_ch2tpc, ch2tpc, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  DevBuf d_eff, d_ch2tpc;
+  if (n) {
+    CK(d_eff.ensure(n * sizeof(double)));
+    CK(d_ch2tpc.ensure(n * sizeof(int32_t)));
+    HIPCHK(hipMemcpy(d_eff.p, eff, n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ch2tpc.p, ch2tpc, n * sizeof(int32_t), hipMemcpyHostToDevice));
+    ctx->light_eff_plain = 1;           // finite, non-negative efficiencies: what light_incidence4_kernel's zero fill assumes
+    for (int32_t i = 0; i < n; i++)
+      if (!(eff[i] >= 0.0 && eff[i] <= 1.7e308)) ctx->light_eff_plain = 0;
+  }
+  ctx->d_eff = std::move(d_eff);
+  ctx->d_ch2tpc = std::move(d_ch2tpc);
+  ctx->n_light_ch = n;
   return 0;
 }
 
@@ -483,14 +406,15 @@ extern "C" int ldsim_set_light_lut(ldsim_ctx* ctx, const float* vis, const float
   NEED(ctx && vis && t0 && t0_avg && time_dist, "null LUT plane");
   CK(light_join(ctx));
   size_t nv = (size_t)nx * ny * nz * ndet;
-  float** dst[] = {&ctx->d_lut_vis, &ctx->d_lut_t0, &ctx->d_lut_t0avg, &ctx->d_lut_td};
+  DevBuf* dst[] = {&ctx->d_lut_vis, &ctx->d_lut_t0, &ctx->d_lut_t0avg, &ctx->d_lut_td};
   const float* src[] = {vis, t0, t0_avg, time_dist};
   size_t cnt[] = {nv, nv, nv, nv * nprof};
+  DevBuf nb[4];
   for (int i = 0; i < 4; i++) {
-    if (*dst[i]) HIPCHK(hipFree(*dst[i]));
-    HIPCHK(hipMalloc((void**)dst[i], cnt[i] * sizeof(float)));
-    HIPCHK(hipMemcpy(*dst[i], src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice));
+    CK(nb[i].ensure(cnt[i] * sizeof(float)));
+    HIPCHK(hipMemcpy(nb[i].p, src[i], cnt[i] * sizeof(float), hipMemcpyHostToDevice));
   }
+  for (int i = 0; i < 4; i++) *dst[i] = std::move(nb[i]);
   ctx->lut_nx = nx; ctx->lut_ny = ny; ctx->lut_nz = nz; ctx->lut_ndet = ndet; ctx->lut_nprof = nprof;
   return 0;
 }
@@ -667,8 +591,8 @@ extern "C" int ldsim_dev_quench_drift(ldsim_ctx* ctx, int32_t mode) {
 
 // ---- drift-field maps ----------------------------------------------------------------------------------------------------
 static int fmap_upload_desc(ldsim_ctx* ctx) {
-  if (!ctx->d_fmap) HIPCHK(hipMalloc((void**)&ctx->d_fmap, sizeof(ctx->h_fmap)));
-  HIPCHK(hipMemcpyAsync(ctx->d_fmap, ctx->h_fmap, sizeof(ctx->h_fmap), hipMemcpyHostToDevice, ctx->stream));
+  CK(ctx->d_fmap.ensure(sizeof(ctx->h_fmap)));
+  HIPCHK(hipMemcpyAsync(ctx->d_fmap.p, ctx->h_fmap, sizeof(ctx->h_fmap), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -743,21 +667,20 @@ extern "C" int ldsim_clear_field_maps(ldsim_ctx* ctx) {
   LDSIM_ENTER(ctx);
   NEED(ctx, "null ctx");
   ctx->fmap_gen++;
-  if (ctx->n_fmap == 0 && !ctx->fmap_view.p) return 0;
+  if (ctx->n_fmap == 0 && !ctx->fmap_view.p && !ctx->d_fmap.p) return 0;
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (int t = 0; t < LDSIM_MAX_TPC; t++) {
     ctx->h_fmap[t] = FieldMapDesc{};
-    if (ctx->fmap_nodes[t].p) HIPCHK(hipFree(ctx->fmap_nodes[t].p));
-    ctx->fmap_nodes[t] = DevBuf{};
+    ctx->fmap_nodes[t].reset();
   }
   ctx->n_fmap = 0;
-  if (ctx->fmap_view.p) HIPCHK(hipFree(ctx->fmap_view.p));
-  ctx->fmap_view = DevBuf{};
+  ctx->fmap_view.reset();
   ctx->fmap_view_cap = 0;
+  ctx->d_fmap.reset();                                      // (read by the mapped quench_drift only: the next set uploads it again)
   if (ctx->drift_map_gen >= 0) ctx->drift_map_gen = -2;     // the store's drift came from a map that is gone
-  return fmap_upload_desc(ctx);
+  return 0;
 }
 
 extern "C" int ldsim_dev_anode_view_download(ldsim_ctx* ctx, double* out) {
@@ -851,21 +774,31 @@ extern "C" int ldsim_time_intervals(ldsim_ctx* ctx, const void* tracks, int64_t 
   return 0;
 }
 
-extern "C" int ldsim_tracks_current(ldsim_ctx* ctx, const void* tracks, int64_t n, const LdsimTrackLayout* layout,
-                                    const int32_t* pixels, int32_t P, float* signals, int32_t T) {
-  LDSIM_ENTER(ctx);
-  NEED(pixels && signals && P >= 0 && T >= 0, "bad tracks_current arguments");
-  NEED(ctx && ctx->d_resp, "no response table set (ldsim_set_response)");
+// ldsim_tracks_current and ldsim_tracks_current_mc (mc = 1: current_mc_kernel, which draws random numbers)
+static int tracks_current_stage(ldsim_ctx* ctx, const void* tracks, int64_t n, const LdsimTrackLayout* layout,
+                                const int32_t* pixels, int32_t P, float* signals, int32_t T, int mc) {
+  NEED(pixels && signals && P >= 0 && T >= 0, mc ? "bad tracks_current_mc arguments" : "bad tracks_current arguments");
+  NEED(ctx && ctx->d_resp.p, "no response table set (ldsim_set_response)");
+  if (mc && ctx->rng_keyed) {
+    ldsim_set_error(LDSIM_KEYED_STAGE_MSG, "ldsim_tracks_current_mc");
+    return LDSIM_ESTATE;
+  }
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
   size_t bp = (size_t)n * P * 4, bs = (size_t)n * P * T * 4;
   if (bs == 0) return 0;
   CK(ldsim_ensure(ctx, SB_NEIGH, bp));
   CK(ldsim_ensure(ctx, SB_WAVES, bs));
   HIPCHK(hipMemcpyAsync(ctx->scratch[SB_NEIGH].p, pixels, bp, hipMemcpyHostToDevice, ctx->stream));
-  CK(chain_tracks_current(ctx, (const int32_t*)ctx->scratch[SB_NEIGH].p, P, (float*)ctx->scratch[SB_WAVES].p, T, 0));
+  CK(chain_tracks_current(ctx, (const int32_t*)ctx->scratch[SB_NEIGH].p, P, (float*)ctx->scratch[SB_WAVES].p, T, mc));
   HIPCHK(hipMemcpyAsync(signals, ctx->scratch[SB_WAVES].p, bs, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+extern "C" int ldsim_tracks_current(ldsim_ctx* ctx, const void* tracks, int64_t n, const LdsimTrackLayout* layout,
+                                    const int32_t* pixels, int32_t P, float* signals, int32_t T) {
+  LDSIM_ENTER(ctx);
+  return tracks_current_stage(ctx, tracks, n, layout, pixels, P, signals, T, 0);
 }
 
 extern "C" int ldsim_tracks_current_stats(ldsim_ctx* ctx, LdsimChainStats* stats) {
@@ -878,22 +811,7 @@ extern "C" int ldsim_tracks_current_stats(ldsim_ctx* ctx, LdsimChainStats* stats
 extern "C" int ldsim_tracks_current_mc(ldsim_ctx* ctx, const void* tracks, int64_t n, const LdsimTrackLayout* layout,
                                        const int32_t* pixels, int32_t P, float* signals, int32_t T) {
   LDSIM_ENTER(ctx);
-  NEED(pixels && signals && P >= 0 && T >= 0, "bad tracks_current_mc arguments");
-  NEED(ctx && ctx->d_resp, "no response table set (ldsim_set_response)");
-  if (ctx->rng_keyed) {
-    ldsim_set_error(LDSIM_KEYED_STAGE_MSG, "ldsim_tracks_current_mc");
-    return LDSIM_ESTATE;
-  }
-  CK(upload_tracks(ctx, tracks, n, layout, nullptr));
-  size_t bp = (size_t)n * P * 4, bs = (size_t)n * P * T * 4;
-  if (bs == 0) return 0;
-  CK(ldsim_ensure(ctx, SB_NEIGH, bp));
-  CK(ldsim_ensure(ctx, SB_WAVES, bs));
-  HIPCHK(hipMemcpyAsync(ctx->scratch[SB_NEIGH].p, pixels, bp, hipMemcpyHostToDevice, ctx->stream));
-  CK(chain_tracks_current(ctx, (const int32_t*)ctx->scratch[SB_NEIGH].p, P, (float*)ctx->scratch[SB_WAVES].p, T, 1));
-  HIPCHK(hipMemcpyAsync(signals, ctx->scratch[SB_WAVES].p, bs, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return 0;
+  return tracks_current_stage(ctx, tracks, n, layout, pixels, P, signals, T, 1);
 }
 
 extern "C" int ldsim_track_pixel_map(ldsim_ctx* ctx, const int32_t* unique_pix, int64_t U, const int32_t* pixels,
@@ -902,8 +820,8 @@ extern "C" int ldsim_track_pixel_map(ldsim_ctx* ctx, const int32_t* unique_pix, 
   LDSIM_ENTER(ctx);
   NEED(ctx && track_pixel_map && (unique_pix || U == 0), "bad track_pixel_map arguments");
   HIPCHK(hipSetDevice(ctx->device));
-  Tmp du, dp, dd, dm;
-  CK(du.alloc(U * 4)); CK(dp.alloc((size_t)n * P * 4)); CK(dd.alloc((size_t)n * P * 4)); CK(dm.alloc((size_t)U * M * 8));
+  DevBuf du, dp, dd, dm;
+  CK(du.ensure(U * 4)); CK(dp.ensure((size_t)n * P * 4)); CK(dd.ensure((size_t)n * P * 4)); CK(dm.ensure((size_t)U * M * 8));
   if (U) HIPCHK(hipMemcpyAsync(du.p, unique_pix, U * 4, hipMemcpyHostToDevice, ctx->stream));
   if (n * P) {
     HIPCHK(hipMemcpyAsync(dp.p, pixels, (size_t)n * P * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -924,11 +842,11 @@ extern "C" int ldsim_sum_pixel_signals(ldsim_ctx* ctx, const float* signals, int
   NEED(ctx && signals && track_starts && pim && tpm && pixels_signals && overflow, "null argument");
   HIPCHK(hipSetDevice(ctx->device));
   const int NT = ctx->h_consts.n_time_ticks;
-  Tmp ds, dst, dpim, dtpm, dps, dpts, dov;
+  DevBuf ds, dst, dpim, dtpm, dps, dpts, dov;
   size_t bs = (size_t)n * P * T * 4;
-  CK(ds.alloc(bs)); CK(dst.alloc(n * 8)); CK(dpim.alloc((size_t)n * P * 8)); CK(dtpm.alloc((size_t)U * M * 8));
-  CK(dps.alloc((size_t)U * NT * 8)); CK(dov.alloc(U * 8));
-  if (pts) CK(dpts.alloc((size_t)U * NT * M * 8));
+  CK(ds.ensure(bs)); CK(dst.ensure(n * 8)); CK(dpim.ensure((size_t)n * P * 8)); CK(dtpm.ensure((size_t)U * M * 8));
+  CK(dps.ensure((size_t)U * NT * 8)); CK(dov.ensure(U * 8));
+  if (pts) CK(dpts.ensure((size_t)U * NT * M * 8));
   HIPCHK(hipMemcpyAsync(ds.p, signals, bs, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dst.p, track_starts, n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(dpim.p, pim, (size_t)n * P * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -960,15 +878,15 @@ extern "C" int ldsim_get_adc_values(ldsim_ctx* ctx, const double* ps, const doub
     return LDSIM_ESTATE;
   }
   const int A = h.max_adc_values;
-  Tmp dps, dpts, dthr, dadc, dtk, dfr, dz, dnd;
-  CK(dps.alloc((size_t)U * NT * 8)); CK(dthr.alloc(U * 8)); CK(dadc.alloc((size_t)U * A * 8)); CK(dtk.alloc((size_t)U * A * 8));
-  if (pts) CK(dpts.alloc((size_t)U * NT * M * 8));
-  if (fractions) CK(dfr.alloc((size_t)U * A * M * 8));
+  DevBuf dps, dpts, dthr, dadc, dtk, dfr, dz, dnd;
+  CK(dps.ensure((size_t)U * NT * 8)); CK(dthr.ensure(U * 8)); CK(dadc.ensure((size_t)U * A * 8)); CK(dtk.ensure((size_t)U * A * 8));
+  if (pts) CK(dpts.ensure((size_t)U * NT * M * 8));
+  if (fractions) CK(dfr.ensure((size_t)U * A * M * 8));
   int nd = 0;
   if (noisy) {      // rng_states[ip] of the reference's call (fee.py:557): state ip of the table, advanced in place
     CK(rng_ensure_states(ctx, U));
     nd = rng_fee_draws_per_pixel(h, NT);
-    CK(dz.alloc((size_t)U * nd * 4)); CK(dnd.alloc((size_t)U * 4 + 4));
+    CK(dz.ensure((size_t)U * nd * 4)); CK(dnd.ensure((size_t)U * 4 + 4));
     CK(rng_launch_fee_noise(ctx, U, nd, dz.as<float>()));
   }
   HIPCHK(hipMemcpyAsync(dps.p, ps, (size_t)U * NT * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -992,9 +910,9 @@ extern "C" int ldsim_digitize(ldsim_ctx* ctx, const double* integral, int64_t n,
   LDSIM_ENTER(ctx);
   NEED(ctx && integral && adcs, "null argument");
   HIPCHK(hipSetDevice(ctx->device));
-  Tmp di, dg, dout;
-  CK(di.alloc(n * 8)); CK(dout.alloc(n * 8));
-  if (gain) CK(dg.alloc(n * 8));
+  DevBuf di, dg, dout;
+  CK(di.ensure(n * 8)); CK(dout.ensure(n * 8));
+  if (gain) CK(dg.ensure(n * 8));
   if (n) HIPCHK(hipMemcpyAsync(di.p, integral, n * 8, hipMemcpyHostToDevice, ctx->stream));
   if (gain && n) HIPCHK(hipMemcpyAsync(dg.p, gain, n * 8, hipMemcpyHostToDevice, ctx->stream));
   CK(fee_launch_digitize(ctx, di.as<double>(), gain ? dg.as<double>() : nullptr, dout.as<double>(), n));
@@ -1007,12 +925,12 @@ extern "C" int ldsim_light_incidence(ldsim_ctx* ctx, const void* tracks, int64_t
                                      int32_t n_out, float* nph, float* t0det, int32_t* voxel) {
   LDSIM_ENTER(ctx);
   NEED(ctx && nph && t0det && voxel && n_out >= 0, "null argument");
-  NEED(ctx->d_lut_vis && ctx->d_eff, "light LUT / channel tables not set");
+  NEED(ctx->d_lut_vis.p && ctx->d_eff.p, "light LUT / channel tables not set");
   NEED(n_out <= ctx->n_light_ch, "more output channels than light channels configured");
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
-  Tmp dn, dt, dv;
+  DevBuf dn, dt, dv;
   size_t bc = (size_t)n * n_out * 4;
-  CK(dn.alloc(bc)); CK(dt.alloc(bc)); CK(dv.alloc((size_t)n * 12));
+  CK(dn.ensure(bc)); CK(dt.ensure(bc)); CK(dv.ensure((size_t)n * 12));
   HIPCHK(hipMemsetAsync(dn.p, 0, bc, ctx->stream));
   HIPCHK(hipMemsetAsync(dt.p, 0, bc, ctx->stream));
   HIPCHK(hipMemsetAsync(dv.p, 0, (size_t)n * 12, ctx->stream));
@@ -1033,14 +951,14 @@ extern "C" int ldsim_sum_light_signals(ldsim_ctx* ctx, const void* tracks, int64
                                        double* true_ph, int32_t max_truth) {
   LDSIM_ENTER(ctx);
   NEED(ctx && voxel && track_id && nph && op_channel && sorted_indices && out, "null argument");
-  NEED(ctx->d_lut_t0avg, "light LUT not set");
+  NEED(ctx->d_lut_t0avg.p, "light LUT not set");
   NEED(max_truth == 0 || (true_id && true_ph), "truth arrays missing");
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
-  Tmp dv, dti, dn, dop, dsi, dout, dtid, dtph;
+  DevBuf dv, dti, dn, dop, dsi, dout, dtid, dtph;
   size_t bo = (size_t)n_det * n_ticks;
-  CK(dv.alloc((size_t)n * 12)); CK(dti.alloc(n * 8)); CK(dn.alloc((size_t)n * n_inc * 4)); CK(dop.alloc(n_det * 4));
-  CK(dsi.alloc((size_t)n_det * n * 4)); CK(dout.alloc(bo * 4)); CK(dtid.alloc(bo * max_truth * 8 + 8));
-  CK(dtph.alloc(bo * max_truth * 8 + 8));
+  CK(dv.ensure((size_t)n * 12)); CK(dti.ensure(n * 8)); CK(dn.ensure((size_t)n * n_inc * 4)); CK(dop.ensure(n_det * 4));
+  CK(dsi.ensure((size_t)n_det * n * 4)); CK(dout.ensure(bo * 4)); CK(dtid.ensure(bo * max_truth * 8 + 8));
+  CK(dtph.ensure(bo * max_truth * 8 + 8));
   if (n) {
     HIPCHK(hipMemcpyAsync(dv.p, voxel, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(dti.p, track_id, n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1073,7 +991,7 @@ extern "C" int ldsim_dev_light_incidence(ldsim_ctx* ctx, int32_t n_out) {
   LDSIM_ENTER(ctx);
   NEED(ctx && n_out > 0, "bad argument");
   NEED_RESIDENT(ctx);
-  NEED(ctx->d_lut_vis && ctx->d_eff, "light LUT / channel tables not set");
+  NEED(ctx->d_lut_vis.p && ctx->d_eff.p, "light LUT / channel tables not set");
   NEED(n_out <= ctx->n_light_ch, "more output channels than light channels configured");
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
@@ -1166,7 +1084,7 @@ extern "C" int ldsim_dev_sum_light(ldsim_ctx* ctx, int64_t seg_begin, int64_t se
   LDSIM_ENTER(ctx);
   NEED(ctx && op_channel && n_det > 0 && n_ticks >= 0 && max_truth >= 0, "bad argument");
   NEED_LIGHT_INC(ctx);
-  NEED(ctx->d_lut_t0avg, "light LUT not set");
+  NEED(ctx->d_lut_t0avg.p, "light LUT not set");
   NEED(seg_begin >= 0 && seg_end >= seg_begin && seg_end <= ctx->seg.n, "segment range outside the resident store");
   // (the driver passes the same channel list batch after batch: checked and sent when it changes)
   const bool same_opc = ctx->light_opc.p && (int64_t)ctx->h_opc.size() == n_det && ctx->h_opc_n_out == ctx->light_n_out &&
@@ -1198,10 +1116,10 @@ extern "C" int ldsim_dev_sum_light(ldsim_ctx* ctx, int64_t seg_begin, int64_t se
     if (!ctx->light_stream) {
       int prio_lo = 0, prio_hi = 0;          // (the small sums ahead of the charge chain's grids when both have workgroups to place)
       HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-      HIPCHK(hipStreamCreateWithPriority(&ctx->light_stream, hipStreamNonBlocking, prio_hi));
+      CK(ctx->light_stream.ensure(hipStreamNonBlocking, prio_hi));
     }
-    if (!ctx->ev_light_in) HIPCHK(hipEventCreateWithFlags(&ctx->ev_light_in, hipEventDisableTiming));
-    if (!ctx->ev_light_done) HIPCHK(hipEventCreateWithFlags(&ctx->ev_light_done, hipEventDisableTiming));
+    CK(ctx->ev_light_in.ensure(hipEventDisableTiming));
+    CK(ctx->ev_light_done.ensure(hipEventDisableTiming));
     // (the first sum since the last join waits for what the ctx's stream holds; while sums are pending, whatever writes their
     // inputs there joins first -- light_join -- so the following sums have nothing new to wait for)
     if (!ctx->light_pending) {
@@ -1252,7 +1170,7 @@ extern "C" int ldsim_dev_sum_light(ldsim_ctx* ctx, int64_t seg_begin, int64_t se
       const size_t half = (((size_t)cap_det * 8 + 16 + (size_t)cap_list * 4 + 255) / 256) * 256;
       ctx->light_nt_ndet_cap = ctx->light_nt_list_cap = 0;
       ctx->light_nt_valid = 0;
-      if (ctx->light_act.p) { HIPCHK(hipFree(ctx->light_act.p)); ctx->light_act.p = nullptr; ctx->light_act.bytes = 0; }
+      ctx->light_act.reset();
       CK(ldsim_ensure_buf(ctx, &ctx->light_act, 2 * half));
       ctx->light_nt_ndet_cap = cap_det;
       ctx->light_nt_list_cap = cap_list;
@@ -1408,10 +1326,10 @@ static int light_response_stage(ldsim_ctx* ctx, bool response, const float* inc,
                                 const double* gain, float* out, int64_t* out_tid, double* out_tph) {
   HIPCHK(hipSetDevice(ctx->device));
   const size_t bo = (size_t)n_det * n_ticks, bt = bo * (size_t)max_truth;
-  Tmp dinc, dtid, dtph, dw, dg, dout, dotid, dotph;
-  CK(dinc.alloc(bo * 4 + 8)); CK(dout.alloc(bo * 4 + 8)); CK(dw.alloc(weights.size() * 8));
-  CK(dtid.alloc(bt * 8 + 8)); CK(dtph.alloc(bt * 8 + 8)); CK(dotid.alloc(bt * 8 + 8)); CK(dotph.alloc(bt * 8 + 8));
-  CK(dg.alloc((size_t)n_det * 8 + 8));
+  DevBuf dinc, dtid, dtph, dw, dg, dout, dotid, dotph;
+  CK(dinc.ensure(bo * 4 + 8)); CK(dout.ensure(bo * 4 + 8)); CK(dw.ensure(weights.size() * 8));
+  CK(dtid.ensure(bt * 8 + 8)); CK(dtph.ensure(bt * 8 + 8)); CK(dotid.ensure(bt * 8 + 8)); CK(dotph.ensure(bt * 8 + 8));
+  CK(dg.ensure((size_t)n_det * 8 + 8));
   hipStream_t st = ctx->stream;
   HIPCHK(hipMemcpyAsync(dinc.p, inc, bo * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dout.p, out, bo * 4, hipMemcpyHostToDevice, st));          // accumulates into the caller's array
@@ -1524,8 +1442,8 @@ extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain
     ctx->light_resp_valid = 1;
     return 0;
   }
-  hipEvent_t ev[4];
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  Event ev[4];
+  for (Event& e : ev) CK(e.ensure());
   HIPCHK(hipEventRecord(ev[0], st));
   CK(light_response_launch(ctx, false, (const float*)ctx->light_out.p, (const int64_t*)ctx->light_tid.p,
                            (const double*)ctx->light_tph.p, D, T, Mt, (const double*)ctx->light_w[0].p, (int)C, nullptr,
@@ -1547,7 +1465,6 @@ extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain
     HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
     ctx->ms_light_resp[i] = ms;
   }
-  for (auto& e : ev) (void)hipEventDestroy(e);
   ctx->light_resp_valid = 1;
   return 0;
 }
@@ -1583,7 +1500,7 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
                                   LdsimChainStats* stats) {
   LDSIM_ENTER(ctx);
   NEED(ctx, "null ctx");
-  NEED(ctx->d_resp, "no response table set (ldsim_set_response)");
+  NEED(ctx->d_resp.p, "no response table set (ldsim_set_response)");
   NEED_RESIDENT(ctx);
   NEED(seg_begin >= 0 && seg_end >= seg_begin && seg_end <= ctx->seg.n, "segment range outside the resident store");
   if (ctx->drift_map_gen != -1 || ctx->n_fmap > 0) {
@@ -1606,6 +1523,26 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
   return rc;
 }
 
+// the per-pixel arrays of the last chain launch to the host on `st` (asynchronous; fractions made complete first)
+static int chain_copy_out(ldsim_ctx* ctx, hipStream_t st, int32_t* unique_pix, int32_t* batch, double* adc_list,
+                          double* adc_ticks, double* adc_digit, int64_t* tpm, double* fractions) {
+  const int64_t U = ctx->chain_U;
+  const int A = ctx->h_consts.max_adc_values, M = ctx->h_consts.max_tracks_per_pixel;
+  if (unique_pix) HIPCHK(hipMemcpyAsync(unique_pix, ctx->scratch[SB_UPIX].p, U * 4, hipMemcpyDeviceToHost, st));
+  if (batch) HIPCHK(hipMemcpyAsync(batch, ctx->scratch[SB_UBATCH].p, U * 4, hipMemcpyDeviceToHost, st));
+  if (adc_list) HIPCHK(hipMemcpyAsync(adc_list, ctx->scratch[SB_ADC].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
+  if (adc_ticks) HIPCHK(hipMemcpyAsync(adc_ticks, ctx->scratch[SB_TICKS].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
+  if (adc_digit) HIPCHK(hipMemcpyAsync(adc_digit, ctx->scratch[SB_DIGIT].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
+  if (tpm) HIPCHK(hipMemcpyAsync(tpm, ctx->scratch[SB_TPM].p, (size_t)U * M * 8, hipMemcpyDeviceToHost, st));
+  if (fractions) {
+    CK(fractions_complete(ctx));
+    // (completed on the compute stream: drained before another stream reads the rows)
+    if (st != ctx->stream) HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpyAsync(fractions, ctx->scratch[SB_FRAC].p, (size_t)U * A * M * 8, hipMemcpyDeviceToHost, st));
+  }
+  return 0;
+}
+
 extern "C" int ldsim_chain_download(ldsim_ctx* ctx, int64_t capacity, int32_t* unique_pix, int32_t* batch,
                                     double* adc_list, double* adc_ticks, double* adc_digit, int64_t* tpm,
                                     double* fractions) {
@@ -1617,19 +1554,9 @@ extern "C" int ldsim_chain_download(ldsim_ctx* ctx, int64_t capacity, int32_t* u
     return LDSIM_ENOSPC;
   }
   if (U == 0) return 0;
-  const int A = ctx->h_consts.max_adc_values, M = ctx->h_consts.max_tracks_per_pixel;
   HIPCHK(hipSetDevice(ctx->device));
-  if (unique_pix) HIPCHK(hipMemcpyAsync(unique_pix, ctx->scratch[SB_UPIX].p, U * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (batch) HIPCHK(hipMemcpyAsync(batch, ctx->scratch[SB_UBATCH].p, U * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (adc_list) HIPCHK(hipMemcpyAsync(adc_list, ctx->scratch[SB_ADC].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (adc_ticks) HIPCHK(hipMemcpyAsync(adc_ticks, ctx->scratch[SB_TICKS].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (adc_digit) HIPCHK(hipMemcpyAsync(adc_digit, ctx->scratch[SB_DIGIT].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (tpm) HIPCHK(hipMemcpyAsync(tpm, ctx->scratch[SB_TPM].p, (size_t)U * M * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (fractions) {
-    NEED(ctx->want_fractions, "fractions were not requested in the last ldsim_charge_chain call");
-    CK(fractions_complete(ctx));
-    HIPCHK(hipMemcpyAsync(fractions, ctx->scratch[SB_FRAC].p, (size_t)U * A * M * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  if (fractions) NEED(ctx->want_fractions, "fractions were not requested in the last ldsim_charge_chain call");
+  CK(chain_copy_out(ctx, ctx->stream, unique_pix, batch, adc_list, adc_ticks, adc_digit, tpm, fractions));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -1648,7 +1575,7 @@ extern "C" int ldsim_chain_download_async(ldsim_ctx* ctx, int64_t capacity, int3
     return LDSIM_ENOSPC;
   }
   HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->copy_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  CK(ctx->copy_stream.ensure(hipStreamNonBlocking));
   if (ctx->copy_pending) {
     HIPCHK(hipStreamSynchronize(ctx->copy_stream));
     ctx->copy_pending = 0;
@@ -1656,19 +1583,8 @@ extern "C" int ldsim_chain_download_async(ldsim_ctx* ctx, int64_t capacity, int3
   ctx->async_out = 1;
   if (U == 0) return 0;
   if (fractions) NEED(ctx->want_fractions, "fractions were not requested in the last ldsim_charge_chain call");
-  const int A = ctx->h_consts.max_adc_values, M = ctx->h_consts.max_tracks_per_pixel;
-  hipStream_t cs = ctx->copy_stream;      // (ldsim_charge_chain returns with its stream drained: the rows are complete)
-  if (unique_pix) HIPCHK(hipMemcpyAsync(unique_pix, ctx->scratch[SB_UPIX].p, U * 4, hipMemcpyDeviceToHost, cs));
-  if (batch) HIPCHK(hipMemcpyAsync(batch, ctx->scratch[SB_UBATCH].p, U * 4, hipMemcpyDeviceToHost, cs));
-  if (adc_list) HIPCHK(hipMemcpyAsync(adc_list, ctx->scratch[SB_ADC].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, cs));
-  if (adc_ticks) HIPCHK(hipMemcpyAsync(adc_ticks, ctx->scratch[SB_TICKS].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, cs));
-  if (adc_digit) HIPCHK(hipMemcpyAsync(adc_digit, ctx->scratch[SB_DIGIT].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, cs));
-  if (tpm) HIPCHK(hipMemcpyAsync(tpm, ctx->scratch[SB_TPM].p, (size_t)U * M * 8, hipMemcpyDeviceToHost, cs));
-  if (fractions) {
-    CK(fractions_complete(ctx));                        // (on the compute stream: drained before the copy stream reads the rows)
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpyAsync(fractions, ctx->scratch[SB_FRAC].p, (size_t)U * A * M * 8, hipMemcpyDeviceToHost, cs));
-  }
+  // (ldsim_charge_chain returns with its stream drained: the rows are complete)
+  CK(chain_copy_out(ctx, ctx->copy_stream, unique_pix, batch, adc_list, adc_ticks, adc_digit, tpm, fractions));
   ctx->copy_pending = 1;
   ctx->pending_gen = ctx->out_gen;
   return 0;

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <exception>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/ldsim.h"
@@ -17,7 +18,7 @@
 // Values are held "as stored": after a kernel mutates a field the column holds the value narrowed
 // through the record's storage dtype (f4 rounding / u4 truncation), exactly what the next reference
 // kernel would read back from the record.
-struct SegStore {
+struct SegStore {                // (its columns are aliases into the ctx's seg_block)
   double* f[LDSIM_NFIELDS - 1];  // all float-like fields (index = enum ldsim_field), n_electrons included
   int32_t* pixel_plane;
   int32_t* batch;                // (event, TPC-group, sub-batch) id; <0 = not simulated
@@ -32,7 +33,7 @@ struct alignas(32) FieldMapNode {
   double e, dx, dy, dz;
 };
 struct FieldMapDesc {
-  const FieldMapNode* node;      // [n[0]][n[1]][n[2]]; nullptr: this TPC has no map
+  const FieldMapNode* node;      // [n[0]][n[1]][n[2]] (alias of the ctx's fmap_nodes[tpc]); nullptr: this TPC has no map
   int32_t n[3];
   int32_t has_e;                 // 0: the map carries no E channel (E = the constants' e_field, whatever module is loaded)
   double origin[3], inv_spacing[3];
@@ -94,9 +95,126 @@ __device__ __forceinline__ bool pix_in_range(const LdsimConsts* c, int64_t x, in
 }
 
 // ---- host-side context --------------------------------------------------------------------------------
+void ldsim_set_error(const char* fmt, ...);
+#define HIPCHK(expr)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) {                                                               \
+      ldsim_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return LDSIM_EHIP;                                                                  \
+    }                                                                                     \
+  } while (0)
+#define CK(x)                \
+  do {                       \
+    int rc_ = (x);           \
+    if (rc_) return rc_;     \
+  } while (0)
+#define NEED(cond, msg)            \
+  do {                             \
+    if (!(cond)) {                 \
+      ldsim_set_error("%s", msg);  \
+      return LDSIM_EINVAL;         \
+    }                              \
+  } while (0)
+
+// ---- owners of device objects ------------------------------------------------------------------------------------------
+// Every device allocation, stream and event of the library is held by one of the three types below: they alone call the
+// HIP create / destroy functions, and they alone move ldsim_live (device buffers, streams, events held process-wide:
+// ldsim_debug_live_objects).  All three are move-only; a pointer or handle copied out of one is an alias and is marked so.
+extern std::atomic<int64_t> ldsim_live[3];
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.p; bytes = o.bytes;
+      o.p = nullptr; o.bytes = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p) {
+      (void)hipFree(p);
+      ldsim_live[0]--;
+    }
+    p = nullptr;
+    bytes = 0;
+  }
+  // kept when it holds `need` bytes, else freed and allocated again with headroom (contents lost); an empty buffer always
+  // allocates, so ensure(0) still gives a valid pointer
+  int ensure(size_t need) {
+    if (need <= bytes && p) return 0;
+    reset();
+    const size_t want = need + need / 8 + 256;
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, want));
+    p = q;
+    bytes = want;
+    ldsim_live[0]++;
+    return 0;
+  }
+  // grown to hold at least `need` bytes, its first `keep` bytes kept (copied on `st`, which is drained before the old
+  // allocation goes); untouched on failure
+  int grow_keep(hipStream_t st, size_t keep, size_t need) {
+    if (need <= bytes && p) return 0;
+    DevBuf nb;
+    CK(nb.ensure(need * 2));
+    if (keep) HIPCHK(hipMemcpyAsync(nb.p, p, keep, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *this = std::move(nb);
+    return 0;
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() {
+    if (s) {
+      (void)hipStreamDestroy(s);
+      ldsim_live[1]--;
+    }
+  }
+  // created on first use (priority 0: the default one)
+  int ensure(unsigned flags = hipStreamDefault, int priority = 0) {
+    if (s) return 0;
+    if (priority) HIPCHK(hipStreamCreateWithPriority(&s, flags, priority));
+    else HIPCHK(hipStreamCreateWithFlags(&s, flags));
+    ldsim_live[1]++;
+    return 0;
+  }
+  operator hipStream_t() const { return s; }
+};
+
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e) {
+      (void)hipEventDestroy(e);
+      ldsim_live[2]--;
+    }
+  }
+  int ensure(unsigned flags = hipEventDefault) {   // created on first use
+    if (e) return 0;
+    HIPCHK(hipEventCreateWithFlags(&e, flags));
+    ldsim_live[2]++;
+    return 0;
+  }
+  operator hipEvent_t() const { return e; }
 };
 
 // photon sum without truth slots over a device-built list of the lit (detector, tick tile) cells (kernels_light.hip)
@@ -122,20 +240,20 @@ struct ldsim_ctx {
   std::atomic<std::thread::id> owner{};
   int owner_depth = 0;          // entry points call each other (ldsim_ctx_create -> ldsim_set_consts ...): re-entrant for the owner
   int device = 0;
-  hipStream_t stream = nullptr;
+  // the streams come first: members go in reverse order, so every buffer and event is gone before the streams are
+  hipStream_t stream = nullptr;              // the current stream (not owned): main_stream, or light_stream inside ldsim_dev_sum_light
+  Stream main_stream, copy_stream, light_stream, tab_stream;
   LdsimConsts h_consts;
-  LdsimConsts* d_consts = nullptr;
+  DevBuf d_consts;
   // response table
-  double* d_resp = nullptr;
+  DevBuf d_resp;
   int32_t ni = 0, nj = 0, nk = 0;
   int32_t resp_k_first = 0, resp_k_last = -1;  // support of the table over all cells (exact zeros outside)
   // per-pixel discrimination thresholds / gains of the fused chain: dense tables indexed by pixel id (NULL = constant)
-  double* d_pix_thr = nullptr;
-  double* d_pix_gain = nullptr;
+  DevBuf d_pix_thr, d_pix_gain;
   int64_t pix_table_n = 0;      // n_pixels[0] * n_pixels[1] * n_tpc the tables were built for
   // light
-  double* d_eff = nullptr;
-  int32_t* d_ch2tpc = nullptr;
+  DevBuf d_eff, d_ch2tpc;                    // f64, i32 per channel
   int32_t n_light_ch = 0;
   DevBuf resp_pad;                           // zero-padded copy of the response rows for mac_shift_kernel
   int32_t resp_pad_lo = 0, resp_pad_hi = -2; // staged range it was built for (-2: not built)
@@ -147,7 +265,6 @@ struct ldsim_ctx {
   DevBuf light_env;                          // per offset of a wave's first tick from an input tick: the largest weight its 64 ticks meet it with (light_env_kernel)
   int light_truth_lds = 1;                   // truth slots of the light response stages by light_truth_lds_kernel (0: inside light_conv_kernel, slot-major copies)
   DevBuf light_tmax;                         // per (detector, tick) bound on the truth slots' photons (light_truth_max_kernel)
-  hipStream_t copy_stream = nullptr;
   DevBuf out_alt[7];                         // the other set of SB_UPIX, SB_UBATCH, SB_ADC, SB_TICKS, SB_DIGIT, SB_TPM, SB_FRAC
   int async_out = 0;                         // alternate the output buffers from launch to launch (set by the first async download)
   int copy_pending = 0;
@@ -155,7 +272,7 @@ struct ldsim_ctx {
   int light_eff_plain = 0;                   // every OP_CHANNEL_EFFICIENCY finite and >= 0
   int light_incidence_scalar = 0;            // 1 = the one-channel-per-lane light_incidence_kernel (A/B checks)
   int mac_mode = 1;                          // M = 1 correlation: 1 = mac_shift_kernel (DPP window), 0 = mac_kernel<1> (LDS rows)
-  float *d_lut_vis = nullptr, *d_lut_t0 = nullptr, *d_lut_t0avg = nullptr, *d_lut_td = nullptr;
+  DevBuf d_lut_vis, d_lut_t0, d_lut_t0avg, d_lut_td;   // f32 planes
   int32_t lut_nx = 0, lut_ny = 0, lut_nz = 0, lut_ndet = 0, lut_nprof = 0;
   // options
   double prune_log = 23.0;                   // exp(-23) = 1e-10 of the pair's peak weight, the accuracy the node rule is fitted for
@@ -168,12 +285,11 @@ struct ldsim_ctx {
   int debug_lds_pad_kb = 0;                  // timing tools: KB taken off the LDS budget of gcorr_kernel's small class
   long long frac_clean_gen = -1;             // out_gen of the output set whose dense fractions array has been completed with zeros
   // launch constants of the FEE kernels (kernels_fee.hip fee_tables_kernel): wtap[64] | G[64], built for (fee_tab_dt, fee_tab_rt)
-  double* d_fee_tab = nullptr;
+  DevBuf d_fee_tab;
   double fee_tab_dt = 0, fee_tab_rt = -1;
   int fee_one_class = 0;                     // option: 1 = pixel_adc_kernel with 256 threads and the whole tick axis for every pixel (A/B checks)
   int gform_chunks = 1;                      // tables and correlation of the node-separable form in this many pair ranges, the tables of range c + 1 on a second stream beside the correlation of range c (1: one after the other)
-  hipStream_t tab_stream = nullptr;          // that second stream, and its per-range events
-  hipEvent_t tab_ev[34] = {};
+  Event tab_ev[34];                          // per-range events of that second stream (tab_stream)
   int gform_wave_tables = 1;                 // 1: gtables_wave_kernel (a wave per pair) for the pairs that fit it, 0: gtables_kernel for all
   int debug_gform = 0;                       // timing tools: parts of gtables_kernel / gcorr_kernel switched off (tools/gform_phases.py)
   int split_kernels = 1;            // 1: weights_kernel + mac_kernel (default), 0: monolithic current_kernel
@@ -184,8 +300,8 @@ struct ldsim_ctx {
                                         // the matrix form is ahead on full-support tables too, profiles/r04_dense_handover.log; 768 until then: wider tables took the shifted-window kernels)
   int mc_current = 0;               // 1: the chain's induced currents come from current_mc_kernel (tracks_current_mc) instead of tracks_current
   int numba_f32 = 0;                // 1: evaluate the sub-expressions Numba types f32 for f4 record fields in float
-  double* d_glx = nullptr;          // Gauss-Legendre nodes / weights on [-1, 1] for every N <= gl_nmax, rule N at N(N-1)/2
-  double* d_glw = nullptr;
+  DevBuf d_glx;                     // Gauss-Legendre nodes / weights on [-1, 1] for every N <= gl_nmax, rule N at N(N-1)/2
+  DevBuf d_glw;
   int gl_nmax = 0;
   double wbuf_learned = 0;          // high-water demand per pair seen so far (x1.25): later calls size the pool with it
   int64_t n_fallback = 0;   // bit0: weights phase, bit1: correlation phase (timing experiments only)
@@ -208,23 +324,22 @@ struct ldsim_ctx {
   // (detector, tick) cells except where the records still sorted in light_tmp[4] fell
   int light_lazy_valid = 0, light_lazy_mt = 0, light_lazy_tick_bits = 16;
   long long light_lazy_nrec = 0, light_lazy_nticks = 0;
-  unsigned* light_flag_dev = nullptr;    // 8 bytes of device memory for that flag (sticky until read)
-  unsigned* light_emit_flag = nullptr;   // device word of the last compact photon sum: a pair ran out of record slots (checked at the next synchronising light call)
+  DevBuf light_flag_dev;                 // 8 bytes of device memory for that flag (sticky until read)
+  unsigned* light_emit_flag = nullptr;   // (alias of light_flag_dev) device word of the last compact photon sum: a pair ran out of record slots (checked at the next synchronising light call)
   size_t light_clean_cells = 0, light_lazy_cap[3] = {0, 0, 0};
-  void *light_lazy_out = nullptr, *light_lazy_tid = nullptr, *light_lazy_tph = nullptr;
+  void *light_lazy_out = nullptr, *light_lazy_tid = nullptr, *light_lazy_tph = nullptr;   // (aliases of light_out / light_tid / light_tph, compared only)
   // the same for a sum without truth slots: clean except the tiles in light_act's list (LightAct; geometry of that sum below)
   DevBuf light_act;                            // two halves (this sum's, the previous one's) of: [cap] u64 masks, count u32, list i32
   int light_nt_valid = 0, light_nt_ntile = 0, light_nt_ndet_cap = 0, light_nt_half = 0, light_nt_list_cap = 0;
   long long light_nt_nticks = 0;
-  void* light_nt_out = nullptr;
+  void* light_nt_out = nullptr;                // (alias of light_out, compared only)
   size_t light_nt_cap = 0;
   int32_t h_opc_n_out = 0;
   int light_sum_no_list = 0;                   // option: 1 = the grid over every (detector, tile) and a full clear (A/B checks)
   std::vector<int32_t> h_opc;                  // host copy of light_opc's contents (validated once, re-sent only when it changes)
   // option light_sum_async: the sums without truth slots run on a stream of their own, beside whatever the ctx's stream carries
   // next (the charge chain).  light_pending: the last such sum has not been joined into ctx->stream yet (light_join, ldsim_abi.hip)
-  hipStream_t light_stream = nullptr;
-  hipEvent_t ev_light_in = nullptr, ev_light_done = nullptr;
+  Event ev_light_in, ev_light_done;
   int light_async = 0, light_pending = 0;
   int light_sum_timed = 1;                     // 0: evl[2..3] of the last sum not yet read into ms_light_sum
   // resident waveform stages on the last photon sum (ldsim_dev_light_response): scintillation profile (+ truth), Poisson
@@ -235,7 +350,7 @@ struct ldsim_ctx {
   uint64_t light_noise_calls = 0;
   double ms_light_resp[3] = {0, 0, 0};
   double ms_light_inc = 0, ms_light_sum = 0;
-  hipEvent_t evl[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event evl[4];
   // random streams (kernels_rng.hip): numba-style table of xoroshiro128p states, grown on demand
   DevBuf d_rng;
   int64_t rng_n = 0;
@@ -251,7 +366,7 @@ struct ldsim_ctx {
   // drift-field maps (ldsim_set_field_map), keyed by the global TPC index: they outlive ldsim_set_consts
   FieldMapDesc h_fmap[LDSIM_MAX_TPC] = {};
   DevBuf fmap_nodes[LDSIM_MAX_TPC];
-  FieldMapDesc* d_fmap = nullptr;        // device copy of h_fmap
+  DevBuf d_fmap;                         // device copy of h_fmap (while a map is set)
   int n_fmap = 0;                        // TPCs with a map
   int64_t fmap_gen = 0;                  // advances on every set / clear
   int64_t drift_map_gen = -1;            // fmap_gen of the mapped quench_drift whose results the store holds (-1: none)
@@ -277,7 +392,7 @@ struct ldsim_ctx {
   int64_t cpt_n[4] = {0, 0, 0, 0};   // compact result of the last ldsim_chain_compact_build: hit pixels, hits, track entries, fraction entries
   int64_t cpt_gen = -1;              // chain launch it was built for
   int want_fractions = 0;
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Event ev[8];
   double ms_current = 0, ms_adc = 0, ms_total = 0;
   double ms_weights = 0, ms_mac = 0, ms_fallback = 0;   // split path: per-kernel share of ms_current
 };
@@ -289,7 +404,6 @@ enum {
   SB_DIGIT, SB_TPM, SB_FRAC, SB_HITS, SB_ITEMS, SB_HDR, SB_CORR, SB_WBUF, SB_NOISE, SB_NDRAWS, SB_PPAR, SB_CPT, SB_CPO, SB_WIN, SB_SPAN, SB_GMAPS, SB_FEESLOT
 };
 
-void ldsim_set_error(const char* fmt, ...);
 // the segment store the charge kernels read: after a mapped quench_drift its nine position columns are the anode view
 static inline SegStore charge_store(const ldsim_ctx* ctx) {
   SegStore s = ctx->seg;
@@ -297,8 +411,8 @@ static inline SegStore charge_store(const ldsim_ctx* ctx) {
     for (int k = 0; k < LDSIM_NVIEW; k++) s.f[k] = (double*)ctx->fmap_view.p + (size_t)k * ctx->fmap_view_cap;
   return s;
 }
-int ldsim_ensure(ldsim_ctx* ctx, int slot, size_t bytes);
-int ldsim_ensure_buf(ldsim_ctx* ctx, DevBuf* b, size_t bytes);
+static inline int ldsim_ensure_buf(ldsim_ctx*, DevBuf* b, size_t bytes) { return b->ensure(bytes); }
+static inline int ldsim_ensure(ldsim_ctx* ctx, int slot, size_t bytes) { return ctx->scratch[slot].ensure(bytes); }
 // refusal of a host-array stage call that draws random numbers while the ctx is in keyed mode (its rows have no identity)
 #define LDSIM_KEYED_STAGE_MSG \
   "%s draws random numbers, but the context is in keyed mode and this stage call carries no identity for its rows: " \
@@ -332,12 +446,3 @@ struct CtxEnter {
     ldsim_set_error("ctx in use by another thread (a ctx is thread-compatible, not thread-safe: one per thread)"); \
     return LDSIM_ESTATE;                                                                                      \
   }
-
-#define HIPCHK(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      ldsim_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return LDSIM_EHIP;                                                                  \
-    }                                                                                     \
-  } while (0)

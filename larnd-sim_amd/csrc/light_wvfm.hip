@@ -20,34 +20,6 @@
 
 extern "C++" int rng_ensure_states(ldsim_ctx* ctx, int64_t n);      // kernels_rng.hip
 
-#define LW_CK(x)             \
-  do {                       \
-    int rc_ = (x);           \
-    if (rc_) return rc_;     \
-  } while (0)
-#define LW_NEED(cond, msg)         \
-  do {                             \
-    if (!(cond)) {                 \
-      ldsim_set_error("%s", msg);  \
-      return LDSIM_EINVAL;         \
-    }                              \
-  } while (0)
-
-namespace {
-struct LTmp {                       // temporary device buffer
-  void* p = nullptr;
-  ~LTmp() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    HIPCHK(hipMalloc(&p, bytes ? bytes : 8));
-    return 0;
-  }
-  template <class T>
-  T* as() { return (T*)p; }
-};
-}  // namespace
-
 // ---- calc_stat_fluctuations ----------------------------------------------------------------------------------------------
 // xoroshiro128p_poisson_int32 (:186-216): inversion with one float32 uniform below a mean of 30, else a normal truncated at 0
 // (st: an RngState, or a KeyedPoisson in keyed mode)
@@ -116,7 +88,7 @@ extern "C++" int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float
     HIPCHK(hipGetLastError());
     return 0;
   }
-  LW_CK(rng_ensure_states(ctx, n));
+  CK(rng_ensure_states(ctx, n));
   hipLaunchKernelGGL(light_stat_fluct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, inc, out,
                      (RngState*)ctx->d_rng.p, n, ctx->h_consts.light_tick_size);
   HIPCHK(hipGetLastError());
@@ -205,20 +177,20 @@ static int light_triggers_run(ldsim_ctx* ctx, const float* d_signal, int32_t n_d
                               int64_t* trig_idx, int32_t* trig_mod, int64_t capacity, int64_t* n_trig) {
   const LdsimConsts& h = ctx->h_consts;
   const int per = h.op_channel_per_trig;
-  LW_NEED(per > 0 && n_grp * per == n_det, "n_det must be n_grp * OP_CHANNEL_PER_TRIG");
-  LW_NEED(h.light_tick_size > 0 && h.light_digit_sample_spacing > 0, "light constants not set");
+  NEED(per > 0 && n_grp * per == n_det, "n_det must be n_grp * OP_CHANNEL_PER_TRIG");
+  NEED(h.light_tick_size > 0 && h.light_digit_sample_spacing > 0, "light constants not set");
   const int64_t sf = llrint(h.light_digit_sample_spacing / h.light_tick_size);        // Python round(): half to even
-  LW_NEED(sf >= 1 && sf <= LW_MAX_SF, "LIGHT_DIGIT_SAMPLE_SPACING / LIGHT_TICK_SIZE must round to 1..128");
-  for (int i = 0; i < n_det; i++) LW_NEED(row_module[i] >= -1 && row_module[i] < n_mod, "row_module out of range");
+  NEED(sf >= 1 && sf <= LW_MAX_SF, "LIGHT_DIGIT_SAMPLE_SPACING / LIGHT_TICK_SIZE must round to 1..128");
+  for (int i = 0; i < n_det; i++) NEED(row_module[i] >= -1 && row_module[i] < n_mod, "row_module out of range");
   *n_trig = 0;
   if (n_ticks == 0 || n_mod == 0) return 0;
   const int64_t padding = sf - n_ticks % sf;
   const int64_t n_blocks = (n_ticks + padding) / sf;
   const int64_t digit_ticks = (int64_t)ceil((h.light_trig_window[1] + h.light_trig_window[0]) / h.light_tick_size);
-  LTmp d_thr, d_rm, d_above;
-  LW_CK(d_thr.alloc((size_t)n_grp * 8));
-  LW_CK(d_rm.alloc((size_t)n_det * 4));
-  LW_CK(d_above.alloc((size_t)n_mod * n_ticks));
+  DevBuf d_thr, d_rm, d_above;
+  CK(d_thr.ensure((size_t)n_grp * 8));
+  CK(d_rm.ensure((size_t)n_det * 4));
+  CK(d_above.ensure((size_t)n_mod * n_ticks));
   hipStream_t st = ctx->stream;
   HIPCHK(hipMemcpyAsync(d_thr.p, group_threshold, (size_t)n_grp * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_rm.p, row_module, (size_t)n_det * 4, hipMemcpyHostToDevice, st));
@@ -345,9 +317,9 @@ static int light_noise_run(ldsim_ctx* ctx, const double* h_tab, int32_t n_ch, in
   const LdsimConsts& h = ctx->h_consts;
   const int R = (int)chan.size(), nn = (int)ticks.size();
   if (R == 0 || nn == 0) return 0;
-  LW_NEED(n_samples >= 2, "gen_light_detector_noise needs at least 2 samples (the reference divides by an empty mean below that)");
-  LW_NEED(nbins >= 2 && n_samples < (1LL << 30), "noise spectrum needs >= 2 bins");
-  for (int c : chan) LW_NEED(c >= 0 && c < n_ch, "optical channel outside the noise spectrum table");
+  NEED(n_samples >= 2, "gen_light_detector_noise needs at least 2 samples (the reference divides by an empty mean below that)");
+  NEED(nbins >= 2 && n_samples < (1LL << 30), "noise spectrum needs >= 2 bins");
+  for (int c : chan) NEED(c >= 0 && c < n_ch, "optical channel outside the noise spectrum table");
   const int m = (int)(n_samples / 2 + 1);
   // np.fft.rfftfreq(n, d): arange(n//2 + 1) * (1.0 / (n * d))
   const int64_t n_noise = 2 * (int64_t)(nbins - 1);
@@ -380,14 +352,14 @@ static int light_noise_run(ldsim_ctx* ctx, const double* h_tab, int32_t n_ch, in
       dxp[(size_t)k] = xp[(size_t)j + 1] - xp[(size_t)j];
     }
   }
-  LTmp d_tab, d_chan, d_j, d_dx, d_dxp, d_ph, d_spec, d_ticks;
-  LW_CK(d_tab.alloc((size_t)n_ch * nbins * 8));
-  LW_CK(d_chan.alloc((size_t)R * 4));
-  LW_CK(d_j.alloc((size_t)m * 4));
-  LW_CK(d_dx.alloc((size_t)m * 8));
-  LW_CK(d_dxp.alloc((size_t)m * 8));
-  LW_CK(d_spec.alloc((size_t)R * m * 16));
-  LW_CK(d_ticks.alloc((size_t)nn * 4));
+  DevBuf d_tab, d_chan, d_j, d_dx, d_dxp, d_ph, d_spec, d_ticks;
+  CK(d_tab.ensure((size_t)n_ch * nbins * 8));
+  CK(d_chan.ensure((size_t)R * 4));
+  CK(d_j.ensure((size_t)m * 4));
+  CK(d_dx.ensure((size_t)m * 8));
+  CK(d_dxp.ensure((size_t)m * 8));
+  CK(d_spec.ensure((size_t)R * m * 16));
+  CK(d_ticks.ensure((size_t)nn * 4));
   hipStream_t st = ctx->stream;
   HIPCHK(hipMemcpyAsync(d_tab.p, h_tab, (size_t)n_ch * nbins * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_chan.p, chan.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
@@ -396,7 +368,7 @@ static int light_noise_run(ldsim_ctx* ctx, const double* h_tab, int32_t n_ch, in
   HIPCHK(hipMemcpyAsync(d_dxp.p, dxp.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_ticks.p, ticks.data(), (size_t)nn * 4, hipMemcpyHostToDevice, st));
   if (h_phases) {
-    LW_CK(d_ph.alloc((size_t)R * m * 8));
+    CK(d_ph.ensure((size_t)R * m * 8));
     HIPCHK(hipMemcpyAsync(d_ph.p, h_phases, (size_t)R * m * 8, hipMemcpyHostToDevice, st));
   }
   hipLaunchKernelGGL(light_noise_spec_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)R), dim3(256), 0, st,
@@ -537,7 +509,7 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
     HIPCHK(hipMemsetAsync(d_dtid, 0xFF, n_out * Mt * 8, st));
     HIPCHK(hipMemsetAsync(d_dtph, 0, n_out * Mt * 8, st));
   }
-  LW_NEED(h.light_tick_size > 0 && h.light_digit_sample_spacing > 0, "light constants not set");
+  NEED(h.light_tick_size > 0 && h.light_digit_sample_spacing > 0, "light constants not set");
   // padding (:566-587)
   int64_t tmin = trig_idx[0], tmax = trig_idx[0];
   for (int i = 1; i < ntrig; i++) {
@@ -557,7 +529,7 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
     Tp += post + tmax + n0 - Tp;
     is_f4 = false;
   }
-  LW_NEED(Tp < (1LL << 30), "padded waveform too long");
+  NEED(Tp < (1LL << 30), "padded waveform too long");
   // channels of the triggers the signal does not hold, appended and everything sorted by channel (:594-609)
   std::vector<int32_t> chan(sig_op, sig_op + R), src_row((size_t)R);
   for (int i = 0; i < R; i++) src_row[(size_t)i] = i;
@@ -637,11 +609,11 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
   }
   const int nn = (int)ticks.size();
   // noise of the two gen_light_detector_noise calls (:592, :597), rows in padded order
-  LTmp d_noise;
+  DevBuf d_noise;
   bool any_noise = false;
   if (noise_tab)
     for (int r = 0; r < Rp && !any_noise; r++) {
-      LW_NEED(chan[(size_t)r] >= 0 && chan[(size_t)r] < n_ch, "optical channel outside the noise spectrum table");
+      NEED(chan[(size_t)r] >= 0 && chan[(size_t)r] < n_ch, "optical channel outside the noise spectrum table");
       for (int b = 0; b < nbins; b++)
         if (noise_tab[(size_t)chan[(size_t)r] * nbins + b] != 0.0) { any_noise = true; break; }
     }
@@ -649,7 +621,7 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
     const int m = (int)(Tp / 2 + 1);
     std::vector<double> ph;
     if (ph_signal || ph_missing) {
-      LW_NEED(ph_signal && (n_missing == 0 || ph_missing), "phases of both noise calls are needed");
+      NEED(ph_signal && (n_missing == 0 || ph_missing), "phases of both noise calls are needed");
       ph.resize((size_t)Rp * m);
       for (int r = 0; r < Rp; r++) {
         const int f = first_call_row[(size_t)r];
@@ -660,24 +632,24 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
       ldsim_set_error("the noise spectrum is non-zero but no random state exists: call ldsim_rng_seed first");
       return LDSIM_ESTATE;
     }
-    LW_CK(d_noise.alloc((size_t)Rp * nn * 8));
+    CK(d_noise.ensure((size_t)Rp * nn * 8));
     const uint64_t seed = light_noise_seed(ctx);
-    LW_CK(light_noise_run(ctx, noise_tab, n_ch, nbins, chan, Tp, ticks, ph.empty() ? nullptr : ph.data(), seed,
+    CK(light_noise_run(ctx, noise_tab, n_ch, nbins, chan, Tp, ticks, ph.empty() ? nullptr : ph.data(), seed,
                           d_noise.as<double>()));
   }
   // device copies of the small host tables
-  LTmp d_src, d_ticks, d_sig, d_mode, d_s0, d_s1, d_frac, d_it0, d_it1, d_trow, d_top;
-  LW_CK(d_src.alloc((size_t)Rp * 4));
-  LW_CK(d_ticks.alloc((size_t)(nn ? nn : 1) * 4));
-  LW_CK(d_sig.alloc((size_t)Rp * (nn ? nn : 1) * 8));
-  LW_CK(d_mode.alloc((size_t)ns * 4));
-  LW_CK(d_s0.alloc((size_t)ns * 4));
-  LW_CK(d_s1.alloc((size_t)ns * 4));
-  LW_CK(d_frac.alloc((size_t)ns * 8));
-  LW_CK(d_it0.alloc((size_t)ns * 8));
-  LW_CK(d_it1.alloc((size_t)ns * 8));
-  LW_CK(d_trow.alloc(trig_row.size() * 4));
-  LW_CK(d_top.alloc(trig_row.size() * 4));
+  DevBuf d_src, d_ticks, d_sig, d_mode, d_s0, d_s1, d_frac, d_it0, d_it1, d_trow, d_top;
+  CK(d_src.ensure((size_t)Rp * 4));
+  CK(d_ticks.ensure((size_t)(nn ? nn : 1) * 4));
+  CK(d_sig.ensure((size_t)Rp * (nn ? nn : 1) * 8));
+  CK(d_mode.ensure((size_t)ns * 4));
+  CK(d_s0.ensure((size_t)ns * 4));
+  CK(d_s1.ensure((size_t)ns * 4));
+  CK(d_frac.ensure((size_t)ns * 8));
+  CK(d_it0.ensure((size_t)ns * 8));
+  CK(d_it1.ensure((size_t)ns * 8));
+  CK(d_trow.ensure(trig_row.size() * 4));
+  CK(d_top.ensure(trig_row.size() * 4));
   HIPCHK(hipMemcpyAsync(d_src.p, src_row.data(), (size_t)Rp * 4, hipMemcpyHostToDevice, st));
   if (nn) HIPCHK(hipMemcpyAsync(d_ticks.p, ticks.data(), (size_t)nn * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_mode.p, mode.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st));
@@ -718,8 +690,8 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
 extern "C" int ldsim_stat_fluctuations(ldsim_ctx* ctx, const float* light_sample_inc, int32_t n_det, int32_t n_ticks,
                                        float* light_sample_inc_disc) {
   LDSIM_ENTER(ctx);
-  LW_NEED(ctx && light_sample_inc && light_sample_inc_disc && n_det >= 0 && n_ticks >= 0, "bad argument");
-  LW_NEED(ctx->h_consts.light_tick_size > 0, "light constants not set");
+  NEED(ctx && light_sample_inc && light_sample_inc_disc && n_det >= 0 && n_ticks >= 0, "bad argument");
+  NEED(ctx->h_consts.light_tick_size > 0, "light constants not set");
   if (ctx->rng_keyed) {
     ldsim_set_error(LDSIM_KEYED_STAGE_MSG, "ldsim_stat_fluctuations");
     return LDSIM_ESTATE;
@@ -727,11 +699,11 @@ extern "C" int ldsim_stat_fluctuations(ldsim_ctx* ctx, const float* light_sample
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n = (size_t)n_det * n_ticks;
   if (n == 0) return 0;
-  LTmp din, dout;
-  LW_CK(din.alloc(n * 4));
-  LW_CK(dout.alloc(n * 4));
+  DevBuf din, dout;
+  CK(din.ensure(n * 4));
+  CK(dout.ensure(n * 4));
   HIPCHK(hipMemcpyAsync(din.p, light_sample_inc, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  LW_CK(light_launch_stat_fluct(ctx, din.as<float>(), dout.as<float>(), (int64_t)n, n_ticks));
+  CK(light_launch_stat_fluct(ctx, din.as<float>(), dout.as<float>(), (int64_t)n, n_ticks));
   HIPCHK(hipMemcpyAsync(light_sample_inc_disc, dout.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -741,17 +713,17 @@ extern "C" int ldsim_light_triggers(ldsim_ctx* ctx, const float* signal, int32_t
                                     const double* group_threshold, int32_t n_grp, const int32_t* row_module, int32_t n_mod,
                                     int64_t* trigger_idx, int32_t* trigger_module, int64_t capacity, int64_t* n_trig) {
   LDSIM_ENTER(ctx);
-  LW_NEED(ctx && group_threshold && row_module && n_trig && n_det >= 0 && n_ticks >= 0 && n_grp >= 0 && n_mod >= 0 &&
+  NEED(ctx && group_threshold && row_module && n_trig && n_det >= 0 && n_ticks >= 0 && n_grp >= 0 && n_mod >= 0 &&
               capacity >= 0 && (capacity == 0 || (trigger_idx && trigger_module)), "bad argument");
   HIPCHK(hipSetDevice(ctx->device));
-  LTmp dsig;
+  DevBuf dsig;
   const float* d_signal;
   if (signal) {
-    LW_CK(dsig.alloc((size_t)n_det * n_ticks * 4));
+    CK(dsig.ensure((size_t)n_det * n_ticks * 4));
     HIPCHK(hipMemcpyAsync(dsig.p, signal, (size_t)n_det * n_ticks * 4, hipMemcpyHostToDevice, ctx->stream));
     d_signal = dsig.as<float>();
   } else {
-    LW_NEED(ctx->light_resp_valid && ctx->light_sum_ndet == n_det && ctx->light_sum_nticks == n_ticks,
+    NEED(ctx->light_resp_valid && ctx->light_sum_ndet == n_det && ctx->light_sum_nticks == n_ticks,
             "no resident detector response of that shape (ldsim_dev_light_response)");
     d_signal = (const float*)ctx->light_resp.p;
   }
@@ -762,7 +734,7 @@ extern "C" int ldsim_light_triggers(ldsim_ctx* ctx, const float* signal, int32_t
 extern "C" int ldsim_light_detector_noise(ldsim_ctx* ctx, int32_t n_rows, int32_t n_samples, const double* spectrum,
                                           int32_t nbins, const double* phases, double* noise) {
   LDSIM_ENTER(ctx);
-  LW_NEED(ctx && spectrum && noise && n_rows >= 0 && n_samples >= 0 && nbins >= 0, "bad argument");
+  NEED(ctx && spectrum && noise && n_rows >= 0 && n_samples >= 0 && nbins >= 0, "bad argument");
   HIPCHK(hipSetDevice(ctx->device));
   if (n_rows == 0 || n_samples == 0) return 0;
   if (!phases && !ctx->rng_seeded) {
@@ -772,10 +744,10 @@ extern "C" int ldsim_light_detector_noise(ldsim_ctx* ctx, int32_t n_rows, int32_
   std::vector<int32_t> chan((size_t)n_rows), ticks((size_t)n_samples);
   for (int i = 0; i < n_rows; i++) chan[(size_t)i] = i;
   for (int i = 0; i < n_samples; i++) ticks[(size_t)i] = i;
-  LTmp dout;
-  LW_CK(dout.alloc((size_t)n_rows * n_samples * 8));
+  DevBuf dout;
+  CK(dout.ensure((size_t)n_rows * n_samples * 8));
   const uint64_t seed = light_noise_seed(ctx);
-  LW_CK(light_noise_run(ctx, spectrum, n_rows, nbins, chan, n_samples, ticks, phases, seed, dout.as<double>()));
+  CK(light_noise_run(ctx, spectrum, n_rows, nbins, chan, n_samples, ticks, phases, seed, dout.as<double>()));
   HIPCHK(hipMemcpy(noise, dout.p, (size_t)n_rows * n_samples * 8, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -788,47 +760,47 @@ extern "C" int ldsim_sim_triggers(ldsim_ctx* ctx, const float* signal, const int
                                   const double* phases_signal, const double* phases_missing, double* digit_signal,
                                   int64_t* digit_true_track_id, double* digit_true_photons) {
   LDSIM_ENTER(ctx);
-  LW_NEED(ctx && n_det >= 0 && n_ticks >= 0 && max_truth >= 0 && n_trig >= 0 && n_det_trig >= 0 && digit_samples >= 0,
+  NEED(ctx && n_det >= 0 && n_ticks >= 0 && max_truth >= 0 && n_trig >= 0 && n_det_trig >= 0 && digit_samples >= 0,
           "bad argument");
-  LW_NEED(n_det == 0 || signal_op_channel_idx, "signal_op_channel_idx missing");
-  LW_NEED(n_trig == 0 || (trigger_idx && trigger_op_channel_idx && digit_signal), "trigger arrays missing");
+  NEED(n_det == 0 || signal_op_channel_idx, "signal_op_channel_idx missing");
+  NEED(n_trig == 0 || (trigger_idx && trigger_op_channel_idx && digit_signal), "trigger arrays missing");
   HIPCHK(hipSetDevice(ctx->device));
   const size_t n_out = (size_t)n_trig * n_det_trig * digit_samples;
   if (n_out == 0) return 0;
   const size_t bo = (size_t)n_det * n_ticks;
   hipStream_t st = ctx->stream;
-  LTmp dsig, dtid, dtph, dd, ddt, ddp;
+  DevBuf dsig, dtid, dtph, dd, ddt, ddp;
   const float* d_signal;
   const int64_t* d_tid = nullptr;
   const double* d_tph = nullptr;
   if (signal) {
-    LW_NEED(max_truth == 0 || (signal_true_track_id && signal_true_photons), "truth arrays missing");
-    LW_CK(dsig.alloc(bo * 4));
+    NEED(max_truth == 0 || (signal_true_track_id && signal_true_photons), "truth arrays missing");
+    CK(dsig.ensure(bo * 4));
     HIPCHK(hipMemcpyAsync(dsig.p, signal, bo * 4, hipMemcpyHostToDevice, st));
     d_signal = dsig.as<float>();
     if (max_truth) {
-      LW_CK(dtid.alloc(bo * max_truth * 8));
-      LW_CK(dtph.alloc(bo * max_truth * 8));
+      CK(dtid.ensure(bo * max_truth * 8));
+      CK(dtph.ensure(bo * max_truth * 8));
       HIPCHK(hipMemcpyAsync(dtid.p, signal_true_track_id, bo * max_truth * 8, hipMemcpyHostToDevice, st));
       HIPCHK(hipMemcpyAsync(dtph.p, signal_true_photons, bo * max_truth * 8, hipMemcpyHostToDevice, st));
       d_tid = dtid.as<int64_t>();
       d_tph = dtph.as<double>();
     }
   } else {                                                  // the resident detector response
-    LW_NEED(ctx->light_resp_valid && ctx->light_sum_ndet == n_det && ctx->light_sum_nticks == n_ticks &&
+    NEED(ctx->light_resp_valid && ctx->light_sum_ndet == n_det && ctx->light_sum_nticks == n_ticks &&
                 ctx->light_sum_truth == max_truth,
             "no resident detector response of that shape (ldsim_dev_light_response)");
     d_signal = (const float*)ctx->light_resp.p;
     d_tid = (const int64_t*)ctx->light_resp_tid.p;
     d_tph = (const double*)ctx->light_resp_tph.p;
   }
-  LW_NEED(max_truth == 0 || (digit_true_track_id && digit_true_photons), "output truth arrays missing");
-  LW_CK(dd.alloc(n_out * 8));
+  NEED(max_truth == 0 || (digit_true_track_id && digit_true_photons), "output truth arrays missing");
+  CK(dd.ensure(n_out * 8));
   if (max_truth) {
-    LW_CK(ddt.alloc(n_out * max_truth * 8));
-    LW_CK(ddp.alloc(n_out * max_truth * 8));
+    CK(ddt.ensure(n_out * max_truth * 8));
+    CK(ddp.ensure(n_out * max_truth * 8));
   }
-  LW_CK(sim_triggers_run(ctx, d_signal, signal_op_channel_idx, n_det, n_ticks, d_tid, d_tph, max_truth, trigger_idx, n_trig,
+  CK(sim_triggers_run(ctx, d_signal, signal_op_channel_idx, n_det, n_ticks, d_tid, d_tph, max_truth, trigger_idx, n_trig,
                          trigger_op_channel_idx, n_det_trig, digit_samples, light_det_noise, n_noise_channels, n_noise_bins,
                          phases_signal, phases_missing, dd.as<double>(), ddt.as<int64_t>(), ddp.as<double>()));
   HIPCHK(hipMemcpyAsync(digit_signal, dd.p, n_out * 8, hipMemcpyDeviceToHost, st));

@@ -259,7 +259,7 @@ int sort_batch_first(ldsim_ctx* ctx, int64_t seg_begin, int64_t n, int32_t batch
 int sort_tmax_batch(ldsim_ctx* ctx, int64_t seg_begin, int64_t n, int32_t batch0, double* starts, int32_t* tmax_b,
                     unsigned long long* tran_b) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(tmax_batch_kernel, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, charge_store(ctx), ctx->d_consts,
+  hipLaunchKernelGGL(tmax_batch_kernel, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, charge_store(ctx), ctx->d_consts.as<LdsimConsts>(),
                      seg_begin, n, batch0, starts, tmax_b, tran_b);
   HIPCHK(hipGetLastError());
   return 0;
