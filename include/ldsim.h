@@ -391,6 +391,28 @@ int ldsim_clear_field_maps(ldsim_ctx* ctx);
  * position fields in enum order (x_start, y_start, z_start, x_end, y_end, z_end, x, y, z) */
 int ldsim_dev_anode_view_download(ldsim_ctx* ctx, double* out);
 
+/* ---- charge statistics -----------------------------------------------------------------------
+ * Opt-in, off by default: while enabled, ldsim_dev_quench_drift counts charge instead of writing mean values.  Per
+ * simulated segment (batch id >= 0), in f64:
+ *   N_i = max(0, rint(dE / W_ion + sqrt(fano * dE / W_ion) * z0))       ion pairs (fano = 0: rint(dE / W_ion) exactly)
+ *   n_q ~ Binomial(N_i, R)                                              R = the Box / Birks factor (at the local field
+ *                                                                       under a field map), clamped to [0, 1]
+ *   n_photons = (dE / W_ph - n_q) * scint_prescale
+ *   n_electrons ~ Binomial(n_q, exp(-t_drift / lifetime)) inside a TPC, n_q outside every TPC
+ * Binomial(n, p): with pm = min(p, 1 - p), n * pm >= 30 draws clamp(rint(n p + sqrt(n p (1 - p)) z), 0, n) from one normal;
+ * below, inversion on the minority outcome at u - 2^-25 of one uniform, the walk stopping at min(n, 256).  Every other drift
+ * output is what it is with the mode off; segments with batch id < 0 and a NaN recombination (LDSIM_EINVAL, as with the mode
+ * off) keep the mean values.  Draws: keyed stream (stage tag 5, key_mix(batch key, index of the segment within its batch)),
+ * draw 0 = Fano normal, 1 / 2 = recombination normal / uniform, 3 / 4 = attachment normal / uniform, whichever branch is
+ * taken -- the same charge at any chunking or rank count.
+ * State rules: ldsim_dev_quench_drift returns LDSIM_ESTATE unless the ctx is in keyed mode (ldsim_rng_keyed_seed) and
+ * ldsim_chain_set_batch_keys covers every batch id of the upload; the host-array stage calls that take records refuse
+ * (LDSIM_ESTATE) while the mode is enabled, as under a field map; ldsim_charge_chain refuses (LDSIM_ESTATE) when the setting
+ * differs from the one of the last ldsim_dev_quench_drift.  fano must be finite and >= 0 (LDSIM_EINVAL); it is kept when
+ * enable = 0. */
+int ldsim_set_charge_statistics(ldsim_ctx* ctx, int32_t enable, double fano);
+int ldsim_get_charge_statistics(ldsim_ctx* ctx, int32_t* enable, double* fano);
+
 typedef struct {
   int64_t n_segments;      /* segments simulated in this call */
   int64_t n_pairs;         /* (segment, pixel) pairs with a valid pixel id */

@@ -78,16 +78,38 @@ def _parser():
     ap.add_argument("--field_map", default=None,
                     help="drift-field maps (.npz, larndsim_amd/field_map.py): per TPC the local field of the recombination and "
                          "the displacement / drift-time shift of the charge on its way to the anode (default: uniform field)")
+    ap.add_argument("--charge_statistics", action="store_true",
+                    help="count the charge: Fano-smeared ion pairs, binomial recombination and electron attachment drawn from "
+                         "keyed streams (larndsim_amd/charge_stats.py) instead of mean values; needs --rng keyed")
+    ap.add_argument("--fano_factor", type=float, default=None,
+                    help="Fano factor of the ion-pair count under --charge_statistics (default 0.107)")
     ap.add_argument("--chunk_segments", type=int, default=50000,
                     help="segments per chain launch (whole batches, at least this many; default 50000)")
     return ap
+
+
+CHARGE_STATISTICS_NEEDS_KEYED = ("--charge_statistics draws from keyed random streams (one per segment, whatever the "
+                                 "chunking or rank count): give --rng keyed as well")
+
+
+def _parse_args(argv=None):
+    """the parsed options, after the checks that need more than one of them"""
+    ap = _parser()
+    a = ap.parse_args(argv)
+    if a.fano_factor is not None and not a.charge_statistics:
+        ap.error("--fano_factor sets the Fano factor of --charge_statistics: give --charge_statistics as well")
+    if a.charge_statistics and a.rng != "keyed":
+        ap.error(CHARGE_STATISTICS_NEEDS_KEYED)
+    if a.fano_factor is not None and not (0 <= a.fano_factor < float("inf")):
+        ap.error("--fano_factor must be finite and >= 0")
+    return a
 
 
 def launch_ranks_if_asked(argv=None):
     """--n_gpus N (or --n_gpus 1 --force_dist) without a launcher: N fresh child processes, one rank each, and exit with the
     worst child's code.  Runs before the simulation modules are imported: this parent loads neither numpy nor the HIP
     library, touches no GPU and is never replaced by exec.  Returns (without doing anything) in every other case."""
-    a = vars(_parser().parse_args(argv))
+    a = vars(_parse_args(argv))
     try:
         _, world = launch.dist_mode(a["n_gpus"], a["force_dist"])  # (refuses a WORLD_SIZE that contradicts --n_gpus)
     except ValueError as e:
@@ -112,7 +134,7 @@ if __name__ == "__main__":
 import numpy as np  # noqa: E402
 import numpy.lib.recfunctions as rfn  # noqa: E402
 
-from larndsim_amd import batching, consts, fee, light_sim, packets, synth  # noqa: E402
+from larndsim_amd import batching, charge_stats, consts, fee, light_sim, packets, synth  # noqa: E402
 from larndsim_amd import config as cfgmod  # noqa: E402
 from larndsim_amd import dist as ldist  # noqa: E402
 from larndsim_amd import field_map as lfmap  # noqa: E402
@@ -317,7 +339,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    pixel_thresholds_file=None, pixel_gains_file=None, rand_seed=None, config_root=None,
                    tracks_current_mc=False, chunk_segments=50000, raw_arrays=False, overlap_downloads=None,
                    pixel_layout_id=None, response_id=None, light_lut_id=None, pixel_thresholds_id=None, pixel_gains_id=None,
-                   numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, **ignored):
+                   numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
+                   fano_factor=None, **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -455,6 +478,11 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     print("Random streams:", rng, f"(--rng {rng})")
     field_maps = lfmap.load(field_map, len(det.TPC_BORDERS)) if field_map is not None else None
     print("Drift-field map:", f"{field_map} (TPCs {sorted(field_maps)})" if field_maps else "none (uniform field)")
+    if charge_statistics and rng != "keyed":
+        raise ValueError(CHARGE_STATISTICS_NEEDS_KEYED)
+    fano = charge_stats.FANO_DEFAULT if fano_factor is None else float(fano_factor)
+    print("Charge statistics:", f"on (--charge_statistics, Fano factor {fano:g})" if charge_statistics
+          else "off (mean-value charge)")
     lib.set_option("numba_f32", f32_mode)
     dist = None
     if world is not None:
@@ -485,6 +513,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             chain.clear_pixel_tables()
             if field_maps:
                 chain.set_field_map(field_maps)
+            if charge_statistics:
+                chain.set_charge_statistics(True, fano)
             if not rng_seeded:
                 # create_xoroshiro128p_states(1024*256, seed) (:396), once; rank r of a sharded run seeds rand_seed + r.
                 # Keyed mode: every rank seeds rand_seed (the streams follow the identity of what is simulated)
@@ -540,6 +570,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     finally:
         lib.set_option("mc_current", 0)
         lib.set_option("numba_f32", 0)
+        if charge_statistics:                                       # (the ctx is process-wide: leave it as it was found)
+            lib.check(lib.load().ldsim_set_charge_statistics(lib.context(refresh_consts=False), 0, 0))
     print(f"simulated {totals['n_segments']} segments in {totals['n_batches']} batches -> {totals['n_hits']} hits, "
           f"{totals['n_packets']} packets" + (f", {totals['n_light_triggers']} light triggers" if light_simulated else ""))
     print("Output saved in:", output_filename)
@@ -939,7 +971,7 @@ def _launch_ranges(edges, nsim, chunk_segments):
 
 def main(argv=None):
     launch_ranks_if_asked(argv)                                     # (does not return when it started the ranks)
-    a = vars(_parser().parse_args(argv))
+    a = vars(_parse_args(argv))
     rank, world = launch.dist_mode(a["n_gpus"], a["force_dist"])
     if world is not None and os.environ.get("LDSIM_CLI_REHEARSAL"):
         # CPU rehearsal of the launch path (tests/test_cpu_multirank.py): the ranks meet over the ncclUniqueId hand-out and stop

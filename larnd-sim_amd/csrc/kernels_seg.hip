@@ -2,6 +2,7 @@
 // All of these are HBM-bound (184 B of compulsory traffic per segment); one thread per segment over
 // SoA columns so every load/store is a coalesced 8-byte stream.
 #include "ldsim_dev.h"
+#include "rng.h"
 
 // ---- AoS <-> SoA ------------------------------------------------------------------------------------------
 __device__ __forceinline__ double load_field(const unsigned char* rec, int off, int code) {
@@ -250,6 +251,147 @@ __global__ void __launch_bounds__(256) quench_drift_map_kernel(SegStore s, const
   if (in_tpc) drift_at(s, c, plane, i, n_e, pos[LDSIM_Z], pos[LDSIM_Z_START], pos[LDSIM_Z_END]);
 }
 
+// ---- charge statistics: keyed binomial recombination and attachment ------------------------------
+// Binomial(n, p) from one normal draw z and one uniform draw u, n a whole number held in a double.  Design constants:
+// BINOM_NORMAL_MIN = 30 (n * min(p, 1 - p) from which the rounded normal is drawn) and BINOM_WALK_MAX = 256 (where the
+// inversion walk stops).  Below 30: inversion on the minority outcome at the centre u - 2^-25 of the uniform's 24-bit cell,
+// P(0) = exp(n log1p(-pm)), P(j + 1) = P(j) (n - j) / (j + 1) * (pm / (1 - pm)), j = the first running sum >= the centre.
+// larndsim_amd/charge_stats.py restates this operation for operation.
+#define BINOM_NORMAL_MIN 30.0
+#define BINOM_WALK_MAX 256.0
+__device__ __forceinline__ double binomial_draw(double n, double p, float z, float u) {
+  if (!(n > 0) || !(p > 0)) return 0;
+  if (p >= 1) return n;
+  const double pm = fmin(p, 1 - p);
+  if (n * pm >= BINOM_NORMAL_MIN) return fmin(fmax(rint(n * p + sqrt(n * p * (1 - p)) * (double)z), 0.0), n);
+  const double centre = (double)u - 0x1p-25, ratio = pm / (1 - pm), jmax = fmin(n, BINOM_WALK_MAX);
+  double q = exp(n * log1p(-pm)), sum = q, j = 0;
+  while (sum < centre && j < jmax) {
+    q = q * (n - j) / (j + 1) * ratio;
+    j += 1;
+    sum += q;
+  }
+  return p <= 0.5 ? j : n - j;
+}
+
+// quench_at's recombination factor alone: 0 = recomb set, 1 = unknown mode, 2 = NaN
+__device__ __forceinline__ int recomb_at(const LdsimConsts* __restrict__ c, int mode, double e_field, double dEdx,
+                                         double& recomb) {
+  recomb = 0;
+  if (mode == 1) {  // BOX
+    double csi = c->box_beta * dEdx / (e_field * c->lar_density);
+    double r = log(c->box_alpha + csi) / csi;
+    recomb = (r > 0) ? r : 0;
+  } else if (mode == 2) {  // BIRKS
+    recomb = c->birks_ab / (1 + c->birks_kb * dEdx / (e_field * c->lar_density));
+  } else {
+    return 1;
+  }
+  return isnan(recomb) ? 2 : 0;
+}
+
+// drift_at without n_electrons: widths and times written, the drift time returned
+__device__ __forceinline__ double drift_times_at(SegStore& s, const LdsimConsts* __restrict__ c, int32_t plane, int64_t i,
+                                                 double z, double zs, double ze) {
+  double z_anode = c->tpc_borders[plane][2][0];
+  double t0 = s.f[LDSIM_T0][i];
+  double drift_distance = fabs(z - z_anode);
+  double drift_start = fabs(fmin(zs, ze) - z_anode);
+  double drift_end = fabs(fmax(zs, ze) - z_anode);
+  double drift_time = drift_distance / c->v_drift;
+  s.f[LDSIM_LONG_DIFF][i] = narrow_store(sqrt(drift_time * 2 * c->long_diff), s.store_code[LDSIM_LONG_DIFF]);
+  s.f[LDSIM_TRAN_DIFF][i] = narrow_store(sqrt(drift_time * 2 * c->tran_diff), s.store_code[LDSIM_TRAN_DIFF]);
+  s.f[LDSIM_T][i] = narrow_store(s.f[LDSIM_T][i] + (drift_time + t0), s.store_code[LDSIM_T]);
+  s.f[LDSIM_T_START][i] = narrow_store(s.f[LDSIM_T_START][i] + (fmin(drift_start, drift_end) / c->v_drift + t0),
+                                       s.store_code[LDSIM_T_START]);
+  s.f[LDSIM_T_END][i] = narrow_store(s.f[LDSIM_T_END][i] + (fmax(drift_start, drift_end) / c->v_drift + t0),
+                                     s.store_code[LDSIM_T_END]);
+  return drift_time;
+}
+
+// One thread per segment; quench_drift_kernel (maps = view = NULL) or quench_drift_map_kernel with counted charge:
+//   N_i = max(0, rint(dE / W_ion + sqrt(F dE / W_ion) z0)), n_q ~ Binomial(N_i, R), R the recombination factor in [0, 1],
+//   n_photons = (dE / W_ph - n_q) scint_prescale, and inside a TPC n_electrons ~ Binomial(n_q, exp(-t_drift / lifetime)).
+// Stream (RNG_TAG_CHARGE, key_mix(batch key, index of the segment within its batch)); draw 0 = Fano normal, 1 / 2 =
+// recombination normal / uniform, 3 / 4 = attachment normal / uniform, whichever branch a sampler takes.  Segments that are
+// not simulated (batch < 0) and a NaN recombination (err = 2) take the mean-value path.
+__global__ void __launch_bounds__(256) quench_drift_stat_kernel(SegStore s, const LdsimConsts* __restrict__ c, int mode,
+                                                                const FieldMapDesc* __restrict__ maps,
+                                                                double* __restrict__ view, int64_t cap, uint64_t seed,
+                                                                const uint64_t* __restrict__ batch_keys,
+                                                                const int32_t* __restrict__ batch_first, int32_t batch0,
+                                                                double fano, int* __restrict__ err) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= s.n) return;
+  double pos[LDSIM_NVIEW];
+#pragma unroll
+  for (int k = 0; k < LDSIM_NVIEW; k++) pos[k] = s.f[k][i];
+  const int32_t plane = tpc_of(c, pos[LDSIM_X], pos[LDSIM_Y], pos[LDSIM_Z]);
+  const bool in_tpc = plane != c->default_plane_index;
+  const FieldMapDesc* m = (maps && in_tpc && maps[plane].node) ? &maps[plane] : nullptr;
+  double e_field = c->e_field;
+  if (m) {
+    double v[4];
+    fmap_eval(*m, &pos[LDSIM_X], m->has_e != 0, v);
+    if (m->has_e) e_field = v[0];
+    double d[LDSIM_NVIEW] = {0, 0, 0, 0, 0, 0, v[1], v[2], v[3]};
+    for (int p = 0; p < 2; p++) {
+      fmap_eval(*m, &pos[3 * p], false, v);
+      d[3 * p] = v[1];
+      d[3 * p + 1] = v[2];
+      d[3 * p + 2] = v[3];
+    }
+    const double(*b)[2] = c->tpc_borders[plane];
+#pragma unroll
+    for (int k = 0; k < LDSIM_NVIEW; k++) {
+      const int a = k % 3;
+      const double lo = fmin(fmin(b[a][0], b[a][1]), pos[k]), hi = fmax(fmax(b[a][0], b[a][1]), pos[k]);
+      pos[k] = narrow_store(fmin(fmax(pos[k] + d[k], lo), hi), s.store_code[k]);
+    }
+  }
+  if (view) {
+#pragma unroll
+    for (int k = 0; k < LDSIM_NVIEW; k++) view[k * cap + i] = pos[k];
+  }
+  const int32_t b = s.batch[i];
+  double n_e = s.f[LDSIM_N_ELECTRONS][i];
+  float z_att = 0, u_att = 0;
+  bool drawn = false;
+  int q;
+  if (b < 0) {
+    q = quench_at(s, c, mode, e_field, i, n_e);
+  } else {
+    double recomb;
+    q = recomb_at(c, mode, e_field, s.f[LDSIM_DEDX][i], recomb);
+    if (q == 0) {
+      const uint64_t key = key_mix(batch_keys[b], (uint64_t)(i - batch_first[b - batch0]));
+      const double dE = s.f[LDSIM_DE][i], n0 = dE / c->w_ion;
+      const double n_i = fmax(0.0, rint(n0 + sqrt(fano * n0) * (double)keyed_normal(seed, RNG_TAG_CHARGE, key, 0)));
+      n_e = binomial_draw(n_i, fmin(fmax(recomb, 0.0), 1.0), keyed_normal(seed, RNG_TAG_CHARGE, key, 1),
+                          keyed_uniform(seed, RNG_TAG_CHARGE, key, 2));
+      z_att = keyed_normal(seed, RNG_TAG_CHARGE, key, 3);
+      u_att = keyed_uniform(seed, RNG_TAG_CHARGE, key, 4);
+      s.f[LDSIM_N_ELECTRONS][i] = narrow_store(n_e, s.store_code[LDSIM_N_ELECTRONS]);
+      s.f[LDSIM_N_PHOTONS][i] = narrow_store((dE / c->w_ph - n_e) * c->scint_prescale, s.store_code[LDSIM_N_PHOTONS]);
+      drawn = true;
+    }
+  }
+  if (q == 1) {
+    *err = 1;
+    return;
+  }
+  if (q == 2) *err = 2;
+  s.pixel_plane[i] = plane;
+  if (!in_tpc) return;
+  if (!drawn) {
+    drift_at(s, c, plane, i, n_e, pos[LDSIM_Z], pos[LDSIM_Z_START], pos[LDSIM_Z_END]);
+    return;
+  }
+  const double drift_time = drift_times_at(s, c, plane, i, pos[LDSIM_Z], pos[LDSIM_Z_START], pos[LDSIM_Z_END]);
+  s.f[LDSIM_N_ELECTRONS][i] =
+      narrow_store(binomial_draw(n_e, exp(-drift_time / c->electron_lifetime), z_att, u_att), s.store_code[LDSIM_N_ELECTRONS]);
+}
+
 // ---- pixel walk (pixels_from_track.py:43-65, 111-199) ----------------------------------------------------------
 struct Walk {
   int64_t x0, y0, x1, y1, plane;
@@ -429,6 +571,15 @@ int seg_launch_quench_drift_map(ldsim_ctx* ctx, int mode, int* d_err) {
   hipLaunchKernelGGL(quench_drift_map_kernel, dim3(nblk(ctx->seg.n, 256)), dim3(256), 0, ctx->stream, ctx->seg,
                      ctx->d_consts.as<LdsimConsts>(), mode, (const FieldMapDesc*)ctx->d_fmap.as<FieldMapDesc>(), (double*)ctx->fmap_view.p, ctx->fmap_view_cap,
                      d_err);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int seg_launch_quench_drift_stat(ldsim_ctx* ctx, int mode, bool map, const int32_t* d_first, int32_t batch0, int* d_err) {
+  if (ctx->seg.n == 0) return 0;
+  hipLaunchKernelGGL(quench_drift_stat_kernel, dim3(nblk(ctx->seg.n, 256)), dim3(256), 0, ctx->stream, ctx->seg,
+                     ctx->d_consts.as<LdsimConsts>(), mode, map ? (const FieldMapDesc*)ctx->d_fmap.as<FieldMapDesc>() : nullptr,
+                     map ? (double*)ctx->fmap_view.p : nullptr, ctx->fmap_view_cap, ctx->rng_seed,
+                     (const uint64_t*)ctx->d_batch_keys.p, d_first, batch0, ctx->charge_stat_fano, d_err);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -19,6 +19,7 @@ int seg_launch_unpack(ldsim_ctx*, const LdsimTrackLayout*, int64_t);
 int seg_launch_repack(ldsim_ctx*, const LdsimTrackLayout*, int64_t);
 int seg_launch_quench_drift(ldsim_ctx*, int, int, int, int*);
 int seg_launch_quench_drift_map(ldsim_ctx*, int, int*);
+int seg_launch_quench_drift_stat(ldsim_ctx*, int, bool, const int32_t*, int32_t, int*);
 int seg_launch_max_pixels(ldsim_ctx*, int64_t, int64_t, int32_t*, unsigned long long*);
 int seg_launch_get_pixels(ldsim_ctx*, int64_t, int64_t, int, int32_t*, int, int32_t*, int32_t*, int, double*, const int32_t*,
                           int32_t);
@@ -461,11 +462,17 @@ static int upload_tracks(ldsim_ctx* ctx, const void* tracks, int64_t n, const Ld
                     "ldsim_clear_field_maps first, or run the resident chain");
     return LDSIM_ESTATE;
   }
+  if (!batch_id_is_resident && ctx->charge_stat) {
+    ldsim_set_error("charge statistics are enabled: the host-array stage calls keep the reference's mean-value charge; "
+                    "ldsim_set_charge_statistics(ctx, 0, ...) first, or run the resident chain");
+    return LDSIM_ESTATE;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
   CK(seg_reserve(ctx, n));
   ctx->seg.n = n;
   ctx->drift_map_gen = -1;
+  ctx->drift_stat_on = -1;
   ctx->seg_owner = batch_id_is_resident ? 1 : 2;
   ctx->light_n = -1;
   ctx->seg_layout = *lay;
@@ -548,20 +555,61 @@ extern "C" int ldsim_segments_reset(ldsim_ctx* ctx) {
   CK(light_join(ctx));
   ctx->light_n = -1;
   ctx->drift_map_gen = -1;
+  ctx->drift_stat_on = -1;
   return seg_launch_unpack(ctx, &ctx->seg_layout, ctx->seg.n);
 }
 
-// map = true (the resident chain while a drift-field map is set): quench_drift_map_kernel, which also writes the anode view
-static int run_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, bool map = false) {
+// charge statistics: the batch id range of the resident segments (checked against the batch keys) and the first index of
+// every batch over the whole store, which gives a segment its index within its batch
+static int stat_batch_first(ldsim_ctx* ctx, int32_t* batch0) {
+  if (!ctx->rng_keyed) {
+    ldsim_set_error("charge statistics draw keyed random streams: call ldsim_rng_keyed_seed (and ldsim_chain_set_batch_keys "
+                    "after the upload) before ldsim_dev_quench_drift");
+    return LDSIM_ESTATE;
+  }
+  const int64_t n = ctx->seg.n;
+  if ((int64_t)ctx->h_batch.size() < n) {
+    ldsim_set_error("resident batch ids missing: ldsim_segments_upload first");
+    return LDSIM_ESTATE;
+  }
+  int32_t lo = INT32_MAX, hi = -1;
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t b = ctx->h_batch[(size_t)i];
+    if (b < 0) continue;
+    lo = b < lo ? b : lo;
+    hi = b > hi ? b : hi;
+  }
+  if (hi < 0) lo = 0;                       // nothing is simulated: the kernel reads neither table
+  if ((int64_t)hi >= ctx->rng_batch_keys_n) {
+    ldsim_set_error("charge statistics: no key for batch id %d (ldsim_chain_set_batch_keys holds %lld): call "
+                    "ldsim_chain_set_batch_keys after every upload", hi, (long long)ctx->rng_batch_keys_n);
+    return LDSIM_ESTATE;
+  }
+  const size_t bytes = (size_t)((int64_t)hi - lo + 1 > 0 ? (int64_t)hi - lo + 1 : 1) * sizeof(int32_t);
+  CK(ctx->d_stat_first.ensure(bytes));
+  HIPCHK(hipMemsetAsync(ctx->d_stat_first.p, 0, bytes, ctx->stream));
+  CK(sort_batch_first(ctx, 0, n, lo, ctx->d_stat_first.as<int32_t>()));
+  *batch0 = lo;
+  return 0;
+}
+
+// map = true (the resident chain while a drift-field map is set): quench_drift_map_kernel, which also writes the anode view;
+// stat = true (the resident chain with charge statistics enabled): quench_drift_stat_kernel, with or without maps
+static int run_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, bool map = false, bool stat = false) {
   CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
   int* d_err = (int*)ctx->scratch[SB_MISC].p;
   HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
   ctx->drift_map_gen = -1;
-  if (map) {
-    if (ctx->fmap_view_cap < ctx->seg.cap) {
-      CK(ldsim_ensure_buf(ctx, &ctx->fmap_view, (size_t)ctx->seg.cap * LDSIM_NVIEW * sizeof(double)));
-      ctx->fmap_view_cap = ctx->seg.cap;
-    }
+  ctx->drift_stat_on = -1;
+  if (map && ctx->fmap_view_cap < ctx->seg.cap) {
+    CK(ldsim_ensure_buf(ctx, &ctx->fmap_view, (size_t)ctx->seg.cap * LDSIM_NVIEW * sizeof(double)));
+    ctx->fmap_view_cap = ctx->seg.cap;
+  }
+  if (stat) {
+    int32_t batch0 = 0;
+    CK(stat_batch_first(ctx, &batch0));
+    CK(seg_launch_quench_drift_stat(ctx, mode, map, ctx->d_stat_first.as<int32_t>(), batch0, d_err));
+  } else if (map) {
     CK(seg_launch_quench_drift_map(ctx, mode, d_err));
   } else {
     CK(seg_launch_quench_drift(ctx, mode, do_q, do_d, d_err));
@@ -578,6 +626,8 @@ static int run_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, bool m
     return LDSIM_EINVAL;
   }
   if (map) ctx->drift_map_gen = ctx->fmap_gen;
+  ctx->drift_stat_on = stat ? 1 : 0;
+  ctx->drift_stat_fano = ctx->charge_stat_fano;
   return 0;
 }
 
@@ -586,7 +636,28 @@ extern "C" int ldsim_dev_quench_drift(ldsim_ctx* ctx, int32_t mode) {
   NEED(ctx, "null ctx");
   NEED_RESIDENT(ctx);
   CK(light_join(ctx));
-  return run_quench_drift(ctx, mode, 1, 1, ctx->n_fmap > 0);
+  return run_quench_drift(ctx, mode, 1, 1, ctx->n_fmap > 0, ctx->charge_stat != 0);
+}
+
+// ---- charge statistics -----------------------------------------------------------------------------------------------------
+extern "C" int ldsim_set_charge_statistics(ldsim_ctx* ctx, int32_t enable, double fano) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  if (enable && !(std::isfinite(fano) && fano >= 0)) {
+    ldsim_set_error("charge statistics: the Fano factor %g must be finite and >= 0", fano);
+    return LDSIM_EINVAL;
+  }
+  ctx->charge_stat = enable ? 1 : 0;
+  if (enable) ctx->charge_stat_fano = fano;
+  return 0;
+}
+
+extern "C" int ldsim_get_charge_statistics(ldsim_ctx* ctx, int32_t* enable, double* fano) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  if (enable) *enable = ctx->charge_stat;
+  if (fano) *fano = ctx->charge_stat_fano;
+  return 0;
 }
 
 // ---- drift-field maps ----------------------------------------------------------------------------------------------------
@@ -1508,6 +1579,14 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
     if (ctx->drift_map_gen != ctx->fmap_gen) {
       ldsim_set_error("the drift-field maps changed since the last ldsim_dev_quench_drift: upload (or reset) and quench_drift "
                       "again");
+      return LDSIM_ESTATE;
+    }
+  }
+  if (ctx->drift_stat_on != -1 || ctx->charge_stat) {
+    // the chain reads the charge of the last quench_drift: it must have been made under the setting that holds now
+    if (ctx->drift_stat_on != ctx->charge_stat || (ctx->charge_stat && ctx->drift_stat_fano != ctx->charge_stat_fano)) {
+      ldsim_set_error("the charge statistics setting changed since the last ldsim_dev_quench_drift: upload (or reset) and "
+                      "quench_drift again");
       return LDSIM_ESTATE;
     }
   }

@@ -372,6 +372,13 @@ struct ldsim_ctx {
   int64_t drift_map_gen = -1;            // fmap_gen of the mapped quench_drift whose results the store holds (-1: none)
   DevBuf fmap_view;                      // [LDSIM_NVIEW][fmap_view_cap] anode-view columns (allocated while a map is set)
   int64_t fmap_view_cap = 0;
+  // charge statistics (ldsim_set_charge_statistics): counted ion pairs, binomial recombination and attachment in the
+  // resident quench_drift (quench_drift_stat_kernel); needs keyed mode and batch keys
+  int charge_stat = 0;
+  double charge_stat_fano = 0.107;
+  int drift_stat_on = -1;                // setting of the quench_drift whose results the store holds (-1: none since the upload)
+  double drift_stat_fano = 0;
+  DevBuf d_stat_first;                   // [batches of the upload] i32 first segment index of every batch over the whole store
   // multi-GPU exchange (comm.hip): RCCL communicator, rows accumulated over the chain calls of a pass, gathered rows
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 0;

@@ -23,6 +23,7 @@ class ChargeChain:
         if response is not None:
             lib.set_response(response, self.ctx)
         self.clear_field_map()          # the ctx is process-wide: a fresh chain starts with the uniform field
+        self.set_charge_statistics(False)                         # ... and with mean-value charge
 
     def set_field_map(self, maps):
         """Drift-field maps (``field_map``: {tpc: {"origin", "spacing", "E" / "dx" / "dy" / "dz"}}, or the path of an .npz),
@@ -51,6 +52,18 @@ class ChargeChain:
         out = np.empty((9, self.n), dtype=np.float64)
         lib.check(lib.load().ldsim_dev_anode_view_download(self.ctx, lib.ptr(out)))
         return out
+
+    def set_charge_statistics(self, enable=True, fano=0.107):
+        """Charge statistics (``charge_stats``): the next ``quench_drift`` counts ion pairs (Fano factor ``fano``) and draws
+        recombination and attachment as binomials from keyed streams, instead of writing mean values.  Needs ``seed_keyed`` and
+        ``set_batch_keys`` before ``quench_drift``; ``run`` refuses until ``quench_drift`` has run under the new setting."""
+        lib.check(lib.load().ldsim_set_charge_statistics(self.ctx, C.c_int32(int(bool(enable))), C.c_double(float(fano))))
+
+    def charge_statistics(self):
+        """(enabled, Fano factor) as the context holds them"""
+        on, f = C.c_int32(), C.c_double()
+        lib.check(lib.load().ldsim_get_charge_statistics(self.ctx, C.byref(on), C.byref(f)))
+        return bool(on.value), f.value
 
     def seed_rng(self, seed, n_states=1024 * 256):
         """``create_xoroshiro128p_states(1024*256, seed=rand_seed)`` of the driver (cli/simulate_pixels.py:396): needed before

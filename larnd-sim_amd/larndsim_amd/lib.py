@@ -35,6 +35,7 @@ EXPORTS = [
     "ldsim_scintillation_effect", "ldsim_light_detector_response",
     "ldsim_segments_upload", "ldsim_segments_download", "ldsim_segments_reset", "ldsim_dev_quench_drift", "ldsim_charge_chain",
     "ldsim_set_field_map", "ldsim_clear_field_maps", "ldsim_dev_anode_view_download",
+    "ldsim_set_charge_statistics", "ldsim_get_charge_statistics",
     "ldsim_chain_download", "ldsim_chain_download_async", "ldsim_chain_download_wait", "ldsim_chain_compact_hits", "ldsim_chain_compact_build", "ldsim_chain_compact_download", "ldsim_chain_kernel_ms", "ldsim_chain_kernel_ms_detail",
     "ldsim_dev_light_incidence", "ldsim_dev_light_incidence_download", "ldsim_dev_light_t0_range", "ldsim_dev_sum_light",
     "ldsim_dev_light_download", "ldsim_light_kernel_ms",

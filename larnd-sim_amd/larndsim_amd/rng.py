@@ -51,7 +51,7 @@ def maybe_create_rng_states(n, seed=0, rng_states=None, ctx=None):
 # numbers at any chunking, rank count or event subset.
 MASK64 = (1 << 64) - 1
 KEY_ROOT = 0x6A09E667F3BCC909
-TAG_FEE, TAG_LIGHT_FLUCT, TAG_LIGHT_NOISE, TAG_MC = 1, 2, 3, 4
+TAG_FEE, TAG_LIGHT_FLUCT, TAG_LIGHT_NOISE, TAG_MC, TAG_CHARGE = 1, 2, 3, 4, 5
 
 
 def _fin(z):
