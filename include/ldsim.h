@@ -435,6 +435,51 @@ typedef struct {
  * stage ran, n_fallback counts the pairs the monolithic kernel recomputed */
 int ldsim_tracks_current_stats(ldsim_ctx* ctx, LdsimChainStats* stats);
 
+/* Slots of the census below.  Every count but the first three is over the pairs the node-separable form emitted itself
+ * (tables built, not flagged for the monolithic kernel). */
+enum {
+  LDSIM_GC_PAIRS = 0,      /* pairs of the launch */
+  LDSIM_GC_TABLES,         /* pairs with tables (status 1), flagged ones included */
+  LDSIM_GC_FLAGGED,        /* pairs flagged for the monolithic kernel */
+  LDSIM_GC_EMITTED,        /* pairs with tables that are not flagged */
+  LDSIM_GC_T_WAVE,         /* tables kernel: gtables_wave_kernel<M, 55> */
+  LDSIM_GC_T_WIDE,         /*                its wide instantiation <M, 81> */
+  LDSIM_GC_T_WG,           /*                the workgroup gtables_kernel<M>, for any of the four reasons below */
+  LDSIM_GC_WG_SHIFTS,      /*   more than 256 response shifts */
+  LDSIM_GC_WG_BINS,        /*   more than 80 X | Y bins */
+  LDSIM_GC_WG_SLICES,      /*   neither: more than 64 slices (or a sample count the wave kernel's maps do not cover) */
+  LDSIM_GC_WG_FORCED,      /*   a pair the wave kernels take, under option gform_wave_tables 0 */
+  LDSIM_GC_NB1,            /* node batches: 1 */
+  LDSIM_GC_NB2,            /*               2 */
+  LDSIM_GC_NB3P,           /*               3 or more */
+  LDSIM_GC_ROWS4,          /* node rows of the last batch: 4 */
+  LDSIM_GC_ROWS8,
+  LDSIM_GC_ROWS12,
+  LDSIM_GC_ROWS16,
+  LDSIM_GC_CLS0,           /* LDS class of the correlation: 0 (the launch over all pairs) */
+  LDSIM_GC_CLS1,           /*                               1 (listed) */
+  LDSIM_GC_CLS2,           /*                               2 (listed) */
+  LDSIM_GC_CLS0_ZREC,      /* of that class, the pairs whose Z table the correlation reads from the record (z_lds false) */
+  LDSIM_GC_CLS1_ZREC,
+  LDSIM_GC_CLS2_ZREC,
+  LDSIM_GC_NU_OVER_CAP,    /* more response shifts than the LDS copy of Z holds (NU > 128) */
+  LDSIM_GC_EMASK0,         /* window-edge columns: bit 0 of emask set */
+  LDSIM_GC_EMASK1,
+  LDSIM_GC_EMASK2,
+  LDSIM_GC_M,              /* launch scalars: TIME_SAMPLING / RESPONSE_SAMPLING */
+  LDSIM_GC_TT,             /*   ticks per tile */
+  LDSIM_GC_QB0,            /*   1 = the launch over all pairs ran the 4-node-block instance of gcorr_kernel, 0 = the 16-node product */
+  LDSIM_GC_QB12,           /*   the same for the listed launches */
+  LDSIM_GFORM_CENSUS_N
+};
+/* Test seam.  Which code paths the pairs of the last ldsim_tracks_current / ldsim_charge_chain call took in the node-separable
+ * form (weights_mode 2): counts[LDSIM_GFORM_CENSUS_N] int64, n >= LDSIM_GFORM_CENSUS_N.  With n >= LDSIM_GFORM_CENSUS_N + pairs
+ * of the launch, counts[LDSIM_GFORM_CENSUS_N + p] is in addition the set of slots pair p was counted in (bit s = slot s; slots
+ * 0 and 28.. are never set), so that a caller can tell WHICH pairs a slot held.  Counted on the host from the launch's own
+ * per-pair records with the functions the launch dealt the pairs by.  LDSIM_ESTATE if the last current stage did not run
+ * that form, or its records are gone. */
+int ldsim_debug_gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n);
+
 /* Fused a5-a16 (max_pixels .. digitize) on resident segments [seg_begin, seg_end):
  * per unique (batch, pixel), sorted by batch then pixel id exactly like the reference's concatenated
  * per-batch `unique_pix`.  Results stay in HBM; fetch with ldsim_chain_download(). */

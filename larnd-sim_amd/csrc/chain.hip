@@ -61,6 +61,7 @@ static int run_tracks_current(ldsim_ctx* ctx, CurArgs& a, int64_t n_seg, unsigne
   int32_t* win = a.win;
   a.win = nullptr;
   if (win_used) *win_used = false;
+  ctx->gform_rec.valid = 0;            // (gform_launch sets it: every other path leaves no census)
   if (ctx->mc_current) return current_mc_launch(ctx, a, n_seg);   // the driver's call site (cli/simulate_pixels.py:1016)
   // The node-separable form pays per response tick of the staged support (nodes x cells x ticks on the matrix pipe), the
   // shifted-window kernels per 512-tick tile and (weight, tick) pair.  Until round 4 a table with full support (no exact zeros
@@ -166,7 +167,10 @@ int chain_tracks_current(ldsim_ctx* ctx, const int32_t* d_pixels, int P, float* 
   ctx->stage_stats.n_pairs = a.n_pairs;
   ctx->stage_stats.max_neigh = P;
   ctx->stage_stats.max_length = T;
-  if (mc) return current_mc_launch(ctx, a, ctx->seg.n);
+  if (mc) {
+    ctx->gform_rec.valid = 0;
+    return current_mc_launch(ctx, a, ctx->seg.n);
+  }
   bool split_timed = false;
   const int keep_mc = ctx->mc_current;
   ctx->mc_current = 0;                 // the stage call names its kernel itself

@@ -724,7 +724,7 @@ __global__ void __launch_bounds__(256) gflag_list_kernel(const int32_t* __restri
 
 extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters, int32_t** flags_out,
                               const int32_t** flag_list, const unsigned long long** flag_count) {
-  const int M = gform_M(ctx, a);
+  const int M = gform_M(ctx, a);      // (ctx->gform_rec was marked invalid by run_tracks_current, the one owner of that)
   if (!M) return 1;
   const int64_t n = a.n_pairs;
   hipStream_t st = ctx->stream;
@@ -819,14 +819,15 @@ extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long lo
   GA.glx = ctx->d_glx.as<double>();
   GA.glw = ctx->d_glw.as<double>();
   GA.resp_pad = (const double*)ctx->resp_pad.p;
+  // (the 4-node-block kernel: the listed classes, and at M = 2 the launch over all pairs too -- 109 VGPRs, four waves per SIMD
+  // instead of five at 96: ndlar 12.33 -> 11.88 ms per 50 k; at M = 1 six waves at 80 VGPRs beat four: 4.93 against 5.67.
+  // debug_gform 4096: the 16-node product in every launch; 65536: the 4-node blocks in every launch)
+  auto qb_of = [&](int cls) { return (cls > 0 || M == 2 || (ctx->debug_gform & 65536)) && !(ctx->debug_gform & 4096); };
   auto corr = [&](int cls, int64_t pair0, int64_t count) -> int {
     if (count <= 0) return 0;
     const int32_t* list = cls == 0 ? nullptr : d_big + (int64_t)(cls - 1) * n;
     const size_t dyn = (size_t)(cls == 0 ? b0 : (cls == 1 ? b1 : b2));
-    // (the 4-node-block kernel: the listed classes, and at M = 2 the launch over all pairs too -- 109 VGPRs, four waves per SIMD
-    // instead of five at 96: ndlar 12.33 -> 11.88 ms per 50 k; at M = 1 six waves at 80 VGPRs beat four: 4.93 against 5.67.
-    // debug_gform 4096: the 16-node product in every launch; 65536: the 4-node blocks in every launch)
-    const bool qb = (cls > 0 || M == 2 || (ctx->debug_gform & 65536)) && !(ctx->debug_gform & 4096);
+    const bool qb = qb_of(cls);
     if (M == 1 && !qb) hipLaunchKernelGGL((gcorr_kernel<1, false>), dim3((unsigned)count), dim3(GT), dyn, st, GA, TT, b0, b1, b2, list, cls, (int)pair0);
     else if (M == 1) hipLaunchKernelGGL((gcorr_kernel<1, true>), dim3((unsigned)count), dim3(GT), dyn, st, GA, TT, b0, b1, b2, list, cls, (int)pair0);
     else if (!qb) hipLaunchKernelGGL((gcorr_kernel<2, false>), dim3((unsigned)count), dim3(GT), dyn, st, GA, TT, b0, b1, b2, list, cls, (int)pair0);
@@ -870,5 +871,79 @@ extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long lo
   HIPCHK(hipGetLastError());
   *flag_list = d_wg + n;
   *flag_count = d_total + 4;
+  {      // what this launch decided, for ldsim_debug_gform_census
+    ldsim_ctx::GformRecord& R = ctx->gform_rec;
+    R.M = M; R.TT = TT; R.b0 = b0; R.b1 = b1; R.b2 = b2; R.Mz = Mz;
+    for (int cls = 0; cls < 3; cls++) { R.qb[cls] = qb_of(cls); R.n_cls[cls] = n_cls[cls]; }
+    R.wave_tables = !(GA.dbg & 64);
+    R.n = n; R.n_wg = n_wg; R.n_w2 = n_w2;
+    R.gi = gi; R.flags = GA.flags;
+    R.valid = 1;
+  }
+  return 0;
+}
+
+// ldsim_debug_gform_census (include/ldsim.h): the launch's GInfo array and flags copied back, the pairs counted with the
+// functions gbig_list_kernel / gcorr_kernel / gtables_list_kernel dealt them by
+extern "C++" int gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n_out) {
+  const ldsim_ctx::GformRecord& R = ctx->gform_rec;
+  if (!R.valid || R.gi != ctx->scratch[SB_HDR].p || R.flags != ctx->scratch[SB_ITEMS].p) {
+    ldsim_set_error("the last current stage did not run the node-separable form (or its records are gone)");
+    return LDSIM_ESTATE;
+  }
+  const int64_t n = R.n;
+  std::vector<GInfo> h((size_t)n);
+  std::vector<int32_t> fl((size_t)n);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(h.data(), R.gi, (size_t)n * sizeof(GInfo), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(fl.data(), R.flags, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (int s = 0; s < LDSIM_GFORM_CENSUS_N; s++) counts[s] = 0;
+  const bool per_pair = (int64_t)n_out >= LDSIM_GFORM_CENSUS_N + n;
+  unsigned long long l_wg = 0, l_w2 = 0, l_cls[3] = {0, 0, 0};      // the launch's lists hold flagged pairs too
+  for (int64_t p = 0; p < n; p++) {
+    const GInfo& g = h[(size_t)p];
+    int64_t m = 0;
+    auto hit = [&](int slot) { m |= (int64_t)1 << slot; };
+    if (g.status == 1) hit(LDSIM_GC_TABLES);
+    if (fl[(size_t)p]) hit(LDSIM_GC_FLAGGED);
+    if (g.status == 1) {
+      const int cls = g_lds_class(g.ncol, g.NJ, g.NU, R.TT, R.b0, R.b1, R.Mz);
+      const int tk = (!R.wave_tables || g.wave_ok == 0) ? 0 : g.wave_ok;      // gtables_list_kernel
+      l_cls[cls]++;
+      l_wg += tk == 0;
+      l_w2 += tk == 2;
+      if (!fl[(size_t)p]) {
+        hit(LDSIM_GC_EMITTED);
+        hit(tk == 1 ? LDSIM_GC_T_WAVE : (tk == 2 ? LDSIM_GC_T_WIDE : LDSIM_GC_T_WG));
+        if (tk == 0) {
+          if (g.wave_ok != 0) hit(LDSIM_GC_WG_FORCED);
+          else {
+            if (g.NU > 2 * G_NUCAP) hit(LDSIM_GC_WG_SHIFTS);
+            if (g.ncol + g.NJ > 80) hit(LDSIM_GC_WG_BINS);
+            if (g.NU <= 2 * G_NUCAP && g.ncol + g.NJ <= 80) hit(LDSIM_GC_WG_SLICES);
+          }
+        }
+        hit(g.NB == 1 ? LDSIM_GC_NB1 : (g.NB == 2 ? LDSIM_GC_NB2 : LDSIM_GC_NB3P));
+        hit(LDSIM_GC_ROWS4 + g_rows(g.NQ, g.NB - 1) / 4 - 1);
+        hit(LDSIM_GC_CLS0 + cls);
+        if (!g_lds_layout(g.ncol, g.NJ, g.NU, R.TT, cls == 0 ? R.b0 : (cls == 1 ? R.b1 : R.b2), R.Mz).z_lds) hit(LDSIM_GC_CLS0_ZREC + cls);
+        if (g.NU > G_NUCAP) hit(LDSIM_GC_NU_OVER_CAP);
+        for (int e = 0; e < 3; e++)
+          if (g.emask & (1 << e)) hit(LDSIM_GC_EMASK0 + e);
+      }
+    }
+    for (int s = 1; s < LDSIM_GC_M; s++) counts[s] += (m >> s) & 1;
+    if (per_pair) counts[LDSIM_GFORM_CENSUS_N + p] = m;
+  }
+  if (l_wg != R.n_wg || l_w2 != R.n_w2 || l_cls[1] != R.n_cls[1] || l_cls[2] != R.n_cls[2]) {
+    ldsim_set_error("gform census disagrees with the launch's own lists (workgroup tables %llu / %llu, wide wave %llu / %llu, "
+                    "LDS class 1 %llu / %llu, class 2 %llu / %llu)", l_wg, R.n_wg, l_w2, R.n_w2, l_cls[1], R.n_cls[1], l_cls[2], R.n_cls[2]);
+    return LDSIM_ESTATE;
+  }
+  counts[LDSIM_GC_PAIRS] = n;
+  counts[LDSIM_GC_M] = R.M;
+  counts[LDSIM_GC_TT] = R.TT;
+  counts[LDSIM_GC_QB0] = R.qb[0];
+  counts[LDSIM_GC_QB12] = R.qb[1];
   return 0;
 }

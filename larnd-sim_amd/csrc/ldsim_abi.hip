@@ -879,6 +879,14 @@ extern "C" int ldsim_tracks_current_stats(ldsim_ctx* ctx, LdsimChainStats* stats
   return 0;
 }
 
+int gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n_out);
+extern "C" int ldsim_debug_gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && counts && n >= LDSIM_GFORM_CENSUS_N, "bad gform census arguments");
+  HIPCHK(hipSetDevice(ctx->device));
+  return gform_census(ctx, counts, n);
+}
+
 extern "C" int ldsim_tracks_current_mc(ldsim_ctx* ctx, const void* tracks, int64_t n, const LdsimTrackLayout* layout,
                                        const int32_t* pixels, int32_t P, float* signals, int32_t T) {
   LDSIM_ENTER(ctx);

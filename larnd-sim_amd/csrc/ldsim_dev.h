@@ -292,6 +292,14 @@ struct ldsim_ctx {
   Event tab_ev[34];                          // per-range events of that second stream (tab_stream)
   int gform_wave_tables = 1;                 // 1: gtables_wave_kernel (a wave per pair) for the pairs that fit it, 0: gtables_kernel for all
   int debug_gform = 0;                       // timing tools: parts of gtables_kernel / gcorr_kernel switched off (tools/gform_phases.py)
+  // what gform_launch decided for the last current stage (ldsim_debug_gform_census counts the pairs from it); valid = 0 once
+  // another current path ran: its GInfo array (SB_HDR) and flags (SB_ITEMS) are that path's then
+  struct GformRecord {
+    int valid = 0, M = 0, TT = 0, b0 = 0, b1 = 0, b2 = 0, Mz = 0, qb[3] = {0, 0, 0}, wave_tables = 1;
+    int64_t n = 0;
+    unsigned long long n_wg = 0, n_w2 = 0, n_cls[3] = {0, 0, 0};
+    const void *gi = nullptr, *flags = nullptr;      // (aliases of the two scratch buffers, compared only)
+  } gform_rec;
   int split_kernels = 1;            // 1: weights_kernel + mac_kernel (default), 0: monolithic current_kernel
   int wbuf_doubles_per_pair = 6144; // initial average budget of the split path's weight pool, doubles per pair
   int split_max_items = 0;          // validation knob, see CurArgs

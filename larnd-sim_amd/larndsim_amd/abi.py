@@ -58,6 +58,13 @@ class LdsimChainStats(C.Structure):
 
 ABI_VERSION = 8      # include/ldsim.h LDSIM_ABI_VERSION: the struct layouts of this file
 
+# slots of ldsim_debug_gform_census, in the order of include/ldsim.h's LDSIM_GC_* enum (tests/test_cpu_host.py compares the two)
+GFORM_CENSUS_SLOTS = (
+    "pairs", "tables", "flagged", "emitted", "t_wave", "t_wide", "t_wg", "wg_shifts", "wg_bins", "wg_slices", "wg_forced",
+    "nb1", "nb2", "nb3p", "rows4", "rows8", "rows12", "rows16", "cls0", "cls1", "cls2", "cls0_zrec", "cls1_zrec", "cls2_zrec",
+    "nu_over_cap", "emask0", "emask1", "emask2", "m", "tt", "qb0", "qb12")
+GFORM_CENSUS_N = len(GFORM_CENSUS_SLOTS)
+
 
 def pack_consts(noise_zero=False):
     """Freeze the current ``consts`` namespaces into the plain struct the C-ABI takes."""

@@ -50,6 +50,25 @@ def tracks_current_stats():
     return st
 
 
+def gform_census(per_pair=False, n_pairs=None):
+    """Which code paths the pairs of the last ``tracks_current`` / chain launch took in the node-separable form
+    (``ldsim_debug_gform_census``): a dict of counts by ``abi.GFORM_CENSUS_SLOTS``.  ``per_pair``: also ``"pair_slots"``, an
+    int64 array over the launch's pairs whose bit s tells that the pair was counted in slot s (``n_pairs``: their number, if the
+    caller knows it -- it spares the call that asks).  Raises ``LdsimError`` when the
+    last current stage ran other kernels."""
+    from .abi import GFORM_CENSUS_N, GFORM_CENSUS_SLOTS
+    ctx = lib.context(refresh_consts=False)
+    c = np.zeros(GFORM_CENSUS_N + (int(n_pairs) if per_pair and n_pairs is not None else 0), dtype=np.int64)
+    lib.check(lib.load().ldsim_debug_gform_census(ctx, lib.ptr(c), C.c_int32(c.size)))
+    if per_pair and c.size < GFORM_CENSUS_N + int(c[0]):
+        c = np.zeros(GFORM_CENSUS_N + int(c[0]), dtype=np.int64)
+        lib.check(lib.load().ldsim_debug_gform_census(ctx, lib.ptr(c), C.c_int32(c.size)))
+    out = {name: int(c[k]) for k, name in enumerate(GFORM_CENSUS_SLOTS)}
+    if per_pair:
+        out["pair_slots"] = c[GFORM_CENSUS_N:GFORM_CENSUS_N + int(c[0])].copy()
+    return out
+
+
 @kernel
 def tracks_current_mc(signals, pixels, tracks, response, rng_states):
     """``tracks_current_mc[bpg, tpb](signals, pixels, tracks, response, rng_states)`` -- the reference driver's call site

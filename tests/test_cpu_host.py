@@ -35,6 +35,15 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert l.ldsim_abi_version() == abi.ABI_VERSION == 8
 
 
+def test_gform_census_slots_match_header():
+    """abi.GFORM_CENSUS_SLOTS names the LDSIM_GC_* enumerators of include/ldsim.h in their order; LDSIM_GFORM_CENSUS_N closes it."""
+    hdr = open(os.path.join(REPO, "include", "ldsim.h")).read()
+    body = hdr[hdr.index("LDSIM_GC_PAIRS = 0"):hdr.index("LDSIM_GFORM_CENSUS_N\n")]
+    names = re.findall(r"\bLDSIM_GC_([A-Z0-9_]+)\b", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert tuple(n.lower() for n in names) == abi.GFORM_CENSUS_SLOTS
+    assert abi.GFORM_CENSUS_N == len(names) == 32 and len(set(names)) == 32
+
+
 def test_graft_entry_build_succeeds():
     """The driver's build check: __graft_entry__.build() compiles the HIP library and the oracle and imports the package
     (an incremental make here).  It once asserted a stale ABI version after the header had moved on."""
