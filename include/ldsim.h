@@ -515,6 +515,50 @@ int ldsim_chain_compact_download(ldsim_ctx* ctx, int32_t* hit_pixels, int64_t* t
  * hits are (batch i32, pixel i32, adc u8-as-i32, tick f64) rows for every written ADC slot. */
 int ldsim_chain_compact_hits(ldsim_ctx* ctx, void** dev_rows, int64_t* n_rows, int32_t* row_bytes);
 
+/* ---- pixel charge truth: induced charge per pixel and per (pixel, track) of the last chain launch ---------------------
+ * Mirrors nothing in the reference, whose output ends in hits: it keeps neither the charge that never triggered, nor the
+ * pixels without a hit, nor the absolute charge a segment put on a pixel (its backtracking fractions are normalised per
+ * hit).  One reduction pass over what the launch left in HBM -- the per-pair current rows and the set-up record of the sum
+ * sum_pixel_signals stands for (detsim.py:468-527) -- per unique-pixel row u of ldsim_chain_download, in the unit of
+ * adc_list (electrons), dt = time_sampling:
+ *   q_track[u][k]  dt * sum_t wf_k[t], k < the pixel's filled track_pixel_map slots (the others 0): the f32 current row of
+ *                  slot k over exactly the ticks the pixel sum takes from it (its written window on the pixel's time axis,
+ *                  clipped to [0, N_t)), accumulated in f64
+ *   q_induced[u]   dt * sum_t S[t], S the pixel's summed waveform as the FEE kernel forms it (f64, slots added in slot order)
+ *   q_abs[u]       dt * sum_t |S[t]|: a pixel that only saw induction has q_induced ~ 0 and q_abs > 0
+ *   n_hits[u], q_hits[u] = sum_{h < n_hits} adc_list[u][h], read from the launch's own results: with FEE noise on, q_hits
+ *                  includes the noise charges the hits were read out with; the three values above never do.
+ * ldsim_chain_pixel_truth runs the pass and a selection on the device: a pixel is kept when n_hits > 0 or
+ * q_abs >= min_abs_charge (electrons; 0 keeps every unique pixel).  sizes[2] = kept pixels, track entries (one per filled
+ * slot of a kept pixel); one synchronisation.  A launch without unique pixels gives sizes 0, 0.
+ * ldsim_chain_pixel_truth_download: the compact form, pixel rows in row order and track entries pixel after pixel, slot 0
+ * up; either pointer may be NULL.  ldsim_chain_pixel_truth_dense_download: the dense arrays of the last pass, U = the
+ * launch's n_unique, q_track [U][M] with M = MAX_TRACKS_PER_PIXEL; any pointer may be NULL.
+ * State rules: the pass reads scratch buffers the library reuses, so it returns LDSIM_ESTATE, with a message naming the
+ * call, once anything may have rewritten them since the launch: ldsim_segments_upload, ldsim_segments_reset,
+ * ldsim_dev_quench_drift, any host-array stage call, ldsim_set_consts with other constants, a later ldsim_charge_chain that
+ * failed.  The downloads return LDSIM_ESTATE unless the pass has run for the last chain launch.
+ * ldsim_chain_pixel_truth_row_samples (timing tools): the current samples q_track sums over all pixels of the last launch,
+ * counted on the device from the same record under the same state rule; the bytes the pass reads from the current rows
+ * are four times that. */
+typedef struct LdsimPixelTruthRow {
+  int32_t row;          /* u: index in the arrays of ldsim_chain_download */
+  int32_t pixel_id;
+  int32_t batch;
+  int32_t n_hits;
+  int32_t n_tracks;     /* filled track_pixel_map slots = the pixel's track entries */
+  int32_t pad;
+  double q_hits, q_induced, q_abs;
+} LdsimPixelTruthRow;
+typedef struct LdsimPixelTruthTrack {
+  int64_t segment;      /* segment index within the batch, as in track_pixel_map */
+  double q;             /* q_track */
+} LdsimPixelTruthTrack;
+int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, int64_t sizes[2]);
+int ldsim_chain_pixel_truth_download(ldsim_ctx* ctx, LdsimPixelTruthRow* pixel_rows, LdsimPixelTruthTrack* track_entries);
+int ldsim_chain_pixel_truth_dense_download(ldsim_ctx* ctx, int64_t U, double* q_induced, double* q_abs, double* q_track);
+int ldsim_chain_pixel_truth_row_samples(ldsim_ctx* ctx, int64_t* n_samples);
+
 /* ---- device-resident light leg (cli/simulate_pixels.py:749-797 and :1120-1153 on the resident segments) ---------- */
 /* lightLUT.calculate_light_incidence[bpg,tpb](tracks, lut, light_sim_dat, track_light_voxel) over ALL resident segments,
  * after ldsim_dev_quench_drift (it needs n_photons and pixel_plane): n_photons_det [n][n_out] f4, t0_det [n][n_out] f4

@@ -83,6 +83,12 @@ def _parser():
                          "keyed streams (larndsim_amd/charge_stats.py) instead of mean values; needs --rng keyed")
     ap.add_argument("--fano_factor", type=float, default=None,
                     help="Fano factor of the ion-pair count under --charge_statistics (default 0.107)")
+    ap.add_argument("--pixel_truth", action="store_true",
+                    help="also store the true induced charge per pixel and per (pixel, segment) of every chain launch "
+                         "(datasets pixel_truth and pixel_truth_tracks, larndsim_amd/pixel_truth.py); one GPU only")
+    ap.add_argument("--pixel_truth_min_charge", type=float, default=None,
+                    help="under --pixel_truth: pixels without a hit are stored when they saw at least this much |charge| "
+                         "[electrons] (default 0: every pixel a segment reached)")
     ap.add_argument("--chunk_segments", type=int, default=50000,
                     help="segments per chain launch (whole batches, at least this many; default 50000)")
     return ap
@@ -102,6 +108,10 @@ def _parse_args(argv=None):
         ap.error(CHARGE_STATISTICS_NEEDS_KEYED)
     if a.fano_factor is not None and not (0 <= a.fano_factor < float("inf")):
         ap.error("--fano_factor must be finite and >= 0")
+    if a.pixel_truth_min_charge is not None and not a.pixel_truth:
+        ap.error("--pixel_truth_min_charge sets the selection of --pixel_truth: give --pixel_truth as well")
+    if a.pixel_truth_min_charge is not None and not (0 <= a.pixel_truth_min_charge < float("inf")):
+        ap.error("--pixel_truth_min_charge must be finite and >= 0")
     return a
 
 
@@ -117,6 +127,9 @@ def launch_ranks_if_asked(argv=None):
     if world is not None and world > 1 and a["raw_arrays"]:
         raise SystemExit("simulate_pixels.py: --raw_arrays is not available with --n_gpus > 1 (the compact path is the "
                          "production one)")
+    if world is not None and world > 1 and a["pixel_truth"]:
+        raise SystemExit("simulate_pixels.py: --pixel_truth is not available with --n_gpus > 1 (its rows are not gathered "
+                         "over the ranks)")
     if world is None or "WORLD_SIZE" in os.environ:
         return
     if os.path.exists(a["output_filename"]):
@@ -138,6 +151,7 @@ from larndsim_amd import batching, charge_stats, consts, fee, light_sim, packets
 from larndsim_amd import config as cfgmod  # noqa: E402
 from larndsim_amd import dist as ldist  # noqa: E402
 from larndsim_amd import field_map as lfmap  # noqa: E402
+from larndsim_amd import pixel_truth as lptruth  # noqa: E402
 from larndsim_amd import rng as lrng  # noqa: E402
 from larndsim_amd.chain import ChargeChain  # noqa: E402
 
@@ -203,6 +217,8 @@ class _Output:
         if filename.endswith((".h5", ".hdf5")) and self.h5py is None:
             raise RuntimeError("HDF5 output needs h5py; give an .npz output name instead")
         self.parts = {}
+        self.appended = set()           # datasets `append` has written rows of
+        self.pixel_truth_tracks = 0     # rows of pixel_truth_tracks so far (pixel_truth's track_begin counts over the file)
 
     def append_packets(self, pk, assn):
         if self.h5py is not None:
@@ -215,6 +231,7 @@ class _Output:
         """resizable dataset grown along axis 0 (light_trig, light_wvfm, light_wvfm_mc_assn)"""
         if data.shape[0] == 0:
             return
+        self.appended.add(name)
         if self.h5py is not None:
             with self.h5py.File(self.filename, "a") as f:
                 light_sim._append(f, name, data, (None,) * data.ndim)
@@ -340,7 +357,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    tracks_current_mc=False, chunk_segments=50000, raw_arrays=False, overlap_downloads=None,
                    pixel_layout_id=None, response_id=None, light_lut_id=None, pixel_thresholds_id=None, pixel_gains_id=None,
                    numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
-                   fano_factor=None, **ignored):
+                   fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -348,6 +365,10 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     if world is not None and world > 1 and raw_arrays:
         raise ValueError("--raw_arrays is not available with --n_gpus > 1: the per-pixel arrays stay on the rank that made them "
                          "(the compact path is the production one)")
+    if world is not None and world > 1 and pixel_truth:
+        raise ValueError("--pixel_truth is not available with --n_gpus > 1: its rows are not gathered over the ranks")
+    if pixel_truth_min_charge is not None and not pixel_truth:
+        raise ValueError("--pixel_truth_min_charge sets the selection of --pixel_truth: give --pixel_truth as well")
     if not os.path.exists(input_filename):
         raise Exception(f"Input file {input_filename} does not exist.")
     if rank == 0 and os.path.exists(output_filename):             # (only rank 0 writes)
@@ -483,6 +504,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     fano = charge_stats.FANO_DEFAULT if fano_factor is None else float(fano_factor)
     print("Charge statistics:", f"on (--charge_statistics, Fano factor {fano:g})" if charge_statistics
           else "off (mean-value charge)")
+    truth_min = None if not pixel_truth else float(pixel_truth_min_charge or 0.0)
+    if pixel_truth:                     # (without the flag the header, like the file, is what it was)
+        print("Pixel charge truth:", f"on (--pixel_truth, --pixel_truth_min_charge {truth_min:g} e)")
     lib.set_option("numba_f32", f32_mode)
     dist = None
     if world is not None:
@@ -533,7 +557,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             res = _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field,
                                    per_module(light_lut_filename, i_mod) if light_simulated else None, light_det_noise_filename,
                                    cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist,
-                                   keyed=rng == "keyed")
+                                   keyed=rng == "keyed", pixel_truth_min=truth_min)
             for k in totals:
                 totals[k] += res[k]
             rows_per_rank += res["rows_per_rank"]
@@ -566,6 +590,10 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             out.put(f"light_dat/light_dat_module{i_mod - 1}" if m2m else "light_dat/light_dat_allmodules", dat)
         for k, v in truth.items():
             out.put(k, v)
+        if pixel_truth:                 # (both datasets exist even when no pixel was reached)
+            for name, dt in (("pixel_truth", lptruth.FILE_PIXEL), ("pixel_truth_tracks", lptruth.FILE_TRACK)):
+                if name not in out.appended:
+                    out.put(name, np.zeros(0, dtype=dt))
         out.close(pixel_layout if isinstance(pixel_layout, str) else None if pixel_layout is None else list(pixel_layout))
     finally:
         lib.set_option("mc_current", 0)
@@ -582,7 +610,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
 
 def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field, light_lut,
                      light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None,
-                     dist=None, keyed=False):
+                     dist=None, keyed=False, pixel_truth_min=None):
     """One pass of the driver's module loop body (cli/simulate_pixels.py:717-1232) on the device-resident chain: quench + drift,
     light leg, charge chain, packets.  ``tracks``: the module's active segments (all active segments without module
     variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out).
@@ -888,6 +916,17 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
             r["event_id"] = np.array([t[0] for t in table])[r["batch"]]
             parts.append(r)
 
+    def export_pixel_truth():
+        """--pixel_truth: the last launch's pixel charge truth (ChargeChain.pixel_truth) as rows of the file's two datasets;
+        segment ids mapped like mc_packets_assn's (packets.compact_to_rows), track_begin counted over the whole file"""
+        if pixel_truth_min is None:
+            return
+        rows, entries = lptruth.file_rows(chain.pixel_truth(pixel_truth_min), event_of_batch, first_seg_of_batch, seg_ids_all,
+                                          out.pixel_truth_tracks)
+        out.pixel_truth_tracks += len(entries)
+        out.append("pixel_truth", rows)
+        out.append("pixel_truth_tracks", entries)
+
     # What crosses PCIe per launch: the compact form (hit pixels, hits, per-hit fractions: ldsim_chain_compact_*), expanded on the
     # host to the dense rows of the hit pixels -- the only rows the exporter reads.  --raw_arrays wants every unique pixel's
     # arrays and takes the dense download: launch k's rows then travel on the library's copy stream (download_async) while
@@ -919,11 +958,13 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
                 export_chunk_compact(prev)
             chain.wait()
             prev = chain.download_compact()
+            export_pixel_truth()
         if prev is not None:
             export_chunk_compact(prev)
         launches = []
     for b, e in launches:
         chain.run(int(b), int(e), want_fractions=True)
+        export_pixel_truth()
         if not overlapped:
             export_chunk(chain.download())
             continue

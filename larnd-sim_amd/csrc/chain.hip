@@ -145,6 +145,7 @@ static void stats_from_counters(LdsimChainStats& s, const unsigned long long* h_
 // chain: the per-tick parity tests reach the default (split) kernels through this call; ldsim_tracks_current_stats tells
 // which kernels carried the pairs.
 int chain_tracks_current(ldsim_ctx* ctx, const int32_t* d_pixels, int P, float* d_signals, int T, int mc) {
+  launch_invalidate(ctx, "a host-array tracks_current stage call reused the launch's buffers");
   CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
   unsigned long long* counters = (unsigned long long*)((char*)ctx->scratch[SB_MISC].p + 256);
   HIPCHK(hipMemsetAsync(counters, 0, STAT_BYTES, ctx->stream));

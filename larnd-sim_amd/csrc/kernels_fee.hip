@@ -9,6 +9,7 @@
 // 64-tick chunks, and the per-hit backtracking fractions are wave reductions over the hit spans.
 #include <algorithm>
 #include "ldsim_args.h"
+#include "fee_record.h"
 #include "rng.h"
 
 #define FEE_THREADS 256
@@ -236,25 +237,6 @@ __global__ void __launch_bounds__(64) fee_tables_kernel(double dt, double rt, do
     }
   }
 }
-
-// What the set-up pass (fee_setup_kernel) leaves per pixel: a header, and one row per slot in a pool indexed like the sorted pair
-// list (slot k of the pixel whose pairs start at p0: row p0 + k), so the record is sized by the slots that exist, not by M.
-struct __attribute__((aligned(32))) FeeHdr {
-  int32_t u;            // the unique pixel
-  int32_t n_slots;      // valid pairs, at most M
-  int32_t overflow;     // the pixel has pairs beyond its slots
-  int32_t t_lo, t_hi;   // the ticks the slots' windows cover (t_lo = NT, t_hi = 0: none)
-  int32_t s_lo;         // first tick held in LDS by the one-wave form
-  int32_t bfirst;       // first relative segment index of the pixel's batch
-  int32_t ubatch;
-  int64_t p0;           // first pair
-  int64_t pad;
-};
-struct __attribute__((aligned(16))) FeeSlot {
-  int32_t start;        // tick of the row's element 0 on the pixel's time axis (detsim.py:506)
-  int32_t w0, w1;       // the ticks of the row tracks_current wrote
-  int32_t track;        // segment index in the batch (track_pixel_map)
-};
 
 template <int THREADS>
 __device__ __forceinline__ void fee_sync() {
@@ -516,6 +498,9 @@ extern "C++" int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0) {
   FeeHdr* d_hdr = (FeeHdr*)ctx->scratch[SB_SPAN].p;
   FeeSlot* d_slots = (FeeSlot*)ctx->scratch[SB_FEESLOT].p;
   unsigned long long* d_counts = one_class ? nullptr : (unsigned long long*)((char*)ctx->scratch[SB_SPAN].p + hdr_bytes);
+  // what ldsim_chain_pixel_truth needs to read this record after the launch: the layout of the headers, and the rows
+  ctx->fee_rec = ldsim_ctx::FeeRecord{one_class ? 0 : 1, F.U, F.n_pairs, F.T, h.n_time_ticks, h.max_tracks_per_pixel, h.max_adc_values,
+                                      h.time_sampling};
   if (d_counts) HIPCHK(hipMemsetAsync(d_counts, 0, 16, ctx->stream));
   hipLaunchKernelGGL(fee_setup_kernel, dim3((unsigned)((F.U + 255) / 256)), dim3(256), 0, ctx->stream, F, d_slots, d_hdr, d_counts);
   HIPCHK(hipGetLastError());

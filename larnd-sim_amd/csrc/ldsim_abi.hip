@@ -189,7 +189,10 @@ extern "C" int ldsim_set_consts(ldsim_ctx* ctx, const LdsimConsts* consts) {
   NEED(consts->n_tpc >= 0 && consts->n_tpc <= LDSIM_MAX_TPC, "n_tpc out of range");
   // another configuration has another demand on the split path's weight pool (ndlar needs ~4x module0's): relearn it
   // instead of keeping the high-water mark of everything this process has ever run
-  if (memcmp(&ctx->h_consts, consts, sizeof(LdsimConsts)) != 0) ctx->wbuf_learned = 0;
+  if (memcmp(&ctx->h_consts, consts, sizeof(LdsimConsts)) != 0) {
+    ctx->wbuf_learned = 0;
+    launch_invalidate(ctx, "ldsim_set_consts changed the constants since the launch");
+  }
   ctx->h_consts = *consts;
   HIPCHK(hipMemcpyAsync(ctx->d_consts.p, &ctx->h_consts, sizeof(LdsimConsts), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -469,6 +472,8 @@ static int upload_tracks(ldsim_ctx* ctx, const void* tracks, int64_t n, const Ld
   }
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
+  launch_invalidate(ctx, batch_id_is_resident ? "ldsim_segments_upload replaced the resident segments since the launch"
+                                              : "a host-array stage call reused the launch's buffers");
   CK(seg_reserve(ctx, n));
   ctx->seg.n = n;
   ctx->drift_map_gen = -1;
@@ -553,6 +558,7 @@ extern "C" int ldsim_segments_reset(ldsim_ctx* ctx) {
   NEED(ctx->seg.n == 0 || ctx->raw.p, "no uploaded records");
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
+  launch_invalidate(ctx, "ldsim_segments_reset rewrote the resident segments since the launch");
   ctx->light_n = -1;
   ctx->drift_map_gen = -1;
   ctx->drift_stat_on = -1;
@@ -636,6 +642,7 @@ extern "C" int ldsim_dev_quench_drift(ldsim_ctx* ctx, int32_t mode) {
   NEED(ctx, "null ctx");
   NEED_RESIDENT(ctx);
   CK(light_join(ctx));
+  launch_invalidate(ctx, "ldsim_dev_quench_drift rewrote the resident segments since the launch");
   return run_quench_drift(ctx, mode, 1, 1, ctx->n_fmap > 0, ctx->charge_stat != 0);
 }
 
@@ -1599,6 +1606,8 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
     }
   }
   HIPCHK(hipSetDevice(ctx->device));
+  // (from here on the scratch buffers and the output set are this launch's: the swap of the output sets, then every stage)
+  launch_invalidate(ctx, "a later ldsim_charge_chain did not complete");
   int rc;
   try {
     rc = chain_run(ctx, seg_begin, seg_end, want_fractions);
@@ -1606,6 +1615,7 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
     ldsim_set_error("chain_run: %s", e.what());
     rc = LDSIM_EINVAL;
   }
+  if (rc == 0) ctx->launch_stale = nullptr;
   if (stats) *stats = ctx->stats;
   return rc;
 }

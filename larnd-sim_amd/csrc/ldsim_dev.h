@@ -407,6 +407,23 @@ struct ldsim_ctx {
   int64_t cpt_n[4] = {0, 0, 0, 0};   // compact result of the last ldsim_chain_compact_build: hit pixels, hits, track entries, fraction entries
   int64_t cpt_gen = -1;              // chain launch it was built for
   int want_fractions = 0;
+  // pixel charge truth (ldsim_chain_pixel_truth, kernels_pixtruth.hip) reads what the last chain launch left in the scratch
+  // buffers: the current rows (SB_WAVES), the FEE set-up record (SB_SPAN headers, SB_FEESLOT slot rows), SB_UPIX, SB_UBATCH,
+  // SB_ADC, SB_TPM and the hit counts (SB_PAIRPIX).  launch_stale = nullptr while all of them are that launch's: set by a
+  // successful ldsim_charge_chain, and named again (launch_invalidate) by every entry point that may rewrite or regrow one
+  const char* launch_stale = "no ldsim_charge_chain has run on this context";
+  struct FeeRecord {             // the set-up record fee_launch_chain left (fee_record.h) and the sizes the launch ran with
+    int lists;                   // 0: headers [U], header u at index u; 1: lists [2][U] | counts u64 [2] behind them
+    int64_t U, n_pairs;
+    int32_t T, NT, M, A;
+    double dt;
+  } fee_rec{};
+  DevBuf pt_dense;               // last pass: q_induced f64 [U] | q_abs f64 [U] | q_track f64 [U][M] | n_slots i32 [U]
+  DevBuf pt_sel;                 // keep flags, entry counts and their exclusive scans, i32 [4][U] | the u64 of the sample count
+  DevBuf pt_out;                 // compact form: pixel rows (LdsimPixelTruthRow) | track entries (LdsimPixelTruthTrack)
+  int64_t pt_gen = -1;           // chain launch (out_gen) the last pass ran on (-1: none)
+  int64_t pt_U = 0, pt_n[2] = {0, 0};   // rows of the dense arrays; kept pixels and track entries of the compact form
+  int32_t pt_M = 0;
   Event ev[8];
   double ms_current = 0, ms_adc = 0, ms_total = 0;
   double ms_weights = 0, ms_mac = 0, ms_fallback = 0;   // split path: per-kernel share of ms_current
@@ -426,6 +443,8 @@ static inline SegStore charge_store(const ldsim_ctx* ctx) {
     for (int k = 0; k < LDSIM_NVIEW; k++) s.f[k] = (double*)ctx->fmap_view.p + (size_t)k * ctx->fmap_view_cap;
   return s;
 }
+// the scratch buffers no longer hold (or may no longer hold) the last chain launch: `by` names the call, for the refusal
+static inline void launch_invalidate(ldsim_ctx* ctx, const char* by) { ctx->launch_stale = by; }
 static inline int ldsim_ensure_buf(ldsim_ctx*, DevBuf* b, size_t bytes) { return b->ensure(bytes); }
 static inline int ldsim_ensure(ldsim_ctx* ctx, int slot, size_t bytes) { return ctx->scratch[slot].ensure(bytes); }
 // refusal of a host-array stage call that draws random numbers while the ctx is in keyed mode (its rows have no identity)

@@ -259,6 +259,38 @@ class ChargeChain:
                                                           lib.ptr(out["fractions"])))
         return out
 
+    def pixel_truth(self, min_abs_charge=0.0, dense=False):
+        """Pixel charge truth of the last run() (``pixel_truth``, ``ldsim_chain_pixel_truth``): the induced charge per unique
+        pixel and per (pixel, track), reduced on the device from what the launch left in HBM.  Returns
+        ``dict(pixels=, tracks=)``: structured rows (``pixel_truth.PIXEL_ROW``: row, pixel_id, batch, n_hits, n_tracks, q_hits,
+        q_induced, q_abs) of the pixels that hold a hit or saw ``q_abs >= min_abs_charge`` electrons (0 keeps every unique
+        pixel), in row order, and their track entries (``pixel_truth.TRACK_ENTRY``: segment as in ``track_pixel_map``, q),
+        pixel after pixel.  ``dense=True``: ``dict(q_induced [U], q_abs [U], q_track [U][M])`` in the row order of
+        ``download()`` instead.  ``q_hits`` includes the FEE noise charges when noise is on; the other values never do.
+        Raises ``LdsimError`` (LDSIM_ESTATE) once anything (upload, reset, quench_drift, a host-array stage call) may have
+        rewritten the launch's buffers: ``run()`` again."""
+        from . import pixel_truth as pt
+        self._check_constants()
+        L = lib.load()
+        sizes = (C.c_int64 * 2)()
+        lib.check(L.ldsim_chain_pixel_truth(self.ctx, C.c_double(float(min_abs_charge)), sizes))
+        if dense:
+            U, M = int(self.stats.n_unique), consts.sim.MAX_TRACKS_PER_PIXEL
+            out = dict(q_induced=np.zeros(U), q_abs=np.zeros(U), q_track=np.zeros((U, M)))
+            lib.check(L.ldsim_chain_pixel_truth_dense_download(self.ctx, C.c_int64(U), lib.ptr(out["q_induced"]),
+                                                               lib.ptr(out["q_abs"]), lib.ptr(out["q_track"])))
+            return out
+        out = dict(pixels=np.zeros(int(sizes[0]), dtype=pt.PIXEL_ROW), tracks=np.zeros(int(sizes[1]), dtype=pt.TRACK_ENTRY))
+        lib.check(L.ldsim_chain_pixel_truth_download(self.ctx, lib.ptr(out["pixels"]), lib.ptr(out["tracks"])))
+        return out
+
+    def pixel_truth_row_samples(self):
+        """current samples the pixel-truth pass sums for the last run() (``ldsim_chain_pixel_truth_row_samples``, timing tools):
+        the bytes it reads from the current rows are four times that"""
+        n = C.c_int64()
+        lib.check(lib.load().ldsim_chain_pixel_truth_row_samples(self.ctx, C.byref(n)))
+        return int(n.value)
+
     def download_async(self, fractions=None):
         """Start copying the results of the last run() to page-locked host arrays on the library's copy stream and return them
         at once (``ldsim_chain_download_async``): the next ``run()`` overlaps with the transfer.  The arrays hold the rows
