@@ -7,27 +7,8 @@
 
 #include <vector>
 
-#include "ldsim_args.h"
+#include "launchers.h"
 #include <utility>
-
-int seg_launch_max_pixels(ldsim_ctx*, int64_t, int64_t, int32_t*, unsigned long long*);
-int seg_launch_get_pixels(ldsim_ctx*, int64_t, int64_t, int, int32_t*, int, int32_t*, int32_t*, int, double*, const int32_t*,
-                          int32_t);
-int sort_make_keys(ldsim_ctx*, const int32_t*, const int32_t*, int64_t, int32_t, int, int64_t, unsigned long long*,
-                   int32_t*, unsigned long long*);
-int sort_pairs(ldsim_ctx*, unsigned long long*, unsigned long long*, int32_t*, int32_t*, int64_t);
-int sort_pairs_bits(ldsim_ctx*, unsigned long long*, unsigned long long*, int32_t*, int32_t*, int64_t, int, int);
-int sort_compact_valid(ldsim_ctx*, const unsigned long long*, int64_t, unsigned long long*, int32_t*, unsigned int*);
-int sort_exclusive_scan_i32(ldsim_ctx*, const int32_t*, int32_t*, int64_t);
-int sort_heads(ldsim_ctx*, const unsigned long long*, int64_t, int32_t*);
-int sort_fill_unique(ldsim_ctx*, const unsigned long long*, const int32_t*, const int32_t*, int64_t, int32_t, int32_t*,
-                     int32_t*, int64_t*, int64_t);
-int sort_batch_first(ldsim_ctx*, int64_t, int64_t, int32_t, int32_t*);
-int sort_tmax_batch(ldsim_ctx*, int64_t, int64_t, int32_t, double*, int32_t*, unsigned long long*);
-int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters, int32_t** flags_out,
-                 const int32_t** flag_list, const unsigned long long** flag_count);
-int sort_compact_hits(ldsim_ctx*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const double*,
-                      const double*, int, int64_t, int32_t*);
 
 static void fill_cur_common(ldsim_ctx* ctx, CurArgs& a) {
   a.s = charge_store(ctx);   // (the anode view after a mapped quench_drift)
@@ -50,7 +31,7 @@ static void fill_cur_common(ldsim_ctx* ctx, CurArgs& a) {
 
 // a9-a12 for the pairs of `a` (sorted pair list of the chain, or the dense [S][P] grid of the stage call) by the configured
 // kernels: tracks_current_mc, the split path (weights stage + correlation, overflowed pairs recomputed by the monolithic
-// kernel) or the monolithic kernel for everything.  counters = the 16 u64 of the misc block, zeroed by the caller.
+// kernel) or the monolithic kernel for everything.  counters = ChainMisc::counters, zeroed by the caller.
 // a.win set: *win_used tells whether the kernels that ran wrote the windows (else every row is complete and a.win is unset).
 static int run_tracks_current(ldsim_ctx* ctx, CurArgs& a, int64_t n_seg, unsigned long long* counters, bool* split_timed,
                               bool* win_used = nullptr) {
@@ -90,10 +71,10 @@ static int run_tracks_current(ldsim_ctx* ctx, CurArgs& a, int64_t n_seg, unsigne
     a.flag_count = nullptr;
   }
   if (!(ctx->split_kernels && n_valid > 0 && split_sizes(ctx, a, &ib, &hb, &cb) > 0)) return current_launch(ctx, a);
-  CK(ldsim_ensure(ctx, SB_ITEMS, (size_t)n_valid * ib));
-  CK(ldsim_ensure(ctx, SB_HDR, (size_t)n_valid * hb));
-  CK(ldsim_ensure(ctx, SB_CORR, (size_t)n_valid * cb));
-  // The weights go to one pool shared by all pairs of the launch (bump allocator, counters[7] = doubles requested).
+  CK(ctx->scratch[SB_ITEMS].ensure((size_t)n_valid * ib));
+  CK(ctx->scratch[SB_HDR].ensure((size_t)n_valid * hb));
+  CK(ctx->scratch[SB_CORR].ensure((size_t)n_valid * cb));
+  // The weights go to one pool shared by all pairs of the launch (bump allocator, counters[ST_POOL_CURSOR] = doubles requested).
   // Which pairs lose when it runs dry depends on scheduling order, and a pair recomputed by the monolithic kernel
   // agrees only to rounding -- so a launch that exhausted the pool is never used: the pool is grown to the demand
   // (a lower bound then: an exhausted pair stops requesting) and weights_kernel runs again.  The size per pair is
@@ -103,16 +84,16 @@ static int run_tracks_current(ldsim_ctx* ctx, CurArgs& a, int64_t n_seg, unsigne
   bool fits = false;
   for (int attempt = 0; attempt < 6 && !fits; attempt++) {
     wcap = (unsigned long long)ceil(per_pair * (double)n_valid);
-    CK(ldsim_ensure(ctx, SB_WBUF, (size_t)wcap * 8));
+    CK(ctx->scratch[SB_WBUF].ensure((size_t)wcap * 8));
     if (attempt > 0) {
-      HIPCHK(hipMemsetAsync(&counters[7], 0, 8, st));                      // pool cursor
-      HIPCHK(hipMemsetAsync(&counters[16], 0, STAT_BYTES - 128, st));     // the kernels' stripes (nothing earlier adds to them)
+      HIPCHK(hipMemsetAsync(&counters[ST_POOL_CURSOR], 0, 8, st));
+      HIPCHK(hipMemsetAsync(&counters[ST_N], 0, STAT_BYTES - 8 * ST_N, st));     // the kernels' stripes (nothing earlier adds to them)
     }
     int rc = split_launch_weights(ctx, a, ctx->scratch[SB_ITEMS].p, ctx->scratch[SB_HDR].p, ctx->scratch[SB_CORR].p,
-                                  (double*)ctx->scratch[SB_WBUF].p, wcap, &counters[7]);
+                                  ctx->scratch[SB_WBUF].as<double>(), wcap, &counters[ST_POOL_CURSOR]);
     if (rc > 0) { ldsim_set_error("split path refused a configuration split_sizes accepted"); return LDSIM_ESTATE; }
     if (rc < 0) return rc;
-    HIPCHK(hipMemcpyAsync(&demand, &counters[7], 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&demand, &counters[ST_POOL_CURSOR], 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     fits = demand <= wcap;
     if (!fits) per_pair = 1.5 * (double)(demand > wcap ? demand : wcap) / (double)n_valid;
@@ -120,25 +101,25 @@ static int run_tracks_current(ldsim_ctx* ctx, CurArgs& a, int64_t n_seg, unsigne
   ctx->wbuf_learned = fmax(ctx->wbuf_learned, 1.25 * (double)demand / (double)n_valid);
   HIPCHK(hipEventRecord(ctx->ev[5], st));
   int rc = split_launch_mac(ctx, a, ctx->scratch[SB_ITEMS].p, ctx->scratch[SB_HDR].p, ctx->scratch[SB_CORR].p,
-                            (double*)ctx->scratch[SB_WBUF].p, wcap, &counters[7]);
+                            ctx->scratch[SB_WBUF].as<double>(), wcap, &counters[ST_POOL_CURSOR]);
   if (rc > 0) { ldsim_set_error("split path refused a configuration split_sizes accepted"); return LDSIM_ESTATE; }
   if (rc < 0) return rc;
   HIPCHK(hipEventRecord(ctx->ev[6], st));
   *split_timed = true;
   // pairs beyond the per-pair item / correction / run capacities (and, after 6 attempts, a pool that still does not
   // fit): recomputed by the monolithic kernel
-  a.only_flagged = (const int32_t*)ctx->scratch[SB_HDR].p;
+  a.only_flagged = ctx->scratch[SB_HDR].as<const int32_t>();
   a.flag_stride = (int32_t)(hb / 4);
   return current_launch(ctx, a);
 }
 
 static void stats_from_counters(LdsimChainStats& s, const unsigned long long* h_cnt) {
-  s.n_ambiguous = (int32_t)h_cnt[0];
-  s.n_samples = (int64_t)h_cnt[1];
-  s.n_dfma = (int64_t)h_cnt[5];
-  s.n_fallback = (int64_t)h_cnt[6];
-  s.n_wbuf = (int64_t)h_cnt[7];
-  s.n_dfma_useful = (int64_t)h_cnt[8];
+  s.n_ambiguous = (int32_t)h_cnt[ST_AMBIGUOUS];
+  s.n_samples = (int64_t)h_cnt[ST_SAMPLES];
+  s.n_dfma = (int64_t)h_cnt[ST_DFMA];
+  s.n_fallback = (int64_t)h_cnt[ST_FALLBACK];
+  s.n_wbuf = (int64_t)h_cnt[ST_POOL_CURSOR];
+  s.n_dfma_useful = (int64_t)h_cnt[ST_DFMA_USEFUL];
 }
 
 // materialising tracks_current: dense [S][P] pixel array, signals [S][P][T].  Runs the kernels the options select, like the
@@ -146,8 +127,8 @@ static void stats_from_counters(LdsimChainStats& s, const unsigned long long* h_
 // which kernels carried the pairs.
 int chain_tracks_current(ldsim_ctx* ctx, const int32_t* d_pixels, int P, float* d_signals, int T, int mc) {
   launch_invalidate(ctx, "a host-array tracks_current stage call reused the launch's buffers");
-  CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
-  unsigned long long* counters = (unsigned long long*)((char*)ctx->scratch[SB_MISC].p + 256);
+  CK(ctx->scratch[SB_MISC].ensure(MISC_BYTES));
+  unsigned long long* counters = ctx->scratch[SB_MISC].as<ChainMisc>()->counters;
   HIPCHK(hipMemsetAsync(counters, 0, STAT_BYTES, ctx->stream));
   CurArgs a{};
   fill_cur_common(ctx, a);
@@ -178,7 +159,7 @@ int chain_tracks_current(ldsim_ctx* ctx, const int32_t* d_pixels, int P, float* 
   int rc = run_tracks_current(ctx, a, ctx->seg.n, counters, &split_timed);
   ctx->mc_current = keep_mc;
   if (rc) return rc;
-  unsigned long long h_cnt[16], h_raw[STAT_WORDS];
+  unsigned long long h_cnt[ST_N], h_raw[STAT_WORDS];
   HIPCHK(hipMemcpyAsync(h_raw, counters, STAT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   stat_sum(h_raw, h_cnt);
@@ -217,11 +198,11 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   hipStream_t st = ctx->stream;
   HIPCHK(hipEventRecord(ctx->ev[0], st));
 
-  // ---- misc block: [0] err, [8] nmax i32, [16] tran bits u64, [256..] counters u64[16] ----------------------------
-  CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
-  char* misc = (char*)ctx->scratch[SB_MISC].p;
-  unsigned long long* counters = (unsigned long long*)(misc + 256);
-  HIPCHK(hipMemsetAsync(misc, 0, 256 + STAT_BYTES, st));
+  // ---- misc block (ChainMisc) -------------------------------------------------------------------------------------------
+  CK(ctx->scratch[SB_MISC].ensure(MISC_BYTES));
+  ChainMisc* misc = ctx->scratch[SB_MISC].as<ChainMisc>();
+  unsigned long long* counters = misc->counters;
+  HIPCHK(hipMemsetAsync(misc, 0, offsetof(ChainMisc, tail), st));
 
   // batch id range of this call: the non-negative ids are non-decreasing (checked at upload against the host copy kept
   // in the ctx), so the first and the last one are the range; negative = not simulated
@@ -257,23 +238,22 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   }
 
   // ---- a8 time_intervals per batch, and the per-batch max tran_diff that sets max_radius -------------------------------
-  CK(ldsim_ensure(ctx, SB_STARTS, (size_t)n * 8));
-  CK(ldsim_ensure(ctx, SB_NLIST, (size_t)n_batches * 24 + 64));   // [nb] tmax i32 | [nb] first i32 | [nb] tran u64 | [nb] radius i32
-  int32_t* d_tmax_b = (int32_t*)ctx->scratch[SB_NLIST].p;
-  int32_t* d_first_b = d_tmax_b + n_batches;
-  unsigned long long* d_tran_b = (unsigned long long*)((char*)ctx->scratch[SB_NLIST].p + ((n_batches * 8 + 15) / 16) * 16);
-  int32_t* d_radius_b = (int32_t*)(d_tran_b + n_batches);
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_NLIST].p, 0, (size_t)n_batches * 24 + 64, st));
-  double* d_starts = (double*)ctx->scratch[SB_STARTS].p;
+  CK(ctx->scratch[SB_STARTS].ensure((size_t)n * 8));
+  CK(ctx->scratch[SB_BATCH].ensure(batch_block_bytes(n_batches)));
+  const BatchBlock bb = batch_block(ctx->scratch[SB_BATCH].p, n_batches);
+  int32_t *d_tmax_b = bb.tmax, *d_first_b = bb.first, *d_radius_b = bb.radius;
+  unsigned long long* d_tran_b = bb.tran;
+  HIPCHK(hipMemsetAsync(ctx->scratch[SB_BATCH].p, 0, batch_block_bytes(n_batches), st));
+  double* d_starts = ctx->scratch[SB_STARTS].as<double>();
   CK(sort_tmax_batch(ctx, seg_begin, n, batch0, d_starts, d_tmax_b, d_tran_b));
   CK(sort_batch_first(ctx, seg_begin, n, batch0, d_first_b));
 
   // ---- a5 max_pixels (cli/simulate_pixels.py:918-928) ---------------------------------------------------------------------
-  CK(seg_launch_max_pixels(ctx, seg_begin, seg_end, (int32_t*)(misc + 8), (unsigned long long*)(misc + 16)));
+  CK(seg_launch_max_pixels(ctx, seg_begin, seg_end, &misc->nmax, &misc->tran_bits));
   int32_t nmax = 0;
   std::vector<unsigned long long> h_tran(n_batches);
   std::vector<int32_t> h_radius(n_batches);
-  HIPCHK(hipMemcpyAsync(&nmax, misc + 8, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&nmax, &misc->nmax, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(h_tran.data(), d_tran_b, n_batches * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   int radius = 0;
@@ -295,34 +275,34 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
     ldsim_set_error("chain call too large: %lld (segment, pixel) slots; split the segment range", (long long)n_entries);
     return LDSIM_EINVAL;
   }
-  CK(ldsim_ensure(ctx, SB_ACTIVE, (size_t)n * nmax * 4));
-  CK(ldsim_ensure(ctx, SB_NEIGH, (size_t)n_entries * 4));
-  CK(ldsim_ensure(ctx, SB_NRAD, (size_t)n_entries * 4));
+  CK(ctx->scratch[SB_ACTIVE].ensure((size_t)n * nmax * 4));
+  CK(ctx->scratch[SB_NEIGH].ensure((size_t)n_entries * 4));
+  CK(ctx->scratch[SB_NRAD].ensure((size_t)n_entries * 4));
   HIPCHK(hipMemsetAsync(ctx->scratch[SB_ACTIVE].p, 0xFF, (size_t)n * nmax * 4, st));
   HIPCHK(hipMemsetAsync(ctx->scratch[SB_NEIGH].p, 0xFF, (size_t)n_entries * 4, st));
   HIPCHK(hipMemsetAsync(ctx->scratch[SB_NRAD].p, 0xFF, (size_t)n_entries * 4, st));
-  int32_t* d_neigh = (int32_t*)ctx->scratch[SB_NEIGH].p;
-  int32_t* d_nrad = (int32_t*)ctx->scratch[SB_NRAD].p;
-  CK(seg_launch_get_pixels(ctx, seg_begin, seg_end, radius, (int32_t*)ctx->scratch[SB_ACTIVE].p, nmax, d_neigh, d_nrad,
+  int32_t* d_neigh = ctx->scratch[SB_NEIGH].as<int32_t>();
+  int32_t* d_nrad = ctx->scratch[SB_NRAD].as<int32_t>();
+  CK(seg_launch_get_pixels(ctx, seg_begin, seg_end, radius, ctx->scratch[SB_ACTIVE].as<int32_t>(), nmax, d_neigh, d_nrad,
                            P, nullptr, d_radius_b, batch0));
 
   // ---- a7 unique pixels: stable radix sort of (batch, pixel, ring code) --------------------------------------------------------
-  CK(ldsim_ensure(ctx, SB_KEYS, (size_t)n_entries * 8));
-  CK(ldsim_ensure(ctx, SB_KEYS2, (size_t)n_entries * 8));
-  CK(ldsim_ensure(ctx, SB_VALS, (size_t)n_entries * 4));
-  CK(ldsim_ensure(ctx, SB_VALS2, (size_t)n_entries * 4));
-  unsigned long long* d_keys = (unsigned long long*)ctx->scratch[SB_KEYS].p;
-  unsigned long long* d_keys2 = (unsigned long long*)ctx->scratch[SB_KEYS2].p;
-  int32_t* d_vals = (int32_t*)ctx->scratch[SB_VALS].p;
-  int32_t* d_vals2 = (int32_t*)ctx->scratch[SB_VALS2].p;
+  CK(ctx->scratch[SB_KEYS].ensure((size_t)n_entries * 8));
+  CK(ctx->scratch[SB_KEYS2].ensure((size_t)n_entries * 8));
+  CK(ctx->scratch[SB_VALS].ensure((size_t)n_entries * 4));
+  CK(ctx->scratch[SB_VALS2].ensure((size_t)n_entries * 4));
+  unsigned long long* d_keys = ctx->scratch[SB_KEYS].as<unsigned long long>();
+  unsigned long long* d_keys2 = ctx->scratch[SB_KEYS2].as<unsigned long long>();
+  int32_t* d_vals = ctx->scratch[SB_VALS].as<int32_t>();
+  int32_t* d_vals2 = ctx->scratch[SB_VALS2].as<int32_t>();
   CK(sort_make_keys(ctx, d_neigh, d_nrad, seg_begin, batch0, P, n_entries, d_keys, d_vals, counters));
   // The empty slots (key ~0: three quarters of the entries of the module0 bench) are dropped before the sort -- a stable compaction, so
   // equal keys keep the order of their entries -- and the count comes back with the per-batch tick counts, before the sort instead
   // of after it.
-  CK(sort_compact_valid(ctx, d_keys, n_entries, d_keys2, d_vals2, (unsigned int*)(misc + 64)));      // (its count: a word of its own; the launch uses counters[4])
+  CK(sort_compact_valid(ctx, d_keys, n_entries, d_keys2, d_vals2, &misc->n_compact));      // (its count: a word of its own; the launch uses counters[ST_VALID_PAIRS])
   unsigned long long n_valid_ull = 0;
   std::vector<int32_t> h_tmax(n_batches);
-  HIPCHK(hipMemcpyAsync(&n_valid_ull, &counters[4], 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&n_valid_ull, &counters[ST_VALID_PAIRS], 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(h_tmax.data(), d_tmax_b, n_batches * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   {
@@ -341,10 +321,10 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   ctx->stats.max_length = T;
   if (n_valid == 0 || T == 0) return 0;
 
-  CK(ldsim_ensure(ctx, SB_HEADS, (size_t)n_valid * 4 + 16));
-  CK(ldsim_ensure(ctx, SB_UOFF, (size_t)n_valid * 4 + 16));   // uidx (exclusive scan of heads)
-  int32_t* d_heads = (int32_t*)ctx->scratch[SB_HEADS].p;
-  int32_t* d_uidx = (int32_t*)ctx->scratch[SB_UOFF].p;
+  CK(ctx->scratch[SB_HEADS].ensure((size_t)n_valid * 4 + 16));
+  CK(ctx->scratch[SB_UIDX].ensure((size_t)n_valid * 4 + 16));
+  int32_t* d_heads = ctx->scratch[SB_HEADS].as<int32_t>();
+  int32_t* d_uidx = ctx->scratch[SB_UIDX].as<int32_t>();
   CK(sort_heads(ctx, d_keys2, n_valid, d_heads));
   CK(sort_exclusive_scan_i32(ctx, d_heads, d_uidx, n_valid));
   int32_t last_idx = 0, last_head = 0;
@@ -355,17 +335,17 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   ctx->stats.n_unique = U;
   ctx->chain_U = U;
 
-  CK(ldsim_ensure(ctx, SB_UPIX, (size_t)U * 4));
-  CK(ldsim_ensure(ctx, SB_UBATCH, (size_t)U * 4));
-  CK(ldsim_ensure(ctx, SB_PAIRSEG, (size_t)(U + 1) * 8));     // uoff
-  int32_t* d_upix = (int32_t*)ctx->scratch[SB_UPIX].p;
-  int32_t* d_ubatch = (int32_t*)ctx->scratch[SB_UBATCH].p;
-  int64_t* d_uoff = (int64_t*)ctx->scratch[SB_PAIRSEG].p;
+  CK(ctx->scratch[SB_UPIX].ensure((size_t)U * 4));
+  CK(ctx->scratch[SB_UBATCH].ensure((size_t)U * 4));
+  CK(ctx->scratch[SB_PIXOFF].ensure((size_t)(U + 1) * 8));
+  int32_t* d_upix = ctx->scratch[SB_UPIX].as<int32_t>();
+  int32_t* d_ubatch = ctx->scratch[SB_UBATCH].as<int32_t>();
+  int64_t* d_uoff = ctx->scratch[SB_PIXOFF].as<int64_t>();
   CK(sort_fill_unique(ctx, d_keys2, d_heads, d_uidx, n_valid, batch0, d_upix, d_ubatch, d_uoff, U));
 
   // ---- a9-a12 induced current per sorted pair -------------------------------------------------------------------------------------
-  CK(ldsim_ensure(ctx, SB_WAVES, (size_t)n_valid * T * 4));
-  float* d_waves = (float*)ctx->scratch[SB_WAVES].p;
+  CK(ctx->scratch[SB_WAVES].ensure((size_t)n_valid * T * 4));
+  float* d_waves = ctx->scratch[SB_WAVES].as<float>();
   CurArgs a{};
   fill_cur_common(ctx, a);
   a.pair_val = d_vals2;
@@ -382,22 +362,22 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   a.counters = counters;
   a.only_flagged = nullptr;
   a.flag_stride = 0;
-  CK(ldsim_ensure(ctx, SB_WIN, (size_t)n_valid * 8 + 8));
-  a.win = (int32_t*)ctx->scratch[SB_WIN].p;
+  CK(ctx->scratch[SB_WIN].ensure((size_t)n_valid * 8 + 8));
+  a.win = ctx->scratch[SB_WIN].as<int32_t>();
   HIPCHK(hipEventRecord(ctx->ev[1], st));
   bool split_timed = false, win_used = false;
   CK(run_tracks_current(ctx, a, n, counters, &split_timed, &win_used));
   HIPCHK(hipEventRecord(ctx->ev[2], st));
 
   // ---- a13-a16 per-pixel sum, trigger scan, digitise ---------------------------------------------------------------------------------
-  CK(ldsim_ensure(ctx, SB_ADC, (size_t)U * A * 8));
-  CK(ldsim_ensure(ctx, SB_TICKS, (size_t)U * A * 8));
-  CK(ldsim_ensure(ctx, SB_DIGIT, (size_t)U * A * 8));
-  CK(ldsim_ensure(ctx, SB_TPM, (size_t)U * M * 8));
-  CK(ldsim_ensure(ctx, SB_PAIRPIX, (size_t)U * 8 + 16));      // hit_count i32 [U], hit_off i32 [U]
-  if (want_fractions) CK(ldsim_ensure(ctx, SB_FRAC, (size_t)U * A * M * 8));
-  int32_t* d_hitcnt = (int32_t*)ctx->scratch[SB_PAIRPIX].p;
-  int32_t* d_hitoff = d_hitcnt + U;
+  CK(ctx->scratch[SB_ADC].ensure((size_t)U * A * 8));
+  CK(ctx->scratch[SB_TICKS].ensure((size_t)U * A * 8));
+  CK(ctx->scratch[SB_DIGIT].ensure((size_t)U * A * 8));
+  CK(ctx->scratch[SB_TPM].ensure((size_t)U * M * 8));
+  CK(ctx->scratch[SB_HITCNT].ensure(hit_counts_bytes(U)));
+  if (want_fractions) CK(ctx->scratch[SB_FRAC].ensure((size_t)U * A * M * 8));
+  const HitCounts hc = hit_counts(ctx->scratch[SB_HITCNT].p, U);
+  int32_t *d_hitcnt = hc.count, *d_hitoff = hc.off;
   FeeArgs F{};
   F.c = ctx->d_consts.as<LdsimConsts>();
   F.k = FEEK_FROM(h);
@@ -408,7 +388,7 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   F.P = P;
   F.track_starts = d_starts;
   F.waves = d_waves;
-  F.win = win_used ? (const int32_t*)ctx->scratch[SB_WIN].p : nullptr;
+  F.win = win_used ? ctx->scratch[SB_WIN].as<const int32_t>() : nullptr;
   F.T = T;
   F.batch_first = d_first_b;
   F.batch0 = batch0;
@@ -416,11 +396,11 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   F.thr_table = tables_fit ? ctx->d_pix_thr.as<double>() : nullptr;
   F.gain_table = tables_fit ? ctx->d_pix_gain.as<double>() : nullptr;
   F.time_padding = 0.0;                             // cli/simulate_pixels.py:1092
-  F.adc_list = (double*)ctx->scratch[SB_ADC].p;
-  F.adc_ticks = (double*)ctx->scratch[SB_TICKS].p;
-  F.adc_digit = (double*)ctx->scratch[SB_DIGIT].p;
-  F.tpm = (int64_t*)ctx->scratch[SB_TPM].p;
-  F.fractions = want_fractions ? (double*)ctx->scratch[SB_FRAC].p : nullptr;
+  F.adc_list = ctx->scratch[SB_ADC].as<double>();
+  F.adc_ticks = ctx->scratch[SB_TICKS].as<double>();
+  F.adc_digit = ctx->scratch[SB_DIGIT].as<double>();
+  F.tpm = ctx->scratch[SB_TPM].as<int64_t>();
+  F.fractions = want_fractions ? ctx->scratch[SB_FRAC].as<double>() : nullptr;
   F.counters = counters;
   F.hit_count = d_hitcnt;
   F.debug = ctx->debug_phases;
@@ -434,21 +414,21 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   } else if (noisy && ctx->rng_keyed) {
     // debug_rng_materialize: the keyed normals written into the table layout and read by the table scan (tests)
     const int nd = rng_fee_draws_per_pixel(h, h.n_time_ticks);
-    CK(ldsim_ensure(ctx, SB_NOISE, (size_t)U * nd * 4));
-    CK(ldsim_ensure(ctx, SB_NDRAWS, (size_t)U * 4 + 4));
-    CK(rng_launch_fee_keyed_fill(ctx, d_ubatch, d_upix, U, nd, (float*)ctx->scratch[SB_NOISE].p));
-    F.noise_z = (const float*)ctx->scratch[SB_NOISE].p;
+    CK(ctx->scratch[SB_NOISE].ensure((size_t)U * nd * 4));
+    CK(ctx->scratch[SB_NDRAWS].ensure((size_t)U * 4 + 4));
+    CK(rng_launch_fee_keyed_fill(ctx, d_ubatch, d_upix, U, nd, ctx->scratch[SB_NOISE].as<float>()));
+    F.noise_z = ctx->scratch[SB_NOISE].as<const float>();
     F.noise_nd = nd;
-    F.n_draws = (int32_t*)ctx->scratch[SB_NDRAWS].p;
+    F.n_draws = ctx->scratch[SB_NDRAWS].as<int32_t>();
   } else if (noisy) {
     CK(rng_ensure_states(ctx, U));
     const int nd = rng_fee_draws_per_pixel(h, h.n_time_ticks);
-    CK(ldsim_ensure(ctx, SB_NOISE, (size_t)U * nd * 4));
-    CK(ldsim_ensure(ctx, SB_NDRAWS, (size_t)U * 4 + 4));
-    CK(rng_launch_fee_noise(ctx, U, nd, (float*)ctx->scratch[SB_NOISE].p));
-    F.noise_z = (const float*)ctx->scratch[SB_NOISE].p;
+    CK(ctx->scratch[SB_NOISE].ensure((size_t)U * nd * 4));
+    CK(ctx->scratch[SB_NDRAWS].ensure((size_t)U * 4 + 4));
+    CK(rng_launch_fee_noise(ctx, U, nd, ctx->scratch[SB_NOISE].as<float>()));
+    F.noise_z = ctx->scratch[SB_NOISE].as<const float>();
     F.noise_nd = nd;
-    F.n_draws = (int32_t*)ctx->scratch[SB_NDRAWS].p;
+    F.n_draws = ctx->scratch[SB_NDRAWS].as<int32_t>();
   }
   CK(fee_launch_chain(ctx, F));
   if (noisy && !ctx->rng_keyed) CK(rng_launch_advance(ctx, U, F.n_draws));
@@ -458,24 +438,26 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   // (the rows are sized by their bound, U x MAX_ADC_VALUES -- 140 MB per 100 k segments -- so that the hit count comes back with
   // the launch's last synchronisation instead of one of its own)
   CK(sort_exclusive_scan_i32(ctx, d_hitcnt, d_hitoff, U));
-  CK(ldsim_ensure(ctx, SB_HITS, (size_t)U * A * 24 + 24));
+  CK(ctx->scratch[SB_HITS].ensure((size_t)U * A * 24 + 24));
   CK(sort_compact_hits(ctx, d_upix, d_ubatch, d_hitcnt, d_hitoff, F.adc_digit, F.adc_ticks, A, U,
-                       (int32_t*)ctx->scratch[SB_HITS].p));
-  unsigned long long h_cnt[16], h_raw[STAT_WORDS];
+                       ctx->scratch[SB_HITS].as<int32_t>()));
+  unsigned long long h_cnt[ST_N], h_raw[STAT_WORDS];
   HIPCHK(hipMemcpyAsync(h_raw, counters, STAT_BYTES, hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(ctx->ev[4], st));
   HIPCHK(hipStreamSynchronize(st));
   stat_sum(h_raw, h_cnt);
   if (ctx->debug_gform & 128)       // timing tools: cycle stamps of gcorr_kernel's waves (kernels_gcorr.hip)
     fprintf(stderr, "gcorr stamps (shader cycles, summed over waves): info %llu stage %llu G %llu P %llu edges %llu tail %llu life %llu\n",
-            h_cnt[9], h_cnt[10], h_cnt[11], h_cnt[12], h_cnt[13], h_cnt[14], h_cnt[15]);
+            h_cnt[ST_GCORR_INFO], h_cnt[ST_GCORR_STAGE], h_cnt[ST_GCORR_G], h_cnt[ST_GCORR_P], h_cnt[ST_GCORR_EDGES],
+            h_cnt[ST_GCORR_TAIL], h_cnt[ST_GCORR_LIFE]);
   if (ctx->debug_gform & 2048)      // the same stripes, written by gtables_wave_kernel's waves instead (kernels_gtables.hip)
     fprintf(stderr, "gtables stamps (shader cycles, summed over waves): loads %llu maps %llu batch_prologue %llu tables_xy %llu tables_z %llu cells %llu life %llu\n",
-            h_cnt[9], h_cnt[10], h_cnt[11], h_cnt[12], h_cnt[13], h_cnt[14], h_cnt[15]);
-  ctx->stats.n_overflow = (int64_t)h_cnt[2];
-  ctx->chain_hits = (int64_t)h_cnt[3];
+            h_cnt[ST_GTAB_LOADS], h_cnt[ST_GTAB_MAPS], h_cnt[ST_GTAB_BATCH_PROLOGUE], h_cnt[ST_GTAB_TABLES_XY],
+            h_cnt[ST_GTAB_TABLES_Z], h_cnt[ST_GTAB_CELLS], h_cnt[ST_GTAB_LIFE]);
+  ctx->stats.n_overflow = (int64_t)h_cnt[ST_OVERFLOW_PIXELS];
+  ctx->chain_hits = (int64_t)h_cnt[ST_HITS];
   stats_from_counters(ctx->stats, h_cnt);
-  ctx->n_fallback = (int64_t)h_cnt[6];
+  ctx->n_fallback = (int64_t)h_cnt[ST_FALLBACK];
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2])); ctx->ms_current = ms;
   HIPCHK(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3])); ctx->ms_adc = ms;

@@ -5,7 +5,7 @@
 // The communicator is bootstrapped from an ncclUniqueId the host side hands to every rank (larndsim_amd/comm.py).
 #include <rccl/rccl.h>
 
-#include "ldsim_dev.h"
+#include "ldsim_args.h"
 
 #define NCCLCHK(expr)                                                                                  \
   do {                                                                                                 \
@@ -70,7 +70,7 @@ extern "C" int ldsim_comm_allreduce_f64(ldsim_ctx* ctx, double* value, int32_t o
   LDSIM_ENTER(ctx);
   NEED(ctx && value && ctx->comm, "no communicator");
   HIPCHK(hipSetDevice(ctx->device));
-  int rc = ldsim_ensure_buf(ctx, &ctx->comm_tmp, 64 + 8 * (size_t)ctx->comm_world);
+  int rc = ctx->comm_tmp.ensure(64 + 8 * (size_t)ctx->comm_world);
   if (rc) return rc;
   double* d = (double*)ctx->comm_tmp.p;
   HIPCHK(hipMemcpyAsync(d, value, 8, hipMemcpyHostToDevice, ctx->stream));
@@ -91,7 +91,7 @@ extern "C" int ldsim_hits_accumulate(ldsim_ctx* ctx, int32_t reset) {
   if (n == 0) return 0;
   const size_t need = (size_t)(ctx->hits_acc_rows + n) * 24;
   CK(ctx->hits_acc.grow_keep(ctx->stream, (size_t)ctx->hits_acc_rows * 24, need));
-  HIPCHK(hipMemcpyAsync((char*)ctx->hits_acc.p + (size_t)ctx->hits_acc_rows * 24, ctx->scratch[SB_HITS].p, (size_t)n * 24,
+  HIPCHK(hipMemcpyAsync((char*)ctx->hits_acc.p + (size_t)ctx->hits_acc_rows * 24, chain_view(ctx).hits, (size_t)n * 24,
                         hipMemcpyDeviceToDevice, ctx->stream));
   ctx->hits_acc_rows += n;
   return 0;
@@ -105,7 +105,7 @@ extern "C" int ldsim_comm_allgather_hits(ldsim_ctx* ctx, void** gathered, int64_
   HIPCHK(hipSetDevice(ctx->device));
   const int W = ctx->comm_world;
   ncclComm_t comm = (ncclComm_t)ctx->comm;
-  int rc = ldsim_ensure_buf(ctx, &ctx->comm_tmp, 64 + 8 * (size_t)W);
+  int rc = ctx->comm_tmp.ensure(64 + 8 * (size_t)W);
   if (rc) return rc;
   int64_t* d_mine = (int64_t*)ctx->comm_tmp.p;
   int64_t* d_all = (int64_t*)((char*)ctx->comm_tmp.p + 64);
@@ -120,7 +120,7 @@ extern "C" int ldsim_comm_allgather_hits(ldsim_ctx* ctx, void** gathered, int64_
     NEED(h[r] >= 0, "negative row count received");
     total += h[r];
   }
-  if ((rc = ldsim_ensure_buf(ctx, &ctx->hits_all, (size_t)(total > 0 ? total : 1) * 24))) return rc;
+  if ((rc = ctx->hits_all.ensure((size_t)(total > 0 ? total : 1) * 24))) return rc;
   NCCLCHK(ncclGroupStart());
   int64_t off = 0;
   for (int r = 0; r < W; r++) {
@@ -176,8 +176,8 @@ extern "C" int ldsim_compact_accumulate(ldsim_ctx* ctx, int32_t reset) {
   ctx->cpt_acc_gen = ctx->cpt_gen;
   const int64_t n_hp = ctx->cpt_n[0], n_hits = ctx->cpt_n[1], n_trk = ctx->cpt_n[2], n_frac = ctx->cpt_n[3];
   const size_t b_hp = ((size_t)n_hp * 20 + 7) & ~(size_t)7, b_trk = (size_t)n_trk * 8, b_chg = (size_t)n_hits * 8;
-  const char* base = (const char*)ctx->scratch[SB_CPO].p;
-  const void* src[5] = {base, base + b_hp, ctx->scratch[SB_HITS].p, base + b_hp + b_trk, base + b_hp + b_trk + b_chg};
+  const char* base = ctx->scratch[SB_CPO].as<const char>();
+  const void* src[5] = {base, base + b_hp, chain_view(ctx).hits, base + b_hp + b_trk, base + b_hp + b_trk + b_chg};
   const int64_t cnt[5] = {n_hp, n_trk, n_hits, n_hits, n_frac};
   for (int k = 0; k < 5; k++) {
     if (cnt[k] == 0) continue;
@@ -201,7 +201,7 @@ extern "C" int ldsim_comm_gather_compact(ldsim_ctx* ctx, int32_t root, int32_t s
   ncclComm_t comm = (ncclComm_t)ctx->comm;
   hipStream_t st = ctx->stream;
   ctx->cpt_all_root = ctx->cpt_all_src = -1;
-  int rc = ldsim_ensure_buf(ctx, &ctx->comm_tmp, 64 + 40 * (size_t)W);
+  int rc = ctx->comm_tmp.ensure(64 + 40 * (size_t)W);
   if (rc) return rc;
   int64_t* d_mine = (int64_t*)ctx->comm_tmp.p;
   int64_t* d_all = (int64_t*)((char*)ctx->comm_tmp.p + 64);
@@ -220,7 +220,7 @@ extern "C" int ldsim_comm_gather_compact(ldsim_ctx* ctx, int32_t root, int32_t s
   const int64_t* n = &h[(size_t)src_rank * 5];
   if (me == root)
     for (int k = 0; k < 5; k++)
-      if ((rc = ldsim_ensure_buf(ctx, &ctx->cpt_all[k], (size_t)(n[k] > 0 ? n[k] : 1) * CPT_ELEM[k]))) return rc;
+      if ((rc = ctx->cpt_all[k].ensure((size_t)(n[k] > 0 ? n[k] : 1) * CPT_ELEM[k]))) return rc;
   if (src_rank == root) {
     if (me == root)                                    // root's own stream: a device-to-device copy
       for (int k = 0; k < 5; k++)
@@ -274,7 +274,7 @@ extern "C" int ldsim_comm_gatherv_bytes(ldsim_ctx* ctx, int32_t root, const void
   ncclComm_t comm = (ncclComm_t)ctx->comm;
   hipStream_t st = ctx->stream;
   ctx->gv_all_root = -1;
-  int rc = ldsim_ensure_buf(ctx, &ctx->comm_tmp, 64 + 8 * (size_t)W);
+  int rc = ctx->comm_tmp.ensure(64 + 8 * (size_t)W);
   if (rc) return rc;
   int64_t* d_mine = (int64_t*)ctx->comm_tmp.p;
   int64_t* d_all = (int64_t*)((char*)ctx->comm_tmp.p + 64);
@@ -295,10 +295,10 @@ extern "C" int ldsim_comm_gatherv_bytes(ldsim_ctx* ctx, int32_t root, const void
     return LDSIM_EINVAL;
   }
   if (me == root) {
-    if ((rc = ldsim_ensure_buf(ctx, &ctx->gv_all, (size_t)(total > 0 ? total : 1)))) return rc;
+    if ((rc = ctx->gv_all.ensure((size_t)(total > 0 ? total : 1)))) return rc;
     if (n) HIPCHK(hipMemcpyAsync((char*)ctx->gv_all.p + mine_off, host, (size_t)n, hipMemcpyHostToDevice, st));
   } else if (n) {
-    if ((rc = ldsim_ensure_buf(ctx, &ctx->gv_send, (size_t)n))) return rc;
+    if ((rc = ctx->gv_send.ensure((size_t)n))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->gv_send.p, host, (size_t)n, hipMemcpyHostToDevice, st));
   }
   NCCLCHK(ncclGroupStart());

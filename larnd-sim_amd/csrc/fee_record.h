@@ -1,6 +1,7 @@
 // fee_record.h -- the set-up record of a chain launch's FEE stage: written by fee_setup_kernel, read by the pixel_adc kernels
 // (kernels_fee.hip) and, after the launch, by pixel_truth_kernel (kernels_pixtruth.hip).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 // What the set-up pass (fee_setup_kernel) leaves per pixel: a header, and one row per slot in a pool indexed like the sorted pair
@@ -21,3 +22,16 @@ struct __attribute__((aligned(16))) FeeSlot {
   int32_t w0, w1;       // the ticks of the row tracks_current wrote
   int32_t track;        // segment index in the batch (track_pixel_map)
 };
+
+// The headers in their slot (SB_FEEHDR).  lists = 0: headers [U], header u at index u.  lists = 1: two lists [2][U] (list 1 behind
+// list 0's U places), and behind them the two lists' counts u64 [2].  hdr_bytes: the headers alone (where the counts start);
+// bytes: with the counts.
+struct FeeHdrView {
+  FeeHdr* hdr;
+  unsigned long long* counts;   // [2], or NULL without lists
+  size_t hdr_bytes, bytes;
+};
+static inline FeeHdrView fee_hdr_view(void* base, int lists, int64_t U) {
+  const size_t hb = (size_t)U * sizeof(FeeHdr) * (lists ? 2 : 1);
+  return FeeHdrView{(FeeHdr*)base, lists && base ? (unsigned long long*)((char*)base + hb) : nullptr, hb, hb + (lists ? 16 : 0)};
+}

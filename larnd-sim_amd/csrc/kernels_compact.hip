@@ -13,9 +13,7 @@
 //   per hit x slot  the backtracking fraction
 // a few MB per launch; larndsim_amd.chain.expand_compact rebuilds the dense rows of the hit pixels on the host (tested equal
 // to the dense download).
-#include "ldsim_args.h"
-
-int sort_exclusive_scan_i32(ldsim_ctx*, const int32_t*, int32_t*, int64_t);
+#include "launchers.h"
 
 __global__ void __launch_bounds__(256) compact_count_kernel(const int32_t* __restrict__ hit_count, const int64_t* __restrict__ tpm,
                                                             const int32_t* __restrict__ ubatch,
@@ -63,21 +61,20 @@ extern "C" int ldsim_chain_compact_build(ldsim_ctx* ctx, int64_t* sizes) {
   LDSIM_ENTER(ctx);
   if (!ctx || !sizes) { ldsim_set_error("null argument"); return LDSIM_EINVAL; }
   HIPCHK(hipSetDevice(ctx->device));
-  const int64_t U = ctx->chain_U;
-  const int A = ctx->h_consts.max_adc_values, M = ctx->h_consts.max_tracks_per_pixel;
+  const ChainView v = chain_view(ctx);      // (what follows grows SB_CPT, SB_CPO and SB_SORTTMP only: none of its slots)
+  const int64_t U = v.U;
+  const int A = v.A, M = v.M;
   for (int k = 0; k < 4; k++) ctx->cpt_n[k] = 0;
   ctx->cpt_gen = ctx->out_gen;
   if (U == 0) { for (int k = 0; k < 4; k++) sizes[k] = 0; return 0; }
   hipStream_t st = ctx->stream;
   int rc;
-  if ((rc = ldsim_ensure(ctx, SB_CPT, (size_t)(6 * U + 16) * 4))) return rc;
-  int32_t* c_hp = (int32_t*)ctx->scratch[SB_CPT].p;
+  if ((rc = ctx->scratch[SB_CPT].ensure((size_t)(6 * U + 16) * 4))) return rc;
+  int32_t* c_hp = ctx->scratch[SB_CPT].as<int32_t>();
   int32_t *c_trk = c_hp + U, *c_frac = c_trk + U, *o_hp = c_frac + U, *o_trk = o_hp + U, *o_frac = o_trk + U;
-  const int32_t* d_hitcnt = (const int32_t*)ctx->scratch[SB_PAIRPIX].p;
-  const int32_t* d_hitoff = d_hitcnt + U;
   const unsigned g0 = (unsigned)((U + 255) / 256);
-  hipLaunchKernelGGL(compact_count_kernel, dim3(g0), dim3(256), 0, st, d_hitcnt, (const int64_t*)ctx->scratch[SB_TPM].p,
-                     (const int32_t*)ctx->scratch[SB_UBATCH].p, M, U, c_hp, c_trk, c_frac);
+  hipLaunchKernelGGL(compact_count_kernel, dim3(g0), dim3(256), 0, st, v.hit_count, v.tpm, v.ubatch, M, U, c_hp, c_trk,
+                     c_frac);
   HIPCHK(hipGetLastError());
   if ((rc = sort_exclusive_scan_i32(ctx, c_hp, o_hp, U))) return rc;
   if ((rc = sort_exclusive_scan_i32(ctx, c_trk, o_trk, U))) return rc;
@@ -91,15 +88,13 @@ extern "C" int ldsim_chain_compact_build(ldsim_ctx* ctx, int64_t* sizes) {
   HIPCHK(hipMemcpyAsync(&last_o[2], o_frac + (U - 1), 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const int64_t n_hp = (int64_t)last_c[0] + last_o[0], n_trk = (int64_t)last_c[1] + last_o[1];
-  const int64_t n_frac = ctx->want_fractions ? (int64_t)last_c[2] + last_o[2] : 0, n_hits = ctx->chain_hits;
+  const int64_t n_frac = ctx->want_fractions ? (int64_t)last_c[2] + last_o[2] : 0, n_hits = v.n_hits;
   // one block: [n_hp][5] i32 | trk_seg i64 | hit_charge f64 | frac_val f64   (each part 8-byte aligned)
   const size_t b_hp = ((size_t)n_hp * 20 + 7) & ~(size_t)7, b_trk = (size_t)n_trk * 8, b_chg = (size_t)n_hits * 8, b_frac = (size_t)n_frac * 8;
-  if ((rc = ldsim_ensure(ctx, SB_CPO, b_hp + b_trk + b_chg + b_frac + 64))) return rc;
-  char* base = (char*)ctx->scratch[SB_CPO].p;
-  hipLaunchKernelGGL(compact_fill_kernel, dim3(g0), dim3(256), 0, st, d_hitcnt, d_hitoff, o_hp, o_trk, o_frac, c_trk,
-                     (const int32_t*)ctx->scratch[SB_UPIX].p, (const int32_t*)ctx->scratch[SB_UBATCH].p,
-                     (const int64_t*)ctx->scratch[SB_TPM].p, (const double*)ctx->scratch[SB_ADC].p,
-                     ctx->want_fractions ? (const double*)ctx->scratch[SB_FRAC].p : nullptr, A, M, U, (int32_t*)base,
+  if ((rc = ctx->scratch[SB_CPO].ensure(b_hp + b_trk + b_chg + b_frac + 64))) return rc;
+  char* base = ctx->scratch[SB_CPO].as<char>();
+  hipLaunchKernelGGL(compact_fill_kernel, dim3(g0), dim3(256), 0, st, v.hit_count, v.hit_off, o_hp, o_trk, o_frac, c_trk,
+                     v.upix, v.ubatch, v.tpm, v.adc, ctx->want_fractions ? v.frac : nullptr, A, M, U, (int32_t*)base,
                      (int64_t*)(base + b_hp), (double*)(base + b_hp + b_trk), (double*)(base + b_hp + b_trk + b_chg));
   HIPCHK(hipGetLastError());
   ctx->cpt_n[0] = n_hp; ctx->cpt_n[1] = n_hits; ctx->cpt_n[2] = n_trk; ctx->cpt_n[3] = n_frac;
@@ -120,10 +115,10 @@ extern "C" int ldsim_chain_compact_download(ldsim_ctx* ctx, int32_t* hit_pixels 
   hipStream_t st = ctx->stream;
   const int64_t n_hp = ctx->cpt_n[0], n_hits = ctx->cpt_n[1], n_trk = ctx->cpt_n[2], n_frac = ctx->cpt_n[3];
   const size_t b_hp = ((size_t)n_hp * 20 + 7) & ~(size_t)7, b_trk = (size_t)n_trk * 8, b_chg = (size_t)n_hits * 8;
-  const char* base = (const char*)ctx->scratch[SB_CPO].p;
+  const char* base = ctx->scratch[SB_CPO].as<const char>();
   if (hit_pixels && n_hp) HIPCHK(hipMemcpyAsync(hit_pixels, base, (size_t)n_hp * 20, hipMemcpyDeviceToHost, st));
   if (track_segments && n_trk) HIPCHK(hipMemcpyAsync(track_segments, base + b_hp, b_trk, hipMemcpyDeviceToHost, st));
-  if (hit_rows && n_hits) HIPCHK(hipMemcpyAsync(hit_rows, ctx->scratch[SB_HITS].p, (size_t)n_hits * 24, hipMemcpyDeviceToHost, st));
+  if (hit_rows && n_hits) HIPCHK(hipMemcpyAsync(hit_rows, chain_view(ctx).hits, (size_t)n_hits * 24, hipMemcpyDeviceToHost, st));
   if (hit_charge && n_hits) HIPCHK(hipMemcpyAsync(hit_charge, base + b_hp + b_trk, b_chg, hipMemcpyDeviceToHost, st));
   if (fractions && n_frac) HIPCHK(hipMemcpyAsync(fractions, base + b_hp + b_trk + b_chg, (size_t)n_frac * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -14,6 +14,7 @@
 // and writes the f32 waveform.  All arithmetic is f64 (the reference's arithmetic type); only the
 // store narrows to f32 like the reference's `signals` array.
 #include "current_common.h"
+#include "launchers.h"
 
 template <int M>
 __device__ __forceinline__ void current_pair(const CurArgs& A, const int64_t pair) {
@@ -187,7 +188,7 @@ __device__ __forceinline__ void current_pair(const CurArgs& A, const int64_t pai
     double tt = g.t_start + it_ref * dt;
     double val = (tt - t0) / dtr;
     double kr = py_round(val);
-    if (count && fabs(val - kr) > 0.5 - 1e-7) stat_add(A.counters, 0, 1ull);
+    if (count && fabs(val - kr) > 0.5 - 1e-7) stat_add(A.counters, ST_AMBIGUOUS, 1ull);
     return (int)kr - M * it_ref;
   };
 
@@ -517,8 +518,8 @@ __device__ __forceinline__ void current_pair(const CurArgs& A, const int64_t pai
   // ticks outside the response-visible window are exactly zero
   for (int it = tid; it < A.T; it += CUR_THREADS)
     if (it < it_w0 || it >= it_w1) out[it] = 0.f;
-  if (lane == 0 && n_blocks) stat_add(A.counters, 5, n_blocks * 64ull * 64ull);
-  if (lane == 0 && n_surv) stat_add(A.counters, 1, n_surv);
+  if (lane == 0 && n_blocks) stat_add(A.counters, ST_DFMA, n_blocks * 64ull * 64ull);
+  if (lane == 0 && n_surv) stat_add(A.counters, ST_SAMPLES, n_surv);
 }
 
 // one workgroup per pair, or -- the recompute pass of the split paths, where flagged pairs are few or none -- a fixed grid over
@@ -536,7 +537,7 @@ __global__ void __launch_bounds__(CUR_THREADS, (M == 1 ? 2 : 1)) current_kernel(
   }
 }
 
-extern "C++" int current_launch(ldsim_ctx* ctx, const CurArgs& args) {
+int current_launch(ldsim_ctx* ctx, const CurArgs& args) {
   if (args.n_pairs == 0) return 0;
   const LdsimConsts& h = ctx->h_consts;
   double ratio = h.time_sampling / h.response_sampling;

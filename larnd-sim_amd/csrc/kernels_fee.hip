@@ -8,7 +8,7 @@
 // (no atomics, no [U][N_t][50] slab), the trigger scan is a wave-64 prefix scan + ballot over
 // 64-tick chunks, and the per-hit backtracking fractions are wave reductions over the hit spans.
 #include <algorithm>
-#include "ldsim_args.h"
+#include "launchers.h"
 #include "fee_record.h"
 #include "rng.h"
 
@@ -331,8 +331,8 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const FeeHdr& H
   }
   if (tid == 0) {
     F.hit_count[u] = nh;
-    if (H.overflow) stat_add(F.counters, 2, 1ull);
-    if (nh) stat_add(F.counters, 3, (unsigned long long)nh);
+    if (H.overflow) stat_add(F.counters, ST_OVERFLOW_PIXELS, 1ull);
+    if (nh) stat_add(F.counters, ST_HITS, (unsigned long long)nh);
   }
   // ---- backtracking fractions (fee.py:572-573, 633-635): sum_jc sig_k[jc]*G[min(ntap, b-jc)] / true_q ------------
   if (F.fractions && !FEEDBG(0x40000)) {
@@ -403,7 +403,7 @@ __global__ void __launch_bounds__(256) fee_clear_fractions_kernel(int64_t U, con
       if (!(h < nh && k < ns)) row[h * M + k] = 0.0;
 }
 
-extern "C++" int fee_clear_unwritten_fractions(ldsim_ctx* ctx, int64_t U, const int32_t* hit_count, const int64_t* tpm, double* fr) {
+int fee_clear_unwritten_fractions(ldsim_ctx* ctx, int64_t U, const int32_t* hit_count, const int64_t* tpm, double* fr) {
   if (U == 0) return 0;
   const LdsimConsts& h = ctx->h_consts;
   hipLaunchKernelGGL(fee_clear_fractions_kernel, dim3((unsigned)U), dim3(256), 0, ctx->stream, U, hit_count, tpm,
@@ -464,7 +464,7 @@ __global__ void __launch_bounds__(256) fee_setup_kernel(FeeArgs F, FeeSlot* __re
   }
 }
 
-extern "C++" int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0) {
+int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0) {
   if (F0.U == 0) return 0;
   const LdsimConsts& h = ctx->h_consts;
   if (h.n_time_ticks > NT_MAX || h.max_adc_values > A_MAX || h.max_tracks_per_pixel > M_MAX ||
@@ -492,12 +492,13 @@ extern "C++" int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0) {
   const bool skip_idle = !F.batch_keys && !F.noise_z && ((F.thr_table != nullptr) || F.threshold > 0);
   const bool one_class = !skip_idle || !F.win || ctx->fee_one_class || h.n_time_ticks <= FEE_SPAN;
   int rc;
-  const size_t hdr_bytes = (size_t)F.U * sizeof(FeeHdr) * (one_class ? 1 : 2);      // headers [U] or lists [2][U] | counts [2]
-  if ((rc = ldsim_ensure(ctx, SB_SPAN, hdr_bytes + 64))) return rc;
-  if ((rc = ldsim_ensure(ctx, SB_FEESLOT, (size_t)F.n_pairs * sizeof(FeeSlot) + 16))) return rc;
-  FeeHdr* d_hdr = (FeeHdr*)ctx->scratch[SB_SPAN].p;
-  FeeSlot* d_slots = (FeeSlot*)ctx->scratch[SB_FEESLOT].p;
-  unsigned long long* d_counts = one_class ? nullptr : (unsigned long long*)((char*)ctx->scratch[SB_SPAN].p + hdr_bytes);
+  // (headers [U] or lists [2][U] | counts [2]: fee_hdr_view; the counts sit in the 64 bytes of slack)
+  if ((rc = ctx->scratch[SB_FEEHDR].ensure(fee_hdr_view(nullptr, !one_class, F.U).hdr_bytes + 64))) return rc;
+  if ((rc = ctx->scratch[SB_FEESLOT].ensure((size_t)F.n_pairs * sizeof(FeeSlot) + 16))) return rc;
+  const FeeHdrView V = fee_hdr_view(ctx->scratch[SB_FEEHDR].p, !one_class, F.U);
+  FeeHdr* d_hdr = V.hdr;
+  FeeSlot* d_slots = ctx->scratch[SB_FEESLOT].as<FeeSlot>();
+  unsigned long long* d_counts = V.counts;
   // what ldsim_chain_pixel_truth needs to read this record after the launch: the layout of the headers, and the rows
   ctx->fee_rec = ldsim_ctx::FeeRecord{one_class ? 0 : 1, F.U, F.n_pairs, F.T, h.n_time_ticks, h.max_tracks_per_pixel, h.max_adc_values,
                                       h.time_sampling};
@@ -643,7 +644,6 @@ __global__ void digitize_kernel(const LdsimConsts* c, const double* q, const dou
   out[i] = digitize_one(c, q[i], gain);
 }
 
-extern "C++" {
 int fee_launch_track_pixel_map(ldsim_ctx* ctx, int64_t* map, const int32_t* upix, int64_t U, const int32_t* pixels,
                                const int32_t* dist, int64_t S, int P, int max_distance, int M) {
   if (U == 0) return 0;
@@ -681,5 +681,4 @@ int fee_launch_digitize(ldsim_ctx* ctx, const double* q, const double* gain, dou
                      gain, out, n);
   HIPCHK(hipGetLastError());
   return 0;
-}
 }

@@ -16,6 +16,7 @@
 // Zi table at the one response index it concerns.  No DPP shifts, no 512-tick tile padding, no weight pool: the matrix pipe
 // carries 16 x cells x ticks FMAs per pair where the shifted-window kernels issue (cells x shifts) x 512.
 #include "gform.h"
+#include "launchers.h"
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -86,7 +87,8 @@ __global__ void __launch_bounds__(GT, (QB ? 4 : (M == 1 ? 6 : 5))) gcorr_kernel(
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t pair = big_list ? (int64_t)big_list[blockIdx.x] : (int64_t)blockIdx.x + pair0;      // (pair0: first pair of a range launch)
   if (pair >= A.n_pairs) return;
-  // timing tools (debug_gform 128): where a wave's residency goes, in shader cycles summed over the waves (counters 9 .. 15:
+  // timing tools (debug_gform 128): where a wave's residency goes, in shader cycles summed over the waves (ST_GCORR_*, the stamp
+  // counters that gtables_wave_kernel writes as ST_GTAB_* in its own debug runs:
   // GInfo wait | table staging incl. its barriers | G loops | P steps | edge columns | final barrier + store | whole life)
 #ifdef LDSIM_GCORR_DEBUG
   const bool stamps = (GA.dbg & 128) != 0;
@@ -646,17 +648,17 @@ __global__ void __launch_bounds__(GT, (QB ? 4 : (M == 1 ? 6 : 5))) gcorr_kernel(
   }
   if (stamps && lane == 0) {
     const unsigned long long t = __builtin_amdgcn_s_memtime();
-    stat_add(A.counters, 9, ts_info - ts0);
-    stat_add(A.counters, 10, ts_stage);
-    stat_add(A.counters, 11, ts_g);
-    stat_add(A.counters, 12, ts_p);
-    stat_add(A.counters, 13, ts_e);
-    stat_add(A.counters, 14, t - ts_mark);
-    stat_add(A.counters, 15, t - ts0);
+    stat_add(A.counters, ST_GCORR_INFO, ts_info - ts0);
+    stat_add(A.counters, ST_GCORR_STAGE, ts_stage);
+    stat_add(A.counters, ST_GCORR_G, ts_g);
+    stat_add(A.counters, ST_GCORR_P, ts_p);
+    stat_add(A.counters, ST_GCORR_EDGES, ts_e);
+    stat_add(A.counters, ST_GCORR_TAIL, t - ts_mark);
+    stat_add(A.counters, ST_GCORR_LIFE, t - ts0);
   }
   if (GDBG(1)) return;
-  if (lane == 0 && (n_mfma | n_mfma4)) stat_add(A.counters, 5, n_mfma * 1024ull + n_mfma4 * 256ull);
-  if (tid == 0 && n_useful) stat_add(A.counters, 8, n_useful);
+  if (lane == 0 && (n_mfma | n_mfma4)) stat_add(A.counters, ST_DFMA, n_mfma * 1024ull + n_mfma4 * 256ull);
+  if (tid == 0 && n_useful) stat_add(A.counters, ST_DFMA_USEFUL, n_useful);
 }
 
 // the pairs of the launches after the first (g_lds_class 1, 2), one atomic per wave and list
@@ -692,18 +694,8 @@ __global__ void __launch_bounds__(256) goff_scatter_kernel(GInfo* __restrict__ g
   }
 }
 
-int sort_exclusive_scan_u64(ldsim_ctx*, const unsigned long long*, unsigned long long*, int64_t);
-extern "C++" int gtables_launch(ldsim_ctx* ctx, const GArgs& GA, int M, const int32_t* wg_list, int64_t n_wg, const int32_t* w2_list,
-                                int64_t n_w2);
-extern "C++" int gtables_launch_range(ldsim_ctx* ctx, const GArgs& GA, int M, hipStream_t ts, int64_t pair0, int64_t n);
-extern "C++" int gtables_launch_lists(ldsim_ctx* ctx, const GArgs& GA, int M, hipStream_t ts, const int32_t* wg_list, int64_t n_wg,
-                                      const int32_t* w2_list, int64_t n_w2);
-extern "C++" int gtables_list_launch(ldsim_ctx* ctx, const GArgs& GA, int32_t* wg_list, unsigned long long* wg_count, int32_t* w2_list,
-                                     unsigned long long* w2_count);
-extern "C++" int resp_pad_ensure(ldsim_ctx* ctx, const CurArgs& A, int* k_lo, int* k_hi, int* nkp);
-
 // M of the form for these constants, 0 = configuration not covered (caller uses the monolithic kernel)
-extern "C++" int gform_M(const ldsim_ctx* ctx, const CurArgs& args) {
+int gform_M(const ldsim_ctx* ctx, const CurArgs& args) {
   const LdsimConsts& h = ctx->h_consts;
   const double ratio = h.time_sampling / h.response_sampling;
   const int M = (int)llround(ratio);
@@ -722,23 +714,23 @@ __global__ void __launch_bounds__(256) gflag_list_kernel(const int32_t* __restri
   if (i < n && flags[i]) list[atomicAdd(count, 1ull)] = (int32_t)i;
 }
 
-extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters, int32_t** flags_out,
+int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters, int32_t** flags_out,
                               const int32_t** flag_list, const unsigned long long** flag_count) {
   const int M = gform_M(ctx, a);      // (ctx->gform_rec was marked invalid by run_tracks_current, the one owner of that)
   if (!M) return 1;
   const int64_t n = a.n_pairs;
   hipStream_t st = ctx->stream;
   int rc;
-  if ((rc = ldsim_ensure(ctx, SB_PPAR, qpair_params_bytes(n)))) return rc;
-  if ((rc = ldsim_ensure(ctx, SB_HDR, (size_t)n * sizeof(GInfo)))) return rc;
-  if ((rc = ldsim_ensure(ctx, SB_ITEMS, (size_t)(n + 16) * 4))) return rc;                    // flags
-  if ((rc = ldsim_ensure(ctx, SB_CORR, (size_t)(2 * n + 8) * 8 + (size_t)(5 * n + 2) * 4))) return rc;      // sizes | offsets | total, 2 class counts, n_wg, n_flagged, n_w2 | 2 class lists | wg list | flagged list | wide-wave list
+  if ((rc = ctx->scratch[SB_PPAR].ensure(qpair_params_bytes(n)))) return rc;
+  if ((rc = ctx->scratch[SB_GINFO].ensure((size_t)n * sizeof(GInfo)))) return rc;
+  if ((rc = ctx->scratch[SB_GFLAGS].ensure((size_t)(n + 16) * 4))) return rc;
+  if ((rc = ctx->scratch[SB_GSIZES].ensure((size_t)(2 * n + 8) * 8 + (size_t)(5 * n + 2) * 4))) return rc;      // sizes | offsets | total, 2 class counts, n_wg, n_flagged, n_w2 | 2 class lists | wg list | flagged list | wide-wave list
   SplitArgs S{};
   S.c = a;
-  GInfo* gi = (GInfo*)ctx->scratch[SB_HDR].p;
-  if ((rc = ldsim_ensure(ctx, SB_GMAPS, (size_t)n * G_MAPB))) return rc;      // the wave tables kernel's maps (gform.h)
+  GInfo* gi = ctx->scratch[SB_GINFO].as<GInfo>();
+  if ((rc = ctx->scratch[SB_GMAPS].ensure((size_t)n * G_MAPB))) return rc;      // the wave tables kernel's maps (gform.h)
   if ((rc = qpair_setup_launch(ctx, S, M, ctx->scratch[SB_PPAR].p, gi, ctx->scratch[SB_GMAPS].p))) return rc;
-  unsigned long long* d_sz = (unsigned long long*)ctx->scratch[SB_CORR].p;
+  unsigned long long* d_sz = ctx->scratch[SB_GSIZES].as<unsigned long long>();
   unsigned long long* d_off = d_sz + n;
   unsigned long long* d_total = d_off + n;
   const unsigned g0 = (unsigned)((n + 255) / 256);
@@ -808,14 +800,14 @@ extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long lo
     fprintf(stderr, "gform: mean columns %.1f rows %.1f shifts %.1f nodes %.1f; pairs with <= 16 columns and rows %ld, <= 32 %ld\n", s_ncol / n1, s_nj / n1,
             s_nu / n1, s_nq / n1, small, mid);
   }
-  if ((rc = ldsim_ensure(ctx, SB_WBUF, (size_t)(total + 16) * 8))) return rc;
-  HIPCHK(hipMemsetAsync(&counters[7], 0, 8, st));
+  if ((rc = ctx->scratch[SB_GREC].ensure((size_t)(total + 16) * 8))) return rc;
+  HIPCHK(hipMemsetAsync(&counters[ST_POOL_CURSOR], 0, 8, st));
   GA.c = a;
-  GA.pp = (const PairParams*)ctx->scratch[SB_PPAR].p;
+  GA.pp = ctx->scratch[SB_PPAR].as<const PairParams>();
   GA.gi = gi;
-  GA.maps = (const unsigned char*)ctx->scratch[SB_GMAPS].p;
-  GA.rec = (double*)ctx->scratch[SB_WBUF].p;
-  GA.flags = (int32_t*)ctx->scratch[SB_ITEMS].p;
+  GA.maps = ctx->scratch[SB_GMAPS].as<const unsigned char>();
+  GA.rec = ctx->scratch[SB_GREC].as<double>();
+  GA.flags = ctx->scratch[SB_GFLAGS].as<int32_t>();
   GA.glx = ctx->d_glx.as<double>();
   GA.glw = ctx->d_glw.as<double>();
   GA.resp_pad = (const double*)ctx->resp_pad.p;
@@ -865,7 +857,7 @@ extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long lo
   }
   HIPCHK(hipEventRecord(ctx->ev[6], st));
   // the pool's size in the statistics slot of the split paths (doubles)
-  HIPCHK(hipMemcpyAsync(&counters[7], d_total, 8, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(&counters[ST_POOL_CURSOR], d_total, 8, hipMemcpyDeviceToDevice, st));
   *flags_out = GA.flags;
   hipLaunchKernelGGL(gflag_list_kernel, dim3(g0), dim3(256), 0, st, GA.flags, n, d_wg + n, d_total + 4);
   HIPCHK(hipGetLastError());
@@ -885,9 +877,9 @@ extern "C++" int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long lo
 
 // ldsim_debug_gform_census (include/ldsim.h): the launch's GInfo array and flags copied back, the pairs counted with the
 // functions gbig_list_kernel / gcorr_kernel / gtables_list_kernel dealt them by
-extern "C++" int gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n_out) {
+int gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n_out) {
   const ldsim_ctx::GformRecord& R = ctx->gform_rec;
-  if (!R.valid || R.gi != ctx->scratch[SB_HDR].p || R.flags != ctx->scratch[SB_ITEMS].p) {
+  if (!R.valid || R.gi != ctx->scratch[SB_GINFO].p || R.flags != ctx->scratch[SB_GFLAGS].p) {
     ldsim_set_error("the last current stage did not run the node-separable form (or its records are gone)");
     return LDSIM_ESTATE;
   }

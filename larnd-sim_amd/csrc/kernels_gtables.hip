@@ -11,6 +11,7 @@
 // Deterministic: every table entry has one owner thread and a fixed order of its terms.
 #include <type_traits>
 #include "gform.h"
+#include "launchers.h"
 #include "wave_ops.h"
 
 #define GQN_LDS 64        // nodes of a rule kept in LDS (longer rules read the table)
@@ -27,7 +28,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) gtables_kernel(GArgs GA, const
   if (status != 1) {
     if (tid == 0) {
       GA.flags[pair] = status == 2;
-      if (status == 2) stat_add(A.counters, 6, 1ull);
+      if (status == 2) stat_add(A.counters, ST_FALLBACK, 1ull);
     }
     return;
   }
@@ -72,7 +73,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) gtables_kernel(GArgs GA, const
       bool amb;
       sh = slice_shift_of<M>(c, s_par[PP_Z_START_INT], s_par[PP_Z_STEP], s_par[PP_Z_ANODE], s_par[PP_T_START], iz_first + lane, z,
                              t0, amb);
-      if (amb) stat_add(A.counters, 0, 1ull);
+      if (amb) stat_add(A.counters, ST_AMBIGUOUS, 1ull);
       dzv = z - s_par[PP_SZ];
       s_dz[lane] = dzv;
 #pragma unroll
@@ -214,7 +215,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) gtables_kernel(GArgs GA, const
   if (ncol != ncol_g || NJ != NJ_g || jmin != gip->jmin) {
     if (tid == 0) {
       GA.flags[pair] = 1;
-      stat_add(A.counters, 6, 1ull);
+      stat_add(A.counters, ST_FALLBACK, 1ull);
     }
     return;
   }
@@ -382,7 +383,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) gtables_kernel(GArgs GA, const
   if (tid == 0) {
     gip->emask = emask_seen & ebound;
     GA.flags[pair] = 0;
-    if (!(GA.dbg & 1)) stat_add(A.counters, 1, (unsigned long long)NQ);
+    if (!(GA.dbg & 1)) stat_add(A.counters, ST_SAMPLES, (unsigned long long)NQ);
   }
 }
 
@@ -406,7 +407,7 @@ __global__ void __launch_bounds__(64, (XYS <= 55 ? 4 : 3)) gtables_wave_kernel(G
   const int64_t pair = list ? (int64_t)list[blockIdx.x] : (int64_t)blockIdx.x + pair0;      // (pair0: first pair of a range launch)
   if (pair >= A.n_pairs) return;
 #ifdef LDSIM_GCORR_DEBUG
-  const bool stamps = (GA.dbg & 2048) != 0;      // timing tools: cycle stamps into the statistics stripes 9..15 (chain.hip prints them)
+  const bool stamps = (GA.dbg & 2048) != 0;      // timing tools: cycle stamps into ST_GTAB_* (gcorr_kernel writes the same stripes as ST_GCORR_*; chain.hip prints them)
 #else
   constexpr bool stamps = false;
 #endif
@@ -426,7 +427,7 @@ __global__ void __launch_bounds__(64, (XYS <= 55 ? 4 : 3)) gtables_wave_kernel(G
   if (status != 1) {           // nothing to compute, or handed to the monolithic kernel
     if (lane == 0 && !list) {
       GA.flags[pair] = status == 2;
-      if (status == 2) stat_add(A.counters, 6, 1ull);
+      if (status == 2) stat_add(A.counters, ST_FALLBACK, 1ull);
     }
     return;
   }
@@ -487,7 +488,7 @@ __global__ void __launch_bounds__(64, (XYS <= 55 ? 4 : 3)) gtables_wave_kernel(G
       const double z = s_par[PP_Z_START_INT] + (iz_lo + lane) * s_par[PP_Z_STEP];
       dzv = z - s_par[PP_SZ];
     }
-    if (lane == 0 && s_mapb[G_MAP_AMB]) stat_add(A.counters, 0, (unsigned long long)s_mapb[G_MAP_AMB]);
+    if (lane == 0 && s_mapb[G_MAP_AMB]) stat_add(A.counters, ST_AMBIGUOUS, (unsigned long long)s_mapb[G_MAP_AMB]);
     const int lo = wave_min_i32(lane < nmax ? sh : (1 << 30)), hi = wave_max_i32(lane < nmax ? sh : -(1 << 30));
     NUc = hi - lo + 1;
     if (nmax != iz_hi - iz_lo + 1 || NUc > NUW || NUc != NU || lo != u_min) bad = true;
@@ -553,7 +554,7 @@ __global__ void __launch_bounds__(64, (XYS <= 55 ? 4 : 3)) gtables_wave_kernel(G
   if (bad) {
     if (lane == 0) {
       GA.flags[pair] = 1;
-      stat_add(A.counters, 6, 1ull);
+      stat_add(A.counters, ST_FALLBACK, 1ull);
     }
     return;
   }
@@ -814,18 +815,18 @@ __global__ void __launch_bounds__(64, (XYS <= 55 ? 4 : 3)) gtables_wave_kernel(G
     if (stamps) ts_cells += __builtin_amdgcn_s_memtime() - ts_m;
   }
   if (stamps && lane == 0) {
-    stat_add(A.counters, 9, ts_ld);
-    stat_add(A.counters, 10, ts_c - (ts0 + ts_ld));
-    stat_add(A.counters, 11, ts_a - (ts0 + ts_ld));
-    stat_add(A.counters, 12, ts_xy);
-    stat_add(A.counters, 13, ts_z);
-    stat_add(A.counters, 14, ts_cells);
-    stat_add(A.counters, 15, __builtin_amdgcn_s_memtime() - ts0);
+    stat_add(A.counters, ST_GTAB_LOADS, ts_ld);
+    stat_add(A.counters, ST_GTAB_MAPS, ts_c - (ts0 + ts_ld));
+    stat_add(A.counters, ST_GTAB_BATCH_PROLOGUE, ts_a - (ts0 + ts_ld));
+    stat_add(A.counters, ST_GTAB_TABLES_XY, ts_xy);
+    stat_add(A.counters, ST_GTAB_TABLES_Z, ts_z);
+    stat_add(A.counters, ST_GTAB_CELLS, ts_cells);
+    stat_add(A.counters, ST_GTAB_LIFE, __builtin_amdgcn_s_memtime() - ts0);
   }
   if (lane == 0) {
     gip->emask = emask;
     GA.flags[pair] = 0;
-    if (!GDBG(1)) stat_add(A.counters, 1, (unsigned long long)NQ);
+    if (!GDBG(1)) stat_add(A.counters, ST_SAMPLES, (unsigned long long)NQ);
   }
 }
 
@@ -849,7 +850,7 @@ __global__ void __launch_bounds__(256) gtables_list_kernel(const GInfo* __restri
   }
 }
 
-extern "C++" int gtables_list_launch(ldsim_ctx* ctx, const GArgs& GA, int32_t* wg_list, unsigned long long* wg_count, int32_t* w2_list,
+int gtables_list_launch(ldsim_ctx* ctx, const GArgs& GA, int32_t* wg_list, unsigned long long* wg_count, int32_t* w2_list,
                                      unsigned long long* w2_count) {
   const int64_t n = GA.c.n_pairs;
   if (n == 0) return 0;
@@ -860,7 +861,7 @@ extern "C++" int gtables_list_launch(ldsim_ctx* ctx, const GArgs& GA, int32_t* w
 }
 
 // the wave kernel over the pair range [pair0, pair0 + n) on stream `ts`
-extern "C++" int gtables_launch_range(ldsim_ctx* ctx, const GArgs& GA, int M, hipStream_t ts, int64_t pair0, int64_t n) {
+int gtables_launch_range(ldsim_ctx* ctx, const GArgs& GA, int M, hipStream_t ts, int64_t pair0, int64_t n) {
   if (n <= 0) return 0;
   if (M == 1) hipLaunchKernelGGL((gtables_wave_kernel<1, 55>), dim3((unsigned)n), dim3(64), 0, ts, GA, (const int32_t*)nullptr, (int)pair0);
   else hipLaunchKernelGGL((gtables_wave_kernel<2, 55>), dim3((unsigned)n), dim3(64), 0, ts, GA, (const int32_t*)nullptr, (int)pair0);
@@ -868,7 +869,7 @@ extern "C++" int gtables_launch_range(ldsim_ctx* ctx, const GArgs& GA, int M, hi
   return 0;
 }
 // its wide instantiation over the `n_w2` pairs of `w2_list`, and the workgroup kernel over the `n_wg` listed ones, on stream `ts`
-extern "C++" int gtables_launch_lists(ldsim_ctx* ctx, const GArgs& GA, int M, hipStream_t ts, const int32_t* wg_list, int64_t n_wg,
+int gtables_launch_lists(ldsim_ctx* ctx, const GArgs& GA, int M, hipStream_t ts, const int32_t* wg_list, int64_t n_wg,
                                       const int32_t* w2_list, int64_t n_w2) {
   if (n_w2 > 0) {
     if (M == 1) hipLaunchKernelGGL((gtables_wave_kernel<1, 81>), dim3((unsigned)n_w2), dim3(64), 0, ts, GA, w2_list, 0);
@@ -885,7 +886,7 @@ extern "C++" int gtables_launch_lists(ldsim_ctx* ctx, const GArgs& GA, int M, hi
 
 // wave kernel over all pairs, its wide instantiation over the `n_w2` pairs of `w2_list`, then the workgroup kernel over the `n_wg`
 // listed ones
-extern "C++" int gtables_launch(ldsim_ctx* ctx, const GArgs& GA, int M, const int32_t* wg_list, int64_t n_wg, const int32_t* w2_list,
+int gtables_launch(ldsim_ctx* ctx, const GArgs& GA, int M, const int32_t* wg_list, int64_t n_wg, const int32_t* w2_list,
                                 int64_t n_w2) {
   if (GA.c.n_pairs == 0) return 0;
   int rc = gtables_launch_range(ctx, GA, M, ctx->stream, 0, GA.c.n_pairs);

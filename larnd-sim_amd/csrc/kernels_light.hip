@@ -18,7 +18,7 @@
 //        records replays them: same f4 accumulation order, same first-come truth slots (light_sim.py:103-110,119-127).
 //        [Rounds 2-3 keyed the records (detector, tick, rank, bin) in 64 bits -- eight passes over 12-byte pairs -- and fetched
 //        photons and segment of a sorted record through its index: 5.2 ms per 2x2 batch of 2.4e7 records.]
-#include "ldsim_dev.h"
+#include "launchers.h"
 
 __device__ __forceinline__ void get_voxel(const LdsimConsts* c, double x, double y, double z, int itpc, int nx, int ny,
                                           int nz, int& i, int& j, int& k) {
@@ -770,7 +770,6 @@ __global__ void __launch_bounds__(64) light_replay_wave_kernel(const unsigned* _
   if (open) close_cell();
 }
 
-extern "C++" {
 int light_launch_reset_cells(ldsim_ctx* ctx, int64_t n_rec, int64_t n_ticks, int max_truth, float* out, int64_t* true_id,
                               double* true_ph) {
   if (n_rec <= 0) return 0;
@@ -800,10 +799,6 @@ int light_launch_clear_list(ldsim_ctx* ctx, const LightAct* act, float* out) {
   return 0;
 }
 
-int sort_pairs(ldsim_ctx*, unsigned long long*, unsigned long long*, int32_t*, int32_t*, int64_t);
-int sort_pairs_bits(ldsim_ctx*, unsigned long long*, unsigned long long*, int32_t*, int32_t*, int64_t, int, int);
-int sort_pairs_u32_u64(ldsim_ctx*, unsigned*, unsigned*, unsigned long long*, unsigned long long*, int64_t, int);
-int sort_exclusive_scan_i32(ldsim_ctx*, const int32_t*, int32_t*, int64_t);
 static inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
 int light_launch_incidence(ldsim_ctx* ctx, int64_t seg0, int64_t n, int n_out, float* nph, float* t0det, int32_t* voxel,
@@ -889,15 +884,15 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
     const int tick_bits = tick_bits_c;
     // ---- resident sum, compact form (kernels above): pairs with photons -> visiting order -> records by wave -> cells -> replay ----
     const int cap = (ctx->h_consts.enable_lut_smearing ? ctx->lut_nprof : 1) + LIGHT_SPARE;
-    if ((rc = ldsim_ensure_buf(ctx, &T[1], 64))) return rc;                        // [0] pairs with photons
+    if ((rc = T[1].ensure(64))) return rc;                        // [0] pairs with photons
     if (!ctx->light_flag_dev.p) {                                                     // record slot overflow: sticky until read
       CK(ctx->light_flag_dev.ensure(8));
       HIPCHK(hipMemsetAsync(ctx->light_flag_dev.as<unsigned>(), 0, 8, st));
     }
-    if ((rc = ldsim_ensure_buf(ctx, &T[3], (size_t)np * 8))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[0], (size_t)np * 8))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[5], (size_t)np * 4))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[6], (size_t)np * 4))) return rc;
+    if ((rc = T[3].ensure((size_t)np * 8))) return rc;
+    if ((rc = T[0].ensure((size_t)np * 8))) return rc;
+    if ((rc = T[5].ensure((size_t)np * 4))) return rc;
+    if ((rc = T[6].ensure((size_t)np * 4))) return rc;
     unsigned* d_cnt = (unsigned*)T[1].p;
     HIPCHK(hipMemsetAsync(d_cnt, 0, 4, st));
     hipLaunchKernelGGL(light_active_pairs_kernel, dim3(nblk(np, 256)), dim3(256), 0, st, L, (unsigned long long*)T[3].p, (int32_t*)T[5].p,
@@ -918,10 +913,10 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
                               52 + det_bits)))
       return rc;
     // records: T[3] keys in, T[4] keys sorted (kept for the next sum's lazy reset), T[7] / T[8] payloads in / sorted
-    if ((rc = ldsim_ensure_buf(ctx, &T[3], (size_t)n_slots * 4))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[4], (size_t)n_slots * 4))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[7], (size_t)n_slots * 8))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[8], (size_t)n_slots * 8))) return rc;
+    if ((rc = T[3].ensure((size_t)n_slots * 4))) return rc;
+    if ((rc = T[4].ensure((size_t)n_slots * 4))) return rc;
+    if ((rc = T[7].ensure((size_t)n_slots * 8))) return rc;
+    if ((rc = T[8].ensure((size_t)n_slots * 8))) return rc;
     unsigned *k0 = (unsigned*)T[3].p, *k1 = (unsigned*)T[4].p;
     unsigned long long *v0 = (unsigned long long*)T[7].p, *v1 = (unsigned long long*)T[8].p;
     hipLaunchKernelGGL(light_emit_wave_kernel, dim3(nblk(n_act, 4)), dim3(256), 0, st, L, (const int32_t*)T[6].p, n_act, cap, tick_bits,
@@ -939,18 +934,18 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
     ctx->light_emit_flag = ctx->light_flag_dev.as<unsigned>();  // (read at the next synchronising call: light_check_emit_overflow)
     return 0;
   }
-  if ((rc = ldsim_ensure_buf(ctx, &T[1], (size_t)np * 4 + 16))) return rc;     // count, then offsets in T[2]
-  if ((rc = ldsim_ensure_buf(ctx, &T[2], (size_t)np * 4 + 16))) return rc;
+  if ((rc = T[1].ensure((size_t)np * 4 + 16))) return rc;     // count, then offsets in T[2]
+  if ((rc = T[2].ensure((size_t)np * 4 + 16))) return rc;
   int32_t* d_count = (int32_t*)T[1].p;
   int32_t* d_offs = (int32_t*)T[2].p;
   const int32_t* d_order = sorted_idx;            // [n_det][n]: the segment visited q-th for detector idet
   if (!sorted_idx) {
     // descending photons per detector (cli/simulate_pixels.py:1141-1144): one sort of the (detector, segment) pairs over the key bits
     // that are used -- detector | inverted photon bits | inverted segment index
-    if ((rc = ldsim_ensure_buf(ctx, &T[3], (size_t)np * 8))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[0], (size_t)np * 8))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[5], (size_t)np * 4))) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &T[6], (size_t)np * 4))) return rc;
+    if ((rc = T[3].ensure((size_t)np * 8))) return rc;
+    if ((rc = T[0].ensure((size_t)np * 8))) return rc;
+    if ((rc = T[5].ensure((size_t)np * 4))) return rc;
+    if ((rc = T[6].ensure((size_t)np * 4))) return rc;
     hipLaunchKernelGGL(light_order_keys_kernel, dim3(nblk(np, 256)), dim3(256), 0, st, L, (unsigned long long*)T[3].p,
                        (int32_t*)T[5].p);
     HIPCHK(hipGetLastError());
@@ -970,10 +965,10 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
   if (n_rec == 0) return 0;
   if (n_rec_out) *n_rec_out = n_rec;
   // records: T[3] keys in, T[4] keys sorted (kept for the next sum's lazy reset), T[7] / T[8] payloads in / sorted
-  if ((rc = ldsim_ensure_buf(ctx, &T[3], (size_t)n_rec * 4))) return rc;
-  if ((rc = ldsim_ensure_buf(ctx, &T[4], (size_t)n_rec * 4))) return rc;
-  if ((rc = ldsim_ensure_buf(ctx, &T[7], (size_t)n_rec * 8))) return rc;
-  if ((rc = ldsim_ensure_buf(ctx, &T[8], (size_t)n_rec * 8))) return rc;
+  if ((rc = T[3].ensure((size_t)n_rec * 4))) return rc;
+  if ((rc = T[4].ensure((size_t)n_rec * 4))) return rc;
+  if ((rc = T[7].ensure((size_t)n_rec * 8))) return rc;
+  if ((rc = T[8].ensure((size_t)n_rec * 8))) return rc;
   unsigned *k0 = (unsigned*)T[3].p, *k1 = (unsigned*)T[4].p;
   unsigned long long *v0 = (unsigned long long*)T[7].p, *v1 = (unsigned long long*)T[8].p;
   hipLaunchKernelGGL(light_fill_ordered_kernel, dim3(nblk(np, 256)), dim3(256), 0, st, L, d_order, d_offs, tick_bits, k0, v0);
@@ -989,5 +984,4 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
                        n_ticks, ctx->h_consts.mc_truth_threshold, out, true_id, true_ph, max_truth);
   HIPCHK(hipGetLastError());
   return 0;
-}
 }

@@ -10,7 +10,7 @@
 // chunks of JCHUNK: the chunk of x and the weights it can meet are staged in LDS; inside a chunk all lanes read the same
 // x[j] (broadcast) and consecutive weights (conflict-free).  Truth slots (optional) follow the reference literally; a
 // per-tick bound on the slots' photons (light_truth_max_kernel) lets a pair (i, j) skip its slot walk when none can pass.
-#include "ldsim_dev.h"
+#include "launchers.h"
 #include "wave_ops.h"
 
 #define LR_THREADS 256
@@ -777,7 +777,7 @@ __global__ void light_widen_kernel(const float* __restrict__ x, int64_t n, doubl
 }
 
 // the plain sum of a stage (no truth slots) on `st`
-extern "C++" int light_response_plain(ldsim_ctx* ctx, hipStream_t st, bool response, const float* inc, int D, int T, const double* weights,
+int light_response_plain(ldsim_ctx* ctx, hipStream_t st, bool response, const float* inc, int D, int T, const double* weights,
                                       int C, const double* gain, float* out) {
   if (D <= 0 || T <= 0) return 0;
   dim3 grid((unsigned)((T + LR_THREADS - 1) / LR_THREADS), (unsigned)D), block(LR_THREADS);
@@ -785,7 +785,7 @@ extern "C++" int light_response_plain(ldsim_ctx* ctx, hipStream_t st, bool respo
   const double* xd = nullptr;
   if (response) {          // (the SiPM stage's blocks of 64 input ticks all take part: the samples once more as doubles)
     const int64_t n = (int64_t)D * T;
-    int rc = ldsim_ensure_buf(ctx, &ctx->light_xd, (size_t)n * 8 + 64);
+    int rc = ctx->light_xd.ensure((size_t)n * 8 + 64);
     if (rc) return rc;
     hipLaunchKernelGGL(light_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, inc, n, (double*)ctx->light_xd.p);
     xd = (const double*)ctx->light_xd.p;
@@ -801,19 +801,19 @@ extern "C++" int light_response_plain(ldsim_ctx* ctx, hipStream_t st, bool respo
 }
 
 // can the truth slots of a stage go by light_truth_lds_kernel?
-extern "C++" bool light_truth_in_lds(const ldsim_ctx* ctx, int Mt) { return Mt > 0 && Mt <= 64 && ctx->light_truth_lds; }
+bool light_truth_in_lds(const ldsim_ctx* ctx, int Mt) { return Mt > 0 && Mt <= 64 && ctx->light_truth_lds; }
 
 // the truth slots of a stage (light_truth_in_lds) on `st`: bounds, weight envelopes, light_truth_lds_kernel.  The scintillation and the
 // SiPM stage of one call share the bound and envelope buffers: both on the same stream.
-extern "C++" int light_response_truth(ldsim_ctx* ctx, hipStream_t st, bool response, const float* inc, const int64_t* tid, const double* tph,
+int light_response_truth(ldsim_ctx* ctx, hipStream_t st, bool response, const float* inc, const int64_t* tid, const double* tph,
                                       int D, int T, int Mt, const double* weights, int C, int64_t* out_tid, double* out_tph) {
   if (D <= 0 || T <= 0) return 0;
   const double thr = ctx->h_consts.mc_truth_threshold;
   const int nblk = (T + 63) / 64, nq = (C + 63) / 64 + 1;
   const int64_t n = (int64_t)D * T;
-  int rc = ldsim_ensure_buf(ctx, &ctx->light_tmax, (size_t)(n + (int64_t)D * nblk) * 8);
+  int rc = ctx->light_tmax.ensure((size_t)(n + (int64_t)D * nblk) * 8);
   if (rc) return rc;
-  if ((rc = ldsim_ensure_buf(ctx, &ctx->light_env, (size_t)(C + 64 + nq) * 8))) return rc;
+  if ((rc = ctx->light_env.ensure((size_t)(C + 64 + nq) * 8))) return rc;
   double* tmax = (double*)ctx->light_tmax.p;
   double* env = (double*)ctx->light_env.p;
   double* env2 = env + C + 64;
@@ -839,7 +839,7 @@ extern "C++" int light_response_truth(ldsim_ctx* ctx, hipStream_t st, bool respo
   return 0;
 }
 
-extern "C++" int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid,
+int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid,
                                        const double* tph, int D, int T, int Mt, const double* weights, int C,
                                        const double* gain, float* out, int64_t* out_tid, double* out_tph) {
   if (D <= 0 || T <= 0) return 0;
@@ -854,7 +854,7 @@ extern "C++" int light_response_launch(ldsim_ctx* ctx, bool response, const floa
   double* tmax = nullptr;
   if (Mt > 0) {
     const int64_t n = (int64_t)D * T;
-    int rc = ldsim_ensure_buf(ctx, &ctx->light_tmax, (size_t)n * 8);
+    int rc = ctx->light_tmax.ensure((size_t)n * 8);
     if (rc) return rc;
     tmax = (double*)ctx->light_tmax.p;
     hipLaunchKernelGGL(light_truth_max_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tid, tph, n, Mt,
@@ -868,9 +868,9 @@ extern "C++" int light_response_launch(ldsim_ctx* ctx, bool response, const floa
   double* w_tph = nullptr;
   if (Mt > 0) {
     const size_t bt = (size_t)D * T * Mt;
-    int rc = ldsim_ensure_buf(ctx, &ctx->light_wtid, bt * 8 + 16);
+    int rc = ctx->light_wtid.ensure(bt * 8 + 16);
     if (rc) return rc;
-    if ((rc = ldsim_ensure_buf(ctx, &ctx->light_wtph, bt * 8 + 16))) return rc;
+    if ((rc = ctx->light_wtph.ensure(bt * 8 + 16))) return rc;
     w_tid = (int64_t*)ctx->light_wtid.p;
     w_tph = (double*)ctx->light_wtph.p;
     dim3 tg((unsigned)((T + TR_TICKS - 1) / TR_TICKS), (unsigned)D);
@@ -879,7 +879,7 @@ extern "C++" int light_response_launch(ldsim_ctx* ctx, bool response, const floa
     hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), (size_t)TR_TICKS * (Mt + 1) * 8, ctx->stream,
                        (const unsigned long long*)out_tph, (unsigned long long*)w_tph, T, Mt);
     if (response) {        // the SiPM stage compares ids of the INPUT row at the output tick (light_sim.py:331-335): slot-major too
-      if ((rc = ldsim_ensure_buf(ctx, &ctx->light_wtid2, bt * 8 + 16))) return rc;
+      if ((rc = ctx->light_wtid2.ensure(bt * 8 + 16))) return rc;
       in_sm = (int64_t*)ctx->light_wtid2.p;
       hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), (size_t)TR_TICKS * (Mt + 1) * 8, ctx->stream,
                          (const unsigned long long*)tid, (unsigned long long*)in_sm, T, Mt);

@@ -12,6 +12,7 @@
 // of.  The first chunk of an item is prefetched into one of two register sets that swap roles from item to item (no copies).  LDS now only carries that tail (broadcast reads); the item's weights are wave-uniform and come through the
 // scalar cache straight into the FMAs' SGPR operand.  Per block: 64 v_fma_f64 + 16 DPP moves.  Arithmetic and summation order are those of mac_kernel<1>: results are bit-identical (tested).
 #include "split_common.h"
+#include "launchers.h"
 
 __device__ __forceinline__ double wave_shl1(double old, double src) {
   // lane L <- lane L+1; lane 63 keeps `old`
@@ -187,7 +188,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 5) mac_shift_kernel(SplitArgs S) 
   }
   for (int it = tid; it < A.T; it += CUR_THREADS)
     if (it < it_w0 || it >= it_w1) out[it] = 0.f;
-  if (lane == 0 && n_blocks) stat_add(A.counters, 5, n_blocks * 64ull * 64ull);
+  if (lane == 0 && n_blocks) stat_add(A.counters, ST_DFMA, n_blocks * 64ull * 64ull);
 }
 
 // ---- M = 2 (TIME_SAMPLING = 2 RESPONSE_SAMPLING, ndlar): tick t of lane L reads R[kb + 16L + 2j + u] -------------------------
@@ -348,7 +349,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) mac_shift2_kernel(SplitArgs S)
   }
   for (int it = tid; it < A.T; it += CUR_THREADS)
     if (it < it_w0 || it >= it_w1) out[it] = 0.f;
-  if (lane == 0 && n_blocks) stat_add(A.counters, 5, n_blocks * 64ull * 64ull);
+  if (lane == 0 && n_blocks) stat_add(A.counters, ST_DFMA, n_blocks * 64ull * 64ull);
 }
 
 // rows of the response table with RESP_PAD zeros in front and behind, and zeros where mac_kernel's staging would put them
@@ -365,7 +366,7 @@ __global__ void __launch_bounds__(256) pad_response_kernel(const double* __restr
 // The zero-padded copy of the response rows (mac_shift kernels, gcorr_kernel): rebuilt when the table or the staged range --
 // the part of the table's support a tick of a window can meet, incl. the partially valid edges (mac_kernel's staging,
 // kernels_split.hip) -- changes.
-extern "C++" int resp_pad_ensure(ldsim_ctx* ctx, const CurArgs& A, int* k_lo_out, int* k_hi_out, int* nkp_out) {
+int resp_pad_ensure(ldsim_ctx* ctx, const CurArgs& A, int* k_lo_out, int* k_hi_out, int* nkp_out) {
   const LdsimConsts& h = ctx->h_consts;
   const int k_lo = A.k_first > 0 ? A.k_first : 0;
   int k_hi;
@@ -383,7 +384,7 @@ extern "C++" int resp_pad_ensure(ldsim_ctx* ctx, const CurArgs& A, int* k_lo_out
   const int64_t n_cells = (int64_t)A.ni * A.nj;
   if (ctx->resp_pad_hi == -2 || ctx->resp_pad_lo != k_lo || ctx->resp_pad_hi != k_hi ||
       ctx->resp_pad.bytes < (size_t)n_cells * nkp * 8) {
-    int rc = ldsim_ensure_buf(ctx, &ctx->resp_pad, (size_t)n_cells * nkp * 8);
+    int rc = ctx->resp_pad.ensure((size_t)n_cells * nkp * 8);
     if (rc) return rc;
     hipLaunchKernelGGL(pad_response_kernel, dim3((unsigned)((n_cells * nkp + 255) / 256)), dim3(256), 0, ctx->stream, A.resp,
                        n_cells, A.nk, nkp, k_lo, k_hi, (double*)ctx->resp_pad.p);
@@ -395,7 +396,7 @@ extern "C++" int resp_pad_ensure(ldsim_ctx* ctx, const CurArgs& A, int* k_lo_out
   return 0;
 }
 
-extern "C++" int mac_shift_launch(ldsim_ctx* ctx, SplitArgs S, int M) {
+int mac_shift_launch(ldsim_ctx* ctx, SplitArgs S, int M) {
   const CurArgs& A = S.c;
   int k_lo, k_hi, nkp;
   int rc = resp_pad_ensure(ctx, A, &k_lo, &k_hi, &nkp);

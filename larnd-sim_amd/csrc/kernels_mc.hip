@@ -7,7 +7,7 @@
 // race on it, so its output is not reproducible.  Here a workgroup owns the pair (geometry computed once), a thread owns
 // ticks tid, tid + 256, .. and every (pair, tick) has its own xoroshiro128p stream derived from that state of the table:
 // reproducible with a seed, statistically equivalent to the reference, never equal to it (unpinned).
-#include "ldsim_args.h"
+#include "launchers.h"
 #include "rng.h"
 
 __device__ __forceinline__ uint64_t splitmix_fin(uint64_t z) {
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(256) rng_step_kernel(RngState* states, int64_t
 }
 
 // signals for args.n_pairs pairs; state index = (relative segment) + n_seg * ipix.  Uses (and steps once) states [0, n_seg * P).
-extern "C++" int current_mc_launch(ldsim_ctx* ctx, const CurArgs& args, int64_t n_seg) {
+int current_mc_launch(ldsim_ctx* ctx, const CurArgs& args, int64_t n_seg) {
   if (args.n_pairs == 0) return 0;
   const LdsimConsts& h = ctx->h_consts;
   if (!(h.min_step_size > 0) || h.mc_sample_multiplier < 1) {

@@ -10,11 +10,9 @@
 //   pass B  the pixel's ticks [t_lo, t_hi) in 64-tick chunks, every lane summing in slot order the slots that cover its tick:
 //           S[t] exactly as pixel_adc_body forms it, so q_induced and q_abs need no S array (the rows come from L2 now)
 // then a selection on the device (flags, two exclusive scans, a gather) into the compact form.
-#include "ldsim_args.h"
+#include "launchers.h"
 #include "fee_record.h"
 #include "wave_ops.h"
-
-int sort_exclusive_scan_i32(ldsim_ctx*, const int32_t*, int32_t*, int64_t);
 
 #define PT_WAVES 4       // pixels per workgroup
 
@@ -182,7 +180,8 @@ extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, in
   }
   CK(pt_need_launch(ctx, "pixel truth"));
   HIPCHK(hipSetDevice(ctx->device));
-  const int64_t U = ctx->chain_U;
+  const ChainView v = chain_view(ctx);      // (the pass grows its own buffers and SB_SORTTMP only)
+  const int64_t U = v.U;
   ctx->pt_gen = ctx->out_gen;
   ctx->pt_U = U;
   ctx->pt_n[0] = ctx->pt_n[1] = 0;
@@ -195,17 +194,14 @@ extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, in
   CK(ctx->pt_sel.ensure((size_t)(4 * U + 4) * 4));
   const PtDense D = pt_dense_of(ctx->pt_dense.p, U, R.M);
   HIPCHK(hipMemsetAsync(ctx->pt_dense.p, 0, D.bytes, st));
-  const FeeHdr* d_hdr = (const FeeHdr*)ctx->scratch[SB_SPAN].p;
-  const unsigned long long* d_counts =
-      R.lists ? (const unsigned long long*)((const char*)ctx->scratch[SB_SPAN].p + (size_t)U * sizeof(FeeHdr) * 2) : nullptr;
-  hipLaunchKernelGGL(pixel_truth_kernel, dim3((unsigned)((U + PT_WAVES - 1) / PT_WAVES)), dim3(64 * PT_WAVES), 0, st, d_hdr, d_counts,
-                     (const FeeSlot*)ctx->scratch[SB_FEESLOT].p, (const float*)ctx->scratch[SB_WAVES].p, U, R.n_pairs, R.T, R.NT, R.M,
-                     R.dt, D.q_induced, D.q_abs, D.q_track, D.n_slots);
+  hipLaunchKernelGGL(pixel_truth_kernel, dim3((unsigned)((U + PT_WAVES - 1) / PT_WAVES)), dim3(64 * PT_WAVES), 0, st,
+                     v.fee.hdr, v.fee.counts, v.fee_slots, v.waves, U, R.n_pairs, R.T, R.NT, R.M, R.dt, D.q_induced, D.q_abs,
+                     D.q_track, D.n_slots);
   HIPCHK(hipGetLastError());
   // ---- selection: flags, exclusive scans of the flags and of the kept pixels' slot counts, then the gather ------------------
   int32_t* keep = ctx->pt_sel.as<int32_t>();
   int32_t *cnt = keep + U, *o_keep = cnt + U, *o_cnt = o_keep + U;
-  const int32_t* d_hitcnt = (const int32_t*)ctx->scratch[SB_PAIRPIX].p;
+  const int32_t* d_hitcnt = v.hit_count;
   const unsigned g0 = (unsigned)((U + 255) / 256);
   hipLaunchKernelGGL(pixel_truth_flag_kernel, dim3(g0), dim3(256), 0, st, U, d_hitcnt, D.q_abs, D.n_slots, min_abs_charge, keep, cnt);
   HIPCHK(hipGetLastError());
@@ -227,8 +223,7 @@ extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, in
   CK(ctx->pt_out.ensure(b_rows + (size_t)n_trk * sizeof(LdsimPixelTruthTrack)));
   if (n_pix) {
     hipLaunchKernelGGL(pixel_truth_gather_kernel, dim3(g0), dim3(256), 0, st, U, R.A, R.M, keep, o_keep, o_cnt,
-                       (const int32_t*)ctx->scratch[SB_UPIX].p, (const int32_t*)ctx->scratch[SB_UBATCH].p, d_hitcnt,
-                       (const double*)ctx->scratch[SB_ADC].p, (const int64_t*)ctx->scratch[SB_TPM].p, D.q_induced, D.q_abs, D.q_track,
+                       v.upix, v.ubatch, d_hitcnt, v.adc, v.tpm, D.q_induced, D.q_abs, D.q_track,
                        D.n_slots, (LdsimPixelTruthRow*)ctx->pt_out.p, (LdsimPixelTruthTrack*)((char*)ctx->pt_out.p + b_rows));
     HIPCHK(hipGetLastError());
   }
@@ -250,12 +245,11 @@ static int pt_need_launch(ldsim_ctx* ctx, const char* who) {
   if (U == 0) return 0;
   const ldsim_ctx::FeeRecord& R = ctx->fee_rec;
   // all of the sizes the launch ran with (an intact launch has them; checked all the same)
-  const size_t hdr_bytes = (size_t)U * sizeof(FeeHdr) * (R.lists ? 2 : 1) + (R.lists ? 16 : 0);
   const bool sized = R.U == U && R.M > 0 && R.M <= 64 && R.A > 0 && R.T > 0 && R.n_pairs > 0 &&
-                     ctx->scratch[SB_SPAN].bytes >= hdr_bytes && ctx->scratch[SB_FEESLOT].bytes >= (size_t)R.n_pairs * sizeof(FeeSlot) &&
+                     ctx->scratch[SB_FEEHDR].bytes >= chain_view(ctx).fee.bytes && ctx->scratch[SB_FEESLOT].bytes >= (size_t)R.n_pairs * sizeof(FeeSlot) &&
                      ctx->scratch[SB_WAVES].bytes >= (size_t)R.n_pairs * R.T * 4 && ctx->scratch[SB_UPIX].bytes >= (size_t)U * 4 &&
                      ctx->scratch[SB_UBATCH].bytes >= (size_t)U * 4 && ctx->scratch[SB_ADC].bytes >= (size_t)U * R.A * 8 &&
-                     ctx->scratch[SB_TPM].bytes >= (size_t)U * R.M * 8 && ctx->scratch[SB_PAIRPIX].bytes >= (size_t)U * 4;
+                     ctx->scratch[SB_TPM].bytes >= (size_t)U * R.M * 8 && ctx->scratch[SB_HITCNT].bytes >= hit_counts_bytes(U);
   if (!sized) {
     ldsim_set_error("pixel truth: the set-up record of the last chain launch does not describe its buffers");
     return LDSIM_ESTATE;
@@ -275,11 +269,9 @@ extern "C" int ldsim_chain_pixel_truth_row_samples(ldsim_ctx* ctx, int64_t* n_sa
   CK(ctx->pt_sel.ensure((size_t)(4 * U + 4) * 4));
   unsigned long long* d_total = (unsigned long long*)(ctx->pt_sel.as<int32_t>() + 4 * U);      // (behind the scans; 16 U bytes in: 8-byte aligned)
   HIPCHK(hipMemsetAsync(d_total, 0, 8, ctx->stream));
-  const FeeHdr* d_hdr = (const FeeHdr*)ctx->scratch[SB_SPAN].p;
-  const unsigned long long* d_counts =
-      R.lists ? (const unsigned long long*)((const char*)ctx->scratch[SB_SPAN].p + (size_t)U * sizeof(FeeHdr) * 2) : nullptr;
-  hipLaunchKernelGGL(pixel_truth_samples_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, ctx->stream, d_hdr, d_counts,
-                     (const FeeSlot*)ctx->scratch[SB_FEESLOT].p, U, R.n_pairs, R.T, R.NT, R.M, d_total);
+  const ChainView v = chain_view(ctx);
+  hipLaunchKernelGGL(pixel_truth_samples_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, ctx->stream,
+                     v.fee.hdr, v.fee.counts, v.fee_slots, U, R.n_pairs, R.T, R.NT, R.M, d_total);
   HIPCHK(hipGetLastError());
   unsigned long long h = 0;
   HIPCHK(hipMemcpyAsync(&h, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));

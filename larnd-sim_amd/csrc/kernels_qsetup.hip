@@ -7,6 +7,7 @@
 // share a wave.  (A wave-per-pair form of the whole weights stage was tried on top of this record and measured slower:
 // DESIGN.md section 4, profiles/r02_qwave_phase_timing.log.)
 #include "gform.h"
+#include "launchers.h"
 
 // =============================================================================================================
 template <int M>
@@ -274,10 +275,10 @@ __global__ void __launch_bounds__(256) pair_setup_kernel(SplitArgs S, PairParams
   gi[pair] = Gi;
 }
 
-extern "C++" size_t qpair_params_bytes(int64_t n_pairs) { return (size_t)n_pairs * sizeof(PairParams); }
+size_t qpair_params_bytes(int64_t n_pairs) { return (size_t)n_pairs * sizeof(PairParams); }
 
 // the per-pair records of both quadrature weight kernels
-extern "C++" int qpair_setup_launch(ldsim_ctx* ctx, const SplitArgs& S, int M, void* params, void* ginfo, void* maps) {
+int qpair_setup_launch(ldsim_ctx* ctx, const SplitArgs& S, int M, void* params, void* ginfo, void* maps) {
   if (S.c.n_pairs == 0) return 0;
   if (!ctx->d_glx.p || !ctx->d_glw.p || !params) {
     ldsim_set_error("Gauss-Legendre tables / pair parameter buffer missing");

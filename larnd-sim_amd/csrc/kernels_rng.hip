@@ -10,7 +10,7 @@
 //   rng_advance_kernel   advances state[u] by the draws actually consumed (2 words per normal), as the reference's in-place
 //                        update of rng_states[ip] leaves it
 // Row u of a chain launch uses state u of the table (for a launch holding one batch that is the reference's rng_states[ip]).
-#include "ldsim_dev.h"
+#include "launchers.h"
 #include "rng.h"
 
 __global__ void __launch_bounds__(256) fee_noise_kernel(const RngState* __restrict__ states, int64_t U, int nd,
@@ -66,7 +66,6 @@ __global__ void __launch_bounds__(256) rng_keyed_draw_kernel(uint64_t seed, uint
   out[i] = normal ? keyed_normal(seed, tag, keys[s], d) : keyed_uniform(seed, tag, keys[s], d);
 }
 
-extern "C++" {
 int rng_launch_fee_keyed_fill(ldsim_ctx* ctx, const int32_t* ubatch, const int32_t* upix, int64_t U, int nd, float* z) {
   if (U == 0) return 0;
   const int64_t n = U * (nd / 4);
@@ -154,7 +153,6 @@ int rng_launch_advance(ldsim_ctx* ctx, int64_t U, const int32_t* n_draws) {
                      (RngState*)ctx->d_rng.p, U, n_draws);
   HIPCHK(hipGetLastError());
   return 0;
-}
 }
 
 // numba.cuda.random.create_xoroshiro128p_states(n, seed) (cli/simulate_pixels.py:92-104,396)
@@ -253,7 +251,7 @@ extern "C" int ldsim_chain_set_batch_keys(ldsim_ctx* ctx, const uint64_t* keys, 
   }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));      // (a launch in flight may still read the old keys)
-  int rc = ldsim_ensure_buf(ctx, &ctx->d_batch_keys, (size_t)(n_batches ? n_batches : 1) * 8);
+  int rc = ctx->d_batch_keys.ensure((size_t)(n_batches ? n_batches : 1) * 8);
   if (rc) return rc;
   if (n_batches) HIPCHK(hipMemcpy(ctx->d_batch_keys.p, keys, (size_t)n_batches * 8, hipMemcpyHostToDevice));
   ctx->rng_batch_keys_n = n_batches;

@@ -1,7 +1,7 @@
 // kernels_seg.hip -- per-segment stages: record unpack/repack, quench, drift, pixel walk, time intervals.
 // All of these are HBM-bound (184 B of compulsory traffic per segment); one thread per segment over
 // SoA columns so every load/store is a coalesced 8-byte stream.
-#include "ldsim_dev.h"
+#include "launchers.h"
 #include "rng.h"
 
 // ---- AoS <-> SoA ------------------------------------------------------------------------------------------
@@ -544,7 +544,6 @@ __global__ void __launch_bounds__(256) time_intervals_kernel(SegStore s, const L
 // ---- host launchers ----------------------------------------------------------------------------------------------
 static inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
-extern "C++" {
 int seg_launch_unpack(ldsim_ctx* ctx, const LdsimTrackLayout* lay, int64_t n) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(unpack_kernel, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream,
@@ -605,5 +604,4 @@ int seg_launch_time_intervals(ldsim_ctx* ctx, int64_t b, int64_t e, double* star
                      ctx->d_consts.as<LdsimConsts>(), b, e, starts, tmax);
   HIPCHK(hipGetLastError());
   return 0;
-}
 }

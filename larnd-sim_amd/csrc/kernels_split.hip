@@ -15,6 +15,7 @@
 // current_kernel (kernels_current.hip), which has no such limits.  The weight pool is sized by chain.hip from the
 // demand of earlier launches; a launch that exhausted it is repeated, never used.
 #include "split_common.h"
+#include "launchers.h"
 
 // =============================================================================================================
 template <int M>
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) weights_kernel(SplitArgs S) {
     double tt = g.t_start + it_ref * dt;
     double val = (tt - t0) / dtr;
     double kr = py_round(val);
-    if (count && fabs(val - kr) > 0.5 - 1e-7) stat_add(A.counters, 0, 1ull);
+    if (count && fabs(val - kr) > 0.5 - 1e-7) stat_add(A.counters, ST_AMBIGUOUS, 1ull);
     return (int)kr - M * it_ref;
   };
   {
@@ -498,7 +499,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) weights_kernel(SplitArgs S) {
     }
     iz_next += n_sl;
   }
-  if (lane == 0 && n_surv) stat_add(A.counters, 1, n_surv);
+  if (lane == 0 && n_surv) stat_add(A.counters, ST_SAMPLES, n_surv);
   __syncthreads();
   if (tid == 0) {
     hdr[0] = s_misc[18] ? 0 : s_misc[16];
@@ -511,7 +512,7 @@ __global__ void __launch_bounds__(CUR_THREADS, 4) weights_kernel(SplitArgs S) {
     hdr[7] = s_misc[18];            // 1 = capacity overflow: the monolithic kernel recomputes this pair
     int r = min(s_misc[19], RUNS_MAX);
     hdr[8 + r] = s_misc[16];
-    if (s_misc[18]) stat_add(A.counters, 6, 1ull);
+    if (s_misc[18]) stat_add(A.counters, ST_FALLBACK, 1ull);
   }
 }
 
@@ -682,7 +683,7 @@ __global__ void __launch_bounds__(CUR_THREADS, (M == 1 ? 4 : 3)) mac_kernel(Spli
   }
   for (int it = tid; it < A.T; it += CUR_THREADS)
     if (it < it_w0 || it >= it_w1) out[it] = 0.f;
-  if (lane == 0 && n_blocks) stat_add(A.counters, 5, n_blocks * 64ull * 64ull);
+  if (lane == 0 && n_blocks) stat_add(A.counters, ST_DFMA, n_blocks * 64ull * 64ull);
 }
 
 // =============================================================================================================
@@ -710,17 +711,15 @@ static SplitArgs split_args(const CurArgs& args, void* items, void* hdr, void* c
   return S;
 }
 
-extern "C++" int mac_shift_launch(ldsim_ctx* ctx, SplitArgs S, int M);
-
 // returns 0 = launched, 1 = not covered by the split path, < 0 = error
-extern "C++" int split_launch_weights(ldsim_ctx* ctx, const CurArgs& args, void* items, void* hdr, void* corr, double* wbuf,
+int split_launch_weights(ldsim_ctx* ctx, const CurArgs& args, void* items, void* hdr, void* corr, double* wbuf,
                                       unsigned long long wbuf_cap, unsigned long long* cursor) {
   if (args.n_pairs == 0) return 0;
   const int M = split_M(ctx, args);
   if (!M) return 1;
   SplitArgs S = split_args(args, items, hdr, corr, wbuf, wbuf_cap, cursor);
   if (ctx->weights_mode) {
-    int rc = ldsim_ensure(ctx, SB_PPAR, qpair_params_bytes(args.n_pairs));
+    int rc = ctx->scratch[SB_PPAR].ensure(qpair_params_bytes(args.n_pairs));
     if (rc) return rc;
     return qweights_launch(ctx, S, M, ctx->scratch[SB_PPAR].p);
   }
@@ -730,7 +729,7 @@ extern "C++" int split_launch_weights(ldsim_ctx* ctx, const CurArgs& args, void*
   return 0;
 }
 
-extern "C++" int split_launch_mac(ldsim_ctx* ctx, const CurArgs& args, void* items, void* hdr, void* corr, double* wbuf,
+int split_launch_mac(ldsim_ctx* ctx, const CurArgs& args, void* items, void* hdr, void* corr, double* wbuf,
                                   unsigned long long wbuf_cap, unsigned long long* cursor) {
   if (args.n_pairs == 0) return 0;
   const int M = split_M(ctx, args);
@@ -744,7 +743,7 @@ extern "C++" int split_launch_mac(ldsim_ctx* ctx, const CurArgs& args, void* ite
 }
 
 // per-pair record sizes of the split path's HBM lists for these constants; returns M (0 = not covered)
-extern "C++" int split_sizes(const ldsim_ctx* ctx, const CurArgs& args, size_t* item_bytes, size_t* hdr_bytes,
+int split_sizes(const ldsim_ctx* ctx, const CurArgs& args, size_t* item_bytes, size_t* hdr_bytes,
                              size_t* corr_bytes) {
   const int M = split_M(ctx, args);
   *item_bytes = sizeof(Item) * (M == 2 ? ItemCap<2>::value : ItemCap<1>::value);

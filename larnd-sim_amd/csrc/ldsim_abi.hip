@@ -10,60 +10,7 @@
 #include <new>
 #include <vector>
 
-#include "ldsim_args.h"
-
-// ---- launchers defined in the kernel translation units ----------------------------------------------------
-struct CurArgs;
-struct FeeArgs;
-int seg_launch_unpack(ldsim_ctx*, const LdsimTrackLayout*, int64_t);
-int seg_launch_repack(ldsim_ctx*, const LdsimTrackLayout*, int64_t);
-int seg_launch_quench_drift(ldsim_ctx*, int, int, int, int*);
-int seg_launch_quench_drift_map(ldsim_ctx*, int, int*);
-int seg_launch_quench_drift_stat(ldsim_ctx*, int, bool, const int32_t*, int32_t, int*);
-int seg_launch_max_pixels(ldsim_ctx*, int64_t, int64_t, int32_t*, unsigned long long*);
-int seg_launch_get_pixels(ldsim_ctx*, int64_t, int64_t, int, int32_t*, int, int32_t*, int32_t*, int, double*, const int32_t*,
-                          int32_t);
-int seg_launch_time_intervals(ldsim_ctx*, int64_t, int64_t, double*, int32_t*);
-int fee_launch_track_pixel_map(ldsim_ctx*, int64_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, int64_t,
-                               int, int, int);
-int fee_launch_sum_pixel_signals(ldsim_ctx*, double*, const float*, const double*, const int64_t*, const int64_t*,
-                                 double*, double*, int64_t, int, int, int, int);
-int fee_launch_adc_dense(ldsim_ctx*, const double*, const double*, int64_t, int, int, const double*, double, double,
-                         const float*, int, int32_t*, double*, double*, double*);
-int rng_ensure_states(ldsim_ctx* ctx, int64_t n);
-int rng_fee_draws_per_pixel(const LdsimConsts& h, int NT);
-int rng_launch_fee_noise(ldsim_ctx* ctx, int64_t U, int nd, float* z);
-int rng_launch_advance(ldsim_ctx* ctx, int64_t U, const int32_t* n_draws);
-int fee_launch_digitize(ldsim_ctx*, const double*, const double*, double*, int64_t);
-int light_launch_incidence(ldsim_ctx*, int64_t, int64_t, int, float*, float*, int32_t*, int);
-int light_launch_t0_range(ldsim_ctx*, const float*, const float*, int64_t, int*);
-int light_launch_sum(ldsim_ctx*, int64_t, int64_t, const int32_t*, const int64_t*, const float*, int, const int32_t*, int,
-                     const int32_t*, double, int64_t, float*, int64_t*, double*, int, int64_t*, const LightAct* = nullptr);
-int light_launch_reset_cells(ldsim_ctx*, int64_t, int64_t, int, float*, int64_t*, double*);
-int light_check_emit_overflow(ldsim_ctx*);
-int sort_make_keys(ldsim_ctx*, const int32_t*, const int32_t*, int64_t, int32_t, int, int64_t, unsigned long long*,
-                   int32_t*, unsigned long long*);
-int sort_pairs(ldsim_ctx*, unsigned long long*, unsigned long long*, int32_t*, int32_t*, int64_t);
-int sort_exclusive_scan_i32(ldsim_ctx*, const int32_t*, int32_t*, int64_t);
-int sort_heads(ldsim_ctx*, const unsigned long long*, int64_t, int32_t*);
-int sort_fill_unique(ldsim_ctx*, const unsigned long long*, const int32_t*, const int32_t*, int64_t, int32_t, int32_t*,
-                     int32_t*, int64_t*, int64_t);
-int sort_batch_first(ldsim_ctx*, int64_t, int64_t, int32_t, int32_t*);
-int sort_compact_hits(ldsim_ctx*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const double*,
-                      const double*, int, int64_t, int32_t*);
-// chain glue implemented in chain.hip (needs the kernel argument structs)
-int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fractions);
-extern "C++" int fee_clear_unwritten_fractions(ldsim_ctx* ctx, int64_t U, const int32_t* hit_count, const int64_t* tpm, double* fr);
-// the dense fractions array of the current output set, complete (entries the FEE kernel did not write: zero)
-static int fractions_complete(ldsim_ctx* ctx) {
-  if (ctx->frac_clean_gen == ctx->out_gen) return 0;
-  int rc = fee_clear_unwritten_fractions(ctx, ctx->chain_U, (const int32_t*)ctx->scratch[SB_PAIRPIX].p,
-                                         (const int64_t*)ctx->scratch[SB_TPM].p, (double*)ctx->scratch[SB_FRAC].p);
-  if (rc) return rc;
-  ctx->frac_clean_gen = ctx->out_gen;
-  return 0;
-}
-int chain_tracks_current(ldsim_ctx* ctx, const int32_t* d_pixels, int P, float* d_signals, int T, int mc);
+#include "launchers.h"
 
 // ---- errors ---------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -440,7 +387,7 @@ static int seg_reserve(ldsim_ctx* ctx, int64_t n) {
   if (n > ctx->seg.cap) {
     int64_t cap = n + n / 8 + 64;
     size_t bytes = (size_t)cap * ((LDSIM_NFIELDS - 1) * sizeof(double) + 2 * sizeof(int32_t));
-    CK(ldsim_ensure_buf(ctx, &ctx->seg_block, bytes));
+    CK(ctx->seg_block.ensure(bytes));
     char* p = (char*)ctx->seg_block.p;
     for (int f = 0; f < LDSIM_NFIELDS - 1; f++) {
       ctx->seg.f[f] = (double*)p;
@@ -484,7 +431,7 @@ static int upload_tracks(ldsim_ctx* ctx, const void* tracks, int64_t n, const Ld
   for (int f = 0; f < LDSIM_NFIELDS; f++) ctx->seg.store_code[f] = lay->offset[f] >= 0 ? lay->dtype[f] : LDSIM_F8;
   if (n == 0) return 0;
   size_t bytes = (size_t)n * lay->itemsize;
-  CK(ldsim_ensure_buf(ctx, &ctx->raw, bytes));
+  CK(ctx->raw.ensure(bytes));
   HIPCHK(hipMemcpyAsync(ctx->raw.p, tracks, bytes, hipMemcpyHostToDevice, ctx->stream));
   CK(seg_launch_unpack(ctx, lay, n));
   if (batch_id)
@@ -602,13 +549,13 @@ static int stat_batch_first(ldsim_ctx* ctx, int32_t* batch0) {
 // map = true (the resident chain while a drift-field map is set): quench_drift_map_kernel, which also writes the anode view;
 // stat = true (the resident chain with charge statistics enabled): quench_drift_stat_kernel, with or without maps
 static int run_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, bool map = false, bool stat = false) {
-  CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
-  int* d_err = (int*)ctx->scratch[SB_MISC].p;
+  CK(ctx->scratch[SB_MISC].ensure(MISC_BYTES));
+  int* d_err = &ctx->scratch[SB_MISC].as<ChainMisc>()->err;
   HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), ctx->stream));
   ctx->drift_map_gen = -1;
   ctx->drift_stat_on = -1;
   if (map && ctx->fmap_view_cap < ctx->seg.cap) {
-    CK(ldsim_ensure_buf(ctx, &ctx->fmap_view, (size_t)ctx->seg.cap * LDSIM_NVIEW * sizeof(double)));
+    CK(ctx->fmap_view.ensure((size_t)ctx->seg.cap * LDSIM_NVIEW * sizeof(double)));
     ctx->fmap_view_cap = ctx->seg.cap;
   }
   if (stat) {
@@ -726,7 +673,7 @@ extern "C" int ldsim_set_field_map(ldsim_ctx* ctx, int32_t tpc, const int64_t sh
   CK(light_join(ctx));
   HIPCHK(hipStreamSynchronize(ctx->stream));     // (a launch in flight may still read the old nodes)
   DevBuf& b = ctx->fmap_nodes[tpc];
-  CK(ldsim_ensure_buf(ctx, &b, (size_t)nn * sizeof(FieldMapNode)));
+  CK(b.ensure((size_t)nn * sizeof(FieldMapNode)));
   HIPCHK(hipMemcpy(b.p, node.data(), (size_t)nn * sizeof(FieldMapNode), hipMemcpyHostToDevice));
   FieldMapDesc& d = ctx->h_fmap[tpc];
   if (!d.node) ctx->n_fmap++;
@@ -798,12 +745,12 @@ extern "C" int ldsim_max_pixels(ldsim_ctx* ctx, const void* tracks, int64_t n, c
   LDSIM_ENTER(ctx);
   NEED(n_max_pixels, "null output");
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
-  CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
-  char* m = (char*)ctx->scratch[SB_MISC].p;
-  HIPCHK(hipMemsetAsync(m, 0, 64, ctx->stream));
-  CK(seg_launch_max_pixels(ctx, 0, n, (int32_t*)(m + 8), (unsigned long long*)(m + 16)));
+  CK(ctx->scratch[SB_MISC].ensure(MISC_BYTES));
+  ChainMisc* m = ctx->scratch[SB_MISC].as<ChainMisc>();
+  HIPCHK(hipMemsetAsync(m, 0, offsetof(ChainMisc, n_compact), ctx->stream));
+  CK(seg_launch_max_pixels(ctx, 0, n, &m->nmax, &m->tran_bits));
   int32_t h = 0;
-  HIPCHK(hipMemcpyAsync(&h, m + 8, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&h, &m->nmax, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (h > *n_max_pixels) *n_max_pixels = h;  // cuda.atomic.max into the caller's array
   return 0;
@@ -816,16 +763,16 @@ extern "C" int ldsim_get_pixels(ldsim_ctx* ctx, const void* tracks, int64_t n, c
   NEED(active && neigh && nrad && max_active >= 0 && P >= 0 && radius >= 0, "bad get_pixels arguments");
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
   size_t ba = (size_t)n * max_active * 4, bn = (size_t)n * P * 4;
-  CK(ldsim_ensure(ctx, SB_ACTIVE, ba));
-  CK(ldsim_ensure(ctx, SB_NEIGH, bn));
-  CK(ldsim_ensure(ctx, SB_NRAD, bn));
-  CK(ldsim_ensure(ctx, SB_NLIST, (size_t)n * 8));
+  CK(ctx->scratch[SB_ACTIVE].ensure(ba));
+  CK(ctx->scratch[SB_NEIGH].ensure(bn));
+  CK(ctx->scratch[SB_NRAD].ensure(bn));
+  CK(ctx->scratch[SB_NLIST].ensure((size_t)n * 8));
   HIPCHK(hipMemsetAsync(ctx->scratch[SB_ACTIVE].p, 0xFF, ba, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->scratch[SB_NEIGH].p, 0xFF, bn, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->scratch[SB_NRAD].p, 0xFF, bn, ctx->stream));
-  CK(seg_launch_get_pixels(ctx, 0, n, radius, (int32_t*)ctx->scratch[SB_ACTIVE].p, max_active,
-                           (int32_t*)ctx->scratch[SB_NEIGH].p, (int32_t*)ctx->scratch[SB_NRAD].p, P,
-                           (double*)ctx->scratch[SB_NLIST].p, nullptr, 0));
+  CK(seg_launch_get_pixels(ctx, 0, n, radius, ctx->scratch[SB_ACTIVE].as<int32_t>(), max_active,
+                           ctx->scratch[SB_NEIGH].as<int32_t>(), ctx->scratch[SB_NRAD].as<int32_t>(), P,
+                           ctx->scratch[SB_NLIST].as<double>(), nullptr, 0));
   if (ba) HIPCHK(hipMemcpyAsync(active, ctx->scratch[SB_ACTIVE].p, ba, hipMemcpyDeviceToHost, ctx->stream));
   if (bn) HIPCHK(hipMemcpyAsync(neigh, ctx->scratch[SB_NEIGH].p, bn, hipMemcpyDeviceToHost, ctx->stream));
   if (bn) HIPCHK(hipMemcpyAsync(nrad, ctx->scratch[SB_NRAD].p, bn, hipMemcpyDeviceToHost, ctx->stream));
@@ -839,14 +786,14 @@ extern "C" int ldsim_time_intervals(ldsim_ctx* ctx, const void* tracks, int64_t 
   LDSIM_ENTER(ctx);
   NEED(track_starts && time_max, "null output");
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
-  CK(ldsim_ensure(ctx, SB_STARTS, (size_t)n * 8 + 8));
-  CK(ldsim_ensure(ctx, SB_MISC, MISC_BYTES));
-  char* m = (char*)ctx->scratch[SB_MISC].p;
-  HIPCHK(hipMemsetAsync(m, 0, 64, ctx->stream));
-  CK(seg_launch_time_intervals(ctx, 0, n, (double*)ctx->scratch[SB_STARTS].p, (int32_t*)(m + 24)));
+  CK(ctx->scratch[SB_STARTS].ensure((size_t)n * 8 + 8));
+  CK(ctx->scratch[SB_MISC].ensure(MISC_BYTES));
+  ChainMisc* m = ctx->scratch[SB_MISC].as<ChainMisc>();
+  HIPCHK(hipMemsetAsync(m, 0, offsetof(ChainMisc, n_compact), ctx->stream));
+  CK(seg_launch_time_intervals(ctx, 0, n, ctx->scratch[SB_STARTS].as<double>(), &m->time_max));
   int32_t h = 0;
   if (n) HIPCHK(hipMemcpyAsync(track_starts, ctx->scratch[SB_STARTS].p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(&h, m + 24, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&h, &m->time_max, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (h > *time_max) *time_max = h;
   return 0;
@@ -864,10 +811,10 @@ static int tracks_current_stage(ldsim_ctx* ctx, const void* tracks, int64_t n, c
   CK(upload_tracks(ctx, tracks, n, layout, nullptr));
   size_t bp = (size_t)n * P * 4, bs = (size_t)n * P * T * 4;
   if (bs == 0) return 0;
-  CK(ldsim_ensure(ctx, SB_NEIGH, bp));
-  CK(ldsim_ensure(ctx, SB_WAVES, bs));
+  CK(ctx->scratch[SB_NEIGH].ensure(bp));
+  CK(ctx->scratch[SB_WAVES].ensure(bs));
   HIPCHK(hipMemcpyAsync(ctx->scratch[SB_NEIGH].p, pixels, bp, hipMemcpyHostToDevice, ctx->stream));
-  CK(chain_tracks_current(ctx, (const int32_t*)ctx->scratch[SB_NEIGH].p, P, (float*)ctx->scratch[SB_WAVES].p, T, mc));
+  CK(chain_tracks_current(ctx, ctx->scratch[SB_NEIGH].as<const int32_t>(), P, ctx->scratch[SB_WAVES].as<float>(), T, mc));
   HIPCHK(hipMemcpyAsync(signals, ctx->scratch[SB_WAVES].p, bs, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -886,7 +833,6 @@ extern "C" int ldsim_tracks_current_stats(ldsim_ctx* ctx, LdsimChainStats* stats
   return 0;
 }
 
-int gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n_out);
 extern "C" int ldsim_debug_gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n) {
   LDSIM_ENTER(ctx);
   NEED(ctx && counts && n >= LDSIM_GFORM_CENSUS_N, "bad gform census arguments");
@@ -1084,9 +1030,9 @@ extern "C" int ldsim_dev_light_incidence(ldsim_ctx* ctx, int32_t n_out) {
   const int64_t n = ctx->seg.n;
   const size_t bc = (size_t)n * n_out * 4;
   const bool trig0 = ctx->h_consts.light_trig_mode == 0;
-  CK(ldsim_ensure_buf(ctx, &ctx->light_nph, bc));
-  if (trig0) CK(ldsim_ensure_buf(ctx, &ctx->light_t0, bc));
-  CK(ldsim_ensure_buf(ctx, &ctx->light_vox, (size_t)n * 12));
+  CK(ctx->light_nph.ensure(bc));
+  if (trig0) CK(ctx->light_t0.ensure(bc));
+  CK(ctx->light_vox.ensure((size_t)n * 12));
   HIPCHK(hipEventRecord(ctx->evl[0], ctx->stream));
   CK(light_launch_incidence(ctx, 0, n, n_out, (float*)ctx->light_nph.p, (float*)ctx->light_t0.p, (int32_t*)ctx->light_vox.p,
                             1));
@@ -1137,7 +1083,7 @@ extern "C" int ldsim_dev_light_t0_range(ldsim_ctx* ctx, int64_t seg_begin, int64
   NEED_LIGHT_INC(ctx);
   NEED(seg_begin >= 0 && seg_end >= seg_begin && seg_end <= ctx->seg.n, "segment range outside the resident store");
   NEED(ctx->h_consts.light_trig_mode == 0, "t0_det is only computed in trigger mode 0");
-  CK(ldsim_ensure_buf(ctx, &ctx->light_tmp[0], 64));
+  CK(ctx->light_tmp[0].ensure(64));
   const int64_t total = (seg_end - seg_begin) * ctx->light_n_out;
   const size_t off = (size_t)seg_begin * ctx->light_n_out;
   CK(light_launch_t0_range(ctx, (const float*)ctx->light_nph.p + off, (const float*)ctx->light_t0.p + off, total,
@@ -1218,10 +1164,10 @@ extern "C" int ldsim_dev_sum_light(ldsim_ctx* ctx, int64_t seg_begin, int64_t se
   StreamScope scope{ctx, ctx->stream, on_light};
   if (on_light) ctx->stream = ctx->light_stream;
   hipStream_t st = ctx->stream;
-  CK(ldsim_ensure_buf(ctx, &ctx->light_out, bo * 4 + 16));
+  CK(ctx->light_out.ensure(bo * 4 + 16));
   if (!same_opc) {
     ctx->h_opc.clear();
-    CK(ldsim_ensure_buf(ctx, &ctx->light_opc, (size_t)n_det * 4));
+    CK(ctx->light_opc.ensure((size_t)n_det * 4));
     HIPCHK(hipMemcpyAsync(ctx->light_opc.p, op_channel, (size_t)n_det * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));              // (pageable source: the copy must have left it before the call returns)
     try {
@@ -1233,9 +1179,9 @@ extern "C" int ldsim_dev_sum_light(ldsim_ctx* ctx, int64_t seg_begin, int64_t se
   }
   HIPCHK(hipEventRecord(ctx->evl[2], st));
   if (max_truth) {
-    CK(ldsim_ensure_buf(ctx, &ctx->light_tid, bo * max_truth * 8 + 16));
-    CK(ldsim_ensure_buf(ctx, &ctx->light_tph, bo * max_truth * 8 + 16));
-    CK(ldsim_ensure_buf(ctx, &ctx->light_trk, (size_t)(n > 0 ? n : 1) * 8));
+    CK(ctx->light_tid.ensure(bo * max_truth * 8 + 16));
+    CK(ctx->light_tph.ensure(bo * max_truth * 8 + 16));
+    CK(ctx->light_trk.ensure((size_t)(n > 0 ? n : 1) * 8));
   }
   // The arrays start at 0 / -1.  After a truth-slot sum they differ from that only in the cells its records fell into (their sorted
   // keys are still in light_tmp[4]): when the same buffers are large enough for this batch those cells are reset instead of clearing
@@ -1257,7 +1203,7 @@ extern "C" int ldsim_dev_sum_light(ldsim_ctx* ctx, int64_t seg_begin, int64_t se
       ctx->light_nt_ndet_cap = ctx->light_nt_list_cap = 0;
       ctx->light_nt_valid = 0;
       ctx->light_act.reset();
-      CK(ldsim_ensure_buf(ctx, &ctx->light_act, 2 * half));
+      CK(ctx->light_act.ensure(2 * half));
       ctx->light_nt_ndet_cap = cap_det;
       ctx->light_nt_list_cap = cap_list;
       act_fresh = true;
@@ -1367,10 +1313,6 @@ extern "C" int ldsim_light_kernel_ms(ldsim_ctx* ctx, double* incidence_ms, doubl
 }
 
 // ---- light waveform response: weight tables on the host, with the reference's expressions -----------------------------
-int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid, const double* tph, int D,
-                          int T, int Mt, const double* weights, int C, const double* gain, float* out, int64_t* out_tid,
-                          double* out_tph);
-
 static int64_t conv_ticks(const LdsimConsts& h) {   // light_sim.py:160 / :315
   return (int64_t)ceil((h.light_window[1] - h.light_window[0]) / h.light_tick_size);
 }
@@ -1479,7 +1421,6 @@ extern "C" int ldsim_light_detector_response(ldsim_ctx* ctx, const float* light_
 
 // light_sim.calc_scintillation_effect -> calc_stat_fluctuations -> calc_light_detector_response on the resident photon sum
 // (cli/simulate_pixels.py:1159-1180), everything staying in HBM
-int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick);      // light_wvfm.hip
 
 extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain, const double* impulse_model,
                                         int32_t n_impulse, int32_t fluctuate) {
@@ -1503,22 +1444,22 @@ extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain
     w1[(size_t)n] = sipm_response_model(n, impulse_model, n_impulse, h);
   }
   hipStream_t st = ctx->stream;
-  CK(ldsim_ensure_buf(ctx, &ctx->light_w[0], w0.size() * 8));
-  CK(ldsim_ensure_buf(ctx, &ctx->light_w[1], w1.size() * 8));
-  CK(ldsim_ensure_buf(ctx, &ctx->light_gain, (size_t)D * 8));
-  CK(ldsim_ensure_buf(ctx, &ctx->light_scint, bo * 4 + 16));
-  CK(ldsim_ensure_buf(ctx, &ctx->light_disc, bo * 4 + 16));
-  CK(ldsim_ensure_buf(ctx, &ctx->light_resp, bo * 4 + 16));
+  CK(ctx->light_w[0].ensure(w0.size() * 8));
+  CK(ctx->light_w[1].ensure(w1.size() * 8));
+  CK(ctx->light_gain.ensure((size_t)D * 8));
+  CK(ctx->light_scint.ensure(bo * 4 + 16));
+  CK(ctx->light_disc.ensure(bo * 4 + 16));
+  CK(ctx->light_resp.ensure(bo * 4 + 16));
   HIPCHK(hipMemcpyAsync(ctx->light_w[0].p, w0.data(), w0.size() * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ctx->light_w[1].p, w1.data(), w1.size() * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(ctx->light_gain.p, light_gain, (size_t)D * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(ctx->light_scint.p, 0, bo * 4, st));
   HIPCHK(hipMemsetAsync(ctx->light_resp.p, 0, bo * 4, st));
   if (Mt) {
-    CK(ldsim_ensure_buf(ctx, &ctx->light_scint_tid, bt * 8 + 16));
-    CK(ldsim_ensure_buf(ctx, &ctx->light_scint_tph, bt * 8 + 16));
-    CK(ldsim_ensure_buf(ctx, &ctx->light_resp_tid, bt * 8 + 16));
-    CK(ldsim_ensure_buf(ctx, &ctx->light_resp_tph, bt * 8 + 16));
+    CK(ctx->light_scint_tid.ensure(bt * 8 + 16));
+    CK(ctx->light_scint_tph.ensure(bt * 8 + 16));
+    CK(ctx->light_resp_tid.ensure(bt * 8 + 16));
+    CK(ctx->light_resp_tph.ensure(bt * 8 + 16));
     HIPCHK(hipMemsetAsync(ctx->light_scint_tid.p, 0xFF, bt * 8, st));
     HIPCHK(hipMemsetAsync(ctx->light_scint_tph.p, 0, bt * 8, st));
     HIPCHK(hipMemsetAsync(ctx->light_resp_tid.p, 0xFF, bt * 8, st));
@@ -1620,22 +1561,32 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
   return rc;
 }
 
+// the dense fractions array of the current output set, complete (entries the FEE kernel did not write: zero)
+static int fractions_complete(ldsim_ctx* ctx) {
+  if (ctx->frac_clean_gen == ctx->out_gen) return 0;
+  const ChainView v = chain_view(ctx);
+  CK(fee_clear_unwritten_fractions(ctx, v.U, v.hit_count, v.tpm, v.frac));
+  ctx->frac_clean_gen = ctx->out_gen;
+  return 0;
+}
+
 // the per-pixel arrays of the last chain launch to the host on `st` (asynchronous; fractions made complete first)
 static int chain_copy_out(ldsim_ctx* ctx, hipStream_t st, int32_t* unique_pix, int32_t* batch, double* adc_list,
                           double* adc_ticks, double* adc_digit, int64_t* tpm, double* fractions) {
-  const int64_t U = ctx->chain_U;
-  const int A = ctx->h_consts.max_adc_values, M = ctx->h_consts.max_tracks_per_pixel;
-  if (unique_pix) HIPCHK(hipMemcpyAsync(unique_pix, ctx->scratch[SB_UPIX].p, U * 4, hipMemcpyDeviceToHost, st));
-  if (batch) HIPCHK(hipMemcpyAsync(batch, ctx->scratch[SB_UBATCH].p, U * 4, hipMemcpyDeviceToHost, st));
-  if (adc_list) HIPCHK(hipMemcpyAsync(adc_list, ctx->scratch[SB_ADC].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
-  if (adc_ticks) HIPCHK(hipMemcpyAsync(adc_ticks, ctx->scratch[SB_TICKS].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
-  if (adc_digit) HIPCHK(hipMemcpyAsync(adc_digit, ctx->scratch[SB_DIGIT].p, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
-  if (tpm) HIPCHK(hipMemcpyAsync(tpm, ctx->scratch[SB_TPM].p, (size_t)U * M * 8, hipMemcpyDeviceToHost, st));
+  const ChainView v = chain_view(ctx);
+  const int64_t U = v.U;
+  const int A = v.A, M = v.M;
+  if (unique_pix) HIPCHK(hipMemcpyAsync(unique_pix, v.upix, U * 4, hipMemcpyDeviceToHost, st));
+  if (batch) HIPCHK(hipMemcpyAsync(batch, v.ubatch, U * 4, hipMemcpyDeviceToHost, st));
+  if (adc_list) HIPCHK(hipMemcpyAsync(adc_list, v.adc, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
+  if (adc_ticks) HIPCHK(hipMemcpyAsync(adc_ticks, v.ticks, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
+  if (adc_digit) HIPCHK(hipMemcpyAsync(adc_digit, v.digit, (size_t)U * A * 8, hipMemcpyDeviceToHost, st));
+  if (tpm) HIPCHK(hipMemcpyAsync(tpm, v.tpm, (size_t)U * M * 8, hipMemcpyDeviceToHost, st));
   if (fractions) {
     CK(fractions_complete(ctx));
     // (completed on the compute stream: drained before another stream reads the rows)
     if (st != ctx->stream) HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpyAsync(fractions, ctx->scratch[SB_FRAC].p, (size_t)U * A * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fractions, v.frac, (size_t)U * A * M * 8, hipMemcpyDeviceToHost, st));
   }
   return 0;
 }
@@ -1701,8 +1652,9 @@ extern "C" int ldsim_chain_download_wait(ldsim_ctx* ctx) {
 extern "C" int ldsim_chain_compact_hits(ldsim_ctx* ctx, void** dev_rows, int64_t* n_rows, int32_t* row_bytes) {
   LDSIM_ENTER(ctx);
   NEED(ctx && dev_rows && n_rows && row_bytes, "null argument");
-  *dev_rows = ctx->scratch[SB_HITS].p;
-  *n_rows = ctx->chain_hits;
+  const ChainView v = chain_view(ctx);
+  *dev_rows = v.hits;
+  *n_rows = v.n_hits;
   *row_bytes = 24;
   return 0;
 }

@@ -293,7 +293,7 @@ struct ldsim_ctx {
   int gform_wave_tables = 1;                 // 1: gtables_wave_kernel (a wave per pair) for the pairs that fit it, 0: gtables_kernel for all
   int debug_gform = 0;                       // timing tools: parts of gtables_kernel / gcorr_kernel switched off (tools/gform_phases.py)
   // what gform_launch decided for the last current stage (ldsim_debug_gform_census counts the pairs from it); valid = 0 once
-  // another current path ran: its GInfo array (SB_HDR) and flags (SB_ITEMS) are that path's then
+  // another current path ran: its GInfo array (SB_GINFO) and flags (SB_GFLAGS) are that path's then
   struct GformRecord {
     int valid = 0, M = 0, TT = 0, b0 = 0, b1 = 0, b2 = 0, Mz = 0, qb[3] = {0, 0, 0}, wave_tables = 1;
     int64_t n = 0;
@@ -408,8 +408,8 @@ struct ldsim_ctx {
   int64_t cpt_gen = -1;              // chain launch it was built for
   int want_fractions = 0;
   // pixel charge truth (ldsim_chain_pixel_truth, kernels_pixtruth.hip) reads what the last chain launch left in the scratch
-  // buffers: the current rows (SB_WAVES), the FEE set-up record (SB_SPAN headers, SB_FEESLOT slot rows), SB_UPIX, SB_UBATCH,
-  // SB_ADC, SB_TPM and the hit counts (SB_PAIRPIX).  launch_stale = nullptr while all of them are that launch's: set by a
+  // buffers, through chain_view: the current rows, the FEE set-up record (headers, slot rows), upix, ubatch, adc, tpm and the
+  // hit counts.  launch_stale = nullptr while all of them are that launch's: set by a
   // successful ldsim_charge_chain, and named again (launch_invalidate) by every entry point that may rewrite or regrow one
   const char* launch_stale = "no ldsim_charge_chain has run on this context";
   struct FeeRecord {             // the set-up record fee_launch_chain left (fee_record.h) and the sizes the launch ran with
@@ -429,11 +429,27 @@ struct ldsim_ctx {
   double ms_weights = 0, ms_mac = 0, ms_fallback = 0;   // split path: per-kernel share of ms_current
 };
 
-// scratch slots
+// scratch slots, named for what they hold.  A slot shared by two paths that never run in the same stage carries both names
+// (one index, one buffer); the layouts inside a slot are in ldsim_args.h (ChainMisc, batch_block, hit_counts) and
+// fee_record.h (fee_hdr_view), and chain_view (ldsim_args.h) gives what a chain launch left as typed pointers.
 enum {
-  SB_ACTIVE = 0, SB_NEIGH, SB_NRAD, SB_NLIST, SB_STARTS, SB_MISC, SB_KEYS, SB_KEYS2, SB_VALS, SB_VALS2,
-  SB_SORTTMP, SB_PAIRSEG, SB_PAIRPIX, SB_HEADS, SB_UOFF, SB_UPIX, SB_UBATCH, SB_WAVES, SB_ADC, SB_TICKS,
-  SB_DIGIT, SB_TPM, SB_FRAC, SB_HITS, SB_ITEMS, SB_HDR, SB_CORR, SB_WBUF, SB_NOISE, SB_NDRAWS, SB_PPAR, SB_CPT, SB_CPO, SB_WIN, SB_SPAN, SB_GMAPS, SB_FEESLOT
+  SB_ACTIVE = 0, SB_NEIGH, SB_NRAD,
+  SB_NLIST, SB_BATCH = SB_NLIST,     // get_pixels stage call: n_list f64 [n] | chain: the per-batch block (batch_block)
+  SB_STARTS, SB_MISC, SB_KEYS, SB_KEYS2, SB_VALS, SB_VALS2, SB_SORTTMP,
+  SB_PIXOFF,                         // uoff i64 [U + 1]: a unique pixel's first pair in the sorted list
+  SB_HITCNT,                         // hit_count i32 [U] | hit_off i32 [U] (hit_counts)
+  SB_HEADS,
+  SB_UIDX,                           // exclusive scan of the heads: a pair's unique-pixel index
+  SB_UPIX, SB_UBATCH, SB_WAVES, SB_ADC, SB_TICKS, SB_DIGIT, SB_TPM, SB_FRAC, SB_HITS,
+  // shifted-window split path | node-separable form (gform_launch):
+  SB_ITEMS, SB_GFLAGS = SB_ITEMS,    //   items                | fallback flags i32 [n]
+  SB_HDR, SB_GINFO = SB_HDR,         //   pair headers         | GInfo [n]
+  SB_CORR, SB_GSIZES = SB_CORR,      //   corrections          | record sizes, offsets, class counts and lists
+  SB_WBUF, SB_GREC = SB_WBUF,        //   weight pool          | table records
+  SB_NOISE, SB_NDRAWS, SB_PPAR, SB_CPT, SB_CPO, SB_WIN,
+  SB_FEEHDR,                         // FEE set-up record: headers (fee_hdr_view)
+  SB_GMAPS,
+  SB_FEESLOT                         // FEE set-up record: slot rows, indexed like the sorted pair list
 };
 
 // the segment store the charge kernels read: after a mapped quench_drift its nine position columns are the anode view
@@ -445,8 +461,6 @@ static inline SegStore charge_store(const ldsim_ctx* ctx) {
 }
 // the scratch buffers no longer hold (or may no longer hold) the last chain launch: `by` names the call, for the refusal
 static inline void launch_invalidate(ldsim_ctx* ctx, const char* by) { ctx->launch_stale = by; }
-static inline int ldsim_ensure_buf(ldsim_ctx*, DevBuf* b, size_t bytes) { return b->ensure(bytes); }
-static inline int ldsim_ensure(ldsim_ctx* ctx, int slot, size_t bytes) { return ctx->scratch[slot].ensure(bytes); }
 // refusal of a host-array stage call that draws random numbers while the ctx is in keyed mode (its rows have no identity)
 #define LDSIM_KEYED_STAGE_MSG \
   "%s draws random numbers, but the context is in keyed mode and this stage call carries no identity for its rows: " \

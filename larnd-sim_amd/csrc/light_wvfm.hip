@@ -15,10 +15,8 @@
 #include <cmath>
 #include <vector>
 
-#include "ldsim_dev.h"
+#include "launchers.h"
 #include "rng.h"
-
-extern "C++" int rng_ensure_states(ldsim_ctx* ctx, int64_t n);      // kernels_rng.hip
 
 // ---- calc_stat_fluctuations ----------------------------------------------------------------------------------------------
 // xoroshiro128p_poisson_int32 (:186-216): inversion with one float32 uniform below a mean of 30, else a normal truncated at 0
@@ -80,7 +78,7 @@ __global__ void __launch_bounds__(256) light_stat_fluct_keyed_kernel(const float
   }
 }
 
-extern "C++" int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick) {
+int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick) {
   if (n == 0) return 0;
   if (ctx->rng_keyed) {
     hipLaunchKernelGGL(light_stat_fluct_keyed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, inc, out,

@@ -20,10 +20,8 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/ldsim.h"
 #include "hostpool.h"
-
-void ldsim_set_error(const char* fmt, ...);
+#include "ldsim_dev.h"
 
 #pragma pack(push, 1)
 struct PacketRow {       // larpix.format.hdf5format 2.4, dataset 'packets' (numpy packed layout, larndsim_amd/packets.py packets_dtype)

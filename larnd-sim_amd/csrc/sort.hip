@@ -6,7 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "ldsim_dev.h"
+#include "launchers.h"
 #include "wave_ops.h"
 
 // key = batch(24) | pixel(32) | ringcode(4, 15 = invalid) ; invalid pairs get ~0 and sort last
@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(256) make_keys_kernel(const int32_t* __restric
   __syncthreads();
   if (threadIdx.x == 0) {
     const int c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    if (c) atomicAdd(&counters[4], (unsigned long long)c);
+    if (c) atomicAdd(&counters[ST_VALID_PAIRS], (unsigned long long)c);
   }
 }
 
@@ -130,7 +130,6 @@ __global__ void compact_hits_kernel(const int32_t* __restrict__ upix, const int3
   }
 }
 
-extern "C++" {
 static inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
 int sort_make_keys(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
@@ -148,7 +147,7 @@ int sort_pairs(ldsim_ctx* ctx, unsigned long long* keys_in, unsigned long long* 
   if (n == 0) return 0;
   size_t tmp = 0;
   HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, 64, ctx->stream));
-  int rc = ldsim_ensure(ctx, SB_SORTTMP, tmp);
+  int rc = ctx->scratch[SB_SORTTMP].ensure(tmp);
   if (rc) return rc;
   HIPCHK(rocprim::radix_sort_pairs(ctx->scratch[SB_SORTTMP].p, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0,
                                    64, ctx->stream));
@@ -175,7 +174,7 @@ int sort_compact_valid(ldsim_ctx* ctx, const unsigned long long* keys_in, int64_
   size_t t1 = 0, t2 = 0;
   HIPCHK(rocprim::select(nullptr, t1, keys_in, keys_out, d_count, (size_t)n, KeyValid(), ctx->stream));
   HIPCHK(rocprim::select(nullptr, t2, idx, flags, vals_out, d_count, (size_t)n, ctx->stream));
-  int rc = ldsim_ensure(ctx, SB_SORTTMP, t1 > t2 ? t1 : t2);
+  int rc = ctx->scratch[SB_SORTTMP].ensure(t1 > t2 ? t1 : t2);
   if (rc) return rc;
   t1 = t2 = ctx->scratch[SB_SORTTMP].bytes;
   HIPCHK(rocprim::select(ctx->scratch[SB_SORTTMP].p, t1, keys_in, keys_out, d_count, (size_t)n, KeyValid(), ctx->stream));
@@ -190,7 +189,7 @@ int sort_pairs_bits(ldsim_ctx* ctx, unsigned long long* keys_in, unsigned long l
   if (end_bit > 64) end_bit = 64;
   size_t tmp = 0;
   HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, begin_bit, end_bit, ctx->stream));
-  int rc = ldsim_ensure(ctx, SB_SORTTMP, tmp);
+  int rc = ctx->scratch[SB_SORTTMP].ensure(tmp);
   if (rc) return rc;
   HIPCHK(rocprim::radix_sort_pairs(ctx->scratch[SB_SORTTMP].p, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, begin_bit,
                                    end_bit, ctx->stream));
@@ -204,7 +203,7 @@ int sort_pairs_u32_u64(ldsim_ctx* ctx, unsigned* keys_in, unsigned* keys_out, un
   if (bits > 32) bits = 32;
   size_t tmp = 0;
   HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, bits, ctx->stream));
-  int rc = ldsim_ensure(ctx, SB_SORTTMP, tmp);
+  int rc = ctx->scratch[SB_SORTTMP].ensure(tmp);
   if (rc) return rc;
   HIPCHK(rocprim::radix_sort_pairs(ctx->scratch[SB_SORTTMP].p, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, bits,
                                    ctx->stream));
@@ -215,7 +214,7 @@ int sort_exclusive_scan_i32(ldsim_ctx* ctx, const int32_t* in, int32_t* out, int
   if (n == 0) return 0;
   size_t tmp = 0;
   HIPCHK(rocprim::exclusive_scan(nullptr, tmp, in, out, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), ctx->stream));
-  int rc = ldsim_ensure(ctx, SB_SORTTMP, tmp);
+  int rc = ctx->scratch[SB_SORTTMP].ensure(tmp);
   if (rc) return rc;
   HIPCHK(rocprim::exclusive_scan(ctx->scratch[SB_SORTTMP].p, tmp, in, out, (int32_t)0, (size_t)n,
                                  rocprim::plus<int32_t>(), ctx->stream));
@@ -226,7 +225,7 @@ int sort_exclusive_scan_u64(ldsim_ctx* ctx, const unsigned long long* in, unsign
   if (n == 0) return 0;
   size_t tmp = 0;
   HIPCHK(rocprim::exclusive_scan(nullptr, tmp, in, out, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), ctx->stream));
-  int rc = ldsim_ensure(ctx, SB_SORTTMP, tmp);
+  int rc = ctx->scratch[SB_SORTTMP].ensure(tmp);
   if (rc) return rc;
   HIPCHK(rocprim::exclusive_scan(ctx->scratch[SB_SORTTMP].p, tmp, in, out, 0ull, (size_t)n,
                                  rocprim::plus<unsigned long long>(), ctx->stream));
@@ -272,5 +271,4 @@ int sort_compact_hits(ldsim_ctx* ctx, const int32_t* upix, const int32_t* ubatch
                      hit_off, digit, ticks, A, U, rows);
   HIPCHK(hipGetLastError());
   return 0;
-}
 }
