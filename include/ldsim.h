@@ -159,6 +159,14 @@ int ldsim_set_light_lut(ldsim_ctx* ctx, const float* vis, const float* t0, const
  * "mac_mode" (split path, correlation stage: 1 = mac_shift_kernel / mac_shift2_kernel (default), 0 = mac_kernel<M>, rows
  * staged in LDS; bit-identical results), "light_incidence_scalar" (1 = calculate_light_incidence with one channel per lane
  * instead of four (the form used when n_out or the LUT's detector count is not a multiple of 4); identical bits; default 0),
+ * "light_lut_interp" (ldsim_light_incidence / ldsim_dev_light_incidence: 0 (default) = the visibility of the LUT voxel that holds
+ * the segment, like the reference; 1 = interpolated trilinearly between the eight voxel centres around it -- per axis, with f the
+ * voxel coordinate lightLUT.get_voxel forms before it truncates, u = f - 0.5, i0 = floor(u), corners clamp(i0) and clamp(i0 + 1) to
+ * [0, n - 1] with weights 1 - (u - i0) and u - i0 (beyond the outermost centres both are the same voxel: constant, no
+ * extrapolation), corner c = 4 dx + 2 dy + dz weighing (wx[dx] * wy[dy]) * wz[dz], n_photons_det from the f64 sum over the
+ * corners in that order; t0_det from the weight-renormalised mean of t0 over the corners with visibility > 0, the nearest
+ * voxel's t0 when none is lit; `voxel` stays the nearest voxel, so the photon sum's time profile is not interpolated; numpy
+ * twin: larndsim_amd/lightLUT.py interpolated_light_incidence; another value returns LDSIM_EINVAL),
  * "light_sum_no_list" (1 = ldsim_dev_sum_light without truth slots launches a workgroup per (detector, tick tile) and clears
  * the whole array first, instead of summing over the device-built list of the lit tiles; same cells, values to the order of
  * the f64 additions; default 0), "light_sum_async" (1 = the ldsim_dev_sum_light calls without truth slots launch on a stream of the

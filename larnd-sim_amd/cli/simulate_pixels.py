@@ -89,10 +89,16 @@ def _parser():
     ap.add_argument("--pixel_truth_min_charge", type=float, default=None,
                     help="under --pixel_truth: pixels without a hit are stored when they saw at least this much |charge| "
                          "[electrons] (default 0: every pixel a segment reached)")
+    ap.add_argument("--light_lut_interpolation", default="nearest", choices=list(LIGHT_LUT_INTERPOLATION),
+                    help="visibility of a segment from the light LUT: nearest (default; the voxel that holds the segment, like "
+                         "the reference) or trilinear (interpolated between the eight voxel centres around it: no step in the "
+                         "light yield at voxel faces; the time profile still comes from the nearest voxel)")
     ap.add_argument("--chunk_segments", type=int, default=50000,
                     help="segments per chain launch (whole batches, at least this many; default 50000)")
     return ap
 
+
+LIGHT_LUT_INTERPOLATION = {"nearest": 0, "trilinear": 1}          # --light_lut_interpolation -> context option light_lut_interp
 
 CHARGE_STATISTICS_NEEDS_KEYED = ("--charge_statistics draws from keyed random streams (one per segment, whatever the "
                                  "chunking or rank count): give --rng keyed as well")
@@ -357,7 +363,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    tracks_current_mc=False, chunk_segments=50000, raw_arrays=False, overlap_downloads=None,
                    pixel_layout_id=None, response_id=None, light_lut_id=None, pixel_thresholds_id=None, pixel_gains_id=None,
                    numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
-                   fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, **ignored):
+                   fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, light_lut_interpolation="nearest", **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -369,6 +375,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         raise ValueError("--pixel_truth is not available with --n_gpus > 1: its rows are not gathered over the ranks")
     if pixel_truth_min_charge is not None and not pixel_truth:
         raise ValueError("--pixel_truth_min_charge sets the selection of --pixel_truth: give --pixel_truth as well")
+    if light_lut_interpolation not in LIGHT_LUT_INTERPOLATION:
+        raise ValueError(f"--light_lut_interpolation must be nearest or trilinear, not {light_lut_interpolation!r}")
     if not os.path.exists(input_filename):
         raise Exception(f"Input file {input_filename} does not exist.")
     if rank == 0 and os.path.exists(output_filename):             # (only rank 0 writes)
@@ -507,7 +515,11 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     truth_min = None if not pixel_truth else float(pixel_truth_min_charge or 0.0)
     if pixel_truth:                     # (without the flag the header, like the file, is what it was)
         print("Pixel charge truth:", f"on (--pixel_truth, --pixel_truth_min_charge {truth_min:g} e)")
+    print("Light LUT interpolation:", light_lut_interpolation if light_lut_interpolation == "nearest"
+          else f"{light_lut_interpolation} (--light_lut_interpolation {light_lut_interpolation})")
     lib.set_option("numba_f32", f32_mode)
+    # once for the process-wide ctx: holds through the module loop and on every rank (each rank runs this function)
+    lib.set_option("light_lut_interp", LIGHT_LUT_INTERPOLATION[light_lut_interpolation])
     dist = None
     if world is not None:
         from larndsim_amd import comm as lcomm
@@ -598,6 +610,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     finally:
         lib.set_option("mc_current", 0)
         lib.set_option("numba_f32", 0)
+        lib.set_option("light_lut_interp", 0)
         if charge_statistics:                                       # (the ctx is process-wide: leave it as it was found)
             lib.check(lib.load().ldsim_set_charge_statistics(lib.context(refresh_consts=False), 0, 0))
     print(f"simulated {totals['n_segments']} segments in {totals['n_batches']} batches -> {totals['n_hits']} hits, "
@@ -1021,6 +1034,8 @@ def main(argv=None):
         print(f"rehearsal: rank {rank} of {world} started (pid {os.getpid()})", flush=True)
         if a["field_map"] is not None:
             print(f"rehearsal: rank {rank} field_map {a['field_map']}", flush=True)
+        if a["light_lut_interpolation"] != "nearest":
+            print(f"rehearsal: rank {rank} light_lut_interpolation {a['light_lut_interpolation']}", flush=True)
         if os.environ.get("LDSIM_CLI_REHEARSAL_FAIL_RANK") == str(rank):
             raise SystemExit(f"rank {rank}: asked to fail (test of the launcher's error path)")
         got = lcomm.exchange_id(bytes(range(128)) if rank == 0 else b"", rank, world, timeout=120.0)

@@ -194,6 +194,239 @@ __global__ void __launch_bounds__(256) light_incidence4_kernel(SegStore s, const
   }
 }
 
+// ---- option light_lut_interp: trilinear visibility between voxel centres --------------------------------------
+// The same stage with the visibility interpolated between the eight voxel centres around the segment instead of taken from the
+// voxel that holds it.  The fractions are get_voxel's before it truncates; per axis u = f - 0.5, i0 = floor(u), the corners
+// clamp(i0) and clamp(i0 + 1) with weights 1 - (u - i0) and u - i0: beyond the outermost centres both corners are the same
+// voxel (constant field, no read outside the table), and an axis of one voxel works by the same rule.  Corner c = 4 dx + 2 dy +
+// dz carries (wx[dx] * wy[dy]) * wz[dz]; the sums run in corner order in f64 (the library is built with -ffp-contract=off: no
+// fused multiply-adds), so both kernel forms and the numpy twin (larndsim_amd/lightLUT.py: interpolated_light_incidence) round alike.
+// t0: a corner without visibility has no arrival time; the mean is taken over the lit corners, renormalised by their weights,
+// and falls back to the nearest voxel's entry when none is lit.  `voxel` stays the nearest voxel (the photon sum takes the time
+// profile from it: the profile's shape is not interpolated).
+// One thread per segment writes the corners' row offsets (int64, like s_vb) and weights to LDS: 32 x 8 x (8 + 8) bytes = 4 KB a
+// tile; every lane then reads a segment's 16 values as broadcasts (one address per wave: no bank conflict).
+__device__ __forceinline__ void li_axis(double f, int n, int& lo, int& hi, double& w0, double& w1) {
+  const double u = f - 0.5, i0 = floor(u);
+  w1 = u - i0;
+  w0 = 1.0 - w1;
+  lo = (int)fmin(fmax(i0, 0.0), (double)(n - 1));          // clamped as doubles: a far-away position cannot overflow the int
+  hi = (int)fmin(fmax(i0 + 1.0, 0.0), (double)(n - 1));
+}
+__device__ __forceinline__ void li_corners(const LdsimConsts* c, double x, double y, double z, int itpc, int nx, int ny, int nz,
+                                           int ndet, int64_t* cb, double* w) {
+  const double(*b)[2] = c->tpc_borders[itpc];
+  const bool is_even = b[2][1] > b[2][0];
+  const double x_min = b[0][0] - 2e-2, x_max = b[0][1] + 2e-2, y_min = b[1][0] - 2e-2, y_max = b[1][1] + 2e-2;
+  const double z_min = b[2][0] - 2e-2, z_max = b[2][1] + 2e-2;
+  const double fx = is_even ? (x - x_min) / (x_max - x_min) * nx : (x_max - x) / (x_max - x_min) * nx;
+  const double fy = (y_max - y) / (y_max - y_min) * ny;
+  const double fz = (z - z_min) / (z_max - z_min) * nz;
+  int ix[2], iy[2], iz[2];
+  double wx[2], wy[2], wz[2];
+  li_axis(fx, nx, ix[0], ix[1], wx[0], wx[1]);
+  li_axis(fy, ny, iy[0], iy[1], wy[0], wy[1]);
+  li_axis(fz, nz, iz[0], iz[1], wz[0], wz[1]);
+#pragma unroll
+  for (int q = 0; q < 8; q++) {
+    const int dx = q >> 2, dy = (q >> 1) & 1, dz = q & 1;
+    cb[q] = (((int64_t)ix[dx] * ny + iy[dy]) * nz + iz[dz]) * ndet;
+    w[q] = (wx[dx] * wy[dy]) * wz[dz];
+  }
+}
+// one corner's share of one channel: visibility sum, and weight / time sums over the lit corners
+struct LiAcc { double v = 0.0, S = 0.0, T = 0.0; };
+__device__ __forceinline__ void li_add(LiAcc& a, double w, float vis, float t0) {
+  a.v += w * (double)vis;
+  if (vis > 0.f) {
+    a.S += w;
+    a.T += w * (double)t0;
+  }
+}
+__device__ __forceinline__ float li_photons(double eff, double vis_i, bool own, double npho) {
+  return (float)(eff * (vis_i * (own ? 1 : 0)) * npho);
+}
+__device__ __forceinline__ float li_t0(const LiAcc& a, float t0_nearest, double t0s) {
+  const double ns = 1.0, mus = 1e-6 * 1e9;
+  const double t0_lut = a.S > 0.0 ? a.T / a.S : (double)t0_nearest;
+  return (float)((t0_lut * ns + t0s * mus) / mus);
+}
+
+// the tile's set-up, shared by both forms: nearest voxel (output and t0 fallback), corners and weights, photons and time
+struct LiTile {
+  int64_t vb[LI_SEGS];             // nearest voxel's row
+  int64_t cb[LI_SEGS][8];          // the eight corners' rows
+  double w[LI_SEGS][8];
+  double np[LI_SEGS], t0[LI_SEGS];
+  int tpc[LI_SEGS];
+};
+__device__ __forceinline__ void li_tile_setup(LiTile& t, const SegStore& s, const LdsimConsts* c, int64_t seg0, int64_t r0, int nt,
+                                              int nx, int ny, int nz, int ndet, int32_t* __restrict__ voxel, int fill) {
+  if (threadIdx.x < nt) {
+    const int64_t r = r0 + threadIdx.x, it = seg0 + r;
+    int itpc = s.pixel_plane[it];
+    if (itpc == c->default_plane_index || itpc < 0 || itpc >= c->n_tpc) {
+      itpc = -1;
+      if (fill) { voxel[r * 3 + 0] = 0; voxel[r * 3 + 1] = 0; voxel[r * 3 + 2] = 0; }
+    } else {
+      int i, j, k;
+      const double x = s.f[LDSIM_X][it], y = s.f[LDSIM_Y][it], z = s.f[LDSIM_Z][it];
+      get_voxel(c, x, y, z, itpc, nx, ny, nz, i, j, k);
+      voxel[r * 3 + 0] = i;
+      voxel[r * 3 + 1] = j;
+      voxel[r * 3 + 2] = k;
+      t.vb[threadIdx.x] = (((int64_t)i * ny + j) * nz + k) * ndet;
+      li_corners(c, x, y, z, itpc, nx, ny, nz, ndet, t.cb[threadIdx.x], t.w[threadIdx.x]);
+      t.np[threadIdx.x] = s.f[LDSIM_N_PHOTONS][it];
+      t.t0[threadIdx.x] = s.f[LDSIM_T0][it];
+    }
+    t.tpc[threadIdx.x] = itpc;
+  }
+}
+
+// one channel per lane: every shape (and option light_incidence_scalar)
+__global__ void __launch_bounds__(256) light_incidence_interp_kernel(SegStore s, const LdsimConsts* __restrict__ c, int64_t seg0,
+                                                                     int64_t n, const float* __restrict__ vis,
+                                                                     const float* __restrict__ t0lut, int nx, int ny, int nz,
+                                                                     int ndet, const double* __restrict__ eff,
+                                                                     const int32_t* __restrict__ ch2tpc, int n_out,
+                                                                     float* __restrict__ nph, float* __restrict__ t0det,
+                                                                     int32_t* __restrict__ voxel, int fill) {
+  __shared__ LiTile t;
+  const int64_t r0 = (int64_t)blockIdx.x * LI_SEGS;
+  const int nt = (int)min((int64_t)LI_SEGS, n - r0);
+  if (nt <= 0) return;
+  li_tile_setup(t, s, c, seg0, r0, nt, nx, ny, nz, ndet, voxel, fill);
+  __syncthreads();
+  const bool trig0 = c->light_trig_mode == 0;
+  int sl = (int)(threadIdx.x / n_out), o = (int)(threadIdx.x % n_out);
+  const int dsl = 256 / n_out, d_o = 256 % n_out;
+  while (sl < nt) {
+    const int64_t idx = (r0 + sl) * (int64_t)n_out + o;
+    const int itpc = t.tpc[sl];
+    if (itpc >= 0) {
+      const int channel_offset = (n_out < c->n_op_channel) ? n_out * (itpc / 2) : 0;
+      const int op = o + channel_offset, li = o % ndet;
+      LiAcc a;
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        const int64_t vb = t.cb[sl][q] + li;
+        li_add(a, t.w[sl][q], vis[vb], trig0 ? t0lut[vb] : 0.f);
+      }
+      nph[idx] = li_photons(eff[op], a.v, ch2tpc[op] == itpc, t.np[sl]);
+      if (trig0) t0det[idx] = li_t0(a, t0lut[t.vb[sl] + li], t.t0[sl]);
+    } else if (fill) {
+      nph[idx] = 0.f;
+      if (trig0) t0det[idx] = 0.f;
+    }
+    sl += dsl;
+    o += d_o;
+    if (o >= n_out) { o -= n_out; sl++; }
+  }
+}
+
+// four channels per lane, under light_incidence4_kernel's conditions and with its layout: float4 loads and stores, ch2tpc quads in
+// registers when every segment reads the same slice (FIXED).  The visibility of the eight corners is gathered for the quads that
+// hold a channel of the segment's TPC; with the threshold trigger (t0_det for every channel, lit corners only) for every quad.
+// A segment's 16 corner values come from LDS once per segment, not per quad.
+template <bool FIXED>
+__global__ void __launch_bounds__(256) light_incidence_interp4_kernel(SegStore s, const LdsimConsts* __restrict__ c, int64_t seg0,
+                                                                      int64_t n, const float* __restrict__ vis,
+                                                                      const float* __restrict__ t0lut, int nx, int ny, int nz,
+                                                                      int ndet, const double* __restrict__ eff,
+                                                                      const int32_t* __restrict__ ch2tpc, int n_out,
+                                                                      float* __restrict__ nph, float* __restrict__ t0det,
+                                                                      int32_t* __restrict__ voxel, int fill) {
+  __shared__ LiTile t;
+  const int64_t r0 = (int64_t)blockIdx.x * LI_SEGS;
+  const int nt = (int)min((int64_t)LI_SEGS, n - r0);
+  if (nt <= 0) return;
+  li_tile_setup(t, s, c, seg0, r0, nt, nx, ny, nz, ndet, voxel, fill);
+  __syncthreads();
+  const bool trig0 = c->light_trig_mode == 0;
+  const int nquad = n_out >> 2;
+  // A row of few channels leaves most of the 256 lanes without a quad (module0: 24 quads), and a segment's row is a chain LDS ->
+  // eight gathers -> store.  The lanes therefore split into groups of G = 64, 128 or 256 (the fewest whole waves that hold a
+  // row's quads), and the groups take the tile's segments in turn: 4, 2 or 1 rows in flight per workgroup.
+  const int G = nquad <= 64 ? 64 : nquad <= 128 ? 128 : 256;
+  const int grp = (int)threadIdx.x / G, ngrp = 256 / G, gl = (int)threadIdx.x % G;
+  for (int q0 = 0; q0 < nquad; q0 += G * LI_QPT) {
+    int4 ct0 = make_int4(-1, -1, -1, -1), ct1 = ct0, ct2 = ct0, ct3 = ct0;
+    const int qa = q0 + gl, qb = qa + G, qc = qa + 2 * G, qd = qa + 3 * G;
+    if (FIXED) {
+      if (qa < nquad) ct0 = *(const int4*)(ch2tpc + 4 * qa);
+      if (qb < nquad) ct1 = *(const int4*)(ch2tpc + 4 * qb);
+      if (qc < nquad) ct2 = *(const int4*)(ch2tpc + 4 * qc);
+      if (qd < nquad) ct3 = *(const int4*)(ch2tpc + 4 * qd);
+    }
+    for (int sl = grp; sl < nt; sl += ngrp) {
+      const int itpc = t.tpc[sl];
+      if (itpc < 0 && !fill) continue;
+      float* rowp = nph + (r0 + sl) * (int64_t)n_out;
+      float* rowt = t0det + (r0 + sl) * (int64_t)n_out;
+      int64_t cb[8], vb0 = 0;
+      double w[8], npho = 0.0, t0s = 0.0;
+#pragma unroll
+      for (int q = 0; q < 8; q++) { cb[q] = 0; w[q] = 0.0; }
+      if (itpc >= 0) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) { cb[q] = t.cb[sl][q]; w[q] = t.w[sl][q]; }
+        vb0 = t.vb[sl];
+        npho = t.np[sl];
+        t0s = t.t0[sl];
+      }
+      const int coff = FIXED ? 0 : n_out * (max(itpc, 0) / 2);
+      const float zv = itpc >= 0 ? (float)(0.0 * npho) : 0.f;
+      auto quad = [&](int q, int4 cq) {
+        if (q >= nquad) return;
+        float4 o4 = make_float4(zv, zv, zv, zv);
+        if (itpc >= 0) {
+          const int op = 4 * q + coff;
+          if (!FIXED) cq = *(const int4*)(ch2tpc + op);
+          const bool m0 = cq.x == itpc, m1 = cq.y == itpc, m2 = cq.z == itpc, m3 = cq.w == itpc;
+          const bool own = m0 | m1 | m2 | m3;
+          const int li = (4 * q) % ndet;                // ndet % 4 == 0: the quad's LUT entries are consecutive, 16-byte aligned
+          if (own || trig0) {
+            LiAcc a0, a1, a2, a3;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+              const float4 v4 = *(const float4*)(vis + cb[k] + li);
+              const float4 l4 = trig0 ? *(const float4*)(t0lut + cb[k] + li) : make_float4(0.f, 0.f, 0.f, 0.f);
+              li_add(a0, w[k], v4.x, l4.x);
+              li_add(a1, w[k], v4.y, l4.y);
+              li_add(a2, w[k], v4.z, l4.z);
+              li_add(a3, w[k], v4.w, l4.w);
+            }
+            if (own) {
+              const double2 e0 = *(const double2*)(eff + op), e1 = *(const double2*)(eff + op + 2);
+              o4.x = li_photons(e0.x, a0.v, m0, npho);
+              o4.y = li_photons(e0.y, a1.v, m1, npho);
+              o4.z = li_photons(e1.x, a2.v, m2, npho);
+              o4.w = li_photons(e1.y, a3.v, m3, npho);
+            }
+            if (trig0) {
+              const float4 n4 = *(const float4*)(t0lut + vb0 + li);
+              float4 t4;
+              t4.x = li_t0(a0, n4.x, t0s);
+              t4.y = li_t0(a1, n4.y, t0s);
+              t4.z = li_t0(a2, n4.z, t0s);
+              t4.w = li_t0(a3, n4.w, t0s);
+              *(float4*)(rowt + 4 * q) = t4;
+            }
+          }
+        } else if (trig0) {
+          *(float4*)(rowt + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        *(float4*)(rowp + 4 * q) = o4;
+      };
+      quad(qa, ct0);
+      quad(qb, ct1);
+      quad(qc, ct2);
+      quad(qd, ct3);
+    }
+  }
+}
+
 // min / max of t0_det over the entries with n_photons_det > 0 (light_sim.get_nticks, light_sim.py:34-39), as ordered ints
 __device__ __forceinline__ int f2ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
 __global__ void __launch_bounds__(256) light_t0_range_kernel(const float* __restrict__ nph, const float* __restrict__ t0det,
@@ -804,6 +1037,16 @@ static inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 int light_launch_incidence(ldsim_ctx* ctx, int64_t seg0, int64_t n, int n_out, float* nph, float* t0det, int32_t* voxel,
                            int fill) {
   if (n == 0 || n_out == 0) return 0;
+  if (ctx->light_lut_interp) {            // option light_lut_interp: the interpolating kernels, chosen by the same conditions
+    const bool quads = n_out % 4 == 0 && ctx->lut_ndet % 4 == 0 && ctx->light_eff_plain && !ctx->light_incidence_scalar;
+    auto kern = !quads ? light_incidence_interp_kernel
+                       : n_out < ctx->h_consts.n_op_channel ? light_incidence_interp4_kernel<false> : light_incidence_interp4_kernel<true>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n + LI_SEGS - 1) / LI_SEGS)), dim3(256), 0, ctx->stream, ctx->seg,
+                       ctx->d_consts.as<LdsimConsts>(), seg0, n, ctx->d_lut_vis.as<float>(), ctx->d_lut_t0.as<float>(), ctx->lut_nx, ctx->lut_ny,
+                       ctx->lut_nz, ctx->lut_ndet, ctx->d_eff.as<double>(), ctx->d_ch2tpc.as<int32_t>(), n_out, nph, t0det, voxel, fill);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   if (n_out % 4 == 0 && ctx->lut_ndet % 4 == 0 && ctx->light_eff_plain && !ctx->light_incidence_scalar) {
     const dim3 grid((unsigned)((n + LI_SEGS - 1) / LI_SEGS));
     if (n_out < ctx->h_consts.n_op_channel)

@@ -84,6 +84,8 @@ int rng_launch_advance(ldsim_ctx* ctx, int64_t U, const int32_t* n_draws);
 int rng_launch_fee_keyed_fill(ldsim_ctx* ctx, const int32_t* ubatch, const int32_t* upix, int64_t U, int nd, float* z);
 
 // ---- light: kernels_light.hip, kernels_light_response.hip, light_wvfm.hip -------------------------------------------------
+// light_incidence_kernel / light_incidence4_kernel, or under option light_lut_interp light_incidence_interp_kernel /
+// light_incidence_interp4_kernel (trilinear visibility between voxel centres); host-buffer stage call and resident leg alike
 int light_launch_incidence(ldsim_ctx* ctx, int64_t seg0, int64_t n, int n_out, float* nph, float* t0det, int32_t* voxel,
                            int fill);
 int light_launch_t0_range(ldsim_ctx* ctx, const float* nph, const float* t0det, int64_t total, int* d_res);

@@ -210,6 +210,10 @@ extern "C" int ldsim_set_option(ldsim_ctx* ctx, const char* name, double value) 
   }
   else if (!strcmp(name, "light_truth_lds")) ctx->light_truth_lds = value != 0;
   else if (!strcmp(name, "light_incidence_scalar")) ctx->light_incidence_scalar = value != 0;
+  else if (!strcmp(name, "light_lut_interp")) {
+    if (!(value == 0 || value == 1)) { ldsim_set_error("light_lut_interp must be 0 or 1"); return LDSIM_EINVAL; }
+    ctx->light_lut_interp = (int)value;
+  }
   else if (!strcmp(name, "light_sum_no_list")) ctx->light_sum_no_list = value != 0;
   else if (!strcmp(name, "light_sum_async")) {
     CK(light_join(ctx));

@@ -271,6 +271,7 @@ struct ldsim_ctx {
   int64_t out_gen = 0, pending_gen = 0;      // chain launches so far; the launch whose results the pending copy reads
   int light_eff_plain = 0;                   // every OP_CHANNEL_EFFICIENCY finite and >= 0
   int light_incidence_scalar = 0;            // 1 = the one-channel-per-lane light_incidence_kernel (A/B checks)
+  int light_lut_interp = 0;                  // 1 = visibility interpolated trilinearly between voxel centres (light_incidence_interp*_kernel)
   int mac_mode = 1;                          // M = 1 correlation: 1 = mac_shift_kernel (DPP window), 0 = mac_kernel<1> (LDS rows)
   DevBuf d_lut_vis, d_lut_t0, d_lut_t0avg, d_lut_td;   // f32 planes
   int32_t lut_nx = 0, lut_ny = 0, lut_nz = 0, lut_ndet = 0, lut_nprof = 0;

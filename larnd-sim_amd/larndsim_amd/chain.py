@@ -322,7 +322,9 @@ class ChargeChain:
     # ---- device-resident light leg (cli/simulate_pixels.py:749-797, 1120-1153) ------------------------------------------------
     def light_incidence(self, lut=None, n_out=None):
         """``lightLUT.calculate_light_incidence`` over all resident segments (after ``quench_drift``); the arrays stay in
-        HBM.  ``lut``: the structured LUT (uploaded unless already resident); ``n_out``: output channels, default all."""
+        HBM.  ``lut``: the structured LUT (uploaded unless already resident); ``n_out``: output channels, default all.
+        Under the context option ``lib.set_option("light_lut_interp", 1)`` the visibility is interpolated trilinearly between
+        voxel centres (``lightLUT.interpolated_light_incidence`` is the numpy twin); the voxel output stays the nearest one."""
         self._check_constants()
         lib.set_light(lut, self.ctx)
         n_out = consts.light.N_OP_CHANNEL if n_out is None else n_out
