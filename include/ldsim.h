@@ -37,6 +37,7 @@ extern "C" {
 #define LDSIM_ENOSPC (-3)   /* caller-provided capacity too small (required size reported) */
 #define LDSIM_ESTATE (-4)   /* call order violated (e.g. no response table set) */
 #define LDSIM_ENODEV (-5)   /* no usable GPU */
+#define LDSIM_ENOMEM (-6)   /* a device allocation of the call failed (the context stays usable) */
 
 /* record field dtype codes */
 enum { LDSIM_F4 = 1, LDSIM_F8 = 2, LDSIM_I4 = 3, LDSIM_U4 = 4, LDSIM_I8 = 5, LDSIM_U8 = 6 };
@@ -566,6 +567,49 @@ int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, int64_t sizes
 int ldsim_chain_pixel_truth_download(ldsim_ctx* ctx, LdsimPixelTruthRow* pixel_rows, LdsimPixelTruthTrack* track_entries);
 int ldsim_chain_pixel_truth_dense_download(ldsim_ctx* ctx, int64_t U, double* q_induced, double* q_abs, double* q_track);
 int ldsim_chain_pixel_truth_row_samples(ldsim_ctx* ctx, int64_t* n_samples);
+
+/* ---- pixel current waveforms: the summed induced current of every pixel of the last chain launch, zero-suppressed ------
+ * Mirrors nothing in the reference.  Per unique-pixel row u of ldsim_chain_download, on the pixel's time axis [0, N_t)
+ * (tick t = the time t * time_sampling on the axis adc_ticks_list uses; N_t = n_time_ticks):
+ *   S[t]     f64: the f32 current rows of the pixel's slots added in slot order, each over its written window placed at
+ *            the slot's start tick and clipped to [0, N_t) -- the sum the FEE kernel and pixel truth form, so
+ *            time_sampling * sum_t S[t] = q_induced.  No FEE noise, ever; 0 outside every window; a pixel with more pairs
+ *            than slots is summed over its slots only.
+ *   active   A = { t : |S[t]| > min_abs_current }, strict, in f64, on the unrounded S (0: the ticks with S != 0)
+ *            (the samples returned are rounded to f32: a threshold equal to a returned sample excludes that tick only
+ *            when its S is exactly an f32, a sum of one slot)
+ *   kept     K = { t in [0, N_t) : some a in A has |t - a| <= pad_ticks }, 0 <= pad_ticks <= 64
+ *   spans    the maximal runs of consecutive ticks of K (padded neighbourhoods that overlap or touch are one span; a span
+ *            clipped at tick 0 or N_t - 1 is shorter); samples: (float)S[t] of a span's ticks in rising t
+ * ldsim_chain_pixel_waveforms runs a count pass, two 64-bit scans and a fill pass on the device.  hits_only != 0: only
+ * pixels with n_hits > 0 (the launch's own hit counts) produce spans.  sizes[3] = spans, samples, N_t; one synchronisation.
+ * A launch without unique pixels gives 0, 0, N_t.  Span rows are ordered by (row, t_begin) and the samples of all spans are
+ * concatenated in that order: no atomics decide a position.  Sample offsets are 64-bit throughout; the only limit is the
+ * device memory the result needs (32 bytes per span + 4 per sample), and a result that does not fit returns LDSIM_ENOMEM
+ * before anything of it is written.
+ * ldsim_chain_pixel_waveforms_download: the compact form of the last pass; either pointer may be NULL.
+ * ldsim_chain_pixel_waveforms_ms (timing tools): HIP-event times of the last pass's count kernel and fill kernel (0 for a
+ * kernel that was not launched); it synchronises; either pointer may be NULL; LDSIM_ESTATE like the download.
+ * ldsim_chain_pixel_waveforms_dense (tests, debugging): (float)S[t] of the rows [u_begin, u_end), zeros included, formed by
+ * the device code the spans are formed by; S holds [u_end - u_begin][N_t] values.
+ * Errors: LDSIM_EINVAL for a negative or non-finite min_abs_current, pad_ticks outside [0, 64], rows that are no range of
+ * [0, n_unique].  State rules: those of pixel truth -- LDSIM_ESTATE, the message naming the call, once anything may have
+ * rewritten the launch's buffers; the download returns LDSIM_ESTATE unless the pass ran for the last chain launch.  The pass
+ * owns its buffers: it and ldsim_chain_pixel_truth may run for one launch in either order, any number of times. */
+typedef struct LdsimPixelWaveSpan {   /* 32 bytes */
+  int32_t row;          /* u: index in the arrays of ldsim_chain_download */
+  int32_t pixel_id;
+  int32_t batch;
+  int32_t t_begin;      /* first tick */
+  int32_t n_samples;
+  int32_t pad;
+  int64_t sample_begin; /* index of its first sample in the samples array */
+} LdsimPixelWaveSpan;
+int ldsim_chain_pixel_waveforms(ldsim_ctx* ctx, double min_abs_current, int32_t pad_ticks, int32_t hits_only,
+                                int64_t sizes[3]);
+int ldsim_chain_pixel_waveforms_download(ldsim_ctx* ctx, LdsimPixelWaveSpan* spans, float* samples);
+int ldsim_chain_pixel_waveforms_dense(ldsim_ctx* ctx, int64_t u_begin, int64_t u_end, float* S);
+int ldsim_chain_pixel_waveforms_ms(ldsim_ctx* ctx, double* count_ms, double* fill_ms);
 
 /* ---- device-resident light leg (cli/simulate_pixels.py:749-797 and :1120-1153 on the resident segments) ---------- */
 /* lightLUT.calculate_light_incidence[bpg,tpb](tracks, lut, light_sim_dat, track_light_voxel) over ALL resident segments,

@@ -89,6 +89,16 @@ def _parser():
     ap.add_argument("--pixel_truth_min_charge", type=float, default=None,
                     help="under --pixel_truth: pixels without a hit are stored when they saw at least this much |charge| "
                          "[electrons] (default 0: every pixel a segment reached)")
+    ap.add_argument("--pixel_waveforms", action="store_true",
+                    help="also store the summed induced current of every pixel of every chain launch, zero-suppressed into "
+                         "spans (datasets pixel_waveforms and pixel_waveform_samples, larndsim_amd/pixel_waveforms.py); one "
+                         "GPU only")
+    ap.add_argument("--pixel_waveforms_threshold", type=float, default=None,
+                    help="under --pixel_waveforms: a tick is active when |current| exceeds this (default 0: every non-zero tick)")
+    ap.add_argument("--pixel_waveforms_pad", type=int, default=None,
+                    help="under --pixel_waveforms: ticks kept on either side of an active tick, 0..64 (default 0)")
+    ap.add_argument("--pixel_waveforms_hits_only", action="store_true",
+                    help="under --pixel_waveforms: only the pixels that hold a hit")
     ap.add_argument("--light_lut_interpolation", default="nearest", choices=list(LIGHT_LUT_INTERPOLATION),
                     help="visibility of a segment from the light LUT: nearest (default; the voxel that holds the segment, like "
                          "the reference) or trilinear (interpolated between the eight voxel centres around it: no step in the "
@@ -118,6 +128,15 @@ def _parse_args(argv=None):
         ap.error("--pixel_truth_min_charge sets the selection of --pixel_truth: give --pixel_truth as well")
     if a.pixel_truth_min_charge is not None and not (0 <= a.pixel_truth_min_charge < float("inf")):
         ap.error("--pixel_truth_min_charge must be finite and >= 0")
+    for flag, given in (("--pixel_waveforms_threshold", a.pixel_waveforms_threshold is not None),
+                        ("--pixel_waveforms_pad", a.pixel_waveforms_pad is not None),
+                        ("--pixel_waveforms_hits_only", a.pixel_waveforms_hits_only)):
+        if given and not a.pixel_waveforms:
+            ap.error(f"{flag} sets the selection of --pixel_waveforms: give --pixel_waveforms as well")
+    if a.pixel_waveforms_threshold is not None and not (0 <= a.pixel_waveforms_threshold < float("inf")):
+        ap.error("--pixel_waveforms_threshold must be finite and >= 0")
+    if a.pixel_waveforms_pad is not None and not (0 <= a.pixel_waveforms_pad <= 64):
+        ap.error("--pixel_waveforms_pad must lie in [0, 64]")
     return a
 
 
@@ -135,6 +154,9 @@ def launch_ranks_if_asked(argv=None):
                          "production one)")
     if world is not None and world > 1 and a["pixel_truth"]:
         raise SystemExit("simulate_pixels.py: --pixel_truth is not available with --n_gpus > 1 (its rows are not gathered "
+                         "over the ranks)")
+    if world is not None and world > 1 and a["pixel_waveforms"]:
+        raise SystemExit("simulate_pixels.py: --pixel_waveforms is not available with --n_gpus > 1 (its rows are not gathered "
                          "over the ranks)")
     if world is None or "WORLD_SIZE" in os.environ:
         return
@@ -158,6 +180,7 @@ from larndsim_amd import config as cfgmod  # noqa: E402
 from larndsim_amd import dist as ldist  # noqa: E402
 from larndsim_amd import field_map as lfmap  # noqa: E402
 from larndsim_amd import pixel_truth as lptruth  # noqa: E402
+from larndsim_amd import pixel_waveforms as lpwave  # noqa: E402
 from larndsim_amd import rng as lrng  # noqa: E402
 from larndsim_amd.chain import ChargeChain  # noqa: E402
 
@@ -225,6 +248,7 @@ class _Output:
         self.parts = {}
         self.appended = set()           # datasets `append` has written rows of
         self.pixel_truth_tracks = 0     # rows of pixel_truth_tracks so far (pixel_truth's track_begin counts over the file)
+        self.pixel_waveform_samples = 0   # values of pixel_waveform_samples so far (pixel_waveforms' sample_begin likewise)
 
     def append_packets(self, pk, assn):
         if self.h5py is not None:
@@ -363,7 +387,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    tracks_current_mc=False, chunk_segments=50000, raw_arrays=False, overlap_downloads=None,
                    pixel_layout_id=None, response_id=None, light_lut_id=None, pixel_thresholds_id=None, pixel_gains_id=None,
                    numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
-                   fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, light_lut_interpolation="nearest", **ignored):
+                   fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, light_lut_interpolation="nearest",
+                   pixel_waveforms=False, pixel_waveforms_threshold=None, pixel_waveforms_pad=None, pixel_waveforms_hits_only=False,
+                   **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -375,6 +401,19 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         raise ValueError("--pixel_truth is not available with --n_gpus > 1: its rows are not gathered over the ranks")
     if pixel_truth_min_charge is not None and not pixel_truth:
         raise ValueError("--pixel_truth_min_charge sets the selection of --pixel_truth: give --pixel_truth as well")
+    if world is not None and world > 1 and pixel_waveforms:
+        raise ValueError("--pixel_waveforms is not available with --n_gpus > 1: its rows are not gathered over the ranks")
+    if (pixel_waveforms_threshold is not None or pixel_waveforms_pad is not None or pixel_waveforms_hits_only) \
+            and not pixel_waveforms:
+        raise ValueError("--pixel_waveforms_threshold, --pixel_waveforms_pad and --pixel_waveforms_hits_only set the selection of "
+                         "--pixel_waveforms: give --pixel_waveforms as well")
+    wave_sel = None
+    if pixel_waveforms:
+        wave_sel = (float(pixel_waveforms_threshold or 0.0), int(pixel_waveforms_pad or 0), bool(pixel_waveforms_hits_only))
+        try:
+            lpwave.check_args(wave_sel[0], wave_sel[1])
+        except ValueError as e:
+            raise ValueError(f"--pixel_waveforms: {e}")
     if light_lut_interpolation not in LIGHT_LUT_INTERPOLATION:
         raise ValueError(f"--light_lut_interpolation must be nearest or trilinear, not {light_lut_interpolation!r}")
     if not os.path.exists(input_filename):
@@ -515,6 +554,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     truth_min = None if not pixel_truth else float(pixel_truth_min_charge or 0.0)
     if pixel_truth:                     # (without the flag the header, like the file, is what it was)
         print("Pixel charge truth:", f"on (--pixel_truth, --pixel_truth_min_charge {truth_min:g} e)")
+    if pixel_waveforms:                 # (likewise)
+        print("Pixel current waveforms:", f"on (--pixel_waveforms, --pixel_waveforms_threshold {wave_sel[0]:g}, "
+              f"--pixel_waveforms_pad {wave_sel[1]}" + (", --pixel_waveforms_hits_only)" if wave_sel[2] else ")"))
     print("Light LUT interpolation:", light_lut_interpolation if light_lut_interpolation == "nearest"
           else f"{light_lut_interpolation} (--light_lut_interpolation {light_lut_interpolation})")
     lib.set_option("numba_f32", f32_mode)
@@ -569,7 +611,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             res = _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field,
                                    per_module(light_lut_filename, i_mod) if light_simulated else None, light_det_noise_filename,
                                    cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist,
-                                   keyed=rng == "keyed", pixel_truth_min=truth_min)
+                                   keyed=rng == "keyed", pixel_truth_min=truth_min, pixel_waveforms_sel=wave_sel)
             for k in totals:
                 totals[k] += res[k]
             rows_per_rank += res["rows_per_rank"]
@@ -606,6 +648,10 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             for name, dt in (("pixel_truth", lptruth.FILE_PIXEL), ("pixel_truth_tracks", lptruth.FILE_TRACK)):
                 if name not in out.appended:
                     out.put(name, np.zeros(0, dtype=dt))
+        if pixel_waveforms:             # (likewise)
+            for name, dt in (("pixel_waveforms", lpwave.FILE_SPAN), ("pixel_waveform_samples", np.dtype("f4"))):
+                if name not in out.appended:
+                    out.put(name, np.zeros(0, dtype=dt))
         out.close(pixel_layout if isinstance(pixel_layout, str) else None if pixel_layout is None else list(pixel_layout))
     finally:
         lib.set_option("mc_current", 0)
@@ -623,7 +669,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
 
 def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field, light_lut,
                      light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None,
-                     dist=None, keyed=False, pixel_truth_min=None):
+                     dist=None, keyed=False, pixel_truth_min=None, pixel_waveforms_sel=None):
     """One pass of the driver's module loop body (cli/simulate_pixels.py:717-1232) on the device-resident chain: quench + drift,
     light leg, charge chain, packets.  ``tracks``: the module's active segments (all active segments without module
     variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out).
@@ -929,6 +975,17 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
             r["event_id"] = np.array([t[0] for t in table])[r["batch"]]
             parts.append(r)
 
+    def export_pixel_waveforms():
+        """--pixel_waveforms: the last launch's pixel current waveforms (ChargeChain.pixel_waveforms) as rows of the file's two
+        datasets, sample_begin counted over the whole file"""
+        if pixel_waveforms_sel is None:
+            return
+        thr, pad, hits_only = pixel_waveforms_sel
+        rows, samples = lpwave.file_rows(chain.pixel_waveforms(thr, pad, hits_only), event_of_batch, out.pixel_waveform_samples)
+        out.pixel_waveform_samples += len(samples)
+        out.append("pixel_waveforms", rows)
+        out.append("pixel_waveform_samples", samples)
+
     def export_pixel_truth():
         """--pixel_truth: the last launch's pixel charge truth (ChargeChain.pixel_truth) as rows of the file's two datasets;
         segment ids mapped like mc_packets_assn's (packets.compact_to_rows), track_begin counted over the whole file"""
@@ -972,12 +1029,14 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
             chain.wait()
             prev = chain.download_compact()
             export_pixel_truth()
+            export_pixel_waveforms()
         if prev is not None:
             export_chunk_compact(prev)
         launches = []
     for b, e in launches:
         chain.run(int(b), int(e), want_fractions=True)
         export_pixel_truth()
+        export_pixel_waveforms()
         if not overlapped:
             export_chunk(chain.download())
             continue

@@ -168,8 +168,6 @@ static PtDense pt_dense_of(void* p, int64_t U, int M) {
   return d;
 }
 
-static int pt_need_launch(ldsim_ctx* ctx, const char* who);
-
 extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, int64_t sizes[2]) {
   LDSIM_ENTER(ctx);
   if (!ctx || !sizes) { ldsim_set_error("null argument"); return LDSIM_EINVAL; }
@@ -234,8 +232,8 @@ extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, in
   return 0;
 }
 
-// the launch is intact and its set-up record describes its buffers (what the pass reads)
-static int pt_need_launch(ldsim_ctx* ctx, const char* who) {
+// the launch is intact and its set-up record describes its buffers (what the pass reads; kernels_pixwave.hip asks the same)
+int pt_need_launch(ldsim_ctx* ctx, const char* who) {
   if (ctx->launch_stale) {
     ldsim_set_error("%s reads what the last chain launch left in HBM, and it is gone: %s; run ldsim_charge_chain again", who,
                     ctx->launch_stale);

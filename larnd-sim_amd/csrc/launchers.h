@@ -76,6 +76,10 @@ int fee_launch_adc_dense(ldsim_ctx* ctx, const double* ps, const double* pts, in
                          double* ticks, double* frac);
 int fee_launch_digitize(ldsim_ctx* ctx, const double* q, const double* gain, double* out, int64_t n);
 
+// ---- kernels_pixtruth.hip ----------------------------------------------------------------------------------------------
+// 0 while the scratch buffers hold the last chain launch and its set-up record describes them; else LDSIM_ESTATE, `who` named
+int pt_need_launch(ldsim_ctx* ctx, const char* who);
+
 // ---- kernels_rng.hip ---------------------------------------------------------------------------------------------------
 int rng_ensure_states(ldsim_ctx* ctx, int64_t n);
 int rng_fee_draws_per_pixel(const LdsimConsts& h, int NT);

@@ -425,6 +425,14 @@ struct ldsim_ctx {
   int64_t pt_gen = -1;           // chain launch (out_gen) the last pass ran on (-1: none)
   int64_t pt_U = 0, pt_n[2] = {0, 0};   // rows of the dense arrays; kept pixels and track entries of the compact form
   int32_t pt_M = 0;
+  // pixel current waveforms (ldsim_chain_pixel_waveforms, kernels_pixwave.hip) read the same launch under the same rule
+  DevBuf pw_sel;                 // u64 [4][U + 1]: span counts | sample counts | their exclusive scans (place U: the totals)
+  DevBuf pw_out;                 // compact form: span rows (LdsimPixelWaveSpan) | samples f32
+  DevBuf pw_dense;               // rows of the last ldsim_chain_pixel_waveforms_dense, f32 [u_end - u_begin][N_t]
+  int64_t pw_gen = -1;           // chain launch (out_gen) the last pass ran on (-1: none)
+  int64_t pw_n[2] = {0, 0};      // spans and samples of the compact form
+  Event pw_ev[4];                // around the count kernel and around the fill kernel of the last pass (ldsim_chain_pixel_waveforms_ms)
+  bool pw_filled = false;        // the last pass launched its fill kernel
   Event ev[8];
   double ms_current = 0, ms_adc = 0, ms_total = 0;
   double ms_weights = 0, ms_mac = 0, ms_fallback = 0;   // split path: per-kernel share of ms_current

@@ -291,6 +291,48 @@ class ChargeChain:
         lib.check(lib.load().ldsim_chain_pixel_truth_row_samples(self.ctx, C.byref(n)))
         return int(n.value)
 
+    def pixel_waveforms(self, min_abs_current=0.0, pad_ticks=0, hits_only=False, dense=False, rows=None):
+        """Pixel current waveforms of the last run() (``pixel_waveforms``, ``ldsim_chain_pixel_waveforms``): the summed induced
+        current ``S[t]`` of every unique pixel, zero-suppressed on the device.  A tick is active when ``|S[t]| >
+        min_abs_current`` (strict, f64), kept when an active tick lies within ``pad_ticks`` (0..64) of it; the spans are the
+        runs of kept ticks.  ``hits_only``: only pixels that hold a hit.  Returns ``dict(spans=, samples=, n_ticks=)``:
+        structured rows (``pixel_waveforms.SPAN_ROW``: row, pixel_id, batch, t_begin, n_samples, sample_begin) ordered by
+        (row, t_begin), and the f32 samples of all spans in that order.  ``dense=True``: ``S`` f32 [len(rows)][N_t] of the
+        row range ``rows`` (a ``range`` or ``(begin, end)``; None: every row) instead, zeros included -- the test and debugging
+        form.  ``S`` never holds FEE noise.  Raises ``LdsimError`` (LDSIM_ESTATE) under the rules of ``pixel_truth``."""
+        from . import pixel_waveforms as pw
+        self._check_constants()
+        L = lib.load()
+        if dense:
+            U = int(self.stats.n_unique)
+            if rows is None:
+                b, e = 0, U
+            elif isinstance(rows, range):
+                if rows.step != 1:
+                    raise ValueError("pixel_waveforms: rows must be a contiguous range")
+                b, e = rows.start, max(rows.stop, rows.start)
+            else:
+                b, e = rows
+            n_t = len(consts.detector.TIME_TICKS)                    # (N_t of the constants _check_constants holds the ctx to)
+            S = np.zeros((max(int(e) - int(b), 0), n_t), dtype=np.float32)
+            lib.check(L.ldsim_chain_pixel_waveforms_dense(self.ctx, C.c_int64(int(b)), C.c_int64(int(e)), lib.ptr(S)))
+            return S
+        if rows is not None:
+            raise ValueError("pixel_waveforms: rows selects the rows of dense=True")
+        sizes = (C.c_int64 * 3)()
+        lib.check(L.ldsim_chain_pixel_waveforms(self.ctx, C.c_double(float(min_abs_current)), C.c_int32(int(pad_ticks)),
+                                                C.c_int32(1 if hits_only else 0), sizes))
+        out = dict(spans=np.zeros(int(sizes[0]), dtype=pw.SPAN_ROW), samples=np.zeros(int(sizes[1]), dtype=np.float32),
+                   n_ticks=int(sizes[2]))
+        lib.check(L.ldsim_chain_pixel_waveforms_download(self.ctx, lib.ptr(out["spans"]), lib.ptr(out["samples"])))
+        return out
+
+    def pixel_waveforms_ms(self):
+        """HIP-event times (count kernel, fill kernel) of the last ``pixel_waveforms`` pass in ms (timing tools)"""
+        a, b = C.c_double(), C.c_double()
+        lib.check(lib.load().ldsim_chain_pixel_waveforms_ms(self.ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def download_async(self, fractions=None):
         """Start copying the results of the last run() to page-locked host arrays on the library's copy stream and return them
         at once (``ldsim_chain_download_async``): the next ``run()`` overlaps with the transfer.  The arrays hold the rows

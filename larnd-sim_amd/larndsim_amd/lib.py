@@ -39,6 +39,8 @@ EXPORTS = [
     "ldsim_chain_download", "ldsim_chain_download_async", "ldsim_chain_download_wait", "ldsim_chain_compact_hits", "ldsim_chain_compact_build", "ldsim_chain_compact_download",
     "ldsim_chain_pixel_truth", "ldsim_chain_pixel_truth_download", "ldsim_chain_pixel_truth_dense_download",
     "ldsim_chain_pixel_truth_row_samples",
+    "ldsim_chain_pixel_waveforms", "ldsim_chain_pixel_waveforms_download", "ldsim_chain_pixel_waveforms_dense",
+    "ldsim_chain_pixel_waveforms_ms",
     "ldsim_chain_kernel_ms", "ldsim_chain_kernel_ms_detail",
     "ldsim_dev_light_incidence", "ldsim_dev_light_incidence_download", "ldsim_dev_light_t0_range", "ldsim_dev_sum_light",
     "ldsim_dev_light_download", "ldsim_light_kernel_ms",
