@@ -611,6 +611,54 @@ int ldsim_chain_pixel_waveforms_download(ldsim_ctx* ctx, LdsimPixelWaveSpan* spa
 int ldsim_chain_pixel_waveforms_dense(ldsim_ctx* ctx, int64_t u_begin, int64_t u_end, float* S);
 int ldsim_chain_pixel_waveforms_ms(ldsim_ctx* ctx, double* count_ms, double* fill_ms);
 
+/* ---- FEE universes: the last chain launch digitised again under varied front-end constants ------------------------------
+ * Mirrors nothing in the reference, where a variation of a front-end constant is another run.  A launch spends its time on
+ * the per-pair current rows; the LArPix front end (fee.py:499-655) only reads them.  This pass forms every unique pixel's
+ * summed waveform S[t] once more from those rows and the launch's set-up record (the sum of pixel current waveforms above)
+ * and runs the launch's own trigger scan and digitisation on it once per universe: universe k of the result is, bit for
+ * bit, what ldsim_charge_chain gives after ldsim_set_consts with the universe's fifteen values (same seed, same batch keys).
+ * A variation holds absolute values, not deltas; ldsim_fee_variation_nominal fills one from the context's constants (scales
+ * 1, offset 0).  With pixel tables set (ldsim_set_pixel_thresholds / ldsim_set_pixel_gains) a universe's threshold is
+ * table[pixel] * threshold_table_scale + threshold_table_offset and its gain table[pixel] * gain_table_scale (each product
+ * and the sum rounded on its own), and discrimination_threshold / gain are not read, as in the launch; without tables the
+ * three table fields are not read.
+ * Not varied: time_sampling, n_time_ticks, max_adc_values, max_tracks_per_pixel, clock_cycle, adc_counts -- they shape the
+ * record or the clock.  Not produced per universe: backtracking fractions and track_pixel_map (the map is the launch's own
+ * and does not depend on the front end).
+ * ldsim_chain_fee_universes runs n universes; n_hits [n] (may be NULL) receives every universe's hits.  Two synchronisations.
+ * ldsim_chain_fee_universe_download: universe k's adc_list, adc_ticks, adc_digit f64 [U][A] and hit_count i32 [U] in the row
+ * order of ldsim_chain_download (capacity >= U rows, else LDSIM_ENOSPC); any pointer may be NULL.
+ * ldsim_chain_fee_universe_hits_download: universe k's compact rows, the 24-byte rows of ldsim_chain_compact_hits {batch i32,
+ * pixel i32, ADC code i32, slot i32, tick f64}, and their charges f64 (adc_list) in the same order; either may be NULL.
+ * ldsim_chain_fee_universes_ms (timing tools): HIP-event time of the last pass's scan kernel; it synchronises.
+ * Errors: LDSIM_EINVAL, nothing written and an earlier result still downloadable, for n outside [1,
+ * LDSIM_FEE_UNIVERSES_MAX], a non-finite field, v_ref == v_cm, a negative delay, cycle count or noise charge, a rise time
+ * beyond the kernel's 62 taps (10 * buffer_risetime / time_sampling > 62, ldsim_charge_chain's own limit), pad != 0; in the
+ * downloads for k outside [0, n).
+ * Noise: a universe with a non-zero noise charge draws from the keyed streams of the launch's pixels (every universe of a
+ * pixel sees the same normals and scales them by its own charges), so the context must be in keyed mode
+ * (ldsim_rng_keyed_seed) with the launch's batch keys set (ldsim_chain_set_batch_keys): LDSIM_ESTATE otherwise.  In table
+ * mode the pass never draws and never advances the table.  A universe with noise walks every tick, whatever the launch did.
+ * State rules: those of pixel truth -- LDSIM_ESTATE, the message naming the call, once anything may have rewritten the
+ * launch's buffers; the downloads return LDSIM_ESTATE unless the pass ran for the last chain launch.  The pass owns its
+ * buffers and writes nothing of the launch (not its results, not its counters, not its tap table): it,
+ * ldsim_chain_pixel_truth and ldsim_chain_pixel_waveforms may run for one launch in any order, any number of times.
+ * Memory: n * U * A * 24 bytes for the dense arrays, 8 n U for the counts, 32 bytes per hit; a result that does not fit
+ * returns LDSIM_ENOMEM before anything of it is written.  A launch without unique pixels returns 0 with zero counts. */
+typedef struct LdsimFeeVariation {   /* 112 bytes; absolute values, not deltas */
+  double discrimination_threshold, gain, v_cm, v_ref, v_pedestal, buffer_risetime;
+  double reset_noise_charge, uncorrelated_noise_charge, discriminator_noise;
+  double threshold_table_scale, threshold_table_offset, gain_table_scale;   /* used only when pixel tables are set */
+  int32_t adc_hold_delay, adc_busy_delay, reset_cycles, pad;
+} LdsimFeeVariation;
+#define LDSIM_FEE_UNIVERSES_MAX 64
+int ldsim_fee_variation_nominal(ldsim_ctx* ctx, LdsimFeeVariation* out);
+int ldsim_chain_fee_universes(ldsim_ctx* ctx, const LdsimFeeVariation* v, int32_t n, int64_t* n_hits);
+int ldsim_chain_fee_universe_download(ldsim_ctx* ctx, int32_t k, int64_t capacity, double* adc_list, double* adc_ticks,
+                                      double* adc_digit, int32_t* hit_count);
+int ldsim_chain_fee_universe_hits_download(ldsim_ctx* ctx, int32_t k, void* hit_rows, double* hit_charge);
+int ldsim_chain_fee_universes_ms(ldsim_ctx* ctx, double* scan_ms);
+
 /* ---- device-resident light leg (cli/simulate_pixels.py:749-797 and :1120-1153 on the resident segments) ---------- */
 /* lightLUT.calculate_light_incidence[bpg,tpb](tracks, lut, light_sim_dat, track_light_voxel) over ALL resident segments,
  * after ldsim_dev_quench_drift (it needs n_photons and pixel_plane): n_photons_det [n][n_out] f4, t0_det [n][n_out] f4

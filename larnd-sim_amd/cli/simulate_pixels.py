@@ -99,6 +99,14 @@ def _parser():
                     help="under --pixel_waveforms: ticks kept on either side of an active tick, 0..64 (default 0)")
     ap.add_argument("--pixel_waveforms_hits_only", action="store_true",
                     help="under --pixel_waveforms: only the pixels that hold a hit")
+    ap.add_argument("--fee_universes", default=None, metavar="FILE.json",
+                    help="also digitise every chain launch again under each universe of FILE.json, a list of {\"name\": ..., "
+                         "\"DISCRIMINATION_THRESHOLD\": ..., ...}: front-end constants by their names in the detector properties "
+                         "(threshold, gain, V_CM / V_REF / V_PEDESTAL, BUFFER_RISETIME, ADC_HOLD_DELAY / ADC_BUSY_DELAY / "
+                         "RESET_CYCLES, the three noise charges, THRESHOLD_TABLE_SCALE / _OFFSET and GAIN_TABLE_SCALE for the pixel "
+                         "tables), the others as configured (datasets fee_universes and fee_universe_hits, "
+                         "larndsim_amd/fee_universes.py); hits only: LArPix packets per universe are out of scope; universes with "
+                         "noise need --rng keyed; one GPU only")
     ap.add_argument("--light_lut_interpolation", default="nearest", choices=list(LIGHT_LUT_INTERPOLATION),
                     help="visibility of a segment from the light LUT: nearest (default; the voxel that holds the segment, like "
                          "the reference) or trilinear (interpolated between the eight voxel centres around it: no step in the "
@@ -109,6 +117,9 @@ def _parser():
 
 
 LIGHT_LUT_INTERPOLATION = {"nearest": 0, "trilinear": 1}          # --light_lut_interpolation -> context option light_lut_interp
+
+FEE_UNIVERSES_NEED_KEYED = ("--fee_universes: universe {} has a non-zero noise charge, and its normals come from the keyed "
+                            "streams of the launch's pixels: give --rng keyed as well")
 
 CHARGE_STATISTICS_NEEDS_KEYED = ("--charge_statistics draws from keyed random streams (one per segment, whatever the "
                                  "chunking or rank count): give --rng keyed as well")
@@ -137,6 +148,16 @@ def _parse_args(argv=None):
         ap.error("--pixel_waveforms_threshold must be finite and >= 0")
     if a.pixel_waveforms_pad is not None and not (0 <= a.pixel_waveforms_pad <= 64):
         ap.error("--pixel_waveforms_pad must lie in [0, 64]")
+    if a.fee_universes is not None:
+        # (what the file alone decides; a universe that inherits the configuration's noise charges is checked once they are loaded)
+        from larndsim_amd import fee_universes as lfu  # (standard library only)
+        try:
+            entries = lfu.read(a.fee_universes)
+        except (OSError, ValueError) as e:
+            ap.error(f"--fee_universes {a.fee_universes}: {e}")
+        for k, (name, changes) in enumerate(entries):
+            if lfu.changes_noisy(changes) and a.rng != "keyed":
+                ap.error(FEE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
     return a
 
 
@@ -158,6 +179,9 @@ def launch_ranks_if_asked(argv=None):
     if world is not None and world > 1 and a["pixel_waveforms"]:
         raise SystemExit("simulate_pixels.py: --pixel_waveforms is not available with --n_gpus > 1 (its rows are not gathered "
                          "over the ranks)")
+    if world is not None and world > 1 and a["fee_universes"]:
+        raise SystemExit("simulate_pixels.py: --fee_universes is not available with --n_gpus > 1 (its rows are not gathered "
+                         "over the ranks)")
     if world is None or "WORLD_SIZE" in os.environ:
         return
     if os.path.exists(a["output_filename"]):
@@ -178,6 +202,7 @@ import numpy.lib.recfunctions as rfn  # noqa: E402
 from larndsim_amd import batching, charge_stats, consts, fee, light_sim, packets, synth  # noqa: E402
 from larndsim_amd import config as cfgmod  # noqa: E402
 from larndsim_amd import dist as ldist  # noqa: E402
+from larndsim_amd import fee_universes as lfu  # noqa: E402
 from larndsim_amd import field_map as lfmap  # noqa: E402
 from larndsim_amd import pixel_truth as lptruth  # noqa: E402
 from larndsim_amd import pixel_waveforms as lpwave  # noqa: E402
@@ -389,7 +414,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
                    fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, light_lut_interpolation="nearest",
                    pixel_waveforms=False, pixel_waveforms_threshold=None, pixel_waveforms_pad=None, pixel_waveforms_hits_only=False,
-                   **ignored):
+                   fee_universes=None, **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -407,6 +432,12 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             and not pixel_waveforms:
         raise ValueError("--pixel_waveforms_threshold, --pixel_waveforms_pad and --pixel_waveforms_hits_only set the selection of "
                          "--pixel_waveforms: give --pixel_waveforms as well")
+    if world is not None and world > 1 and fee_universes:
+        raise ValueError("--fee_universes is not available with --n_gpus > 1: its rows are not gathered over the ranks")
+    if fee_universes is not None:
+        for k, (name, changes) in enumerate(lfu.read(fee_universes)):           # (the file's keys, before anything is simulated)
+            if lfu.changes_noisy(changes) and rng != "keyed":
+                raise ValueError(FEE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
     wave_sel = None
     if pixel_waveforms:
         wave_sel = (float(pixel_waveforms_threshold or 0.0), int(pixel_waveforms_pad or 0), bool(pixel_waveforms_hits_only))
@@ -557,6 +588,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     if pixel_waveforms:                 # (likewise)
         print("Pixel current waveforms:", f"on (--pixel_waveforms, --pixel_waveforms_threshold {wave_sel[0]:g}, "
               f"--pixel_waveforms_pad {wave_sel[1]}" + (", --pixel_waveforms_hits_only)" if wave_sel[2] else ")"))
+    if fee_universes is not None:       # (likewise)
+        print("FEE universes:", f"{fee_universes} (--fee_universes; hits only, no packets per universe)")
     print("Light LUT interpolation:", light_lut_interpolation if light_lut_interpolation == "nearest"
           else f"{light_lut_interpolation} (--light_lut_interpolation {light_lut_interpolation})")
     lib.set_option("numba_f32", f32_mode)
@@ -569,6 +602,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         n_rccl, r_rccl = dist.count()
         if (n_rccl, r_rccl) != (world, rank):
             raise RuntimeError(f"rank {rank} of {world}: the RCCL communicator reports rank {r_rccl} of {n_rccl}")
+    universes_written = False
     try:
         for i_mod in mod_ids:                                       # convention: module ids count from 1 (:676-715)
             if m2m:
@@ -608,10 +642,21 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             if gain_file is not None:                               # :445-449, 1097-1100
                 print("Pixel gains file:", gain_file)
                 chain.set_pixel_gains(*fee.load_pixel_table(gain_file))
+            universes = None
+            if fee_universes is not None:
+                # every universe is this module's constants with the file's keys applied
+                uni_names, universes = lfu.load(fee_universes)
+                for k, v in enumerate(universes):
+                    if lfu.is_noisy(v) and rng != "keyed":
+                        raise ValueError(FEE_UNIVERSES_NEED_KEYED.format(f"{k} ({uni_names[k]})"))
+                if not universes_written:                               # (once: with module variation, the first module's values)
+                    out.put("fee_universes", lfu.universe_rows(uni_names, universes))
+                    universes_written = True
             res = _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field,
                                    per_module(light_lut_filename, i_mod) if light_simulated else None, light_det_noise_filename,
                                    cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist,
-                                   keyed=rng == "keyed", pixel_truth_min=truth_min, pixel_waveforms_sel=wave_sel)
+                                   keyed=rng == "keyed", pixel_truth_min=truth_min, pixel_waveforms_sel=wave_sel,
+                                   fee_universes=universes)
             for k in totals:
                 totals[k] += res[k]
             rows_per_rank += res["rows_per_rank"]
@@ -652,6 +697,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             for name, dt in (("pixel_waveforms", lpwave.FILE_SPAN), ("pixel_waveform_samples", np.dtype("f4"))):
                 if name not in out.appended:
                     out.put(name, np.zeros(0, dtype=dt))
+        if fee_universes is not None and "fee_universe_hits" not in out.appended:
+            out.put("fee_universe_hits", np.zeros(0, dtype=lfu.FILE_HIT))
         out.close(pixel_layout if isinstance(pixel_layout, str) else None if pixel_layout is None else list(pixel_layout))
     finally:
         lib.set_option("mc_current", 0)
@@ -669,7 +716,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
 
 def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field, light_lut,
                      light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None,
-                     dist=None, keyed=False, pixel_truth_min=None, pixel_waveforms_sel=None):
+                     dist=None, keyed=False, pixel_truth_min=None, pixel_waveforms_sel=None, fee_universes=None):
     """One pass of the driver's module loop body (cli/simulate_pixels.py:717-1232) on the device-resident chain: quench + drift,
     light leg, charge chain, packets.  ``tracks``: the module's active segments (all active segments without module
     variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out).
@@ -986,6 +1033,12 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
         out.append("pixel_waveforms", rows)
         out.append("pixel_waveform_samples", samples)
 
+    def export_fee_universes():
+        """--fee_universes: the last launch digitised again under every universe (ChargeChain.fee_universes), as hit rows"""
+        if fee_universes is None:
+            return
+        out.append("fee_universe_hits", lfu.file_rows(chain.fee_universes(fee_universes), event_of_batch))
+
     def export_pixel_truth():
         """--pixel_truth: the last launch's pixel charge truth (ChargeChain.pixel_truth) as rows of the file's two datasets;
         segment ids mapped like mc_packets_assn's (packets.compact_to_rows), track_begin counted over the whole file"""
@@ -1030,6 +1083,7 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
             prev = chain.download_compact()
             export_pixel_truth()
             export_pixel_waveforms()
+            export_fee_universes()
         if prev is not None:
             export_chunk_compact(prev)
         launches = []
@@ -1037,6 +1091,7 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
         chain.run(int(b), int(e), want_fractions=True)
         export_pixel_truth()
         export_pixel_waveforms()
+        export_fee_universes()
         if not overlapped:
             export_chunk(chain.download())
             continue

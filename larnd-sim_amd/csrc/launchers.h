@@ -66,6 +66,7 @@ int gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n_out);
 
 // ---- kernels_fee.hip ---------------------------------------------------------------------------------------------------
 int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0);
+int fee_launch_tables(ldsim_ctx* ctx, double dt, double rt, double* tab);
 int fee_clear_unwritten_fractions(ldsim_ctx* ctx, int64_t U, const int32_t* hit_count, const int64_t* tpm, double* fr);
 int fee_launch_track_pixel_map(ldsim_ctx* ctx, int64_t* map, const int32_t* upix, int64_t U, const int32_t* pixels,
                                const int32_t* dist, int64_t S, int P, int max_distance, int M);

@@ -433,6 +433,17 @@ struct ldsim_ctx {
   int64_t pw_n[2] = {0, 0};      // spans and samples of the compact form
   Event pw_ev[4];                // around the count kernel and around the fill kernel of the last pass (ldsim_chain_pixel_waveforms_ms)
   bool pw_filled = false;        // the last pass launched its fill kernel
+  // FEE universes (ldsim_chain_fee_universes, kernels_feeuni.hip) read the same launch under the same rule
+  DevBuf fu_dense;               // adc_list | adc_ticks | adc_digit, each f64 [n][U][A]
+  DevBuf fu_cnt;                 // hit_count i32 [n][U] | hit_off i32 [n][U] | totals i64 [n] | error word
+  DevBuf fu_uni;                 // the universes' constants [n] | their tap tables f64 [n][128]
+  DevBuf fu_rows;                // compact form: 24-byte hit rows of all universes, universe after universe | their charges f64
+  int64_t fu_gen = -1;           // chain launch (out_gen) the last pass ran on (-1: none)
+  int32_t fu_n = 0, fu_A = 0;    // universes and MAX_ADC_VALUES of the last pass
+  int64_t fu_U = 0;              // rows of its dense arrays
+  std::vector<int64_t> fu_hits, fu_row0;   // [n] hits of every universe; [n + 1] its first row in fu_rows
+  Event fu_ev[2];                // around pixel_adc_universes_kernel of the last pass (ldsim_chain_fee_universes_ms)
+  bool fu_timed = false;         // the last pass launched the kernel
   Event ev[8];
   double ms_current = 0, ms_adc = 0, ms_total = 0;
   double ms_weights = 0, ms_mac = 0, ms_fallback = 0;   // split path: per-kernel share of ms_current

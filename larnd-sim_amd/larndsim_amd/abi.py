@@ -56,6 +56,17 @@ class LdsimChainStats(C.Structure):
                 ("n_dfma_useful", C.c_int64)]
 
 
+class LdsimFeeVariation(C.Structure):
+    """include/ldsim.h LdsimFeeVariation (ldsim_chain_fee_universes): 112 bytes, absolute values"""
+    _fields_ = [("discrimination_threshold", C.c_double), ("gain", C.c_double), ("v_cm", C.c_double), ("v_ref", C.c_double),
+                ("v_pedestal", C.c_double), ("buffer_risetime", C.c_double),
+                ("reset_noise_charge", C.c_double), ("uncorrelated_noise_charge", C.c_double), ("discriminator_noise", C.c_double),
+                ("threshold_table_scale", C.c_double), ("threshold_table_offset", C.c_double), ("gain_table_scale", C.c_double),
+                ("adc_hold_delay", C.c_int32), ("adc_busy_delay", C.c_int32), ("reset_cycles", C.c_int32), ("pad", C.c_int32)]
+
+
+FEE_UNIVERSES_MAX = 64      # include/ldsim.h LDSIM_FEE_UNIVERSES_MAX
+
 ABI_VERSION = 8      # include/ldsim.h LDSIM_ABI_VERSION: the struct layouts of this file
 
 # slots of ldsim_debug_gform_census, in the order of include/ldsim.h's LDSIM_GC_* enum (tests/test_cpu_host.py compares the two)

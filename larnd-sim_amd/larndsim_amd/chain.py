@@ -333,6 +333,56 @@ class ChargeChain:
         lib.check(lib.load().ldsim_chain_pixel_waveforms_ms(self.ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def fee_universes(self, variations, dense=False):
+        """FEE universes of the last run() (``fee_universes``, ``ldsim_chain_fee_universes``): the launch digitised again under
+        each of ``variations`` (1 to 64 dicts of ``fee_universes.variation``: absolute values of threshold, gain, pedestal /
+        V_ref / V_cm, rise time, hold / busy / reset timing, the three noise charges, the pixel tables' scales and offset), from
+        the currents the launch left in HBM.  Returns one dict per universe: ``hit_rows`` (``comm.HIT_ROW``: batch, pixel, adc,
+        slot, tick -- the rows of ``download_compact()``), ``hit_charge`` and ``n_hits``; with ``dense=True`` also ``adc_list``,
+        ``adc_ticks_list``, ``adc_digit`` [U][A] and ``hit_count`` [U] in the row order of ``download()``.  Universe k equals,
+        bit for bit, a fresh run under ``consts`` patched to variation k.  A universe with a non-zero noise charge needs
+        ``seed_keyed`` and ``set_batch_keys``.  Backtracking fractions and ``track_pixel_map`` are not produced per universe.
+        Raises ``ValueError`` for variations ``fee_universes.validate`` refuses and ``LdsimError`` (LDSIM_ESTATE) under the rules
+        of ``pixel_truth``."""
+        from . import fee_universes as fu
+        from .comm import HIT_ROW
+        self._check_constants()
+        variations = list(variations)
+        fu.validate(variations)
+        L = lib.load()
+        n = len(variations)
+        arr = fu.pack(variations)
+        n_hits = (C.c_int64 * n)()
+        lib.check(L.ldsim_chain_fee_universes(self.ctx, arr, C.c_int32(n), n_hits))
+        U, A = int(self.stats.n_unique), consts.sim.MAX_ADC_VALUES
+        out = []
+        for k in range(n):
+            u = dict(n_hits=int(n_hits[k]), hit_rows=np.zeros(int(n_hits[k]), dtype=HIT_ROW), hit_charge=np.zeros(int(n_hits[k])))
+            lib.check(L.ldsim_chain_fee_universe_hits_download(self.ctx, C.c_int32(k), lib.ptr(u["hit_rows"]),
+                                                               lib.ptr(u["hit_charge"])))
+            if dense:
+                u.update(adc_list=np.zeros((U, A)), adc_ticks_list=np.zeros((U, A)), adc_digit=np.zeros((U, A)),
+                         hit_count=np.zeros(U, dtype=np.int32))
+                lib.check(L.ldsim_chain_fee_universe_download(self.ctx, C.c_int32(k), C.c_int64(U), lib.ptr(u["adc_list"]),
+                                                              lib.ptr(u["adc_ticks_list"]), lib.ptr(u["adc_digit"]),
+                                                              lib.ptr(u["hit_count"])))
+            out.append(u)
+        return out
+
+    def fee_universes_ms(self):
+        """HIP-event time of the last ``fee_universes`` pass's scan kernel in ms (timing tools)"""
+        a = C.c_double()
+        lib.check(lib.load().ldsim_chain_fee_universes_ms(self.ctx, C.byref(a)))
+        return a.value
+
+    def fee_variation_nominal(self):
+        """the variation of the constants frozen in the context (``ldsim_fee_variation_nominal``)"""
+        from . import fee_universes as fu
+        from .abi import LdsimFeeVariation
+        v = LdsimFeeVariation()
+        lib.check(lib.load().ldsim_fee_variation_nominal(self.ctx, C.byref(v)))
+        return fu.unpack(v)
+
     def download_async(self, fractions=None):
         """Start copying the results of the last run() to page-locked host arrays on the library's copy stream and return them
         at once (``ldsim_chain_download_async``): the next ``run()`` overlaps with the transfer.  The arrays hold the rows
