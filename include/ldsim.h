@@ -488,6 +488,13 @@ enum {
  * per-pair records with the functions the launch dealt the pairs by.  LDSIM_ESTATE if the last current stage did not run
  * that form, or its records are gone. */
 int ldsim_debug_gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n);
+/* Test seam.  The fused correlation launches (gcorr_fused_kernel<1>, <2>: a short second node batch in the first batch's pass)
+ * of the same call: out[0] = pairs of the launch, out[1], out[2] = pairs the two fused kernels were launched over; with
+ * n >= 3 + 4 pairs, for pair p at out[3 + 4 p]: its mark (1, 2 = the fused kernel that took it, 0 = none), and for a pair of two
+ * node batches with tables the cells listed by the first batch alone, by the second batch alone and by both (read back from the
+ * launch's records; zeros for other pairs).  LDSIM_ESTATE if the last current stage did not run that form, its records are
+ * gone, or the marks and the launched counts disagree. */
+int ldsim_debug_gform_fused(ldsim_ctx* ctx, int64_t* out, int32_t n);
 
 /* Fused a5-a16 (max_pixels .. digitize) on resident segments [seg_begin, seg_end):
  * per unique (batch, pixel), sorted by batch then pixel id exactly like the reference's concatenated

@@ -59,7 +59,7 @@ struct GInfo {
   int32_t emask;                                                // written by gtables_kernel: the edges some slice is invalid at
   int32_t wave_ok;                                              // gtables_wave_kernel takes the pair (one chunk of slices): 1 = <= 128 shifts, X | Y bins <= 54,
                                                                 // 2 = <= 256 / <= 80 (its wide instantiation, over a list); 0 = gtables_kernel
-  int32_t pad;
+  int32_t fused;                                                // written by gbig_list_kernel: 1, 2 = a pair of gcorr_fused_kernel<1> / <2> (the launch over all pairs leaves it out), else 0 (pair_setup_kernel)
   unsigned long long off;                                       // record offset in doubles (exclusive scan of `size`)
   unsigned long long size;                                      // record size in doubles
 };

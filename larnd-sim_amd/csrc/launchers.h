@@ -63,6 +63,7 @@ int gtables_launch(ldsim_ctx* ctx, const GArgs& GA, int M, const int32_t* wg_lis
 int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters, int32_t** flags_out,
                  const int32_t** flag_list, const unsigned long long** flag_count);
 int gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t n_out);
+int gform_fused_report(ldsim_ctx* ctx, int64_t* out, int32_t n_out);
 
 // ---- kernels_fee.hip ---------------------------------------------------------------------------------------------------
 int fee_launch_chain(ldsim_ctx* ctx, const FeeArgs& F0);

@@ -844,6 +844,13 @@ extern "C" int ldsim_debug_gform_census(ldsim_ctx* ctx, int64_t* counts, int32_t
   return gform_census(ctx, counts, n);
 }
 
+extern "C" int ldsim_debug_gform_fused(ldsim_ctx* ctx, int64_t* out, int32_t n) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && out && n >= 3, "bad gform fused report arguments");
+  HIPCHK(hipSetDevice(ctx->device));
+  return gform_fused_report(ctx, out, n);
+}
+
 extern "C" int ldsim_tracks_current_mc(ldsim_ctx* ctx, const void* tracks, int64_t n, const LdsimTrackLayout* layout,
                                        const int32_t* pixels, int32_t P, float* signals, int32_t T) {
   LDSIM_ENTER(ctx);

@@ -299,7 +299,9 @@ struct ldsim_ctx {
     int valid = 0, M = 0, TT = 0, b0 = 0, b1 = 0, b2 = 0, Mz = 0, qb[3] = {0, 0, 0}, wave_tables = 1;
     int64_t n = 0;
     unsigned long long n_wg = 0, n_w2 = 0, n_cls[3] = {0, 0, 0};
+    unsigned long long n_fused[2] = {0, 0};          // pairs gcorr_fused_kernel<1> / <2> were launched over
     const void *gi = nullptr, *flags = nullptr;      // (aliases of the two scratch buffers, compared only)
+    const void* rec = nullptr;                       // (the record pool, SB_GREC: ldsim_debug_gform_fused reads the cell lists from it)
   } gform_rec;
   int split_kernels = 1;            // 1: weights_kernel + mac_kernel (default), 0: monolithic current_kernel
   int wbuf_doubles_per_pair = 6144; // initial average budget of the split path's weight pool, doubles per pair

@@ -69,6 +69,20 @@ def gform_census(per_pair=False, n_pairs=None):
     return out
 
 
+def gform_fused(n_pairs):
+    """The fused correlation launches of the last ``tracks_current`` / chain launch (``ldsim_debug_gform_fused``): a dict with
+    ``launched`` (pairs the two fused kernels ran over), and per pair ``mark`` (1, 2: the fused kernel that took it; 0: none),
+    ``only0``, ``only1``, ``both`` (cells listed by the first node batch alone, by the second alone, by both; pairs of two
+    node batches)."""
+    ctx = lib.context(refresh_consts=False)
+    c = np.zeros(3 + 4 * int(n_pairs), dtype=np.int64)
+    lib.check(lib.load().ldsim_debug_gform_fused(ctx, lib.ptr(c), C.c_int32(c.size)))
+    assert int(c[0]) == int(n_pairs)
+    per = c[3:].reshape(-1, 4)
+    return {"launched": (int(c[1]), int(c[2])), "mark": per[:, 0].copy(), "only0": per[:, 1].copy(), "only1": per[:, 2].copy(),
+            "both": per[:, 3].copy()}
+
+
 @kernel
 def tracks_current_mc(signals, pixels, tracks, response, rng_states):
     """``tracks_current_mc[bpg, tpb](signals, pixels, tracks, response, rng_states)`` -- the reference driver's call site
