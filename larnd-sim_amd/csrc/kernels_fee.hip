@@ -63,18 +63,43 @@ __device__ __forceinline__ void fee_sync() {
   }
 }
 
+// How a pixel's rows are requested.  The rows of a pixel are known once its slot rows have arrived and depend on nothing else, so
+// the loads of a group of slots are issued together, ahead of one wait, with addresses clamped into the slot's own row [0, T)
+// (every load is valid) and the window test at the add.  A term outside its window adds a literal +0.0: a sum that starts at +0.0
+// and only adds is never -0.0, so x + (+0.0) == x to the bit and the result is S[t] += (double)wf[t] over the windows, in slot order.
+#define FEE_RG 5      // one-wave form: slots per group ...
+#define FEE_RS 4      // ... and 64-tick stripes per slot held in registers (a window of <= 193 ticks touches at most four)
+#define FEE_LG 4      // LDS form: slots per pass over a thread's ticks
+#define FEE_FT 2      // fractions: terms of a lane per slot and pass, over 4 slots per group (one-wave form) or 2
+static_assert(FEE_SPAN == 512 && FEE_RS == 4, "pixel_adc_body's register form: eight stripes, a slot's first one of 0..4");
+
+// element it of a row of T = Tm1 + 1 elements, the index clamped into the row; the byte offset in 32 bits, so the load takes the
+// row's address from scalar registers and one VGPR
+__device__ __forceinline__ float fee_row_load(const float* row, int it, int Tm1) {
+  return *(const float*)((const char*)row + ((unsigned)min(max(it, 0), Tm1) << 2));
+}
+// the term of stripe m of a slot: rel0 = the lane's tick of the slot's first stripe minus the window's first tick, wd = its width
+__device__ __forceinline__ double fee_term(float x, int rel0, int m, unsigned wd) {
+  return (double)((unsigned)(rel0 + 64 * m) < wd ? x : 0.0f);
+}
+
 // Two instantiations.  THREADS = 256, the whole tick axis in LDS (16-26 KB: eight pixels per CU), for every pixel when noise is on
 // (the scan then walks every tick) and for pixels whose slots' windows span more than FEE_SPAN ticks.  THREADS = 64 -- a wave per
 // pixel, FEE_SPAN ticks of LDS starting at the pixel's first written tick -- for the others, over a list (fee_setup_kernel).  The
 // kernel is a chain of dependent trips to memory per pixel, so what counts is pixels in flight -- a CU holds 2048 threads: 8
-// pixels of 256 threads, 19 of 64 at 8.4 KB each -- and the length of the chain: header (scalar loads; the list form fetches the
-// next pixel's while this one is worked on) -> slot rows and launch constants, one trip -> waveform rows.  Counting the keys,
-// the slots' starts and windows, the tick range and the batch are the set-up pass's work, done once per pixel there.
+// pixels of 256 threads, 20 of 64 at 7.9 KB and at most 96 VGPRs each -- and the length of the chain: header (scalar loads; the
+// list form fetches the next pixel's while this one is worked on) -> slot rows, launch constants and pixel id, one trip -> waveform
+// rows, a group of slots per trip (above).  Counting the keys, the slots' starts and windows, the tick range and the batch are the
+// set-up pass's work, done once per pixel there.
 template <int THREADS, bool KEYED = false>
 __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const FeeHdr& H, const FeeSlot* __restrict__ slots, const bool windowed,
                                                const int s_cap) {
   const FeeK* c = &F.k;          // (kernel arguments: scalar registers, no loads)
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // (the thread index taken anew per pixel: what follows from it -- a dozen LDS and row addresses -- is a few instructions to form and
+  // would otherwise sit in VGPRs across the list kernel's loop over pixels, beside the rows in flight)
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wv = THREADS == 64 ? 0 : tid >> 6;
   const int NT = c->n_time_ticks;
   const int A = c->max_adc_values, M = c->max_tracks_per_pixel;
   const double dt = c->time_sampling, rt = c->buffer_risetime;
@@ -88,9 +113,18 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const FeeHdr& H
   const int64_t u = H.u, p0 = H.p0;
   const int n_slots = H.n_slots;
   const int ntap = rt > 0 ? (int)ceil(10 * rt / dt) : 0;  // floor(ic - 10*rt/dt) == ic - ceil(10*rt/dt)
+  // the pixel id goes with the pixel's first loads, the two table entries as soon as it is there: not a trip each ahead of the
+  // scan and of the stores
+  // (read through a lane offset of 0 the compiler cannot see through: taken for wave-uniform, the id would be moved to a scalar
+  // register on the spot, which waits for the load; always read -- a branch around it put the wait inside the branch)
+  // (the keyed instance does want it scalar: its stream key is 64-bit integer arithmetic on the id)
+  int lane0 = 0;
+  if (!KEYED) asm volatile("" : "+v"(lane0));
+  const int32_t pix = F.upix[u + lane0];
   // slots: pairs whose ring code is valid, at most M (detsim.py:582-607), in the order of the sorted pair list
+  FeeSlot sl{0, 0, 0, 0};
   if (tid < n_slots) {
-    const FeeSlot sl = slots[p0 + tid];
+    sl = slots[p0 + tid];
     s_start[tid] = sl.start;
     s_w0[tid] = sl.w0;
     s_w1[tid] = sl.w1;
@@ -102,28 +136,103 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const FeeHdr& H
     wtap[tid] = F.tab[tid];
     G[tid] = F.tab[64 + tid];
   }
-  // ---- summed waveform: each thread owns ticks tid, tid+256, ... and adds the slots' rows in slot order, each over the ticks
-  // its window puts on the pixel's time axis (detsim.py:516-520) ------------------------------------------------------------
+  // ---- summed waveform: each thread owns ticks of the pixel's time axis and adds the slots' rows in slot order, each over the
+  // ticks its window puts there (detsim.py:516-520); two forms, the same sums to the bit ----------------------------------------
   // the ticks S holds: all of them, or the pixel's window from the set-up pass (every slot's ticks lie inside it)
   const int s_lo = windowed ? H.s_lo : 0;
   const int s_hi = windowed ? min(s_lo + s_cap, NT) : NT;
-  for (int t = tid; t < s_hi - s_lo; t += THREADS) S[t] = 0;
-  fee_sync<THREADS>();
-  for (int k = 0; k < n_slots && !FEEDBG(0x10000); k++) {
-    const int st = s_start[k];
-    const int lo = max(st + s_w0[k], 0), hi = min(st + s_w1[k], NT);
-    const float* wf = F.waves + (p0 + k) * (int64_t)F.T - st;
-    for (int t = lo + ((tid - lo) & (THREADS - 1)); t < hi; t += THREADS) S[t - s_lo] += (double)wf[t];
+  const double thr = F.thr_table ? F.thr_table[pix] : F.threshold;
+  const double gain = F.gain_table ? F.gain_table[pix] : c->gain * (1e-3 * (1e-6 * 1.0)) / 1.0;   // GAIN * mV / e
+  const int Tm1 = F.T - 1;
+  // one-wave form, registers: lane l owns the ticks s_lo + l + 64 j, j < 8, of the FEE_SPAN ticks S holds, and keeps their sums in
+  // registers: no clear pass, no read-modify-write of LDS, one LDS store per tick for the scan.  A slot's rows are loaded over
+  // FEE_RS stripes from the one its window starts in (at most the fifth, so that they end inside the eight); the slot rows stay in
+  // the lanes that loaded them (v_readlane).  Not for a pixel with a window over more than FEE_RS stripes: the LDS form takes it.
+  bool in_regs = false;
+  if (THREADS == 64 && windowed && s_cap == FEE_SPAN) {
+    const int lo = max(sl.start + sl.w0, 0), hi = min(sl.start + sl.w1, NT);
+    in_regs = __ballot(tid < n_slots && hi > lo && ((hi - 1 - s_lo) >> 6) > min((lo - s_lo) >> 6, 4) + FEE_RS - 1) == 0;
+  }
+  if (THREADS == 64 && in_regs) {
+    // (eight named sums, not an array: indexed by a slot's first stripe the array would leave the registers)
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0, a6 = 0, a7 = 0;
+    for (int k0 = 0; k0 < n_slots && !FEEDBG(0x10000); k0 += FEE_RG) {
+      float x[FEE_RG][FEE_RS];
+      int rel0[FEE_RG], j0[FEE_RG];
+      unsigned wd[FEE_RG];
+      // every load of the group, then the adds in slot order
+#pragma unroll
+      for (int g = 0; g < FEE_RG; g++) {
+        const int k = min(k0 + g, n_slots - 1);      // (past the last slot: its row again, no width)
+        const int st = __builtin_amdgcn_readlane(sl.start, k);
+        const int lo = max(st + __builtin_amdgcn_readlane(sl.w0, k), 0), hi = min(st + __builtin_amdgcn_readlane(sl.w1, k), NT);
+        const float* wf = F.waves + (p0 + k) * (int64_t)F.T;
+        wd[g] = (k0 + g < n_slots && hi > lo) ? hi - lo : 0;
+        j0[g] = min(max((lo - s_lo) >> 6, 0), FEE_SPAN / 64 - FEE_RS);
+        const int t0 = s_lo + 64 * j0[g] + lane;
+        rel0[g] = t0 - lo;
+#pragma unroll
+        for (int m = 0; m < FEE_RS; m++) x[g][m] = fee_row_load(wf, t0 + 64 * m - st, Tm1);
+      }
+#pragma unroll
+      for (int g = 0; g < FEE_RG; g++) {
+#define FEE_ADD4(A, B, C, D)                  \
+  A += fee_term(x[g][0], rel0[g], 0, wd[g]);  \
+  B += fee_term(x[g][1], rel0[g], 1, wd[g]);  \
+  C += fee_term(x[g][2], rel0[g], 2, wd[g]);  \
+  D += fee_term(x[g][3], rel0[g], 3, wd[g]);
+        switch (j0[g]) {
+          case 0: FEE_ADD4(a0, a1, a2, a3) break;
+          case 1: FEE_ADD4(a1, a2, a3, a4) break;
+          case 2: FEE_ADD4(a2, a3, a4, a5) break;
+          case 3: FEE_ADD4(a3, a4, a5, a6) break;
+          default: FEE_ADD4(a4, a5, a6, a7) break;
+        }
+#undef FEE_ADD4
+      }
+    }
+    const double acc[FEE_SPAN / 64] = {a0, a1, a2, a3, a4, a5, a6, a7};
+#pragma unroll
+    for (int j = 0; j < FEE_SPAN / 64; j++) S[lane + 64 * j] = acc[j];
+  } else {
+    // LDS form (256 threads: thread t owns ticks t, t + 256, ...): each thread adds into its own ticks of S, FEE_LG slots per
+    // pass over the ticks the group's windows cover, their loads ahead of the pass's one read and write of S
+    for (int t = tid; t < s_hi - s_lo; t += THREADS) S[t] = 0;
+    fee_sync<THREADS>();
+    for (int k0 = 0; k0 < n_slots && !FEEDBG(0x10000); k0 += FEE_LG) {
+      const float* wf[FEE_LG];
+      int st[FEE_LG], lo[FEE_LG];
+      unsigned wd[FEE_LG];
+      int g_lo = NT, g_hi = 0;
+#pragma unroll
+      for (int g = 0; g < FEE_LG; g++) {
+        const int k = min(k0 + g, n_slots - 1);      // (past the last slot: its row again, no width)
+        st[g] = s_start[k];
+        lo[g] = max(st[g] + s_w0[k], 0);
+        const int hi = min(st[g] + s_w1[k], NT);
+        wd[g] = (k0 + g < n_slots && hi > lo[g]) ? hi - lo[g] : 0;
+        wf[g] = F.waves + (p0 + k) * (int64_t)F.T;
+        if (wd[g]) { g_lo = min(g_lo, lo[g]); g_hi = max(g_hi, hi); }
+      }
+      for (int t = g_lo + ((tid - g_lo) & (THREADS - 1)); t < g_hi; t += THREADS) {
+        float x[FEE_LG];
+#pragma unroll
+        for (int g = 0; g < FEE_LG; g++) x[g] = fee_row_load(wf[g], t - st[g], Tm1);
+        double s = S[t - s_lo];
+#pragma unroll
+        for (int g = 0; g < FEE_LG; g++) s += (double)((unsigned)(t - lo[g]) < wd[g] ? x[g] : 0.0f);
+        S[t - s_lo] = s;
+      }
+    }
   }
   fee_sync<THREADS>();
   // ---- trigger scan on wave 0 ----------------------------------------------------------------------------------------
   int nh = 0;
   if (wv == 0) {
-    const double thr = F.thr_table ? F.thr_table[F.upix[u]] : F.threshold;
     int nd = 0;
     if (FEEDBG(0x20000)) {
     } else if (KEYED) {
-      const KeyedNoise zs{F.rng_seed, key_mix(F.batch_keys[H.ubatch], (uint64_t)(int64_t)F.upix[u])};
+      const KeyedNoise zs{F.rng_seed, key_mix(F.batch_keys[H.ubatch], (uint64_t)(int64_t)pix)};
       nh = adc_scan(c, S, NT, 1 * c->time_interval1, thr, F.time_padding, lane, hits, wtap, ntap, zs, &nd, H.t_lo, H.t_hi, s_lo, s_hi);
     } else {
       const TableNoise zs{F.noise_z ? F.noise_z + u * (int64_t)F.noise_nd : nullptr};
@@ -136,7 +245,6 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const FeeHdr& H
   }
   fee_sync<THREADS>();
   if (THREADS != 64) nh = s_nh;
-  const double gain = F.gain_table ? F.gain_table[F.upix[u]] : c->gain * (1e-3 * (1e-6 * 1.0)) / 1.0;   // GAIN * mV / e
   for (int h = tid; h < A; h += THREADS) {
     double q = h < nh ? hits[h].q : 0.0;
     F.adc_list[u * A + h] = q;
@@ -151,23 +259,61 @@ __device__ __forceinline__ void pixel_adc_body(const FeeArgs& F, const FeeHdr& H
   // ---- backtracking fractions (fee.py:572-573, 633-635): sum_jc sig_k[jc]*G[min(ntap, b-jc)] / true_q ------------
   if (F.fractions && !FEEDBG(0x40000)) {
     double* fr = F.fractions + u * (int64_t)A * M;       // zero on entry (one memset of the whole array by the launcher)
-    for (int k = wv; k < n_slots; k += THREADS / 64) {      // (a wave per slot)
-      const float* wf = F.waves + (p0 + k) * (int64_t)F.T;
-      const int st = s_start[k];
+    // a wave per slot, FEE_FG slots of the wave per group: for a hit, FEE_FT terms of a lane in each of the group's slots are loaded
+    // together (the rows are warm in L2 from the sum), then multiplied and added -- the lane's terms in ascending order, the test at
+    // the multiply-add -- before the wave sums
+    constexpr int NW = THREADS / 64, FEE_FG = THREADS == 64 ? 4 : 2;
+    for (int k0 = wv; k0 < n_slots; k0 += FEE_FG * NW) {
+      const float* wf[FEE_FG];
+      int st[FEE_FG], w0[FEE_FG], w1[FEE_FG];
+#pragma unroll
+      for (int g = 0; g < FEE_FG; g++) {
+        const int k = min(k0 + g * NW, n_slots - 1);      // (past the last slot: its row again, no terms)
+        wf[g] = F.waves + (p0 + k) * (int64_t)F.T;
+        st[g] = s_start[k];
+        w0[g] = st[g] + s_w0[k];
+        w1[g] = k0 + g * NW < n_slots ? st[g] + s_w1[k] - 1 : -(1 << 30);
+      }
       for (int h = 0; h < nh; h++) {
-        int lr = hits[h].lr, b = hits[h].b;
-        int hi = b < NT - 1 ? b : NT - 1;
+        const int lr = hits[h].lr, b = hits[h].b;
+        const int hi = b < NT - 1 ? b : NT - 1;
         // (the ticks of the hit span the slot's window covers: a first hit's span starts at tick 0, a thousand ticks before
         // any window; same terms in the same lane-strided order)
-        const int j0 = max(lr, st + s_w0[k]), j1 = min(hi, st + s_w1[k] - 1);
-        double acc = 0;
-        for (int jc = j0 + ((lr + lane - j0) & 63); jc <= j1; jc += 64) {
-          int it = jc - st;
-          int d = b - jc;
-          acc += (double)wf[it] * (rt > 0 ? G[d < ntap ? d : ntap] : dt);
+        int jc0[FEE_FG], j1[FEE_FG];
+        double acc[FEE_FG];
+        int span = -1;
+#pragma unroll
+        for (int g = 0; g < FEE_FG; g++) {
+          const int j0 = max(lr, w0[g]);
+          j1[g] = min(hi, w1[g]);
+          jc0[g] = j0 + ((lr + lane - j0) & 63);
+          span = max(span, j1[g] - j0);
+          acc[g] = 0;
         }
-        acc = wave_sum(acc);
-        if (lane == 0) fr[h * M + k] = hits[h].tq > 0 ? acc / hits[h].tq : acc;
+        for (int o = 0; o <= span; o += 64 * FEE_FT) {
+          float x[FEE_FG][FEE_FT];
+#pragma unroll
+          for (int g = 0; g < FEE_FG; g++)
+#pragma unroll
+            for (int i = 0; i < FEE_FT; i++) x[g][i] = fee_row_load(wf[g], jc0[g] + o + 64 * i - st[g], Tm1);
+#pragma unroll
+          for (int g = 0; g < FEE_FG; g++)
+#pragma unroll
+            for (int i = 0; i < FEE_FT; i++) {
+              const int jc = jc0[g] + o + 64 * i;
+              const int d = min(max(b - jc, 0), ntap);
+              const double w = G[d];      // (buffer_risetime 0: ntap = 0 and G[0] = dt)
+              // (a term past the span adds +0.0, as in the sum: acc starts at +0.0 and is never -0.0)
+              const double term = (double)x[g][i] * w;
+              acc[g] += jc <= j1[g] ? term : 0.0;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < FEE_FG; g++) {
+          if (k0 + g * NW >= n_slots) break;
+          const double a = wave_sum(acc[g]);
+          if (lane == 0) fr[h * M + k0 + g * NW] = hits[h].tq > 0 ? a / hits[h].tq : a;
+        }
       }
     }
   }
@@ -181,8 +327,11 @@ __global__ void __launch_bounds__(THREADS) pixel_adc_kernel(FeeArgs F, const Fee
 }
 // a fixed grid walks a device-built list of pixels' headers (its length stays on the device: no host round trip to size the
 // launch); the next pixel's header is on its way while this one is worked on
+// (waves per SIMD asked of the register allocator: the five one-wave workgroups per SIMD that 7.9 KB of LDS allow, <= 96 VGPRs; the
+// seven of the 256-thread form before its loads were grouped, <= 72)
 template <int THREADS, bool KEYED = false>
-__global__ void __launch_bounds__(THREADS) pixel_adc_list_kernel(FeeArgs F, const FeeHdr* __restrict__ list,
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS == 64 ? 5 : 7)))
+pixel_adc_list_kernel(FeeArgs F, const FeeHdr* __restrict__ list,
                                                                 const unsigned long long* __restrict__ count,
                                                                 const FeeSlot* __restrict__ slots, bool windowed, int s_cap) {
   const int64_t n = (int64_t)*count;
