@@ -666,6 +666,51 @@ int ldsim_chain_fee_universe_download(ldsim_ctx* ctx, int32_t k, int64_t capacit
 int ldsim_chain_fee_universe_hits_download(ldsim_ctx* ctx, int32_t k, void* hit_rows, double* hit_charge);
 int ldsim_chain_fee_universes_ms(ldsim_ctx* ctx, double* scan_ms);
 
+/* ---- charge universes: the last chain launch re-weighted for recombination and lifetime --------------------------------
+ * Mirrors nothing in the reference, where a variation of a charge constant is another run.  Charge enters the induced
+ * current as one linear factor per segment, and neither the pair list nor the time windows read it, so a universe that only
+ * changes how many electrons a segment delivers is the launch's rows, each times one number per segment, summed and scanned
+ * again.  A charge variation holds absolute values: electron_lifetime, w_ion, box_alpha, box_beta, birks_ab, birks_kb and
+ * recomb_mode (1 = box, 2 = Birks, the mode of ldsim_dev_quench_drift; a universe may switch the model).
+ * Weights: for segment i of the launch's range, n_k[i] is what ldsim_dev_quench_drift would have stored in n_electrons under
+ * the universe's values, by the launch's own arithmetic (recombination at the field the resident quench read -- the map's E
+ * at the true midpoint when a map is set --, the column's truncating store, exp(-t_drift / lifetime) over the drift
+ * coordinate the drift used, the store again); w_k[i] = n_k[i] / n_res[i] in f64, n_res the resident column.  n_res == 0:
+ * weight 0, and the segment is counted (n_unweightable) when n_k != 0: its rows are zero and cannot be re-weighted.
+ * Segments outside every TPC and segments with batch < 0 have no pairs: weight 1.  Under the nominal variation
+ * (ldsim_charge_variation_nominal) the replay equals the resident column bit for bit and every weight is exactly 1.0.
+ * Sum: S_k[t] = sum over the pixel's slots of w_k[segment of the slot] * (double)row[t], in f64 and in slot order, each
+ * product rounded before it is added; windows and clipping as in the FEE universes pass.  The scan and everything behind it
+ * run on S_k with universe k's FEE variation, unchanged.
+ * Not varied: e_field and v_drift (they set the drift times: where the rows sit on the time axis), the diffusion constants
+ * (the rows' shapes), lar_density (redundant with birks_kb and box_beta), w_ph and the light leg (n_photons is not
+ * re-weighted).
+ * ldsim_chain_universes: n universes, universe k with fee[k] and charge[k].  fee == NULL: the nominal FEE variation for every
+ * universe.  charge == NULL: the call is exactly ldsim_chain_fee_universes(ctx, fee, n, n_hits).  The result is the universes
+ * result of the launch: ldsim_chain_fee_universe_download, ldsim_chain_fee_universe_hits_download and
+ * ldsim_chain_fee_universes_ms read it.  State, LDSIM_EINVAL and LDSIM_ENOMEM rules of ldsim_chain_fee_universes, and
+ * nothing of the launch is written.  Validation per universe, before anything is touched, the message naming the universe
+ * and the field: every field finite, electron_lifetime > 0, w_ion > 0, recomb_mode 1 or 2, pad == 0.  LDSIM_ESTATE with
+ * charge variations when the resident charge has no recorded mode (ldsim_dev_quench_drift records it; ldsim_segments_upload
+ * and ldsim_segments_reset forget it: segments uploaded already quenched cannot be replayed), when charge statistics are on
+ * (binomial draws are not linear in the constants), or under option mc_current.  A universe whose recombination comes out
+ * NaN for a segment returns LDSIM_EINVAL once the weights have been formed (the earlier result is gone by then).
+ * ldsim_chain_universe_weights_download (tests, tools): universe k's weights f64 [n_segments] (n_segments = the launch's
+ * range, else LDSIM_EINVAL; w may be NULL) and its count of unweightable segments; LDSIM_ESTATE when the last pass had no
+ * charge variations.  ldsim_chain_universes_weights_ms: HIP-event time of the weights kernel of the last pass.
+ * ldsim_chain_universe_waveforms_dense (tests, tools): f64 S_k of the rows [u_begin, u_end), S [u_end - u_begin][N_t],
+ * formed by the device function the scan kernel forms it with (after a pass without charge variations: the plain sum). */
+typedef struct LdsimChargeVariation {   /* 56 bytes; absolute values, not deltas */
+  double electron_lifetime, w_ion, box_alpha, box_beta, birks_ab, birks_kb;
+  int32_t recomb_mode, pad;
+} LdsimChargeVariation;
+int ldsim_charge_variation_nominal(ldsim_ctx* ctx, LdsimChargeVariation* out);
+int ldsim_chain_universes(ldsim_ctx* ctx, const LdsimFeeVariation* fee, const LdsimChargeVariation* charge, int32_t n,
+                          int64_t* n_hits);
+int ldsim_chain_universe_weights_download(ldsim_ctx* ctx, int32_t k, double* w, int64_t n_segments, int64_t* n_unweightable);
+int ldsim_chain_universes_weights_ms(ldsim_ctx* ctx, double* weights_ms);
+int ldsim_chain_universe_waveforms_dense(ldsim_ctx* ctx, int32_t k, int64_t u_begin, int64_t u_end, double* S);
+
 /* ---- device-resident light leg (cli/simulate_pixels.py:749-797 and :1120-1153 on the resident segments) ---------- */
 /* lightLUT.calculate_light_incidence[bpg,tpb](tracks, lut, light_sim_dat, track_light_voxel) over ALL resident segments,
  * after ldsim_dev_quench_drift (it needs n_photons and pixel_plane): n_photons_det [n][n_out] f4, t0_det [n][n_out] f4

@@ -107,6 +107,13 @@ def _parser():
                          "tables), the others as configured (datasets fee_universes and fee_universe_hits, "
                          "larndsim_amd/fee_universes.py); hits only: LArPix packets per universe are out of scope; universes with "
                          "noise need --rng keyed; one GPU only")
+    ap.add_argument("--charge_universes", default=None, metavar="FILE.json",
+                    help="also re-weight every chain launch for each universe of FILE.json, a list of {\"name\": ..., "
+                         "\"ELECTRON_LIFETIME\": ..., ...}: charge constants (ELECTRON_LIFETIME, W_ION, BOX_ALPHA, BOX_BETA, BIRKS_AB, "
+                         "BIRKS_KB, RECOMB_MODEL \"box\" or \"birks\") and any key of --fee_universes, so one file holds combined "
+                         "universes; the others as configured (datasets charge_universes and charge_universe_hits, "
+                         "larndsim_amd/charge_universes.py); hits only; a separate pass beside --fee_universes; not with "
+                         "--charge_statistics or --tracks_current_mc; universes with noise need --rng keyed; one GPU only")
     ap.add_argument("--light_lut_interpolation", default="nearest", choices=list(LIGHT_LUT_INTERPOLATION),
                     help="visibility of a segment from the light LUT: nearest (default; the voxel that holds the segment, like "
                          "the reference) or trilinear (interpolated between the eight voxel centres around it: no step in the "
@@ -120,6 +127,13 @@ LIGHT_LUT_INTERPOLATION = {"nearest": 0, "trilinear": 1}          # --light_lut_
 
 FEE_UNIVERSES_NEED_KEYED = ("--fee_universes: universe {} has a non-zero noise charge, and its normals come from the keyed "
                             "streams of the launch's pixels: give --rng keyed as well")
+
+CHARGE_UNIVERSES_NEED_KEYED = ("--charge_universes: universe {} has a non-zero noise charge, and its normals come from the keyed "
+                               "streams of the launch's pixels: give --rng keyed as well")
+CHARGE_UNIVERSES_NO_STATISTICS = ("--charge_universes is not available with --charge_statistics: binomial draws are not linear in "
+                                  "the constants, the launch cannot be re-weighted")
+CHARGE_UNIVERSES_NO_MC = ("--charge_universes is not available with --tracks_current_mc: its currents are sampled, not the rows "
+                          "that are re-weighted")
 
 CHARGE_STATISTICS_NEEDS_KEYED = ("--charge_statistics draws from keyed random streams (one per segment, whatever the "
                                  "chunking or rank count): give --rng keyed as well")
@@ -158,6 +172,20 @@ def _parse_args(argv=None):
         for k, (name, changes) in enumerate(entries):
             if lfu.changes_noisy(changes) and a.rng != "keyed":
                 ap.error(FEE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
+    if a.charge_universes is not None:
+        from larndsim_amd import charge_universes as lcu  # (standard library only)
+        from larndsim_amd import fee_universes as lfu
+        if a.charge_statistics:
+            ap.error(CHARGE_UNIVERSES_NO_STATISTICS)
+        if a.tracks_current_mc:
+            ap.error(CHARGE_UNIVERSES_NO_MC)
+        try:
+            entries = lcu.read(a.charge_universes)
+        except (OSError, ValueError) as e:
+            ap.error(f"--charge_universes {a.charge_universes}: {e}")
+        for k, (name, _, fee_changes) in enumerate(entries):
+            if lfu.changes_noisy(fee_changes) and a.rng != "keyed":
+                ap.error(CHARGE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
     return a
 
 
@@ -182,6 +210,9 @@ def launch_ranks_if_asked(argv=None):
     if world is not None and world > 1 and a["fee_universes"]:
         raise SystemExit("simulate_pixels.py: --fee_universes is not available with --n_gpus > 1 (its rows are not gathered "
                          "over the ranks)")
+    if world is not None and world > 1 and a["charge_universes"]:
+        raise SystemExit("simulate_pixels.py: --charge_universes is not available with --n_gpus > 1 (its rows are not gathered "
+                         "over the ranks)")
     if world is None or "WORLD_SIZE" in os.environ:
         return
     if os.path.exists(a["output_filename"]):
@@ -202,6 +233,7 @@ import numpy.lib.recfunctions as rfn  # noqa: E402
 from larndsim_amd import batching, charge_stats, consts, fee, light_sim, packets, synth  # noqa: E402
 from larndsim_amd import config as cfgmod  # noqa: E402
 from larndsim_amd import dist as ldist  # noqa: E402
+from larndsim_amd import charge_universes as lcu  # noqa: E402
 from larndsim_amd import fee_universes as lfu  # noqa: E402
 from larndsim_amd import field_map as lfmap  # noqa: E402
 from larndsim_amd import pixel_truth as lptruth  # noqa: E402
@@ -414,7 +446,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
                    fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, light_lut_interpolation="nearest",
                    pixel_waveforms=False, pixel_waveforms_threshold=None, pixel_waveforms_pad=None, pixel_waveforms_hits_only=False,
-                   fee_universes=None, **ignored):
+                   fee_universes=None, charge_universes=None, **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -438,6 +470,16 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         for k, (name, changes) in enumerate(lfu.read(fee_universes)):           # (the file's keys, before anything is simulated)
             if lfu.changes_noisy(changes) and rng != "keyed":
                 raise ValueError(FEE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
+    if world is not None and world > 1 and charge_universes:
+        raise ValueError("--charge_universes is not available with --n_gpus > 1: its rows are not gathered over the ranks")
+    if charge_universes is not None:
+        if charge_statistics:
+            raise ValueError(CHARGE_UNIVERSES_NO_STATISTICS)
+        if tracks_current_mc:
+            raise ValueError(CHARGE_UNIVERSES_NO_MC)
+        for k, (name, _, fee_changes) in enumerate(lcu.read(charge_universes)):   # (the file's keys, before anything is simulated)
+            if lfu.changes_noisy(fee_changes) and rng != "keyed":
+                raise ValueError(CHARGE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
     wave_sel = None
     if pixel_waveforms:
         wave_sel = (float(pixel_waveforms_threshold or 0.0), int(pixel_waveforms_pad or 0), bool(pixel_waveforms_hits_only))
@@ -590,6 +632,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
               f"--pixel_waveforms_pad {wave_sel[1]}" + (", --pixel_waveforms_hits_only)" if wave_sel[2] else ")"))
     if fee_universes is not None:       # (likewise)
         print("FEE universes:", f"{fee_universes} (--fee_universes; hits only, no packets per universe)")
+    if charge_universes is not None:    # (likewise)
+        print("Charge universes:", f"{charge_universes} (--charge_universes; hits only, no packets per universe)")
     print("Light LUT interpolation:", light_lut_interpolation if light_lut_interpolation == "nearest"
           else f"{light_lut_interpolation} (--light_lut_interpolation {light_lut_interpolation})")
     lib.set_option("numba_f32", f32_mode)
@@ -602,7 +646,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         n_rccl, r_rccl = dist.count()
         if (n_rccl, r_rccl) != (world, rank):
             raise RuntimeError(f"rank {rank} of {world}: the RCCL communicator reports rank {r_rccl} of {n_rccl}")
-    universes_written = False
+    universes_written = charge_universes_written = False
     try:
         for i_mod in mod_ids:                                       # convention: module ids count from 1 (:676-715)
             if m2m:
@@ -652,11 +696,22 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                 if not universes_written:                               # (once: with module variation, the first module's values)
                     out.put("fee_universes", lfu.universe_rows(uni_names, universes))
                     universes_written = True
+            cuni = None
+            if charge_universes is not None:
+                # every universe is this module's constants (and the driver's recombination model) with the file's keys applied
+                cu_names, cu_charge, cu_fee = lcu.load(charge_universes, consts.physics.BIRKS)
+                for k, v in enumerate(cu_fee):
+                    if lfu.is_noisy(v) and rng != "keyed":
+                        raise ValueError(CHARGE_UNIVERSES_NEED_KEYED.format(f"{k} ({cu_names[k]})"))
+                if not charge_universes_written:                        # (once: with module variation, the first module's values)
+                    out.put("charge_universes", lcu.universe_rows(cu_names, cu_charge, cu_fee))
+                    charge_universes_written = True
+                cuni = (cu_fee, cu_charge)
             res = _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field,
                                    per_module(light_lut_filename, i_mod) if light_simulated else None, light_det_noise_filename,
                                    cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist,
                                    keyed=rng == "keyed", pixel_truth_min=truth_min, pixel_waveforms_sel=wave_sel,
-                                   fee_universes=universes)
+                                   fee_universes=universes, charge_universes=cuni)
             for k in totals:
                 totals[k] += res[k]
             rows_per_rank += res["rows_per_rank"]
@@ -699,6 +754,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                     out.put(name, np.zeros(0, dtype=dt))
         if fee_universes is not None and "fee_universe_hits" not in out.appended:
             out.put("fee_universe_hits", np.zeros(0, dtype=lfu.FILE_HIT))
+        if charge_universes is not None and "charge_universe_hits" not in out.appended:
+            out.put("charge_universe_hits", np.zeros(0, dtype=lcu.FILE_HIT))
         out.close(pixel_layout if isinstance(pixel_layout, str) else None if pixel_layout is None else list(pixel_layout))
     finally:
         lib.set_option("mc_current", 0)
@@ -716,7 +773,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
 
 def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field, light_lut,
                      light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None,
-                     dist=None, keyed=False, pixel_truth_min=None, pixel_waveforms_sel=None, fee_universes=None):
+                     dist=None, keyed=False, pixel_truth_min=None, pixel_waveforms_sel=None, fee_universes=None,
+                     charge_universes=None):
     """One pass of the driver's module loop body (cli/simulate_pixels.py:717-1232) on the device-resident chain: quench + drift,
     light leg, charge chain, packets.  ``tracks``: the module's active segments (all active segments without module
     variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out).
@@ -1039,6 +1097,14 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
             return
         out.append("fee_universe_hits", lfu.file_rows(chain.fee_universes(fee_universes), event_of_batch))
 
+    def export_charge_universes():
+        """--charge_universes: the last launch re-weighted and digitised again under every universe (ChargeChain.universes), as
+        hit rows; a pass of its own beside --fee_universes"""
+        if charge_universes is None:
+            return
+        cu_fee, cu_charge = charge_universes
+        out.append("charge_universe_hits", lcu.file_rows(chain.universes(fee=cu_fee, charge=cu_charge), event_of_batch))
+
     def export_pixel_truth():
         """--pixel_truth: the last launch's pixel charge truth (ChargeChain.pixel_truth) as rows of the file's two datasets;
         segment ids mapped like mc_packets_assn's (packets.compact_to_rows), track_begin counted over the whole file"""
@@ -1084,6 +1150,7 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
             export_pixel_truth()
             export_pixel_waveforms()
             export_fee_universes()
+            export_charge_universes()
         if prev is not None:
             export_chunk_compact(prev)
         launches = []
@@ -1092,6 +1159,7 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
         export_pixel_truth()
         export_pixel_waveforms()
         export_fee_universes()
+        export_charge_universes()
         if not overlapped:
             export_chunk(chain.download())
             continue

@@ -3,6 +3,7 @@
 // SoA columns so every load/store is a coalesced 8-byte stream.
 #include "launchers.h"
 #include "rng.h"
+#include "seg_charge.h"   // recomb_at, fmap_eval
 
 // ---- AoS <-> SoA ------------------------------------------------------------------------------------------
 __device__ __forceinline__ double load_field(const unsigned char* rec, int off, int code) {
@@ -172,36 +173,6 @@ __global__ void __launch_bounds__(256) quench_drift_kernel(SegStore s, const Lds
 }
 
 // ---- drift-field map: quench at the local field, then drift the anode view ------------------------
-// Trilinear interpolation of the map at p, clamped to the edge nodes; a + f * (b - a) per axis (z, then y, then x), so a
-// constant map returns its constant exactly.  with_e = 0 leaves v[0] unset.
-__device__ __forceinline__ void fmap_eval(const FieldMapDesc& m, const double p[3], bool with_e, double v[4]) {
-  int64_t i0[3];
-  double f[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    double u = (p[a] - m.origin[a]) * m.inv_spacing[a];
-    u = fmin(fmax(u, 0.0), (double)(m.n[a] - 1));   // (fmax(NaN, 0) = 0: every index stays inside the grid)
-    const int k = min((int)u, m.n[a] - 2);
-    i0[a] = k;
-    f[a] = u - (double)k;
-  }
-  const int64_t sz = m.n[2], sy = (int64_t)m.n[1] * m.n[2];
-  const FieldMapNode* b = m.node + i0[0] * sy + i0[1] * sz + i0[2];
-  FieldMapNode q[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) q[k] = b[((k >> 2) & 1) * sy + ((k >> 1) & 1) * sz + (k & 1)];
-  auto lerp = [](double a0, double a1, double t) { return a0 + t * (a1 - a0); };
-  auto tri = [&](double FieldMapNode::*ch) {
-    const double c00 = lerp(q[0].*ch, q[1].*ch, f[2]), c01 = lerp(q[2].*ch, q[3].*ch, f[2]);
-    const double c10 = lerp(q[4].*ch, q[5].*ch, f[2]), c11 = lerp(q[6].*ch, q[7].*ch, f[2]);
-    return lerp(lerp(c00, c01, f[1]), lerp(c10, c11, f[1]), f[0]);
-  };
-  if (with_e) v[0] = tri(&FieldMapNode::e);
-  v[1] = tri(&FieldMapNode::dx);
-  v[2] = tri(&FieldMapNode::dy);
-  v[3] = tri(&FieldMapNode::dz);
-}
-
 // One thread per segment.  The TPC comes from the true midpoint; E at the midpoint replaces e_field in the recombination;
 // the start, end and midpoint move by (dx, dy, dz) at themselves, clamped into the TPC's box (never further out than the
 // true point already was) and rounded like the record's field; the drift reads the moved z.  The nine moved positions go
@@ -272,22 +243,6 @@ __device__ __forceinline__ double binomial_draw(double n, double p, float z, flo
     sum += q;
   }
   return p <= 0.5 ? j : n - j;
-}
-
-// quench_at's recombination factor alone: 0 = recomb set, 1 = unknown mode, 2 = NaN
-__device__ __forceinline__ int recomb_at(const LdsimConsts* __restrict__ c, int mode, double e_field, double dEdx,
-                                         double& recomb) {
-  recomb = 0;
-  if (mode == 1) {  // BOX
-    double csi = c->box_beta * dEdx / (e_field * c->lar_density);
-    double r = log(c->box_alpha + csi) / csi;
-    recomb = (r > 0) ? r : 0;
-  } else if (mode == 2) {  // BIRKS
-    recomb = c->birks_ab / (1 + c->birks_kb * dEdx / (e_field * c->lar_density));
-  } else {
-    return 1;
-  }
-  return isnan(recomb) ? 2 : 0;
 }
 
 // drift_at without n_electrons: widths and times written, the drift time returned

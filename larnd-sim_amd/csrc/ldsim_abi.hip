@@ -429,6 +429,7 @@ static int upload_tracks(ldsim_ctx* ctx, const void* tracks, int64_t n, const Ld
   ctx->seg.n = n;
   ctx->drift_map_gen = -1;
   ctx->drift_stat_on = -1;
+  ctx->drift_mode = 0;
   ctx->seg_owner = batch_id_is_resident ? 1 : 2;
   ctx->light_n = -1;
   ctx->seg_layout = *lay;
@@ -513,6 +514,7 @@ extern "C" int ldsim_segments_reset(ldsim_ctx* ctx) {
   ctx->light_n = -1;
   ctx->drift_map_gen = -1;
   ctx->drift_stat_on = -1;
+  ctx->drift_mode = 0;
   return seg_launch_unpack(ctx, &ctx->seg_layout, ctx->seg.n);
 }
 
@@ -594,7 +596,10 @@ extern "C" int ldsim_dev_quench_drift(ldsim_ctx* ctx, int32_t mode) {
   NEED_RESIDENT(ctx);
   CK(light_join(ctx));
   launch_invalidate(ctx, "ldsim_dev_quench_drift rewrote the resident segments since the launch");
-  return run_quench_drift(ctx, mode, 1, 1, ctx->n_fmap > 0, ctx->charge_stat != 0);
+  ctx->drift_mode = 0;
+  CK(run_quench_drift(ctx, mode, 1, 1, ctx->n_fmap > 0, ctx->charge_stat != 0));
+  ctx->drift_mode = mode;                   // (charge universes replay the quench under this mode's nominal constants)
+  return 0;
 }
 
 // ---- charge statistics -----------------------------------------------------------------------------------------------------
@@ -1567,7 +1572,11 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
     ldsim_set_error("chain_run: %s", e.what());
     rc = LDSIM_EINVAL;
   }
-  if (rc == 0) ctx->launch_stale = nullptr;
+  if (rc == 0) {
+    ctx->launch_stale = nullptr;
+    ctx->launch_seg[0] = seg_begin;
+    ctx->launch_seg[1] = seg_end;
+  }
   if (stats) *stats = ctx->stats;
   return rc;
 }

@@ -446,6 +446,16 @@ struct ldsim_ctx {
   std::vector<int64_t> fu_hits, fu_row0;   // [n] hits of every universe; [n + 1] its first row in fu_rows
   Event fu_ev[2];                // around pixel_adc_universes_kernel of the last pass (ldsim_chain_fee_universes_ms)
   bool fu_timed = false;         // the last pass launched the kernel
+  // charge universes (ldsim_chain_universes with charge variations, kernels_feeuni.hip): the same pass with per-segment weights
+  int drift_mode = 0;            // recombination mode of the ldsim_dev_quench_drift whose charge the store holds (0: none recorded)
+  int64_t launch_seg[2] = {0, 0};   // segment range of the last ldsim_charge_chain
+  DevBuf cu_w;                   // weights f64 [groups][segments of the launch] | unweightable counts | constants | grouping (cu_parts_of)
+  DevBuf cu_S;                   // rows of the last ldsim_chain_universe_waveforms_dense, f64 [u_end - u_begin][N_t]
+  std::vector<int32_t> cu_group; // [n] the charge group of every universe of the last pass (empty: it had no charge variations)
+  std::vector<unsigned long long> cu_unw;   // [groups] segments with n_res == 0 and n_k != 0
+  int64_t cu_nseg = 0;           // segments the weights cover
+  Event cu_ev[2];                // around charge_weights_kernel of the last pass (ldsim_chain_universes_weights_ms)
+  bool cu_timed = false;
   Event ev[8];
   double ms_current = 0, ms_adc = 0, ms_total = 0;
   double ms_weights = 0, ms_mac = 0, ms_fallback = 0;   // split path: per-kernel share of ms_current

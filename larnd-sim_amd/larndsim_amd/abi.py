@@ -65,6 +65,12 @@ class LdsimFeeVariation(C.Structure):
                 ("adc_hold_delay", C.c_int32), ("adc_busy_delay", C.c_int32), ("reset_cycles", C.c_int32), ("pad", C.c_int32)]
 
 
+class LdsimChargeVariation(C.Structure):
+    """include/ldsim.h LdsimChargeVariation (ldsim_chain_universes): 56 bytes, absolute values"""
+    _fields_ = [("electron_lifetime", C.c_double), ("w_ion", C.c_double), ("box_alpha", C.c_double), ("box_beta", C.c_double),
+                ("birks_ab", C.c_double), ("birks_kb", C.c_double), ("recomb_mode", C.c_int32), ("pad", C.c_int32)]
+
+
 FEE_UNIVERSES_MAX = 64      # include/ldsim.h LDSIM_FEE_UNIVERSES_MAX
 
 ABI_VERSION = 8      # include/ldsim.h LDSIM_ABI_VERSION: the struct layouts of this file

@@ -345,7 +345,6 @@ class ChargeChain:
         Raises ``ValueError`` for variations ``fee_universes.validate`` refuses and ``LdsimError`` (LDSIM_ESTATE) under the rules
         of ``pixel_truth``."""
         from . import fee_universes as fu
-        from .comm import HIT_ROW
         self._check_constants()
         variations = list(variations)
         fu.validate(variations)
@@ -354,6 +353,60 @@ class ChargeChain:
         arr = fu.pack(variations)
         n_hits = (C.c_int64 * n)()
         lib.check(L.ldsim_chain_fee_universes(self.ctx, arr, C.c_int32(n), n_hits))
+        return self._universe_results(n, n_hits, dense)
+
+    def fee_universes_ms(self):
+        """HIP-event time of the last ``fee_universes`` pass's scan kernel in ms (timing tools)"""
+        a = C.c_double()
+        lib.check(lib.load().ldsim_chain_fee_universes_ms(self.ctx, C.byref(a)))
+        return a.value
+
+    def fee_variation_nominal(self):
+        """the variation of the constants frozen in the context (``ldsim_fee_variation_nominal``)"""
+        from . import fee_universes as fu
+        from .abi import LdsimFeeVariation
+        v = LdsimFeeVariation()
+        lib.check(lib.load().ldsim_fee_variation_nominal(self.ctx, C.byref(v)))
+        return fu.unpack(v)
+
+    def universes(self, fee=None, charge=None, dense=False):
+        """Universes of the last run() (``charge_universes``, ``ldsim_chain_universes``): universe k is the launch re-weighted
+        for the charge variation ``charge[k]`` (dicts of ``charge_universes.variation``: absolute values of the electron
+        lifetime, W_ion, the box and Birks parameters, the recombination model) and digitised under the FEE variation
+        ``fee[k]`` (``fee_universes.variation``).  ``fee=None``: the nominal front end for every universe; ``charge=None``: the
+        call is ``fee_universes(fee)``.  Returns the list ``fee_universes`` returns; with ``charge`` every dict also holds
+        ``weights`` (f64 per segment of the launch's range: ``n_k / n_res``, what the replayed quench/drift stores over what
+        is resident) and ``n_unweightable`` (segments with no resident charge that the universe gives some).  Needs a plain
+        ``quench_drift`` (no charge statistics) since the upload.  Raises ``ValueError`` for variations the two ``validate``
+        refuse and ``LdsimError`` (LDSIM_ESTATE) under the rules of ``fee_universes``."""
+        from . import charge_universes as cu
+        from . import fee_universes as fu
+        if charge is None:
+            if fee is None:
+                raise ValueError("universes: give fee variations, charge variations or both")
+            return self.fee_universes(fee, dense=dense)
+        self._check_constants()
+        charge = list(charge)
+        cu.validate(charge)
+        n = len(charge)
+        c_arr, f_arr = cu.pack(charge), None
+        if fee is not None:
+            fee = list(fee)
+            if len(fee) != n:
+                raise ValueError(f"universes: {len(fee)} FEE variations for {n} charge variations")
+            fu.validate(fee)
+            f_arr = fu.pack(fee)
+        L = lib.load()
+        n_hits = (C.c_int64 * n)()
+        lib.check(L.ldsim_chain_universes(self.ctx, f_arr, c_arr, C.c_int32(n), n_hits))
+        out = self._universe_results(n, n_hits, dense)
+        for k, u in enumerate(out):
+            u["weights"], u["n_unweightable"] = self.universe_weights(k)
+        return out
+
+    def _universe_results(self, n, n_hits, dense):
+        from .comm import HIT_ROW
+        L = lib.load()
         U, A = int(self.stats.n_unique), consts.sim.MAX_ADC_VALUES
         out = []
         for k in range(n):
@@ -369,19 +422,38 @@ class ChargeChain:
             out.append(u)
         return out
 
-    def fee_universes_ms(self):
-        """HIP-event time of the last ``fee_universes`` pass's scan kernel in ms (timing tools)"""
+    def universe_weights(self, k):
+        """(weights f64 [segments of the launch's range], n_unweightable) of universe ``k`` of the last ``universes`` pass"""
+        n_seg = int(self.stats.n_segments)
+        w, nu = np.zeros(n_seg), C.c_int64()
+        lib.check(lib.load().ldsim_chain_universe_weights_download(self.ctx, C.c_int32(int(k)), lib.ptr(w), C.c_int64(n_seg),
+                                                                   C.byref(nu)))
+        return w, int(nu.value)
+
+    def universe_waveforms(self, k, rows=None):
+        """``S_k`` f64 [len(rows)][N_t] of universe ``k`` of the last ``universes`` pass, formed by the device code its scan read
+        (``ldsim_chain_universe_waveforms_dense``; tests and tools).  ``rows``: ``(begin, end)``, None: every row."""
+        U = int(self.stats.n_unique)
+        b, e = (0, U) if rows is None else rows
+        S = np.zeros((max(int(e) - int(b), 0), len(consts.detector.TIME_TICKS)))
+        lib.check(lib.load().ldsim_chain_universe_waveforms_dense(self.ctx, C.c_int32(int(k)), C.c_int64(int(b)), C.c_int64(int(e)),
+                                                                  lib.ptr(S)))
+        return S
+
+    def universes_weights_ms(self):
+        """HIP-event time of the last ``universes`` pass's weights kernel in ms (timing tools)"""
         a = C.c_double()
-        lib.check(lib.load().ldsim_chain_fee_universes_ms(self.ctx, C.byref(a)))
+        lib.check(lib.load().ldsim_chain_universes_weights_ms(self.ctx, C.byref(a)))
         return a.value
 
-    def fee_variation_nominal(self):
-        """the variation of the constants frozen in the context (``ldsim_fee_variation_nominal``)"""
-        from . import fee_universes as fu
-        from .abi import LdsimFeeVariation
-        v = LdsimFeeVariation()
-        lib.check(lib.load().ldsim_fee_variation_nominal(self.ctx, C.byref(v)))
-        return fu.unpack(v)
+    def charge_variation_nominal(self):
+        """the charge variation of the constants frozen in the context and the mode of the last ``quench_drift``
+        (``ldsim_charge_variation_nominal``)"""
+        from . import charge_universes as cu
+        from .abi import LdsimChargeVariation
+        v = LdsimChargeVariation()
+        lib.check(lib.load().ldsim_charge_variation_nominal(self.ctx, C.byref(v)))
+        return cu.unpack(v)
 
     def download_async(self, fractions=None):
         """Start copying the results of the last run() to page-locked host arrays on the library's copy stream and return them

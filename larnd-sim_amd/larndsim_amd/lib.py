@@ -43,6 +43,8 @@ EXPORTS = [
     "ldsim_chain_pixel_waveforms_ms",
     "ldsim_fee_variation_nominal", "ldsim_chain_fee_universes", "ldsim_chain_fee_universe_download",
     "ldsim_chain_fee_universe_hits_download", "ldsim_chain_fee_universes_ms",
+    "ldsim_charge_variation_nominal", "ldsim_chain_universes", "ldsim_chain_universe_weights_download",
+    "ldsim_chain_universes_weights_ms", "ldsim_chain_universe_waveforms_dense",
     "ldsim_chain_kernel_ms", "ldsim_chain_kernel_ms_detail",
     "ldsim_dev_light_incidence", "ldsim_dev_light_incidence_download", "ldsim_dev_light_t0_range", "ldsim_dev_sum_light",
     "ldsim_dev_light_download", "ldsim_light_kernel_ms",
