@@ -178,6 +178,8 @@ int ldsim_set_light_lut(ldsim_ctx* ctx, const float* vis, const float* t0, const
  * 64 of them: 1 (default) = by light_truth_lds_kernel, a wave's 64 output rows in LDS beside the plain sum; 0 = inside light_conv_kernel
  * on slot-major copies of the rows in memory -- same bits for rows of distinct ids in front of their first -1, and the only path
  * that follows light_sim.py:331-335 literally for other rows is the default),
+ * "light_universes_nu" (ldsim_dev_light_universes: weight tables that share an input go through light_conv_universes_kernel
+ * this many at a time, 2, 3 or 4 (default); 1 = one light_conv_kernel launch per table; same bits at every value),
  * "numba_f32" (1 = the sub-expressions Numba types float32 for f4 record fields are evaluated in float, detsim.py:74-79,
  * 116-118,141,387; 0 = all-f64, what the reference computes for f8 records and what the goldens pin; default 0),
  * "mc_current" (1 = the fused chain takes its induced currents from tracks_current_mc like the reference driver does;
@@ -749,6 +751,55 @@ int ldsim_dev_light_response_download(ldsim_ctx* ctx, float* scint, float* disc,
                                       int64_t* response_true_track_id, double* response_true_photons);
 /* HIP-event durations of the three stages of the last ldsim_dev_light_response */
 int ldsim_light_response_ms(ldsim_ctx* ctx, double* scint_ms, double* fluct_ms, double* response_ms);
+
+/* ---- light universes: the resident photon sum under varied light constants ---------------------------------------------------
+ * Mirrors nothing in the reference, where a variation of a light constant is another run.  Everything behind
+ * ldsim_dev_sum_light reads only the photon sum and a handful of constants, which enter as two host-tabulated weight tables and
+ * a gain per row; a universe is another pair of tables.  A light variation holds absolute values:
+ *   photon_scale        multiplies the resident photon sum (light yield, W_PH, SCINT_PRESCALE, a global efficiency); finite, > 0
+ *   singlet_fraction    SINGLET_FRACTION; finite, in [0, 1]
+ *   tau_s, tau_t        TAU_S, TAU_T; finite, > 0
+ *   gain_scale          multiplies LIGHT_GAIN[row]; finite, != 0
+ *   response_time, oscillation_period   LIGHT_RESPONSE_TIME, LIGHT_OSCILLATION_PERIOD; finite, > 0.  Under SIPM_RESPONSE_MODEL 1
+ *                       they are not read, and a value that differs from the context's is refused (a knob that does nothing)
+ * Universe k of the photon sum inc:  x_k = (float)((double)inc * photon_scale) (one rounding, exact at 1.0);  scint_k =
+ * calc_scintillation_effect of x_k under (singlet_fraction, tau_s, tau_t), without truth slots;  disc_k =
+ * calc_stat_fluctuations of scint_k under the context's current call key (fluctuate != 0), else scint_k;  resp_k =
+ * calc_light_detector_response of disc_k under (response_time, oscillation_period) or the impulse model, the row gain
+ * light_gain[d] * gain_scale formed once in f64.  Every array equals, bit for bit, what ldsim_dev_light_response gives on x_k
+ * under those constants and the same call key; the nominal universe equals the launch's own arrays.  photon_scale acts on the
+ * summed photons, not on n_photons before the f4 sums: a universe is not bit-equal to a fresh run under a changed W_PH.
+ * With keyed streams the draws of element (detector, tick) depend on the call key only, so all universes see the same random
+ * numbers.  Truth slots are not produced per universe.
+ * ldsim_dev_light_universes: n in [1, LDSIM_LIGHT_UNIVERSES_MAX]; needs a resident photon sum (LDSIM_ESTATE), and with
+ * fluctuate != 0 keyed streams (LDSIM_ESTATE: table-mode draws would advance the state table).  Every universe is validated
+ * before anything is touched, the message naming the universe and the field (LDSIM_EINVAL); a refused call leaves the earlier
+ * result in place.  Universes with byte-equal photon_scale share one input; within it equal (singlet_fraction, tau_s, tau_t)
+ * share one scint and one disc; per disc equal (gain_scale, response_time, oscillation_period) share one response: no stage
+ * runs twice on the same input with the same table, and tables that share an input go through light_conv_universes_kernel
+ * together.  resp_k stays resident for every k, scint_k and disc_k only with keep_stages != 0.  The launch's own arrays
+ * (ldsim_dev_light_response), its truth arrays and the call key are left as they were.  The result is invalidated by the next
+ * ldsim_dev_sum_light, ldsim_dev_light_response, ldsim_segments_upload and ldsim_segments_reset.
+ * ldsim_dev_light_universe_download: any pointer may be NULL; stages that were not kept: LDSIM_ESTATE.
+ * ldsim_dev_light_universe_triggers / _waveforms: ldsim_light_triggers / ldsim_sim_triggers on resp_k without truth slots.
+ * ldsim_light_universes_ms: HIP-event times of the three stages summed over the last ldsim_dev_light_universes. */
+#define LDSIM_LIGHT_UNIVERSES_MAX 64
+typedef struct LdsimLightVariation {   /* 56 bytes; absolute values, not deltas */
+  double photon_scale, singlet_fraction, tau_s, tau_t, gain_scale, response_time, oscillation_period;
+} LdsimLightVariation;
+int ldsim_light_variation_nominal(ldsim_ctx* ctx, LdsimLightVariation* out);
+int ldsim_dev_light_universes(ldsim_ctx* ctx, const LdsimLightVariation* v, int32_t n, const double* light_gain,
+                              const double* impulse_model, int32_t n_impulse, int32_t fluctuate, int32_t keep_stages);
+int ldsim_dev_light_universe_download(ldsim_ctx* ctx, int32_t k, float* scint, float* disc, float* response);
+int ldsim_dev_light_universe_triggers(ldsim_ctx* ctx, int32_t k, int32_t n_det, int32_t n_ticks, const double* group_threshold,
+                                      int32_t n_grp, const int32_t* row_module, int32_t n_mod, int64_t* trigger_idx,
+                                      int32_t* trigger_module, int64_t capacity, int64_t* n_trig);
+int ldsim_dev_light_universe_waveforms(ldsim_ctx* ctx, int32_t k, const int32_t* signal_op_channel_idx, int32_t n_det,
+                                       int32_t n_ticks, const int64_t* trigger_idx, int32_t n_trig,
+                                       const int32_t* trigger_op_channel_idx, int32_t n_det_trig, int32_t digit_samples,
+                                       const double* light_det_noise, int32_t n_noise_channels, int32_t n_noise_bins,
+                                       const double* phases_signal, const double* phases_missing, double* digit_signal);
+int ldsim_light_universes_ms(ldsim_ctx* ctx, double* scint_ms, double* fluct_ms, double* response_ms);
 
 /* ---- multi-GPU: the one exchange step of the batch-sharded path, RCCL over xGMI -------------------------------
  * One process per GPU; (event, TPC-group) batches are sharded over the ranks and never share a pixel, so the only

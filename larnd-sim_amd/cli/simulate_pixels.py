@@ -114,6 +114,14 @@ def _parser():
                          "universes; the others as configured (datasets charge_universes and charge_universe_hits, "
                          "larndsim_amd/charge_universes.py); hits only; a separate pass beside --fee_universes; not with "
                          "--charge_statistics or --tracks_current_mc; universes with noise need --rng keyed; one GPU only")
+    ap.add_argument("--light_universes", default=None, metavar="FILE.json",
+                    help="also run the light response of every sub-batch again under each universe of FILE.json, a list of "
+                         "{\"name\": ..., \"TAU_S\": ..., ...}: light constants by their names (SINGLET_FRACTION, TAU_S, TAU_T, "
+                         "LIGHT_RESPONSE_TIME, LIGHT_OSCILLATION_PERIOD) and PHOTON_SCALE, LIGHT_GAIN_SCALE, TRIG_THRESHOLD_SCALE, "
+                         "NOISE_SCALE, the others as configured (datasets light_universes, light_universe_trig and "
+                         "light_universe_wvfm, larndsim_amd/light_universes.py); all universes of a batch see the same random "
+                         "numbers; no truth slots per universe; needs --rng keyed and simulated light; not with module variation; "
+                         "one GPU only")
     ap.add_argument("--light_lut_interpolation", default="nearest", choices=list(LIGHT_LUT_INTERPOLATION),
                     help="visibility of a segment from the light LUT: nearest (default; the voxel that holds the segment, like "
                          "the reference) or trilinear (interpolated between the eight voxel centres around it: no step in the "
@@ -134,6 +142,13 @@ CHARGE_UNIVERSES_NO_STATISTICS = ("--charge_universes is not available with --ch
                                   "the constants, the launch cannot be re-weighted")
 CHARGE_UNIVERSES_NO_MC = ("--charge_universes is not available with --tracks_current_mc: its currents are sampled, not the rows "
                           "that are re-weighted")
+
+LIGHT_UNIVERSES_NEED_KEYED = ("--light_universes draws every universe's fluctuations and noise from the keyed streams of the "
+                              "batch, so that all universes see the same random numbers: give --rng keyed as well")
+LIGHT_UNIVERSES_NO_MULTI_GPU = "--light_universes is not available with --n_gpus > 1 (its rows are not gathered over the ranks)"
+LIGHT_UNIVERSES_NO_MODVAR = ("--light_universes is not available with module variation (a run with it writes per-module waveform "
+                             "datasets and merges them)")
+LIGHT_UNIVERSES_NEED_LIGHT = "--light_universes varies the light simulation, and light is not simulated in this run"
 
 CHARGE_STATISTICS_NEEDS_KEYED = ("--charge_statistics draws from keyed random streams (one per segment, whatever the "
                                  "chunking or rank count): give --rng keyed as well")
@@ -186,6 +201,18 @@ def _parse_args(argv=None):
         for k, (name, _, fee_changes) in enumerate(entries):
             if lfu.changes_noisy(fee_changes) and a.rng != "keyed":
                 ap.error(CHARGE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
+    if a.light_universes is not None:
+        from larndsim_amd import light_universes as llu  # (standard library only)
+        if a.rng != "keyed":
+            ap.error(LIGHT_UNIVERSES_NEED_KEYED)
+        if a.mod2mod_variation:
+            ap.error(LIGHT_UNIVERSES_NO_MODVAR)
+        if a.light_simulated is False:
+            ap.error(LIGHT_UNIVERSES_NEED_LIGHT)
+        try:
+            llu.read(a.light_universes)
+        except (OSError, ValueError) as e:
+            ap.error(f"--light_universes {a.light_universes}: {e}")
     return a
 
 
@@ -213,6 +240,8 @@ def launch_ranks_if_asked(argv=None):
     if world is not None and world > 1 and a["charge_universes"]:
         raise SystemExit("simulate_pixels.py: --charge_universes is not available with --n_gpus > 1 (its rows are not gathered "
                          "over the ranks)")
+    if world is not None and world > 1 and a["light_universes"]:
+        raise SystemExit(f"simulate_pixels.py: {LIGHT_UNIVERSES_NO_MULTI_GPU}")
     if world is None or "WORLD_SIZE" in os.environ:
         return
     if os.path.exists(a["output_filename"]):
@@ -236,6 +265,7 @@ from larndsim_amd import dist as ldist  # noqa: E402
 from larndsim_amd import charge_universes as lcu  # noqa: E402
 from larndsim_amd import fee_universes as lfu  # noqa: E402
 from larndsim_amd import field_map as lfmap  # noqa: E402
+from larndsim_amd import light_universes as llu  # noqa: E402
 from larndsim_amd import pixel_truth as lptruth  # noqa: E402
 from larndsim_amd import pixel_waveforms as lpwave  # noqa: E402
 from larndsim_amd import rng as lrng  # noqa: E402
@@ -446,7 +476,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
                    fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, light_lut_interpolation="nearest",
                    pixel_waveforms=False, pixel_waveforms_threshold=None, pixel_waveforms_pad=None, pixel_waveforms_hits_only=False,
-                   fee_universes=None, charge_universes=None, **ignored):
+                   fee_universes=None, charge_universes=None, light_universes=None, **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -480,6 +510,15 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         for k, (name, _, fee_changes) in enumerate(lcu.read(charge_universes)):   # (the file's keys, before anything is simulated)
             if lfu.changes_noisy(fee_changes) and rng != "keyed":
                 raise ValueError(CHARGE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
+    if light_universes is not None:
+        if world is not None and world > 1:
+            raise ValueError(LIGHT_UNIVERSES_NO_MULTI_GPU)
+        if rng != "keyed":
+            raise ValueError(LIGHT_UNIVERSES_NEED_KEYED)
+        try:
+            llu.read(light_universes)                                          # (the file's keys, before anything is simulated)
+        except OSError as e:
+            raise ValueError(f"--light_universes {light_universes}: {e}")
     wave_sel = None
     if pixel_waveforms:
         wave_sel = (float(pixel_waveforms_threshold or 0.0), int(pixel_waveforms_pad or 0), bool(pixel_waveforms_hits_only))
@@ -574,6 +613,10 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     if light_simulated and not all(f and os.path.isfile(f) for f in np.atleast_1d(light_lut_filename if light_lut_filename is not None else "")):
         print("light_lut_filename is not provided (required if light_simulated is True): light is not simulated")
         light_simulated = False
+    if light_universes is not None and m2m:
+        raise ValueError(LIGHT_UNIVERSES_NO_MODVAR)
+    if light_universes is not None and not light_simulated:
+        raise ValueError(LIGHT_UNIVERSES_NEED_LIGHT)
     if not rand_seed:
         rand_seed = SEED
     print("Random seed:", rand_seed)
@@ -634,6 +677,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         print("FEE universes:", f"{fee_universes} (--fee_universes; hits only, no packets per universe)")
     if charge_universes is not None:    # (likewise)
         print("Charge universes:", f"{charge_universes} (--charge_universes; hits only, no packets per universe)")
+    if light_universes is not None:     # (likewise)
+        print("Light universes:", f"{light_universes} (--light_universes; triggers and waveforms, no truth slots per universe)")
     print("Light LUT interpolation:", light_lut_interpolation if light_lut_interpolation == "nearest"
           else f"{light_lut_interpolation} (--light_lut_interpolation {light_lut_interpolation})")
     lib.set_option("numba_f32", f32_mode)
@@ -707,11 +752,17 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                     out.put("charge_universes", lcu.universe_rows(cu_names, cu_charge, cu_fee))
                     charge_universes_written = True
                 cuni = (cu_fee, cu_charge)
+            luni = None
+            if light_universes is not None:
+                # every universe is the light constants with the file's keys applied (no module variation: written once)
+                lu_names, lu_vars = llu.load(light_universes)
+                out.put("light_universes", llu.universe_rows(lu_names, lu_vars))
+                luni = lu_vars
             res = _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field,
                                    per_module(light_lut_filename, i_mod) if light_simulated else None, light_det_noise_filename,
                                    cfg, len(mod_ids), bad_list, chunk_segments, raw_arrays, overlap_downloads, dist,
                                    keyed=rng == "keyed", pixel_truth_min=truth_min, pixel_waveforms_sel=wave_sel,
-                                   fee_universes=universes, charge_universes=cuni)
+                                   fee_universes=universes, charge_universes=cuni, light_universes=luni)
             for k in totals:
                 totals[k] += res[k]
             rows_per_rank += res["rows_per_rank"]
@@ -756,6 +807,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
             out.put("fee_universe_hits", np.zeros(0, dtype=lfu.FILE_HIT))
         if charge_universes is not None and "charge_universe_hits" not in out.appended:
             out.put("charge_universe_hits", np.zeros(0, dtype=lcu.FILE_HIT))
+        if light_universes is not None and "light_universe_trig" not in out.appended:
+            out.put("light_universe_trig", llu.file_rows(0, 0, 0.0, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32),
+                                                         np.zeros((0, 1), dtype=np.int32)))
         out.close(pixel_layout if isinstance(pixel_layout, str) else None if pixel_layout is None else list(pixel_layout))
     finally:
         lib.set_option("mc_current", 0)
@@ -774,7 +828,7 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
 def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, event_times, rand_seed, traj_field, light_lut,
                      light_det_noise_filename, cfg, n_mod_ids, bad_list, chunk_segments, raw_arrays, overlap_downloads=None,
                      dist=None, keyed=False, pixel_truth_min=None, pixel_waveforms_sel=None, fee_universes=None,
-                     charge_universes=None):
+                     charge_universes=None, light_universes=None):
     """One pass of the driver's module loop body (cli/simulate_pixels.py:717-1232) on the device-resident chain: quench + drift,
     light leg, charge chain, packets.  ``tracks``: the module's active segments (all active segments without module
     variation); ``all_events``: event ids of every active segment (a module without segments in an event still reads out).
@@ -871,6 +925,15 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
                     acc["typ"].append(np.full(1, light.LIGHT_TRIG_MODE)); acc["opc"].append(op_channel[None, :])
                     for k, v in zip(("wv", "tid", "tph"), null_wvfm):
                         acc[k].append(v)
+                    for ku, lv in enumerate(light_universes or ()):
+                        # --light_universes: the empty response is every universe's; only its noise follows noise_scale
+                        u_wv = null_wvfm[0]
+                        if light_noise is not None and lv["noise_scale"] != 1.0:
+                            u_wv = light_sim.sim_triggers(None, None, zero, op_channel, None, None, np.array([0]),
+                                                          op_channel[None, :], digit_samples, light_noise * lv["noise_scale"])[0]
+                        out.append("light_universe_trig", llu.file_rows(ku, int(ev), 0.0, np.array([0]),
+                                                                        np.full(1, light.LIGHT_TRIG_MODE), op_channel[None, :]))
+                        out.append("light_universe_wvfm", u_wv)
                 for ib in ibs:                                      # sub-batches of BATCH_SIZE segments (:902-905, 1120-1205)
                     b0, b1 = int(edges[ib]), int(edges[ib + 1])
                     n_ticks, t_start = chain.sum_light(b0, b1, op_channel,
@@ -889,6 +952,18 @@ def _simulate_module(chain, out, i_mod, m2m, tracks, all_events, det_borders, ev
                     acc["typ"].append(t_type); acc["opc"].append(t_opc)
                     for k, v in zip(("wv", "tid", "tph"), wv):
                         acc[k].append(v)
+                    if light_universes is not None:
+                        # --light_universes: the same photon sum under every universe's constants and the same call key, then
+                        # the calls just made for the nominal, on each universe's response (thresholds and noise spectrum scaled)
+                        chain.light_universes(light_universes, fluctuate=True)
+                        for ku, lv in enumerate(light_universes):
+                            u_idx, u_opc, u_type = light_sim.get_triggers_universe(ku, thr * lv["trig_threshold_scale"], op_channel,
+                                                                                   table[ib][2])
+                            u_noise = None if light_noise is None else light_noise * lv["noise_scale"]
+                            u_wv = light_sim.sim_triggers_universe(ku, op_channel, u_idx, u_opc, digit_samples, u_noise)
+                            if u_idx.shape[0]:
+                                out.append("light_universe_trig", llu.file_rows(ku, int(ev), t_start, u_idx, u_type, u_opc))
+                                out.append("light_universe_wvfm", u_wv)
                 if not any(len(a) for a in acc["idx"]):
                     continue
                 cat = {k: np.concatenate(v, axis=0) for k, v in acc.items()}

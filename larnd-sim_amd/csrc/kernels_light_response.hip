@@ -903,3 +903,194 @@ int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const
   }
   return 0;
 }
+
+// ---- light universes: up to NU weight tables over one shared input row --------------------------------------------------------
+// light_conv_kernel without truth slots (its Mt == 0 path) for NU tables at once: the chunk of the input row is staged once (f4 for
+// the ballots and the bit-scan form, doubles for the unrolled blocks), each table has its own weight tile in LDS and each thread NU
+// f4 accumulators, updated in the same ascending-j order with the same rounding, so output u equals light_conv_kernel's under table
+// u bit for bit.  The non-zero ballot, the sample fetch and the block bookkeeping are paid once per block for all NU tables, and
+// the NU dependent cvt -> mul -> add -> cvt chains of a term interleave.  RESPONSE: the weights are staged as gain_u[d] * w_u.
+template <int NU>
+struct LightUniArgs {
+  const double* w[NU];          // [C + 1]
+  const double* gain[NU];       // [D] (RESPONSE)
+  float* out[NU];               // [D][T]
+};
+
+// eight consecutive input ticks for all NU tables: weight of tick e at s_w[u][wo - e]; per table the sums stay in ascending-tick order
+template <int NU>
+__device__ __forceinline__ void light_uni_terms8(float (&acc)[NU], const double (*s_w)[JCHUNK + LR_THREADS], int wo,
+                                                 const double (&x8)[8]) {
+  double w8[NU][8];
+#pragma unroll
+  for (int u = 0; u < NU; u++)
+#pragma unroll
+    for (int e = 0; e < 8; e++) w8[u][e] = s_w[u][wo - e];
+#pragma unroll
+  for (int e = 0; e < 8; e++)
+#pragma unroll
+    for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + w8[u][e] * x8[e]);
+}
+
+template <bool RESPONSE, int NU>
+__global__ void __launch_bounds__(LR_THREADS) light_conv_universes_kernel(
+    const float* __restrict__ inc, int D, int T, int C, LightUniArgs<NU> A,
+    const double* __restrict__ inc_f64 /* [D][T]: `inc` widened (light_widen_kernel), or NULL */) {
+  __shared__ float s_x[JCHUNK];
+  __shared__ double s_xd[JCHUNK];
+  __shared__ double s_w[NU][JCHUNK + LR_THREADS];
+  const int d = blockIdx.y;
+  const int i0 = blockIdx.x * LR_THREADS;
+  const int i = i0 + threadIdx.x;
+  const bool live = i < T;
+  const int i_last = min(i0 + LR_THREADS, T) - 1;          // last tick of this workgroup
+  const int j_begin = max(i0 - C, 0);                       // first j any of its ticks can reach
+  const float* x = inc + (int64_t)d * T;
+  const int my_j0 = max(i - C, 0);
+  float acc[NU];
+  double g[NU];
+#pragma unroll
+  for (int u = 0; u < NU; u++) {
+    acc[u] = 0.f;
+    g[u] = RESPONSE ? A.gain[u][d] : 1.0;
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int jc = j_begin; jc <= i_last; jc += JCHUNK) {
+    const int nj = min(JCHUNK, i_last - jc + 1);
+    // weights this chunk can meet: n = i - j in [i0 - (jc + nj - 1), i_last - jc], at most LR_THREADS + JCHUNK - 1 of them
+    const int n_lo = max(i0 - (jc + nj - 1), 0), n_hi = min(i_last - jc, C);
+    __syncthreads();
+    for (int k = threadIdx.x; k < nj; k += LR_THREADS) {
+      const float xv = x[jc + k];
+      s_x[k] = xv;
+      s_xd[k] = (double)xv;
+    }
+#pragma unroll
+    for (int u = 0; u < NU; u++)
+      for (int k = threadIdx.x; k <= n_hi - n_lo; k += LR_THREADS) s_w[u][k] = RESPONSE ? g[u] * A.w[u][n_lo + k] : A.w[u][n_lo + k];
+    __syncthreads();
+    for (int jb = jc; jb <= jc + nj - 1; jb += 64) {
+      const int nb64 = min(64, jc + nj - jb);
+      const float x_l = lane < nb64 ? s_x[jb - jc + lane] : 0.f;
+      const unsigned long long m_nz = RESPONSE ? ~0ull : __ballot(x_l != 0.f);
+      unsigned long long todo = (nb64 == 64 ? ~0ull : ((1ull << nb64) - 1ull)) & m_nz;
+      const int w_i0 = i0 + (wv << 6);
+      const bool inside = w_i0 + 63 < T && jb >= max(w_i0 + 63 - C, 0) && jb + nb64 - 1 <= w_i0;
+      if (inside) {
+        const int wo = (i - jb) - n_lo;          // weight of tick jb + t: s_w[u][wo - t]
+        if (todo == ~0ull) {
+          const double* xd = s_xd + (jb - jc);
+          const double xd_l = (double)x_l;
+          // eight ticks at a time, the loop over them kept rolled: unrolled over all 64 the NU x 64 weight reads are hoisted in
+          // front of the sums and the kernel runs out of registers (512 at NU = 2, scratch at NU = 4)
+          if (inc_f64) {
+            const double* xg = inc_f64 + (int64_t)d * T + jb;
+#pragma unroll 1
+            for (int t8 = 0; t8 < 64; t8 += 8) {
+              double x8[8];
+#pragma unroll
+              for (int e = 0; e < 8; e++) x8[e] = xg[t8 + e];
+              light_uni_terms8<NU>(acc, s_w, wo - t8, x8);
+            }
+          } else {
+#pragma unroll 1
+            for (int t8 = 0; t8 < 64; t8 += 8) {
+              double x8[8];
+#pragma unroll
+              for (int e = 0; e < 8; e++) x8[e] = RESPONSE ? wave_lane_f64(xd_l, t8 + e) : xd[t8 + e];
+              light_uni_terms8<NU>(acc, s_w, wo - t8, x8);
+            }
+          }
+          continue;
+        }
+        for (; todo; todo &= todo - 1) {
+          const int t = __ffsll((long long)todo) - 1;
+          const double xv = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
+#pragma unroll
+          for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + s_w[u][wo - t] * xv);
+        }
+        continue;
+      }
+      for (; todo; todo &= todo - 1) {
+        const int t = __ffsll((long long)todo) - 1;
+        const int j = jb + t;
+        const double xv = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
+        if (live && j >= my_j0 && j <= i) {
+#pragma unroll
+          for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + s_w[u][(i - j) - n_lo] * xv);
+        }
+      }
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int u = 0; u < NU; u++) A.out[u][(int64_t)d * T + i] = acc[u];
+  }
+}
+
+// x_k = (float)((double)x * scale): one rounding (exact at scale 1.0, which the host does not launch)
+__global__ void light_scale_kernel(const float* __restrict__ x, int64_t n, double scale, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) out[e] = (float)((double)x[e] * scale);
+}
+
+int light_universes_scale(ldsim_ctx* ctx, const float* x, int64_t n, double scale, float* out) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(light_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x, n, scale, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+template <bool RESPONSE, int NU>
+static void light_universes_launch_nu(hipStream_t st, dim3 grid, const float* inc, int D, int T, int C, const double* const* w,
+                                      const double* const* gain, float* const* out, const double* xd) {
+  LightUniArgs<NU> A;
+  for (int u = 0; u < NU; u++) {
+    A.w[u] = w[u];
+    A.gain[u] = RESPONSE ? gain[u] : nullptr;
+    A.out[u] = out[u];
+  }
+  hipLaunchKernelGGL((light_conv_universes_kernel<RESPONSE, NU>), grid, dim3(LR_THREADS), 0, st, inc, D, T, C, A, xd);
+}
+
+// K tables (w[k]: [C + 1]; response: gain[k]: [D]) over the one input `inc`, out[k] = the stage's plain sum under table k, on the
+// ctx's stream: light_conv_universes_kernel over ctx->lu_nu tables at a time, light_conv_kernel for a single one (into zeros)
+int light_universes_conv(ldsim_ctx* ctx, bool response, const float* inc, int D, int T, int C, int K, const double* const* w,
+                         const double* const* gain, float* const* out) {
+  if (D <= 0 || T <= 0 || K <= 0) return 0;
+  hipStream_t st = ctx->stream;
+  dim3 grid((unsigned)((T + LR_THREADS - 1) / LR_THREADS), (unsigned)D), block(LR_THREADS);
+  const double* xd = nullptr;
+  if (response) {          // (the SiPM stage's blocks of 64 input ticks all take part: the samples once more as doubles, for all K)
+    const int64_t n = (int64_t)D * T;
+    CK(ctx->lu_xd.ensure((size_t)n * 8 + 64));
+    hipLaunchKernelGGL(light_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, inc, n, (double*)ctx->lu_xd.p);
+    xd = (const double*)ctx->lu_xd.p;
+  }
+  const double thr = ctx->h_consts.mc_truth_threshold;
+  for (int k = 0; k < K;) {
+    const int nu = K - k < ctx->lu_nu ? K - k : ctx->lu_nu;
+    if (nu == 1) {
+      HIPCHK(hipMemsetAsync(out[k], 0, (size_t)D * T * 4, st));
+      if (response)
+        hipLaunchKernelGGL(light_conv_kernel<true>, grid, block, 0, st, inc, (const int64_t*)nullptr, (const double*)nullptr, D, T, 0,
+                           w[k], C, gain[k], thr, out[k], (int64_t*)nullptr, (double*)nullptr, (const double*)nullptr,
+                           (const int64_t*)nullptr, xd);
+      else
+        hipLaunchKernelGGL(light_conv_kernel<false>, grid, block, 0, st, inc, (const int64_t*)nullptr, (const double*)nullptr, D, T, 0,
+                           w[k], C, (const double*)nullptr, thr, out[k], (int64_t*)nullptr, (double*)nullptr, (const double*)nullptr,
+                           (const int64_t*)nullptr, xd);
+    } else if (response) {
+      if (nu == 2) light_universes_launch_nu<true, 2>(st, grid, inc, D, T, C, w + k, gain + k, out + k, xd);
+      else if (nu == 3) light_universes_launch_nu<true, 3>(st, grid, inc, D, T, C, w + k, gain + k, out + k, xd);
+      else light_universes_launch_nu<true, 4>(st, grid, inc, D, T, C, w + k, gain + k, out + k, xd);
+    } else {
+      if (nu == 2) light_universes_launch_nu<false, 2>(st, grid, inc, D, T, C, w + k, gain, out + k, xd);
+      else if (nu == 3) light_universes_launch_nu<false, 3>(st, grid, inc, D, T, C, w + k, gain, out + k, xd);
+      else light_universes_launch_nu<false, 4>(st, grid, inc, D, T, C, w + k, gain, out + k, xd);
+    }
+    HIPCHK(hipGetLastError());
+    k += nu;
+  }
+  return 0;
+}

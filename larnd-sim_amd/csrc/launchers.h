@@ -108,6 +108,11 @@ int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const
                           int Mt, const double* weights, int C, const double* gain, float* out, int64_t* out_tid,
                           double* out_tph);
 int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick);
+// light universes: out = (float)((double)x * scale); K tables over one input by light_conv_universes_kernel (a stage's plain sum
+// under each, bit-equal to light_conv_kernel's)
+int light_universes_scale(ldsim_ctx* ctx, const float* x, int64_t n, double scale, float* out);
+int light_universes_conv(ldsim_ctx* ctx, bool response, const float* inc, int D, int T, int C, int K, const double* const* w,
+                         const double* const* gain, float* const* out);
 
 // ---- chain.hip ---------------------------------------------------------------------------------------------------------
 int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fractions);

@@ -214,6 +214,10 @@ extern "C" int ldsim_set_option(ldsim_ctx* ctx, const char* name, double value) 
     if (!(value == 0 || value == 1)) { ldsim_set_error("light_lut_interp must be 0 or 1"); return LDSIM_EINVAL; }
     ctx->light_lut_interp = (int)value;
   }
+  else if (!strcmp(name, "light_universes_nu")) {
+    if (!(value == 1 || value == 2 || value == 3 || value == 4)) { ldsim_set_error("light_universes_nu must be 1, 2, 3 or 4"); return LDSIM_EINVAL; }
+    ctx->lu_nu = (int)value;
+  }
   else if (!strcmp(name, "light_sum_no_list")) ctx->light_sum_no_list = value != 0;
   else if (!strcmp(name, "light_sum_async")) {
     CK(light_join(ctx));
@@ -483,6 +487,7 @@ extern "C" int ldsim_segments_upload(ldsim_ctx* ctx, const void* tracks, int64_t
       ids[(size_t)i] = batch_id[i];
     }
   }
+  ctx->lu_valid = 0;          // (light universes describe a photon sum of the segments that go now)
   {
     const int rc = upload_tracks(ctx, tracks, n, layout, batch_id, true);
     if (rc) {                 // a failed upload may have overwritten part of the store: nothing is resident any more
@@ -511,6 +516,7 @@ extern "C" int ldsim_segments_reset(ldsim_ctx* ctx) {
   HIPCHK(hipSetDevice(ctx->device));
   CK(light_join(ctx));
   launch_invalidate(ctx, "ldsim_segments_reset rewrote the resident segments since the launch");
+  ctx->lu_valid = 0;
   ctx->light_n = -1;
   ctx->drift_map_gen = -1;
   ctx->drift_stat_on = -1;
@@ -1139,6 +1145,7 @@ extern "C" int ldsim_dev_sum_light(ldsim_ctx* ctx, int64_t seg_begin, int64_t se
                         memcmp(ctx->h_opc.data(), op_channel, (size_t)n_det * 4) == 0;
   if (!same_opc)
     for (int i = 0; i < n_det; i++) NEED(op_channel[i] >= 0 && op_channel[i] < ctx->light_n_out, "op_channel outside the incidence array");
+  ctx->lu_valid = 0;          // (light universes read the photon sum this call replaces)
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = seg_end - seg_begin;
   const size_t bo = (size_t)n_det * n_ticks;
@@ -1454,6 +1461,7 @@ extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain
   const int D = ctx->light_sum_ndet, T = ctx->light_sum_nticks, Mt = ctx->light_sum_truth;
   const size_t bo = (size_t)D * T, bt = bo * (size_t)Mt;
   ctx->light_resp_valid = 0;
+  ctx->lu_valid = 0;
   std::vector<double> w0((size_t)C + 1), w1((size_t)C + 1);
   for (int64_t n = 0; n <= C; n++) {
     w0[(size_t)n] = scintillation_model(n, h);
@@ -1535,6 +1543,219 @@ extern "C" int ldsim_light_response_ms(ldsim_ctx* ctx, double* scint_ms, double*
   if (scint_ms) *scint_ms = ctx->ms_light_resp[0];
   if (fluct_ms) *fluct_ms = ctx->ms_light_resp[1];
   if (response_ms) *response_ms = ctx->ms_light_resp[2];
+  return 0;
+}
+
+// ---- light universes: the resident photon sum under varied light constants (include/ldsim.h) ---------------------------------------
+extern "C" int ldsim_light_variation_nominal(ldsim_ctx* ctx, LdsimLightVariation* out) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && out, "null argument");
+  const LdsimConsts& h = ctx->h_consts;
+  out->photon_scale = 1.0;
+  out->singlet_fraction = h.singlet_fraction;
+  out->tau_s = h.tau_s;
+  out->tau_t = h.tau_t;
+  out->gain_scale = 1.0;
+  out->response_time = h.light_response_time;
+  out->oscillation_period = h.light_oscillation_period;
+  return 0;
+}
+
+static int light_variation_check(const LdsimLightVariation& v, int k, const LdsimConsts& h) {
+#define LU_BAD(field, rule)                                                                                        \
+  do {                                                                                                             \
+    ldsim_set_error("light universes: universe %d: " #field " = %g " rule, k, v.field);                            \
+    return LDSIM_EINVAL;                                                                                           \
+  } while (0)
+  if (!(std::isfinite(v.photon_scale) && v.photon_scale > 0)) LU_BAD(photon_scale, "must be finite and > 0");
+  if (!(std::isfinite(v.singlet_fraction) && v.singlet_fraction >= 0 && v.singlet_fraction <= 1))
+    LU_BAD(singlet_fraction, "must be finite and in [0, 1]");
+  if (!(std::isfinite(v.tau_s) && v.tau_s > 0)) LU_BAD(tau_s, "must be finite and > 0");
+  if (!(std::isfinite(v.tau_t) && v.tau_t > 0)) LU_BAD(tau_t, "must be finite and > 0");
+  if (!(std::isfinite(v.gain_scale) && v.gain_scale != 0)) LU_BAD(gain_scale, "must be finite and != 0");
+  if (!(std::isfinite(v.response_time) && v.response_time > 0)) LU_BAD(response_time, "must be finite and > 0");
+  if (!(std::isfinite(v.oscillation_period) && v.oscillation_period > 0)) LU_BAD(oscillation_period, "must be finite and > 0");
+  if (h.sipm_response_model == 1) {
+    if (v.response_time != h.light_response_time) LU_BAD(response_time, "is not read under SIPM_RESPONSE_MODEL 1 and differs from the context's");
+    if (v.oscillation_period != h.light_oscillation_period)
+      LU_BAD(oscillation_period, "is not read under SIPM_RESPONSE_MODEL 1 and differs from the context's");
+  }
+#undef LU_BAD
+  return 0;
+}
+
+extern "C" int ldsim_dev_light_universes(ldsim_ctx* ctx, const LdsimLightVariation* v, int32_t n, const double* light_gain,
+                                         const double* impulse_model, int32_t n_impulse, int32_t fluctuate, int32_t keep_stages) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && v && light_gain, "bad argument");
+  if (!(n >= 1 && n <= LDSIM_LIGHT_UNIVERSES_MAX)) {
+    ldsim_set_error("light universes: n = %d universes, must lie in [1, %d]", n, LDSIM_LIGHT_UNIVERSES_MAX);
+    return LDSIM_EINVAL;
+  }
+  const LdsimConsts& h = ctx->h_consts;
+  NEED(h.light_tick_size > 0 && h.tau_s > 0 && h.tau_t > 0, "light constants not set");
+  NEED(h.sipm_response_model == 0 || (h.sipm_response_model == 1 && impulse_model && n_impulse > 0 && h.impulse_tick_size > 0),
+       "SIPM_RESPONSE_MODEL 1 needs IMPULSE_MODEL and IMPULSE_TICK_SIZE");
+  const int64_t C = conv_ticks(h);
+  NEED(C >= 0 && C < (1 << 24), "LIGHT_WINDOW / LIGHT_TICK_SIZE out of range");
+  for (int k = 0; k < n; k++) CK(light_variation_check(v[k], k, h));
+  if (ctx->light_sum_ndet <= 0) {
+    ldsim_set_error("light universes: no resident photon sum (ldsim_dev_sum_light)");
+    return LDSIM_ESTATE;
+  }
+  if (fluctuate && !ctx->rng_keyed) {
+    ldsim_set_error("light universes: fluctuations need keyed streams (ldsim_rng_keyed_seed): table-mode draws would advance the "
+                    "state table, and every universe must see the same random numbers");
+    return LDSIM_ESTATE;
+  }
+  // ---- the plan: first appearance first, compared byte by byte like the charge groups
+  const int D = ctx->light_sum_ndet, T = ctx->light_sum_nticks;
+  const size_t bo = ((size_t)D * T + 63) & ~(size_t)63;          // elements between two arrays of a pool
+  const double one = 1.0;
+  struct ScKey { int in; double c[3]; };
+  struct RsKey { int sc; double c[3]; };
+  std::vector<double> in_scale;            // scales other than 1.0
+  std::vector<ScKey> sc_keys;
+  std::vector<RsKey> rs_keys;
+  std::vector<int32_t> u_in((size_t)n), u_sc((size_t)n), u_rs((size_t)n);
+  for (int k = 0; k < n; k++) {
+    int in = -1;                           // -1: the resident sum itself
+    if (memcmp(&v[k].photon_scale, &one, 8) != 0) {
+      for (size_t g = 0; g < in_scale.size() && in < 0; g++)
+        if (!memcmp(&in_scale[g], &v[k].photon_scale, 8)) in = (int)g;
+      if (in < 0) { in = (int)in_scale.size(); in_scale.push_back(v[k].photon_scale); }
+    }
+    ScKey sk;
+    memset(&sk, 0, sizeof(sk));
+    sk.in = in; sk.c[0] = v[k].singlet_fraction; sk.c[1] = v[k].tau_s; sk.c[2] = v[k].tau_t;
+    int sc = -1;
+    for (size_t s = 0; s < sc_keys.size() && sc < 0; s++)
+      if (!memcmp(&sc_keys[s], &sk, sizeof(sk))) sc = (int)s;
+    if (sc < 0) { sc = (int)sc_keys.size(); sc_keys.push_back(sk); }
+    RsKey rk;
+    memset(&rk, 0, sizeof(rk));
+    rk.sc = sc; rk.c[0] = v[k].gain_scale; rk.c[1] = v[k].response_time; rk.c[2] = v[k].oscillation_period;
+    int rs = -1;
+    for (size_t r = 0; r < rs_keys.size() && rs < 0; r++)
+      if (!memcmp(&rs_keys[r], &rk, sizeof(rk))) rs = (int)r;
+    if (rs < 0) { rs = (int)rs_keys.size(); rs_keys.push_back(rk); }
+    u_in[(size_t)k] = in; u_sc[(size_t)k] = sc; u_rs[(size_t)k] = rs;
+  }
+  const size_t n_in = in_scale.size(), n_sc = sc_keys.size(), n_rs = rs_keys.size(), W = (size_t)C + 1;
+  // ---- from here on the earlier result is gone
+  ctx->lu_valid = 0;
+  CK(light_join(ctx));
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // weight tables with the launch's expressions under each universe's constants, row gains as one f64 product
+  std::vector<double> tab((n_sc + n_rs) * W + n_rs * (size_t)D);
+  for (size_t s = 0; s < n_sc; s++) {
+    LdsimConsts hc = h;
+    hc.singlet_fraction = sc_keys[s].c[0]; hc.tau_s = sc_keys[s].c[1]; hc.tau_t = sc_keys[s].c[2];
+    for (int64_t m = 0; m <= C; m++) tab[s * W + (size_t)m] = scintillation_model(m, hc);
+  }
+  for (size_t r = 0; r < n_rs; r++) {
+    LdsimConsts hc = h;
+    hc.light_response_time = rs_keys[r].c[1]; hc.light_oscillation_period = rs_keys[r].c[2];
+    for (int64_t m = 0; m <= C; m++) tab[(n_sc + r) * W + (size_t)m] = sipm_response_model(m, impulse_model, n_impulse, hc);
+    for (int d = 0; d < D; d++) tab[(n_sc + n_rs) * W + r * (size_t)D + (size_t)d] = light_gain[d] * rs_keys[r].c[0];
+  }
+  CK(ctx->lu_tab.ensure(tab.size() * 8 + 8));
+  CK(ctx->lu_x.ensure(n_in * bo * 4 + 16));
+  CK(ctx->lu_scint.ensure(n_sc * bo * 4 + 16));
+  CK(ctx->lu_disc.ensure((fluctuate ? n_sc : 0) * bo * 4 + 16));
+  CK(ctx->lu_resp.ensure(n_rs * bo * 4 + 16));
+  for (Event& e : ctx->lu_ev) CK(e.ensure());
+  ctx->lu_n = n; ctx->lu_D = D; ctx->lu_T = T; ctx->lu_bo = bo;
+  ctx->lu_keep = keep_stages != 0; ctx->lu_fluct = fluctuate != 0;
+  ctx->lu_in = u_in; ctx->lu_sc = u_sc; ctx->lu_rs = u_rs;
+  ctx->ms_lu[0] = ctx->ms_lu[1] = ctx->ms_lu[2] = 0;
+  if ((size_t)D * T == 0) {
+    ctx->lu_valid = 1;
+    return 0;
+  }
+  HIPCHK(hipMemcpyAsync(ctx->lu_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+  const double* d_tab = (const double*)ctx->lu_tab.p;
+  const double* d_gain = d_tab + (n_sc + n_rs) * W;
+  auto in_ptr = [&](int in) { return in < 0 ? (const float*)ctx->light_out.p : (const float*)ctx->lu_x.p + (size_t)in * bo; };
+  auto sc_ptr = [&](size_t s) { return (float*)ctx->lu_scint.p + s * bo; };
+  auto di_ptr = [&](size_t s) { return fluctuate ? (float*)ctx->lu_disc.p + s * bo : sc_ptr(s); };
+  HIPCHK(hipEventRecord(ctx->lu_ev[0], st));
+  for (size_t g = 0; g < n_in; g++)
+    CK(light_universes_scale(ctx, (const float*)ctx->light_out.p, (int64_t)D * T, in_scale[g], (float*)ctx->lu_x.p + g * bo));
+  std::vector<const double*> pw, pg;
+  std::vector<float*> po;
+  for (int in = -1; in < (int)n_in; in++) {          // the scintillation tables of one input together
+    pw.clear(); po.clear();
+    for (size_t s = 0; s < n_sc; s++)
+      if (sc_keys[s].in == in) { pw.push_back(d_tab + s * W); po.push_back(sc_ptr(s)); }
+    CK(light_universes_conv(ctx, false, in_ptr(in), D, T, (int)C, (int)pw.size(), pw.data(), nullptr, po.data()));
+  }
+  HIPCHK(hipEventRecord(ctx->lu_ev[1], st));
+  if (fluctuate)
+    for (size_t s = 0; s < n_sc; s++) CK(light_launch_stat_fluct(ctx, sc_ptr(s), di_ptr(s), (int64_t)D * T, T));
+  HIPCHK(hipEventRecord(ctx->lu_ev[2], st));
+  for (size_t s = 0; s < n_sc; s++) {                // the response tables of one fluctuated array together
+    pw.clear(); pg.clear(); po.clear();
+    for (size_t r = 0; r < n_rs; r++)
+      if (rs_keys[r].sc == (int)s) {
+        pw.push_back(d_tab + (n_sc + r) * W);
+        pg.push_back(d_gain + r * (size_t)D);
+        po.push_back((float*)ctx->lu_resp.p + r * bo);
+      }
+    CK(light_universes_conv(ctx, true, di_ptr(s), D, T, (int)C, (int)pw.size(), pw.data(), pg.data(), po.data()));
+  }
+  HIPCHK(hipEventRecord(ctx->lu_ev[3], st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < 3; i++) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->lu_ev[i], ctx->lu_ev[i + 1]));
+    ctx->ms_lu[i] = ms;
+  }
+  ctx->lu_valid = 1;
+  return 0;
+}
+
+static int light_universe_need(ldsim_ctx* ctx, int32_t k) {
+  if (!ctx->lu_valid) {
+    ldsim_set_error("no resident light universes (ldsim_dev_light_universes; a later photon sum, light response or segment upload "
+                    "invalidates them)");
+    return LDSIM_ESTATE;
+  }
+  if (!(k >= 0 && k < ctx->lu_n)) {
+    ldsim_set_error("light universes: universe %d out of range, the last pass made %d", k, ctx->lu_n);
+    return LDSIM_EINVAL;
+  }
+  return 0;
+}
+
+extern "C" int ldsim_dev_light_universe_download(ldsim_ctx* ctx, int32_t k, float* scint, float* disc, float* response) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  CK(light_universe_need(ctx, k));
+  if ((scint || disc) && !ctx->lu_keep) {
+    ldsim_set_error("light universes: the scintillation and fluctuation stages were not kept (keep_stages = 0)");
+    return LDSIM_ESTATE;
+  }
+  const size_t n = (size_t)ctx->lu_D * ctx->lu_T, bo = ctx->lu_bo;
+  if (n == 0) return 0;
+  hipStream_t st = ctx->stream;
+  const float* sc = (const float*)ctx->lu_scint.p + (size_t)ctx->lu_sc[(size_t)k] * bo;
+  const float* di = ctx->lu_fluct ? (const float*)ctx->lu_disc.p + (size_t)ctx->lu_sc[(size_t)k] * bo : sc;
+  if (scint) HIPCHK(hipMemcpyAsync(scint, sc, n * 4, hipMemcpyDeviceToHost, st));
+  if (disc) HIPCHK(hipMemcpyAsync(disc, di, n * 4, hipMemcpyDeviceToHost, st));
+  if (response)
+    HIPCHK(hipMemcpyAsync(response, (const float*)ctx->lu_resp.p + (size_t)ctx->lu_rs[(size_t)k] * bo, n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" int ldsim_light_universes_ms(ldsim_ctx* ctx, double* scint_ms, double* fluct_ms, double* response_ms) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  if (scint_ms) *scint_ms = ctx->ms_lu[0];
+  if (fluct_ms) *fluct_ms = ctx->ms_lu[1];
+  if (response_ms) *response_ms = ctx->ms_lu[2];
   return 0;
 }
 

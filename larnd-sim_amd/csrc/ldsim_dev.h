@@ -362,6 +362,22 @@ struct ldsim_ctx {
   double ms_light_resp[3] = {0, 0, 0};
   double ms_light_inc = 0, ms_light_sum = 0;
   Event evl[4];
+  // light universes (ldsim_dev_light_universes): the photon sum under varied light constants.  Universes are grouped on the host
+  // (lu_in / lu_sc / lu_rs: per universe the index of its scaled input, its scintillation + fluctuation stage and its response;
+  // equal constants share one), every distinct array is [lu_D][lu_T] f32 at a stride of lu_bo elements
+  DevBuf lu_x;                   // inputs scaled by a photon_scale other than 1.0 (1.0 reads light_out itself)
+  DevBuf lu_scint, lu_disc;      // distinct scintillation profiles and their fluctuated counts (lu_disc unused without fluctuations)
+  DevBuf lu_resp;                // distinct detector responses
+  DevBuf lu_tab;                 // weight tables f64 [n_sc + n_rs][C + 1] | row gains f64 [n_rs][lu_D]
+  DevBuf lu_xd;                  // a response pass's input widened to doubles (light_widen_kernel)
+  DevBuf lu_digit;               // waveforms of the last ldsim_dev_light_universe_waveforms, f64 [n_trig][n_det_trig][samples]
+  int lu_valid = 0, lu_keep = 0, lu_fluct = 0;
+  int32_t lu_n = 0, lu_D = 0, lu_T = 0;
+  size_t lu_bo = 0;
+  std::vector<int32_t> lu_in, lu_sc, lu_rs;
+  int lu_nu = 4;                 // option light_universes_nu: tables per launch of light_conv_universes_kernel (1: light_conv_kernel per table)
+  Event lu_ev[4];                // around the scintillation, fluctuation and response stages of the last pass
+  double ms_lu[3] = {0, 0, 0};
   // random streams (kernels_rng.hip): numba-style table of xoroshiro128p states, grown on demand
   DevBuf d_rng;
   int64_t rng_n = 0;

@@ -729,6 +729,60 @@ extern "C" int ldsim_light_triggers(ldsim_ctx* ctx, const float* signal, int32_t
                             trigger_module, capacity, n_trig);
 }
 
+// ---- light universes: triggers and waveforms of universe k's resident response (ldsim_dev_light_universes), no truth slots ----------
+static int light_universe_response(ldsim_ctx* ctx, int32_t k, int32_t n_det, int32_t n_ticks, const float** resp) {
+  if (!ctx->lu_valid) {
+    ldsim_set_error("no resident light universes (ldsim_dev_light_universes; a later photon sum, light response or segment upload "
+                    "invalidates them)");
+    return LDSIM_ESTATE;
+  }
+  if (!(k >= 0 && k < ctx->lu_n)) {
+    ldsim_set_error("light universes: universe %d out of range, the last pass made %d", k, ctx->lu_n);
+    return LDSIM_EINVAL;
+  }
+  NEED(ctx->lu_D == n_det && ctx->lu_T == n_ticks, "the resident light universes do not have that shape");
+  *resp = (const float*)ctx->lu_resp.p + (size_t)ctx->lu_rs[(size_t)k] * ctx->lu_bo;
+  return 0;
+}
+
+extern "C" int ldsim_dev_light_universe_triggers(ldsim_ctx* ctx, int32_t k, int32_t n_det, int32_t n_ticks,
+                                                 const double* group_threshold, int32_t n_grp, const int32_t* row_module,
+                                                 int32_t n_mod, int64_t* trigger_idx, int32_t* trigger_module, int64_t capacity,
+                                                 int64_t* n_trig) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && group_threshold && row_module && n_trig && n_det >= 0 && n_ticks >= 0 && n_grp >= 0 && n_mod >= 0 &&
+              capacity >= 0 && (capacity == 0 || (trigger_idx && trigger_module)), "bad argument");
+  const float* d_signal = nullptr;
+  CK(light_universe_response(ctx, k, n_det, n_ticks, &d_signal));
+  HIPCHK(hipSetDevice(ctx->device));
+  return light_triggers_run(ctx, d_signal, n_det, n_ticks, group_threshold, n_grp, row_module, n_mod, trigger_idx,
+                            trigger_module, capacity, n_trig);
+}
+
+extern "C" int ldsim_dev_light_universe_waveforms(ldsim_ctx* ctx, int32_t k, const int32_t* signal_op_channel_idx, int32_t n_det,
+                                                  int32_t n_ticks, const int64_t* trigger_idx, int32_t n_trig,
+                                                  const int32_t* trigger_op_channel_idx, int32_t n_det_trig,
+                                                  int32_t digit_samples, const double* light_det_noise, int32_t n_noise_channels,
+                                                  int32_t n_noise_bins, const double* phases_signal, const double* phases_missing,
+                                                  double* digit_signal) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && n_det >= 0 && n_ticks >= 0 && n_trig >= 0 && n_det_trig >= 0 && digit_samples >= 0, "bad argument");
+  NEED(n_det == 0 || signal_op_channel_idx, "signal_op_channel_idx missing");
+  NEED(n_trig == 0 || (trigger_idx && trigger_op_channel_idx && digit_signal), "trigger arrays missing");
+  const float* d_signal = nullptr;
+  CK(light_universe_response(ctx, k, n_det, n_ticks, &d_signal));
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n_out = (size_t)n_trig * n_det_trig * digit_samples;
+  if (n_out == 0) return 0;
+  CK(ctx->lu_digit.ensure(n_out * 8));
+  CK(sim_triggers_run(ctx, d_signal, signal_op_channel_idx, n_det, n_ticks, nullptr, nullptr, 0, trigger_idx, n_trig,
+                      trigger_op_channel_idx, n_det_trig, digit_samples, light_det_noise, n_noise_channels, n_noise_bins,
+                      phases_signal, phases_missing, ctx->lu_digit.as<double>(), nullptr, nullptr));
+  HIPCHK(hipMemcpyAsync(digit_signal, ctx->lu_digit.p, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 extern "C" int ldsim_light_detector_noise(ldsim_ctx* ctx, int32_t n_rows, int32_t n_samples, const double* spectrum,
                                           int32_t nbins, const double* phases, double* noise) {
   LDSIM_ENTER(ctx);

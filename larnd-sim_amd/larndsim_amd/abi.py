@@ -71,7 +71,14 @@ class LdsimChargeVariation(C.Structure):
                 ("birks_ab", C.c_double), ("birks_kb", C.c_double), ("recomb_mode", C.c_int32), ("pad", C.c_int32)]
 
 
+class LdsimLightVariation(C.Structure):
+    """include/ldsim.h LdsimLightVariation (ldsim_dev_light_universes): 56 bytes, absolute values"""
+    _fields_ = [("photon_scale", C.c_double), ("singlet_fraction", C.c_double), ("tau_s", C.c_double), ("tau_t", C.c_double),
+                ("gain_scale", C.c_double), ("response_time", C.c_double), ("oscillation_period", C.c_double)]
+
+
 FEE_UNIVERSES_MAX = 64      # include/ldsim.h LDSIM_FEE_UNIVERSES_MAX
+LIGHT_UNIVERSES_MAX = 64    # include/ldsim.h LDSIM_LIGHT_UNIVERSES_MAX
 
 ABI_VERSION = 8      # include/ldsim.h LDSIM_ABI_VERSION: the struct layouts of this file
 

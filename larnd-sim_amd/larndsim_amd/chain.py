@@ -603,6 +603,60 @@ class ChargeChain:
         lib.check(lib.load().ldsim_light_response_ms(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
         return {"scintillation": a.value, "fluctuations": b.value, "detector_response": c.value}
 
+    # ---- light universes (light_universes.py, ldsim_dev_light_universes) ---------------------------------------------------------
+    def light_variation_nominal(self):
+        """the light variation of the constants frozen in the context (``ldsim_light_variation_nominal``)"""
+        from . import light_universes as lu
+        from .abi import LdsimLightVariation
+        v = LdsimLightVariation()
+        lib.check(lib.load().ldsim_light_variation_nominal(self.ctx, C.byref(v)))
+        return lu.unpack(v)
+
+    def light_universes(self, variations, fluctuate=True, keep_stages=False):
+        """Light universes of the last ``sum_light`` (``light_universes``, ``ldsim_dev_light_universes``): the batch's
+        scintillation profile, Poisson fluctuations (if ``fluctuate``; needs ``seed_keyed`` and the call key of ``set_rng_key``)
+        and detector response run again under each of ``variations`` (1 to 64 dicts of ``light_universes.variation``), in HBM.
+        Universes with equal constants share their stages; tables that share an input go through one multi-table kernel.
+        ``light_sim.get_triggers_universe`` / ``sim_triggers_universe`` then work on universe ``k``'s response and
+        ``download_light_universe`` fetches it (its scintillation and fluctuated arrays only with ``keep_stages``).  The
+        launch's own ``light_response`` result is left as it was.  Every array of universe k equals, bit for bit, a
+        ``light_response`` on the scaled photon sum under ``consts.light`` patched to variation k and the same call key.
+        ``trig_threshold_scale`` and ``noise_scale`` are not used here: they scale arguments of the two ``light_sim`` calls.
+        Raises ``ValueError`` for variations ``light_universes.validate`` refuses and ``LdsimError`` (LDSIM_ESTATE) without a
+        resident photon sum, or with ``fluctuate`` in table mode."""
+        from . import light_universes as lu
+        self._check_constants()
+        variations = list(variations)
+        lu.validate(variations)
+        light = consts.light
+        nd = self._light_shape[0]
+        gain = np.ascontiguousarray(light.LIGHT_GAIN, dtype=np.float64)
+        if gain.shape[0] < nd:
+            raise IndexError(f"LIGHT_GAIN has {gain.shape[0]} entries, the photon sum has {nd} rows")
+        imp = np.ascontiguousarray(light.IMPULSE_MODEL, dtype=np.float64)
+        arr = lu.pack(variations)
+        lib.check(lib.load().ldsim_dev_light_universes(self.ctx, arr, C.c_int32(len(variations)), lib.ptr(gain), lib.ptr(imp),
+                                                       C.c_int32(imp.shape[0]), C.c_int32(int(bool(fluctuate))),
+                                                       C.c_int32(int(bool(keep_stages)))))
+        self._light_universes_shape = self._light_shape[:2]
+
+    def download_light_universe(self, k, stages=False):
+        """response f4 [n_det][n_ticks] of universe ``k`` of the last ``light_universes``; with ``stages`` (kept by
+        ``keep_stages=True``): (scint, disc, response), disc being scint when the pass ran without fluctuations"""
+        nd, nt = self.__dict__.get("_light_universes_shape", self._light_shape[:2])
+        resp = np.zeros((nd, nt), dtype=np.float32)
+        sc = np.zeros((nd, nt), dtype=np.float32) if stages else None
+        di = np.zeros((nd, nt), dtype=np.float32) if stages else None
+        lib.check(lib.load().ldsim_dev_light_universe_download(self.ctx, C.c_int32(int(k)), lib.ptr(sc), lib.ptr(di),
+                                                               lib.ptr(resp)))
+        return (sc, di, resp) if stages else resp
+
+    def light_universes_ms(self):
+        """HIP-event times of the three stages summed over the last ``light_universes`` pass in ms (timing tools)"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        lib.check(lib.load().ldsim_light_universes_ms(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return {"scintillation": a.value, "fluctuations": b.value, "detector_response": c.value}
+
     def download_light(self, truth=True):
         """(light_sample_inc f4 [n_det][n_ticks], true_track_id i8 [..][max_truth], true_photons f8 [..][max_truth])."""
         nd, nt, mt = self._light_shape

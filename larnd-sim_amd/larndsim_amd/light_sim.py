@@ -237,6 +237,65 @@ def sim_triggers(bpg, tpb, signal, signal_op_channel_idx, signal_true_track_id, 
     return digit, dtid.astype(id_dtype, copy=False), dtph.astype(ph_dtype, copy=False)
 
 
+# ---- light universes (light_universes.py): the same two calls on universe k's resident response ------------------------------
+def get_triggers_universe(k, group_threshold, op_channel_idx, i_subbatch):
+    """``get_triggers(None, ...)`` on the resident response of universe ``k`` of the last ``chain.light_universes``.  The
+    caller hands over the thresholds already scaled by the universe's ``trig_threshold_scale``."""
+    light = consts.light
+    op_channel_idx = np.asarray(op_channel_idx)
+    trig, chans, types = [], [], []
+    if light.LIGHT_TRIG_MODE == 0:
+        _, row_module, channels = _module_rows(op_channel_idx)
+        thr = np.ascontiguousarray(group_threshold, dtype=np.float64)
+        n_det = op_channel_idx.shape[0]
+        n_ticks = lib.context_light_shape()[1]
+        cap = max(16, n_ticks // max(1, _digit_ticks()) * len(channels) + len(channels))
+        while True:
+            idx = np.zeros(cap, dtype=np.int64); mod = np.zeros(cap, dtype=np.int32); n = C.c_int64(0)
+            rc = lib.load().ldsim_dev_light_universe_triggers(
+                lib.context(), C.c_int32(int(k)), C.c_int32(n_det), C.c_int32(n_ticks), lib.ptr(thr), C.c_int32(thr.shape[0]),
+                lib.ptr(row_module), C.c_int32(len(channels)), lib.ptr(idx), lib.ptr(mod), C.c_int64(cap), C.byref(n))
+            if rc == lib.LDSIM_ENOSPC:
+                cap = int(n.value)
+                continue
+            lib.check(rc)
+            break
+        for i in range(int(n.value)):
+            trig.append(int(idx[i])); types.append(0); chans.append(channels[int(mod[i])])
+    elif light.LIGHT_TRIG_MODE == 1 and i_subbatch == 0:
+        trig.append(0); chans.append(op_channel_idx); types.append(1)
+    if trig:
+        return np.array(trig), np.array(chans), np.array(types)
+    return np.empty((0,), dtype=int), np.empty((0, len(op_channel_idx)), dtype=int), np.empty((0,), dtype=int)
+
+
+def sim_triggers_universe(k, signal_op_channel_idx, trigger_idx, op_channel_idx, digit_samples, light_det_noise,
+                          phases_signal=None, phases_missing=None):
+    """``sim_triggers(.., None, ..)`` on the resident response of universe ``k`` of the last ``chain.light_universes``, without
+    truth slots: ``digit_signal [ntrigs, ndet_module, digit_samples] f8``.  The caller hands over the noise spectrum already
+    scaled by the universe's ``noise_scale``."""
+    trigger_idx = np.ascontiguousarray(trigger_idx, dtype=np.int64)
+    top = np.ascontiguousarray(op_channel_idx, dtype=np.int32)
+    ntrig = trigger_idx.shape[0]
+    ndm = top.shape[-1] if top.ndim else 0
+    if top.ndim == 1:
+        top = np.ascontiguousarray(np.broadcast_to(top, (ntrig, ndm)))
+    sop = np.ascontiguousarray(signal_op_channel_idx, dtype=np.int32)
+    n_det, n_ticks, _ = lib.context_light_shape()
+    digit = np.zeros((ntrig, ndm, int(digit_samples)), dtype='f8')
+    if ntrig == 0:
+        return digit
+    noise = None if light_det_noise is None else np.ascontiguousarray(light_det_noise, dtype=np.float64)
+    ps = None if phases_signal is None else np.ascontiguousarray(phases_signal, dtype=np.float64)
+    pm = None if phases_missing is None else np.ascontiguousarray(phases_missing, dtype=np.float64)
+    lib.check(lib.load().ldsim_dev_light_universe_waveforms(
+        lib.context(), C.c_int32(int(k)), lib.ptr(sop), C.c_int32(n_det), C.c_int32(n_ticks), lib.ptr(trigger_idx),
+        C.c_int32(ntrig), lib.ptr(top), C.c_int32(ndm), C.c_int32(int(digit_samples)), lib.ptr(noise),
+        C.c_int32(noise.shape[0] if noise is not None else 0), C.c_int32(noise.shape[1] if noise is not None else 0),
+        lib.ptr(ps), lib.ptr(pm), lib.ptr(digit)))
+    return digit
+
+
 # ---- output datasets (light_sim.py:621-757) -------------------------------------------------------------------------------
 light_wvfm_truth_dtype = np.dtype([('trigger_id', 'i4'), ('op_channel_id', 'i4'), ('tick', 'i4'), ('event_id', 'i4'),
                                    ('segment_id', 'i8'), ('pe_current', 'f8')])
