@@ -19,7 +19,7 @@ Faithfulness rules (Numba types arithmetic as f64; NumPy-2 scalars do not):
   * between stages the mutated float fields are rounded through f4 (the HDF5 schema);
   * FEE noise constants are 0 (the Numba RNG stream is third-party and unpinned).
 
-Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,chain,sampled,light,light_response,fee] [--jobs 8]
+Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,pixels_wide,chain,sampled,light,light_response,fee] [--jobs 8]
 """
 import argparse
 import importlib
@@ -399,6 +399,185 @@ def gen_pixels():
         out["segments_in"] = seg[keep]
         np.savez_compressed(os.path.join(GOLD, f"pixels_{cfg}.npz"), **out)
         print("pixels", cfg, "P", out["neigh"].shape, "max_length", out["max_length"])
+
+
+# --------------------------------------------------------------------------
+# pixels_wide: neighbourhoods of radius 1-4 (ring codes 0-8 and -1), the maps and the pixel sums built on them
+# --------------------------------------------------------------------------
+WIDE_CFGS = (("module0", 71), ("ndlar", 73))
+WIDE_RADII = (1, 2, 3, 4)
+WIDE_T = 40
+
+
+def wide_segments(det, seed):
+    """16 hand-placed segments in the TPC frame: 0 hugs the low-x edge of the pixel plane, 1 sits in the far corner, 2 hugs the
+    low-y edge (second TPC), 3 starts beside 0 and leaves the plane over the low-x edge (its active row gets -1 gaps), 4 lies
+    outside every TPC, 5 crosses several pixels (second TPC), 6-15 cluster over a few pixels so that pixels collect many
+    tracks at different ring distances."""
+    seg = hand_segments(det, 16, seed, plane_choices=[0])
+    rng = np.random.default_rng(seed + 7)
+    B = np.asarray(det.TPC_BORDERS)
+    pitch = det.PIXEL_PITCH
+    N0, N1 = int(det.N_PIXELS[0]), int(det.N_PIXELS[1])
+
+    def put(i, p, a, b, zfrac, dz):
+        """end points in pixel units (0.5 = centre of pixel 0) of plane p, depth as a fraction of the drift length"""
+        z = B[p, 2, 0] + zfrac * (B[p, 2, 1] - B[p, 2, 0])
+        seg["x_start"][i], seg["y_start"][i] = B[p, 0, 0] + a[0] * pitch, B[p, 1, 0] + a[1] * pitch
+        seg["x_end"][i], seg["y_end"][i] = B[p, 0, 0] + b[0] * pitch, B[p, 1, 0] + b[1] * pitch
+        seg["z_start"][i], seg["z_end"][i] = z - 0.5 * dz, z + 0.5 * dz
+
+    put(0, 0, (0.4, 50.5), (0.6, 50.7), 0.5, 0.05)
+    put(1, 0, (N0 - 0.3, N1 - 0.4), (N0 - 0.6, N1 - 0.7), 0.3, 0.02)
+    put(2, 1, (30.2, 1.3), (31.7, 0.4), 0.6, 0.1)
+    put(3, 0, (2.3, 52.6), (-1.4, 53.2), 0.4, 0.2)
+    put(4, 0, (20.5, 20.5), (20.9, 20.7), 0.5, 0.05)
+    for f in ("x_start", "x_end"):
+        seg[f][4] += 500.0
+    put(5, 1, (70.2, 140.3), (74.6, 143.8), 0.7, 0.3)
+    for i in range(6, 16):
+        c = np.array([60.5, 120.5]) + rng.uniform(-1.2, 1.2, 2)
+        d = rng.uniform(-0.4, 0.4, 2)
+        put(i, 0, c - d, c + d, rng.uniform(0.2, 0.8), rng.uniform(-0.2, 0.2))
+    for ax in "xyz":
+        seg[ax] = 0.5 * (seg[ax + "_start"].astype(np.float64) + seg[ax + "_end"])
+    d = np.stack([seg[ax + "_end"].astype(np.float64) - seg[ax + "_start"] for ax in "xyz"])
+    seg["dx"] = np.sqrt((d * d).sum(axis=0))
+    seg["dE"] = seg["dEdx"].astype(np.float64) * seg["dx"]
+    return seg
+
+
+def sparse_fields(name, a):
+    """A mostly-zero array as {name_shape, name_step, name_val}: the flat indices of its non-zero entries as differences
+    (first index, then steps; cumsum restores them) and the values, f4 where that loses nothing (tests/helpers.py dense_field)."""
+    flat = np.ascontiguousarray(a).ravel()
+    idx = np.flatnonzero(flat)
+    val = flat[idx]
+    if np.array_equal(val.astype(np.float32).astype(val.dtype), val):
+        val = val.astype(np.float32)
+    return {name + "_shape": np.array(a.shape, dtype=np.int64), name + "_step": np.diff(idx, prepend=0).astype(np.int64),
+            name + "_val": val}
+
+
+def save_npz_fixed(path, arrays):
+    """np.savez_compressed with the members in sorted order and a fixed time stamp: the same arrays give the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for k in sorted(arrays):
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[k]), allow_pickle=False)
+
+
+def _wide_job(args):
+    cfg, seed, radius = args
+    ref = Ref(cfg)
+    det = ref.detector
+    seg = wide_segments(det, seed)
+    r = run_quench_drift(ref, to_ref(seg), ref.physics.BIRKS)
+    n = r.shape[0]
+    # the reference indexes TPC_BORDERS[pixel_plane] with the "no plane" value of a segment outside every TPC (IndexError
+    # here, an out-of-bounds read on the device): its kernels run on the other rows, and the row of that segment keeps what
+    # the driver allocates (-1 ids and codes, 0 pixels; cli/simulate_pixels.py:930-933)
+    inside = r["pixel_plane"] != det.DEFAULT_PLANE_INDEX
+    assert (~inside).sum() == 1 and not inside[4]
+    ri = r[inside]
+    ni = ri.shape[0]
+    bpg = max(1, -(-ni // 128))
+    mp = np.array([0])
+    ref.pixels_from_track.max_pixels[bpg, 128](ri, mp)
+    nmax = int(mp[0])
+    P = (2 * radius + 1) * nmax + (1 + 2 * radius) * radius * 2          # cli/simulate_pixels.py:928
+    act_i = np.full((ni, nmax), -1, dtype=np.int32)
+    neigh_i = np.full((ni, P), -1, dtype=np.int32)
+    nrad_i = np.full((ni, P), -1, dtype=np.int32)
+    nlist_i = np.zeros(ni)
+    ref.pixels_from_track.get_pixels[bpg, 128](ri, act_i, neigh_i, nrad_i, nlist_i, radius)
+    active = np.full((n, nmax), -1, dtype=np.int32); active[inside] = act_i
+    neigh = np.full((n, P), -1, dtype=np.int32); neigh[inside] = neigh_i
+    nrad = np.full((n, P), -1, dtype=np.int32); nrad[inside] = nrad_i
+    nlist = np.zeros(n); nlist[inside] = nlist_i
+    # unique pixels and the index map as the driver forms them (cli/simulate_pixels.py:953-956, 1021-1025)
+    unique_pix = np.unique(neigh.reshape(-1))
+    unique_pix = unique_pix[unique_pix != -1]
+    U = unique_pix.shape[0]
+    pixel_index_map = np.full(neigh.shape, -1, dtype=np.int64)
+    for i_ in range(n):
+        compare = neigh[i_, ..., np.newaxis] == unique_pix
+        idx = np.where(compare)
+        pixel_index_map[i_, idx[0]] = idx[1]
+    max_distance = int(nrad.max()) + 1
+
+    def pixel_map(M):
+        tpm = np.full((U, M), -1, dtype=np.int64)
+        ref.detsim.get_track_pixel_map2[max(1, -(-U // 32)), 32](_PadRows(tpm, 32), _PadVec(unique_pix, 32), neigh, nrad,
+                                                                 max_distance)
+        return tpm
+
+    # synthetic currents: a multiple of 1/16 below 16 per tick (every sum is exact in f8 whatever the order), starts on the
+    # tick grid with one track beginning before tick 0 and one running past the last tick
+    rng = np.random.default_rng(1000 * seed + radius)
+    NT = len(det.TIME_TICKS)
+    signals = (rng.integers(1, 256, size=(n, P, WIDE_T)) / 16.0).astype(np.float32)
+    start_ticks = rng.integers(150, NT - 400, size=n)
+    start_ticks[6] = -15
+    start_ticks[7] = NT - 12
+    track_starts = start_ticks * det.TIME_SAMPLING
+    assert np.array_equal(np.round(track_starts / det.TIME_SAMPLING), start_ticks)
+
+    def sums(tpm):
+        M = tpm.shape[1]
+        ps = np.zeros((U, NT)); pts = np.zeros((U, NT, M)); ovf = np.zeros(U)
+        ref.detsim.sum_pixel_signals[(n, P, -(-WIDE_T // 64)), (1, 1, 64)](ps, signals, track_starts, pixel_index_map, tpm,
+                                                                           pts, ovf)
+        return ps, pts, ovf
+
+    M = int(ref.sim.MAX_TRACKS_PER_PIXEL)
+    tpm = pixel_map(M)
+    # pairs that can take a slot, per unique pixel
+    mappable = np.zeros(U, dtype=np.int64)
+    np.add.at(mappable, pixel_index_map[(pixel_index_map >= 0) & (nrad >= 0)], 1)
+    assert mappable.max() <= M and np.array_equal((tpm >= 0).sum(axis=1), mappable)
+    M_low = max(1, int(mappable.max()) // 2)
+    tpm_low = pixel_map(M_low)
+    # what the fixture is for
+    codes = set(np.unique(nrad[neigh >= 0]).tolist())
+    if radius == 4:
+        assert codes == set(range(-1, 9)), codes
+    if radius >= 3:
+        assert -1 in codes
+        assert ((tpm >= 0).sum(axis=1) == 0).any(), "no unique pixel whose every pair has distance -1"
+    else:
+        assert -1 not in codes
+    assert (mappable > M_low).any(), "the lowered cap overflows on no pixel"
+    assert (active[inside] == -1).any() and (active[3] == -1).any()
+    out = dict(segments_in=seg, radius=radius, max_pixels=nmax, active=active, neigh=neigh, nrad=nrad, n_pixels_list=nlist,
+               unique_pix=unique_pix, pixel_index_map=pixel_index_map.astype(np.int32), track_pixel_map=tpm.astype(np.int32),
+               track_pixel_map_low=tpm_low.astype(np.int32), max_tracks_low=M_low, signals_seed=1000 * seed + radius,
+               signals_ticks=WIDE_T, start_ticks=start_ticks)
+    for tag, m in (("", tpm), ("_low", tpm_low)):
+        ps, pts, ovf = sums(m)
+        assert ps.min() >= 0 and (ps[:, 0] > 0).any() and (ps[:, NT - 1] > 0).any()      # both ends of the tick axis clip
+        out.update(sparse_fields("pixels_signals" + tag, ps))
+        out.update(sparse_fields("pixels_tracks_signals" + tag, pts))
+        out["overflow" + tag] = ovf.astype(np.int8)
+        if tag:
+            assert (ovf[mappable > M_low] == 1).all()
+    path = os.path.join(GOLD, f"pixels_wide_{cfg}_r{radius}.npz")
+    save_npz_fixed(path, out)
+    return (cfg, radius, P, int((neigh >= 0).sum()), U, int(((tpm >= 0).sum(axis=1) == 0).sum()), sorted(codes), M_low,
+            os.path.getsize(path))
+
+
+def gen_pixels_wide(jobs):
+    """get_pixels at radius 1-4 passed as its argument, unique pixels, index map, get_track_pixel_map2 and sum_pixel_signals
+    (synthetic seeded currents; tracks_current is not run) at MAX_TRACKS_PER_PIXEL and at a cap low enough to overflow."""
+    with Pool(jobs) as pool:
+        for res in pool.map(_wide_job, [(cfg, seed, rad) for cfg, seed in WIDE_CFGS for rad in WIDE_RADII], chunksize=1):
+            print("pixels_wide %s radius %d: P %d, %d pairs, %d unique pixels, %d without a slot, codes %s, low cap %d, "
+                  "%d bytes" % res)
 
 
 def _current_job(args):
@@ -1295,7 +1474,8 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     for s in a.sets.split(","):
         {"consts": gen_consts, "qd": gen_qd, "pixels": gen_pixels, "light": gen_light, "light_response": gen_light_response,
-         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_export": gen_light_export, "fee": gen_fee}[s]()
+         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_export": gen_light_export, "fee": gen_fee,
+         "pixels_wide": lambda: gen_pixels_wide(a.jobs)}[s]()
     return 0
 
 

@@ -832,3 +832,26 @@ def test_driver_writes_the_universes(tmp_path, capsys):
         for fld, (ns, name) in _CONSTS.items():
             setattr(getattr(consts, ns), name, nominal[fld])
         _table_mode(synth.make_response("survey"))
+
+
+def test_nominal_is_the_launch_at_radius_3():
+    """universes(charge=[nominal]) over a launch at neighbour radius 3 (module0, TRAN_DIFF x 16) is that launch bit for bit, every
+    weight exactly 1.0, as in test 1: the pass walks the launch's slot list, in which the pixels whose every pair carries ring
+    code -1 have no slot."""
+    H.load_module0_wide(H.RADIUS3_SCALE)
+    try:
+        seg, resp = H.radius3_segments(), synth.make_response("survey")
+        assert H.oracle_radius(seg) == 3
+        ch = ChargeChain(resp)
+        _upload(ch, seg, np.zeros(len(seg), dtype=np.int32))
+        own = _launch_result(ch)
+        nominal = CU.nominal(CU.BIRKS)
+        assert nominal == ch.charge_variation_nominal()
+        u = ch.universes(charge=[nominal], dense=True)[0]
+    finally:
+        H.load_cfg("module0")
+    no_slot = (own["track_pixel_map"] >= 0).sum(axis=1) == 0
+    assert no_slot.sum() >= 10 and u["n_hits"] >= 5
+    assert (u["weights"] == 1.0).all() and len(u["weights"]) == len(seg) and u["n_unweightable"] == 0
+    _assert_same(u, own, "radius 3")
+    assert not u["adc_list"][no_slot].any() and not u["hit_count"][no_slot].any()

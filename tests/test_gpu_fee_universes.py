@@ -736,3 +736,24 @@ def test_driver_writes_the_universes(tmp_path, capsys):
     with pytest.raises(ValueError, match="--rng keyed"):
         cli.run_simulation(output_filename=str(tmp_path / "x.npz"), **dict(common, rng="table"),
                            fee_universes=str(tmp_path / "noisy.json"))
+
+
+def test_identity_on_a_radius_3_launch():
+    """[nominal()] over a launch at neighbour radius 3 (module0, TRAN_DIFF x 16) is that launch bit for bit, as in test 1: the pass
+    walks the launch's slot list, in which the pixels whose every pair carries ring code -1 have no slot."""
+    H.load_module0_wide(H.RADIUS3_SCALE)
+    try:
+        seg, resp = H.radius3_segments(), synth.make_response("survey")
+        assert H.oracle_radius(seg) == 3
+        ch = ChargeChain(resp)
+        _upload(ch, seg, np.zeros(len(seg), dtype=np.int32))
+        own = _launch_result(ch)
+        tpm = ch.download()["track_pixel_map"]
+        assert FU.nominal() == ch.fee_variation_nominal() and not FU.is_noisy(FU.nominal())
+        u = ch.fee_universes([FU.nominal()], dense=True)
+    finally:
+        H.load_cfg("module0")
+    no_slot = (tpm >= 0).sum(axis=1) == 0
+    assert no_slot.sum() >= 10 and len(u) == 1 and u[0]["n_hits"] >= 5
+    _assert_same(u[0], own, "radius 3")
+    assert not u[0]["adc_list"][no_slot].any() and not u[0]["hit_count"][no_slot].any()

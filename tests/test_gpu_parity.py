@@ -391,28 +391,7 @@ def test_fused_chain_golden():
         assert st.n_unique == len(g["unique_pix"]) and st.max_length == int(g["max_length"])
 
 
-def _oracle_chain(seg, response, thr_of_pixel=None, gain_of_pixel=None, rng_states=None):
-    """Reference dataflow on the oracle; `thr_of_pixel` / `gain_of_pixel` are dense arrays over pixel ids standing for
-    the driver's pixel_thresholds_lut[unique_pix] / pixel_gains_lut[unique_pix] (cli/simulate_pixels.py:1079-1100)."""
-    ref = seg.copy()
-    O.quench(ref, consts.physics.BIRKS)
-    O.drift(ref)
-    nmax = O.max_pixels(ref)
-    r = int(np.ceil(ref["tran_diff"].max() * 5 / consts.detector.PIXEL_PITCH))
-    P = (2 * r + 1) * nmax + (1 + 2 * r) * r * 2
-    _, neigh, nrad, _ = O.get_pixels(ref, nmax, P, r)
-    upix = O.unique_pixels(neigh)
-    starts, T = O.time_intervals(ref)
-    sig = O.tracks_current(ref, neigh, T, response)
-    pim = O.pixel_index_map(neigh, upix)
-    tpm = O.track_pixel_map(upix, neigh, nrad, int(nrad.max()) + 1, consts.sim.MAX_TRACKS_PER_PIXEL)
-    ps, pts, ovf = O.sum_pixel_signals(sig, starts, pim, tpm, len(upix))
-    tt = np.linspace(0, consts.detector.TIME_INTERVAL[1], ps.shape[1] + 1)
-    thr = (np.full(len(upix), consts.detector.DISCRIMINATION_THRESHOLD) if thr_of_pixel is None
-           else np.ascontiguousarray(thr_of_pixel[upix]))
-    adc, ticks, frac = O.get_adc_values(ps, pts, tt, thr, rng_states=rng_states)
-    gain = None if gain_of_pixel is None else gain_of_pixel[upix][:, None] * np.ones((1, adc.shape[1]))
-    return dict(unique_pix=upix, tpm=tpm, adc=adc, ticks=ticks, frac=frac, digit=O.digitize(adc, gain), ref=ref)
+_oracle_chain = H.oracle_chain
 
 
 @pytest.mark.parametrize("cfg,kind", [("module0", "survey"), ("2x2_no_modvar", "dense"), ("ndlar", "golden")])

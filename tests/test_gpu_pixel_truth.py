@@ -517,3 +517,26 @@ def test_driver_writes_both_datasets(tmp_path, capsys):
     pos = by_id[np.searchsorted(fseg["segment_id"][by_id], tr["segment_id"])]
     assert np.array_equal(fseg["segment_id"][pos], tr["segment_id"])
     assert np.array_equal(fseg["event_id"][pos], np.repeat(px["event_id"], px["track_count"]))
+
+
+def test_radius_3_launch_with_pixels_without_a_slot():
+    """A launch at neighbour radius 3 (module0, TRAN_DIFF x 16): pairs farther than |dx| + |dy| = 4 from their segment carry ring
+    code -1, make their pixel a row of the results and take no slot (pixels_from_track.py:251-252, detsim.py:582).  Such a pixel
+    has no track and exactly no charge; every other row against the oracle as in test 1."""
+    H.load_module0_wide(H.RADIUS3_SCALE)
+    try:
+        seg, resp = H.radius3_segments(), synth.make_response("survey")
+        assert H.oracle_radius(seg) == 3
+        ref = _reference(seg, resp)
+        ch = ChargeChain(resp)
+        st, out, dense, compact = _launch(ch, seg, np.zeros(len(seg), dtype=np.int32))
+    finally:
+        H.load_cfg("module0")
+    no_slot = (ref["tpm"] >= 0).sum(axis=1) == 0
+    assert no_slot.sum() >= 10 and (ref["ovf"][no_slot] == 1).all() and st.n_unique == len(ref["upix"])
+    _assert_matches_reference(out, dense, {0: ref}, (0,), "radius 3")
+    assert (out["track_pixel_map"][no_slot] == -1).all() and not out["adc_list"][no_slot].any()
+    assert (dense["q_induced"][no_slot] == 0).all() and (dense["q_abs"][no_slot] == 0).all()
+    assert (dense["q_track"][no_slot] == 0).all()
+    rows = _assert_compact_is_the_dense_selection(out, dense, compact, 0.0)
+    assert len(rows) == st.n_unique and (compact["pixels"]["n_tracks"][no_slot] == 0).all()

@@ -589,3 +589,26 @@ def test_driver_writes_both_datasets(tmp_path, capsys):
     none, _ = run("none.npz", pixel_waveforms=True, pixel_waveforms_threshold=1e30, chunk_segments=40)
     assert none["pixel_waveforms"].dtype == PW.FILE_SPAN and len(none["pixel_waveforms"]) == 0
     assert none["pixel_waveform_samples"].dtype == np.float32 and len(none["pixel_waveform_samples"]) == 0
+
+
+def test_dense_radius_3_launch_with_pixels_without_a_slot():
+    """A launch at neighbour radius 3 (module0, TRAN_DIFF x 16): the pixels whose every pair carries ring code -1 are rows of the
+    launch with no slot (pixels_from_track.py:251-252, detsim.py:582); their waveform is exactly 0, every other row is the
+    oracle's sum_pixel_signals as in test 1."""
+    H.load_module0_wide(H.RADIUS3_SCALE)
+    try:
+        seg, resp = H.radius3_segments(), synth.make_response("survey")
+        assert H.oracle_radius(seg) == 3
+        ref = _oracle_sums(seg, resp)
+        ch = ChargeChain(resp)
+        st, out = _launch(ch, seg, np.zeros(len(seg), dtype=np.int32))
+        S = ch.pixel_waveforms(dense=True)
+        compact = ch.pixel_waveforms()
+    finally:
+        H.load_cfg("module0")
+    no_slot = (ref["tpm"] >= 0).sum(axis=1) == 0
+    assert no_slot.sum() >= 10 and not ref["S"][no_slot].any() and st.n_unique == len(ref["upix"])
+    assert np.array_equal(out["track_pixel_map"], ref["tpm"])
+    _assert_dense_matches_oracle(out, S, {0: ref}, (0,), "radius 3")
+    assert not S[no_slot].any() and S[~no_slot].any()
+    assert not np.isin(compact["spans"]["row"], np.flatnonzero(no_slot)).any()      # no span on a pixel without a slot

@@ -247,3 +247,44 @@ def test_light_waveform_chain_golden(name):
     ph_mis = H.det_phases((n_missing, Tp // 2 + 1), int(seeds[1])) if len(seeds) > 1 else None
     d2, _, _ = O.sim_triggers(*args, g["noise_spectrum"], phases_signal=ph_sig, phases_missing=ph_mis)
     assert np.array_equal(d2, g["wvfm_noisy"])
+
+
+@pytest.mark.parametrize("radius", H.WIDE_RADII)
+@pytest.mark.parametrize("cfg", H.WIDE_CFGS)
+def test_wide_neighbourhood_golden(cfg, radius):
+    """get_pixels at radius 1-4 handed in as its argument, the unique pixels, the index map, get_track_pixel_map2 and
+    sum_pixel_signals of the oracle against the reference's own (oracle/gen_golden.py gen_pixels_wide): neighbourhoods clipped by
+    an edge and a corner of the pixel plane, a segment leaving the plane, one outside every TPC, ring codes 0-8, the -1 of
+    |dx| + |dy| > 4 from radius 3 on (pixels that are unique pixels yet take no track), and the slots kept in ring order when
+    MAX_TRACKS_PER_PIXEL is too small.  Integers exact; the sums to rtol 1e-12 and 1e-12 of the largest sum."""
+    H.load_cfg(cfg)
+    g, signals, starts = H.wide_case(cfg, radius)
+    r = H.quench_drift(O, g["segments_in"])
+    assert O.max_pixels(r) == int(g["max_pixels"])
+    P = g["neigh"].shape[1]
+    assert P == (2 * radius + 1) * int(g["max_pixels"]) + (1 + 2 * radius) * radius * 2
+    active, neigh, nrad, nlist = O.get_pixels(r, int(g["max_pixels"]), P, radius)
+    assert np.array_equal(active, g["active"])
+    assert np.array_equal(neigh, g["neigh"])
+    assert np.array_equal(nrad, g["nrad"])
+    assert np.array_equal(nlist, g["n_pixels_list"])
+    upix = O.unique_pixels(neigh)
+    assert np.array_equal(upix, g["unique_pix"])
+    pim = O.pixel_index_map(neigh, upix)
+    assert np.array_equal(pim, g["pixel_index_map"])
+    # what the fixture is there for
+    codes = set(np.unique(nrad[neigh >= 0]).tolist())
+    assert codes == {1: {0, 1, 2}, 2: {0, 1, 2, 3, 4, 6}, 3: set(range(-1, 8)), 4: set(range(-1, 9))}[radius]
+    assert (active[3] == -1).any() and nlist[4] == 0 and (neigh[4] == -1).all()
+    for tag, M in (("", consts.sim.MAX_TRACKS_PER_PIXEL), ("_low", int(g["max_tracks_low"]))):
+        tpm = O.track_pixel_map(upix, neigh, nrad, int(nrad.max()) + 1, M)
+        assert np.array_equal(tpm, g["track_pixel_map" + tag])
+        ps, pts, ovf = O.sum_pixel_signals(signals, starts, pim, tpm, len(upix))
+        top = H.sparse_field(g, "pixels_signals" + tag)[2].max()
+        H.assert_sparse_close(ps, g, "pixels_signals" + tag, rtol=1e-12, atol=1e-12 * top)
+        H.assert_sparse_close(pts, g, "pixels_tracks_signals" + tag, rtol=1e-12, atol=1e-12 * top)
+        assert np.array_equal(ovf, g["overflow" + tag])
+        no_slot = (tpm >= 0).sum(axis=1) == 0
+        assert no_slot.any() == (radius >= 3) and not ps[no_slot].any()
+        if tag:
+            assert ((tpm >= 0).sum(axis=1) == M).any() and ovf.any()
