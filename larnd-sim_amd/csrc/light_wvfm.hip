@@ -674,7 +674,8 @@ static int sim_triggers_run(ldsim_ctx* ctx, const float* d_signal, const int32_t
   A.T = T; A.n0 = n0; A.Tp = Tp; A.Mt = Mt;
   A.truth_threshold = h.mc_truth_threshold;
   A.lsb = ldexp(1.0, 16 - h.light_nbit);
-  A.sig_f32diff = is_f4 && ctx->numba_f32;
+  // appending the missing channels concatenates f8 noise rows (:601): the array digitize_signal receives is f8 then
+  A.sig_f32diff = is_f4 && n_missing == 0 && ctx->numba_f32;
   hipLaunchKernelGGL(light_digitize_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, A, d_digit, d_dtid, d_dtph);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));

@@ -19,7 +19,7 @@ Faithfulness rules (Numba types arithmetic as f64; NumPy-2 scalars do not):
   * between stages the mutated float fields are rounded through f4 (the HDF5 schema);
   * FEE noise constants are 0 (the Numba RNG stream is third-party and unpinned).
 
-Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,pixels_wide,chain,sampled,light,light_response,fee] [--jobs 8]
+Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,pixels_wide,chain,sampled,light,light_response,light_wvfm,light_wvfm_edges,fee] [--jobs 8]
 """
 import argparse
 import importlib
@@ -981,6 +981,448 @@ def gen_light_wvfm():
         np.savez_compressed(os.path.join(GOLD, f"light_wvfm_{cfg}_{icase}.npz"), **out)
 
 
+# --------------------------------------------------------------------------
+# light_wvfm_edges: get_triggers, gen_light_detector_noise and sim_triggers / digitize_signal at constants no shipped
+# configuration has (non-integer LIGHT_DIGIT_SAMPLE_SPACING / LIGHT_TICK_SIZE, sample factors 1..128, tiny transforms, ...)
+# --------------------------------------------------------------------------
+LW_EDGE_MAX_BYTES = 256 * 1024
+LW_EDGE_WINDOW = (0.02, 0.05)          # LIGHT_TRIG_WINDOW of most cases: 20 + 50 ticks of 1 ns
+
+
+def _lw_edge_ref(cfg, over):
+    """The reference loaded for `cfg` with the constants of `over` set on its modules (MC_TRUTH_THRESHOLD lives on sim, the
+    others on light), cupy's round tapped and cupy's random.uniform replaced by det_phases (seed set through the tap)."""
+    ref = Ref(cfg)
+    for k, v in over.items():
+        setattr(ref.sim if k == "MC_TRUTH_THRESHOLD" else ref.light, k, v)
+    cupy = sys.modules["cupy"]
+    tap = types.SimpleNamespace(rounded=[], seed=0, calls=0)
+
+    def tapped_round(a, *args, **kw):
+        tap.rounded.append(np.array(a, dtype=np.float64, copy=True))
+        return np.round(a, *args, **kw)
+
+    def uniform(size=None):
+        u = det_phases(size, tap.seed + tap.calls)
+        tap.calls += 1
+        return u
+    cupy.round = tapped_round
+    cupy.random = types.SimpleNamespace(uniform=uniform)
+    ref.tap = tap
+    return ref
+
+
+def _tie_margin(arrays):
+    """smallest distance of any value from a rounding tie (x.5), in units of the rounding step"""
+    return min(float(np.abs(a - np.floor(a) - 0.5).min()) for a in arrays)
+
+
+def _lw_edge_save(case, cfg, over, out):
+    """One fixture: the arrays, the configuration's name and the overridden constants as JSON (tests/helpers.py
+    load_light_wvfm_edge_case sets them).  Every `reach_*` count must be non-zero: it says the case got where it was sent."""
+    out = dict(out)
+    for k, v in out.items():
+        if k.startswith("reach_"):
+            assert int(v) > 0, (case, k)
+            out[k] = np.int64(v)
+    out["cfg"] = np.array(cfg)
+    out["const_json"] = np.array(json.dumps({k: (list(v) if isinstance(v, tuple) else v) for k, v in over.items()},
+                                            sort_keys=True))
+    path = os.path.join(GOLD, f"light_wvfm_edge_{case}.npz")
+    save_npz_fixed(path, out)
+    size = os.path.getsize(path)
+    assert size < LW_EDGE_MAX_BYTES, (case, size)
+    reach = " ".join(f"{k[6:]}={int(v)}" for k, v in sorted(out.items()) if k.startswith("reach_"))
+    print(f"light_wvfm_edge {case:22s} {size:7d} bytes  {reach}")
+
+
+def _gen_lw_edge_triggers():
+    """get_triggers (light_sim.py:380-477), LIGHT_TRIG_MODE 0.  module0 cases: rows are channels 0..11 (groups 0 and 1 of
+    OP_CHANNEL_PER_TRIG = 6, both of the one module), thresholds handed in."""
+    ms = 0.001
+
+    def pulses(T, spec, nd=12, per=6, sigma=0.05, seed=0):
+        """f4 [nd][T]: a quiet background and, per (group, first tick, n ticks, value per row), a negative-going pulse"""
+        rng = np.random.default_rng(9100 + seed)
+        s = rng.normal(0, sigma, (nd, T)).astype('f4') if sigma else np.zeros((nd, T), dtype='f4')
+        for g, t0, n, v in spec:
+            s[g * per:(g + 1) * per, t0:t0 + n] = np.float32(v)
+        return s
+
+    W = LW_EDGE_WINDOW
+    base = dict(LIGHT_TRIG_MODE=0, LIGHT_TRIG_WINDOW=W, LIGHT_TICK_SIZE=ms)
+    thr0 = [[-50.0, -80.0]]
+    cases = []      # (name, cfg, constants, signal, threshold sets, sample factor, check(triggers per set, signal))
+
+    def add(name, over, sig, thr, sf, check, cfg="module0"):
+        cases.append((name, cfg, dict(base, **over), sig, np.array(thr, dtype='f8'), sf, check))
+
+    # sf = 1: 136 blocks, three workgroups of 64 with a ragged last one; a pulse in the first and one in the last
+    add("trig_sf1", dict(LIGHT_DIGIT_SAMPLE_SPACING=ms), pulses(135, [(0, 3, 3, -20.0), (1, 130, 2, -20.0)], seed=1), thr0, 1,
+        lambda t, s: dict(reach_blocks_past_128=int((t[0] >= 128).sum()), reach_triggers=len(t[0])))
+    # sf = 7, T a multiple of 7: the reference pads a whole block of zeros; a pulse in the last real block
+    add("trig_sf7_allpad", dict(LIGHT_DIGIT_SAMPLE_SPACING=7 * ms), pulses(84, [(1, 0, 7, -20.0), (0, 77, 7, -20.0)], seed=2),
+        thr0, 7, lambda t, s: dict(reach_all_padding_block=int(s.shape[1] % 7 == 0), reach_last_block=int((t[0] == 77).sum())))
+    add("trig_sf8", dict(LIGHT_DIGIT_SAMPLE_SPACING=8 * ms), pulses(100, [(1, 16, 8, -20.0), (0, 96, 4, -40.0)], seed=3), thr0, 8,
+        lambda t, s: dict(reach_triggers=len(t[0]), reach_partial_block=int((t[0] == 96).sum())))
+    # sf = 13: 4 real ticks of -24 (group sum) in the last block, 9 ticks of padding: mean -7.4 with the zeros, -24 without;
+    # threshold -10.  It must not trigger; the pulse of group 1 shows the case is live.
+    add("trig_sf13_tail", dict(LIGHT_DIGIT_SAMPLE_SPACING=13 * ms), pulses(95, [(1, 0, 13, -20.0), (0, 91, 4, -4.0)], seed=4),
+        [[-10.0, -80.0]], 13,
+        lambda t, s: dict(reach_triggers=int((t[0] == 0).sum()), reach_tail_quiet=int(len(t[0]) == 1),
+                          reach_tail_below_unpadded=int(s[:6, 91:].astype('f8').sum(axis=0).mean() < -10.0)))
+    add("trig_sf128", dict(LIGHT_DIGIT_SAMPLE_SPACING=128 * ms), pulses(300, [(0, 128, 128, -10.0), (1, 256, 44, -20.0)], seed=5),
+        thr0, 128, lambda t, s: dict(reach_triggers=int((t[0] == 128).sum()), reach_tail_quiet=int((t[0] < 256).all())))
+    # half-to-even: 2.5 -> 2, 3.5 -> 4.  The first pulse fills one block of the rounded factor with a group sum of -54
+    # against -50: blocks of 3 (or of 3 and 5) ticks would hold it diluted to -36 (-36 and -43) and not cross
+    add("trig_ratio_2p5", dict(LIGHT_DIGIT_SAMPLE_SPACING=0.0025), pulses(101, [(0, 10, 2, -9.0), (1, 100, 1, -30.0)], seed=6),
+        thr0, 2, lambda t, s: dict(reach_triggers=int((t[0] == 10).sum()), reach_last_tick=int((t[0] == 100).sum())))
+    add("trig_ratio_3p5", dict(LIGHT_DIGIT_SAMPLE_SPACING=0.0035), pulses(101, [(0, 16, 4, -9.0), (1, 92, 4, -14.0)], seed=7),
+        thr0, 4, lambda t, s: dict(reach_triggers=int(list(t[0]) == [16, 92])))
+    # a tick that is no power-of-ten fraction: 0.0021 / 0.0007 is 3.0 in f8 (5 * 0.0021 / 0.0007 is not 15: lerp_order)
+    add("trig_tick_0p0007", dict(LIGHT_TICK_SIZE=0.0007, LIGHT_DIGIT_SAMPLE_SPACING=0.0021, LIGHT_TRIG_WINDOW=(0.014, 0.035)),
+        pulses(100, [(0, 9, 3, -9.0), (1, 99, 1, -50.0)], seed=8), thr0, 3,
+        lambda t, s: dict(reach_triggers=int(list(t[0]) == [9, 99])))
+    # block mean == threshold: `<` is strict.  Group sums -3, -6, .. -30 over one block of 10: mean -16.5 exactly
+    eq = np.zeros((12, 80), dtype='f4')
+    eq[:6, 30:40] = -0.5 * np.arange(1, 11, dtype='f4')
+    assert eq[:6, 30:40].astype('f8').sum(axis=0).mean() == -16.5
+    add("trig_mean_eq_thr", dict(LIGHT_DIGIT_SAMPLE_SPACING=10 * ms), eq, [[-16.5, -80.0], [np.nextafter(-16.5, 0.0), -80.0]], 10,
+        lambda t, s: dict(reach_equal_no_trigger=int(len(t[0]) == 0), reach_ulp_trigger=int(list(t[1]) == [30])))
+    # f4 group sum in row order: 1e8 + -3 + -1e8 = 0 in f4, -3 in f8; threshold -1
+    cancel = pulses(80, [(1, 50, 10, -20.0)], sigma=0)
+    cancel[0, 20:30], cancel[1, 20:30], cancel[2, 20:30] = 1e8, -3.0, -1e8
+    add("trig_f4_cancel", dict(LIGHT_DIGIT_SAMPLE_SPACING=10 * ms), cancel, [[-1.0, -80.0]], 10,
+        lambda t, s: dict(reach_f4_sum_quiet=int(list(t[0]) == [50]),
+                          reach_f8_sum_would=int(s[:6, 20:30].astype('f8').sum(axis=0).mean() < -1.0)))
+    # five pulses in one module: the third trigger comes out at the reference's absolute-index re-slicing, not at a crossing
+    add("trig_three_in_module", dict(LIGHT_DIGIT_SAMPLE_SPACING=10 * ms),
+        pulses(700, [(0, 50, 10, -20.0), (0, 200, 10, -20.0), (1, 350, 10, -20.0), (1, 520, 10, -20.0), (1, 640, 10, -20.0)], seed=9),
+        thr0, 10, lambda t, s: dict(reach_triggers=int(len(t[0]) >= 3),
+                                    reach_off_crossing=int(sum(1 for i in t[0] if s[:, int(i)].min() > -10.0))))
+    add("trig_last_tick", dict(LIGHT_DIGIT_SAMPLE_SPACING=2 * ms), pulses(81, [(0, 80, 1, -30.0)], seed=10), thr0, 2,
+        lambda t, s: dict(reach_last_tick=int(list(t[0]) == [80])))
+    # 2x2, groups of 64 rows: group 1 spans the second half of module 1's rows 0..95 and the first third of module 2's
+    g64 = pulses(80, [(1, 32, 16, -100.0)], nd=384, per=64, sigma=0)
+    g64[64:128] += np.random.default_rng(9111).normal(0, 0.05, (64, 80)).astype('f4')
+    add("trig_2x2_group64", dict(LIGHT_DIGIT_SAMPLE_SPACING=0.016, OP_CHANNEL_PER_TRIG=64), g64, [[-4500.0] * 6], 16,
+        lambda t, s: dict(reach_two_modules=int(list(t[0]) == [32, 32])), cfg="2x2_no_modvar")
+
+    for name, cfg, over, sig, thr, sf, check in cases:
+        ref = _lw_edge_ref(cfg, over)
+        light = ref.light
+        assert round(light.LIGHT_DIGIT_SAMPLE_SPACING / light.LIGHT_TICK_SIZE) == sf, (name, sf)
+        nd = sig.shape[0]
+        op_channel = (light.TPC_TO_OP_CHANNEL[:].ravel() if nd != 12 else np.arange(12)).astype('i4')
+        assert op_channel.shape[0] == nd and thr.shape[1] * light.OP_CHANNEL_PER_TRIG == nd
+        out = dict(signal=sig, op_channel=op_channel, group_threshold=thr, sample_factor=np.int64(sf))
+        trigs = []
+        for i, th in enumerate(thr):
+            trig, trig_op, trig_type = ref.light_sim.get_triggers(sig.copy(), th.copy(), _ga(op_channel), 0)   # raising fails the run
+            trig, trig_op = np.asarray(trig).astype('i8'), np.asarray(trig_op).astype('i4')
+            assert len(trig) == 0 or trig_op.shape == (len(trig), 96)
+            out[f"trigger_idx_{i}"], out[f"trigger_op_channel_idx_{i}"] = trig, trig_op
+            out[f"trigger_type_{i}"] = np.asarray(trig_type).astype('i8')
+            trigs.append(trig)
+        if name == "trig_2x2_group64":          # modules 1 and 2 fired, with their own channels
+            assert np.array_equal(out["trigger_op_channel_idx_0"], np.arange(192).reshape(2, 96))
+        out.update(check(trigs, sig))
+        _lw_edge_save(name, cfg, over, out)
+
+
+def _gen_lw_edge_noise():
+    """gen_light_detector_noise (light_sim.py:339-377) with det_phases for the uniform numbers, 3 rows each.  The phase seed
+    moves on until no value of the inverse transform -- what the reference hands to its round -- lies within 1e-6 LSB of a
+    tie: the device's sincos and twiddle rotation (at most 513 terms of up to ~2e4 LSB, error ~1e-9 LSB) cannot cross that."""
+    ms = 0.001
+    tiny = dict(LIGHT_TICK_SIZE=ms, LIGHT_DET_NOISE_SAMPLE_SPACING=ms)
+    cases = (("noise_tiny", tiny, 9, (2, 3, 4, 16, 17), 81),
+             ("noise_beyond_table", dict(LIGHT_TICK_SIZE=ms, LIGHT_DET_NOISE_SAMPLE_SPACING=0.004), 5, (64,), 82),
+             ("noise_chunk", tiny, 9, (1026, 1027, 1028), 83))
+    for name, over, nbins, sizes, seed in cases:
+        ref = _lw_edge_ref("module0", over)
+        light, tap = ref.light, ref.tap
+        rng = np.random.default_rng(seed)
+        spectrum = np.abs(rng.normal(0, 1.0, (3, nbins))) * np.linspace(6000.0, 400.0, nbins) + 50.0
+        out = dict(noise_spectrum=spectrum, n_samples=np.array(sizes, dtype='i8'))
+        seeds, margins = [], []
+        noise_freq = np.fft.rfftfreq((nbins - 1) * 2, d=light.LIGHT_DET_NOISE_SAMPLE_SPACING)
+        for n in sizes:
+            for attempt in range(64):
+                tap.seed, tap.calls = 1000 * seed + 64 * len(seeds) + attempt, 0
+                del tap.rounded[:]
+                nz = ref.light_sim.gen_light_detector_noise((3, n), spectrum)
+                assert tap.calls == 1 and len(tap.rounded) == 1
+                margin = _tie_margin(tap.rounded)
+                if margin >= 1e-6:
+                    break
+            else:
+                raise RuntimeError("no phase seed clear of a rounding tie")
+            assert nz.shape == (3, n) and np.isfinite(nz).all() and (nz != 0).any()
+            out[f"noise_{n}"] = nz
+            seeds.append(tap.seed); margins.append(margin)
+            desired = np.fft.rfftfreq(n, d=light.LIGHT_TICK_SIZE)
+            exact = int(np.isin(desired, noise_freq).sum())
+            out[f"exact_freq_{n}"] = np.int64(exact)
+            out[f"beyond_table_{n}"] = np.int64((desired > noise_freq[-1]).sum())
+            if name == "noise_tiny" and n in (2, 4, 16):          # every desired frequency is a table frequency, the last included
+                assert exact == n // 2 + 1 and desired[-1] == noise_freq[-1]
+                out[f"reach_all_exact_{n}"] = exact
+            if n % 2:
+                assert (nz[:, -1] == 0).all()
+                out[f"reach_odd_zero_{n}"] = 1
+            if name == "noise_beyond_table":
+                out["reach_beyond_table"] = int((desired > noise_freq[-1]).sum() > len(desired) // 2)
+            if name == "noise_chunk":
+                out[f"reach_terms_{n}"] = (n - n % 2) // 2 - 1       # k = 1 .. N/2 - 1 of the inverse transform
+        out["phase_seed"] = np.array(seeds, dtype='i8')
+        out["noise_tie_margin"] = np.array(margins)
+        print(f"  {name}: n_samples {list(sizes)} noise_tie_margin {['%.3g' % m for m in margins]}")
+        _lw_edge_save(name, "module0", over, out)
+
+
+def _lw_edge_padding(light, T, trig):
+    """(front padding, padded length) the way sim_triggers pads (light_sim.py:574-592), for the branch counts only"""
+    pre = int(np.ceil(light.LIGHT_TRIG_WINDOW[0] / light.LIGHT_TICK_SIZE))
+    post = int(np.ceil(light.LIGHT_TRIG_WINDOW[1] / light.LIGHT_TICK_SIZE))
+    n0 = max(pre - int(min(trig)), 0)
+    Tp = T + n0
+    return n0, Tp + max(post + int(max(trig)) + n0 - Tp, 0)
+
+
+def _lw_edge_sample_counts(light, Tp, ns):
+    """which branch of interp (light_sim.py:256-271) each of the ns sample ticks takes in a waveform of Tp ticks"""
+    c = dict(on_tick=0, lerp=0, zero_past_end=0, zero_last_tick=0, off_grid=0)
+    for i in range(ns):
+        st = i * light.LIGHT_DIGIT_SAMPLE_SPACING / light.LIGHT_TICK_SIZE
+        i0 = int(np.floor(st))
+        if i0 > Tp - 1:
+            c["zero_past_end"] += 1
+        elif i0 == st:
+            c["on_tick"] += 1
+        elif i0 > Tp - 2:
+            c["zero_last_tick"] += 1
+        else:
+            c["lerp"] += 1
+        c["off_grid"] += int(st != i * round(light.LIGHT_DIGIT_SAMPLE_SPACING / light.LIGHT_TICK_SIZE, 1))
+    return c
+
+
+def _lw_edge_truth_counts(light, thr, tid, tph, n0, ns):
+    """How often the truth walk of digitize_signal (light_sim.py:511-543) takes each of its ways, over the given rows and the
+    ns sample ticks; the ticks are those of the padded frame, n0 in front."""
+    R, T, Mt = tid.shape
+    c = dict(same_slot=0, other_slot=0, no_match=0, below_threshold=0, minus1_end=0, all_full=0, frac_samples=0)
+    for i in range(ns):
+        st = i * light.LIGHT_DIGIT_SAMPLE_SPACING / light.LIGHT_TICK_SIZE
+        t0, t1 = int(np.floor(st)) - n0, int(np.ceil(st)) - n0
+        c["frac_samples"] += int(t0 != t1)
+        if not 0 <= t0 < T:
+            continue
+        for r in range(R):
+            for j in range(Mt):
+                id0 = tid[r, t0, j]
+                if id0 == -1:
+                    c["minus1_end"] += 1
+                    break
+                if abs(tph[r, t0, j]) < thr:
+                    c["below_threshold"] += 1
+                    continue
+                if t0 == t1 or not 0 <= t1 < T:
+                    continue
+                if tid[r, t1, j] == id0:
+                    c["same_slot"] += 1
+                elif id0 in tid[r, t1]:
+                    c["other_slot"] += 1
+                else:
+                    c["no_match"] += 1
+            else:
+                c["all_full"] += 1
+    return c
+
+
+def _lw_edge_truth(rng, R, T, Mt):
+    """truth slots [R][T][Mt]: 0..Mt ids per tick out of a pool of 5 per row (so the next tick often holds the same id, in the
+    same slot or in another), a fifth of the photon numbers below MC_TRUTH_THRESHOLD"""
+    tid = np.full((R, T, Mt), -1, dtype='i8')
+    tph = np.zeros((R, T, Mt))
+    for r in range(R):
+        for t in range(T):
+            k = int(rng.integers(0, Mt + 1)) if rng.random() < 0.7 else Mt
+            tid[r, t, :k] = 100 * r + rng.choice(5, size=k, replace=False)
+            tph[r, t, :k] = np.where(rng.random(k) < 0.2, rng.uniform(0.001, 0.09, k), rng.uniform(1.0, 50.0, k))
+    return tid, tph
+
+
+def _gen_lw_edge_digitiser():
+    """sim_triggers / digitize_signal (light_sim.py:480-619), module0: the triggers read all 96 channels; the signal holds
+    12 of them, in no order, unless noted (the reference appends the other 84 and sorts).  With truth slots every channel id
+    must be a row of the padded array and every sample tick's ceil inside it: the pure-Python run raises where the kernel
+    guards."""
+    rows12 = np.array([50, 3, 95, 20, 7, 48, 33, 77, 10, 60, 47, 90], dtype='i4')
+    all96 = np.arange(96, dtype='i4')
+    r25 = dict(LIGHT_TICK_SIZE=0.001, LIGHT_DIGIT_SAMPLE_SPACING=0.0025, LIGHT_TRIG_WINDOW=LW_EDGE_WINDOW)
+
+    def run(ref, sig, sop, tid, tph, trig, ns, tab):
+        trig = np.array(trig, dtype='i8')
+        top = np.stack([all96] * len(trig))
+        d, dt, dp = ref.light_sim.sim_triggers((len(trig), 96, -(-ns // 64)), (1, 1, 64), sig.copy(), _ga(sop.copy()), tid.copy(),
+                                              tph.copy(), trig, top, ns, tab)          # raising fails the run
+        return np.asarray(d), np.asarray(dt), np.asarray(dp)
+
+    def f4_values(rng, shape):
+        """f4 numbers of mixed sign and magnitude 1e-3 .. 3e3: v1 - v0 is rarely exact in f4"""
+        return (rng.choice([-1.0, 1.0], shape) * 10 ** rng.uniform(-3, 3.5, shape)).astype('f4')
+
+    # -- lerp_2p5 and lerp_order: truth slots at non-integer sample ticks
+    for name, over, Mt, T, ns, trig_sets, seed in (
+            ("lerp_2p5", dict(r25, LIGHT_NBIT=16), 3, 120, 29, ([5, 60], [30, 60]), 91),
+            ("lerp_order", dict(LIGHT_TICK_SIZE=0.0007, LIGHT_DIGIT_SAMPLE_SPACING=0.0021, LIGHT_TRIG_WINDOW=(0.014, 0.035),
+                                LIGHT_NBIT=16), 2, 120, 24, ([30, 60],), 92)):
+        ref = _lw_edge_ref("module0", over)
+        light = ref.light
+        rng = np.random.default_rng(seed)
+        sig = f4_values(rng, (12, T))
+        tid, tph = _lw_edge_truth(rng, 12, T, Mt)
+        zero_tab = np.zeros((96, 9))
+        out = dict(signal=sig, signal_op_channel=rows12, true_id=tid.astype('i4'), true_photons=tph, digit_samples=np.int64(ns),
+                   trigger_sets=np.array(trig_sets, dtype='i8'), mc_truth_threshold=np.float64(ref.sim.MC_TRUTH_THRESHOLD))
+        total = {}
+        for i, trig in enumerate(trig_sets):
+            n0, Tp = _lw_edge_padding(light, T, trig)
+            d, dt, dp = run(ref, sig, rows12, tid, tph, trig, ns, zero_tab)
+            out[f"wvfm_{i}"], out[f"wvfm_true_id_{i}"], out[f"wvfm_true_photons_{i}"] = d, dt.astype('i4'), dp
+            out[f"padded_{i}"] = np.array([n0, Tp], dtype='i8')
+            for k, v in {**_lw_edge_truth_counts(light, ref.sim.MC_TRUTH_THRESHOLD, tid, tph, n0, ns),
+                         **_lw_edge_sample_counts(light, Tp, ns)}.items():
+                total[k] = total.get(k, 0) + v
+            assert (dt >= 0).any() and (d != 0).any()
+        if name == "lerp_2p5":
+            assert out["padded_0"][0] == 15 and out["padded_1"].tolist() == [0, T]        # front padding; none
+            keys = ("same_slot", "other_slot", "no_match", "below_threshold", "minus1_end", "all_full", "frac_samples", "lerp")
+        else:       # i * S / T falls short of the integer i * 3 for some i (14.999999999999998 at i = 5)
+            assert 5 * light.LIGHT_DIGIT_SAMPLE_SPACING / light.LIGHT_TICK_SIZE == 14.999999999999998 and ns > 5
+            keys = ("off_grid", "lerp", "same_slot", "other_slot", "no_match")
+        out.update({"reach_" + k: total[k] for k in keys})
+        _lw_edge_save(name, "module0", over, out)
+
+    def guarded(ref, seed0, fn):
+        """fn() (sim_triggers runs with a real spectrum: two noise calls each) under the first pair of phase seeds from seed0 on
+        that keeps every value the reference rounds to noise at least 1e-6 LSB from a tie: (result, first seed, margin)"""
+        tap = ref.tap
+        for attempt in range(64):
+            tap.seed = seed0 + 2 * attempt
+            del tap.rounded[:]
+            res = []
+            for r in fn():
+                tap.calls = 0
+                res.append(r())
+                assert tap.calls == 2
+            assert len(tap.rounded) == 3 * len(res)                   # two noise calls, then the digitiser's own rounding
+            margin = _tie_margin([a for i, a in enumerate(tap.rounded) if i % 3 != 2])
+            if margin >= 1e-6:
+                return res, tap.seed, margin
+        raise RuntimeError("no phase seed clear of a rounding tie")
+
+    # -- beyond_end: no truth slots, sample ticks past the waveform.  Unpadded (120 ticks) the ticks 120, 122.5 and 147.5 all
+    # take interp's first zero branch (i0 > len - 1): multiples of 2.5 cannot reach the second (i0 > len - 2) in 120 ticks.
+    # Triggers [30, 78] pad to 128 ticks and tick 127.5 takes it; there a real spectrum puts noise on tick 127, so that a
+    # lerp in its place would show
+    over = dict(r25, LIGHT_NBIT=16, LIGHT_DET_NOISE_SAMPLE_SPACING=0.001)
+    ref = _lw_edge_ref("module0", over)
+    rng = np.random.default_rng(93)
+    T = 120
+    sig = f4_values(rng, (12, T))
+    no_id, no_ph = np.zeros((12, T, 0), dtype='i8'), np.zeros((12, T, 0))
+    tab = np.abs(rng.normal(0, 1.0, (96, 9))) * np.linspace(6000.0, 400.0, 9) + 50.0
+    sizes = (49, 50, 60)
+    out = dict(signal=sig, signal_op_channel=rows12, digit_samples=np.array(sizes, dtype='i8'),
+               trigger_sets=np.array([[30, 60], [30, 78]], dtype='i8'), noise_spectrum=tab, missing_rows=np.int64(84))
+    total = {}
+    for i, trig in enumerate(out["trigger_sets"]):
+        n0, Tp = _lw_edge_padding(ref.light, T, trig)
+        assert (n0, Tp) == ((0, 120), (0, 128))[i]
+        out[f"padded_{i}"] = np.array([n0, Tp], dtype='i8')
+        if i == 0:
+            res = [run(ref, sig, rows12, no_id, no_ph, trig, ns, np.zeros((96, 9))) for ns in sizes]
+        else:
+            res, seed, margin = guarded(ref, 93000, lambda: [(lambda ns=ns: run(ref, sig, rows12, no_id, no_ph, trig, ns, tab))
+                                                             for ns in sizes])
+            out["phase_seeds"], out["noise_tie_margin"] = np.array([seed, seed + 1], dtype='i8'), np.float64(margin)
+            out["noisy_set"] = np.int64(i)
+            print(f"  beyond_end: noise_tie_margin {margin:.3g}")
+        for ns, (d, dt, dp) in zip(sizes, res):
+            assert (ns - 1) * 2.5 == {49: 120.0, 50: 122.5, 60: 147.5}[ns]
+            past = int(np.ceil(Tp / 2.5))                               # first sample at or past the end of the waveform
+            assert dt.shape[-1] == 0 and (d[:, rows12, :40] != 0).any() and (d[:, :, past:] == 0).all()
+            if i == 1 and ns == 60:                                     # tick 127.5: zero between noise on ticks 125 and 127
+                assert past == 52 and (d[:, :, 51] == 0).all() and (d[:, :, 50] != 0).mean() > 0.9
+            out[f"wvfm_{i}_{ns}"] = d
+            for k, v in _lw_edge_sample_counts(ref.light, Tp, ns).items():
+                total[k] = total.get(k, 0) + v
+    out.update({"reach_" + k: total[k] for k in ("zero_past_end", "zero_last_tick", "lerp", "on_tick")})
+    _lw_edge_save("beyond_end", "module0", over, out)
+
+    # -- all_rows_f4 / missing_rows_f4: LIGHT_NBIT = 40 puts the rounding step (2**-24) below what an f4 difference changes.
+    # all_rows_f4: 96 f4 rows, nothing padded or appended -- the reference's array would stay f4 and numpy's scalar promotion
+    # compute interp all-f4 (neither Numba's typing nor f64), so it is handed the f8 copy: the all-f64 mode.
+    # missing_rows_f4: 12 f4 rows handed over as they are; appending the other 84 (:598-604) concatenates f8 noise rows, the
+    # array digitize_signal receives is f8 and `v1 - v0` is an f8 difference whatever the mode.
+    over = dict(r25, LIGHT_NBIT=40)
+    for name, R, sop, seed in (("all_rows_f4", 96, all96, 94), ("missing_rows_f4", 12, rows12, 95)):
+        ref = _lw_edge_ref("module0", over)
+        rng = np.random.default_rng(seed)
+        T, ns, trig = 120, 29, [30, 60]
+        sig = f4_values(rng, (R, T))
+        assert _lw_edge_padding(ref.light, T, trig) == (0, T)
+        d, dt, dp = run(ref, sig.astype('f8') if name == "all_rows_f4" else sig, sop, np.zeros((R, T, 0), dtype='i8'),
+                        np.zeros((R, T, 0)), trig, ns, np.zeros((96, 9)))
+        c = _lw_edge_sample_counts(ref.light, T, ns)
+        # samples where the f4 difference of the two neighbours is not the f8 difference (what option numba_f32 would change)
+        i0 = np.array([int(np.floor(i * 2.5)) for i in range(ns) if i % 2])
+        v0, v1 = sig[:, i0], sig[:, i0 + 1]
+        inexact = int(((v1 - v0).astype('f8') != v1.astype('f8') - v0.astype('f8')).sum())
+        out = dict(signal=sig, signal_op_channel=sop, digit_samples=np.int64(ns), trigger_sets=np.array([trig], dtype='i8'),
+                   wvfm_0=d, reach_lerp=c["lerp"], reach_f4_difference_inexact=inexact, missing_rows=np.int64(96 - R))
+        if R < 96:
+            out["reach_missing_rows"] = 96 - R
+        _lw_edge_save(name, "module0", over, out)
+
+    # -- noisy_odd: a real spectrum, recorded phases of both noise calls; 115 ticks and triggers [30, 71] pad to 121, an odd
+    # length: the inverse transform has 120 samples and the reference appends one zero, which sample 48 (tick 120.0) reads
+    over = dict(r25, LIGHT_NBIT=10, LIGHT_DET_NOISE_SAMPLE_SPACING=0.004)
+    ref = _lw_edge_ref("module0", over)
+    rng = np.random.default_rng(96)
+    T, ns, trig = 115, 49, [30, 71]
+    n0, Tp = _lw_edge_padding(ref.light, T, trig)
+    assert (n0, Tp) == (0, 121) and (ns - 1) * 2.5 == Tp - 1
+    sig = f4_values(rng, (12, T))
+    nbins = 17
+    tab = np.abs(rng.normal(0, 1.0, (96, nbins))) * np.linspace(6000.0, 400.0, nbins) + 50.0
+    res, seed, margin = guarded(ref, 96000, lambda: [lambda: run(ref, sig, rows12, np.zeros((12, T, 0), dtype='i8'),
+                                                                 np.zeros((12, T, 0)), trig, ns, tab)])
+    d = res[0][0]
+    assert (d[:, :, ns - 1] == 0).all() and (d[:, :, :ns - 1] != 0).mean() > 0.9
+    c = _lw_edge_sample_counts(ref.light, Tp, ns)
+    print(f"  noisy_odd: noise_tie_margin {margin:.3g}")
+    _lw_edge_save("noisy_odd", "module0", over, dict(
+        signal=sig, signal_op_channel=rows12, digit_samples=np.int64(ns), trigger_sets=np.array([trig], dtype='i8'),
+        noise_spectrum=tab, phase_seeds=np.array([seed, seed + 1], dtype='i8'), noise_tie_margin=np.float64(margin),
+        noisy_set=np.int64(0),
+        padded_0=np.array([n0, Tp], dtype='i8'), missing_rows=np.int64(84), wvfm_0=d, reach_lerp=c["lerp"],
+        reach_odd_padded_length=Tp % 2, reach_reads_final_tick=int((ns - 1) * 2.5 == Tp - 1)))
+
+
+def gen_light_wvfm_edges():
+    """The reference's get_triggers, gen_light_detector_noise and sim_triggers / digitize_signal with LIGHT_TICK_SIZE,
+    LIGHT_DIGIT_SAMPLE_SPACING, LIGHT_NBIT, OP_CHANNEL_PER_TRIG, LIGHT_DET_NOISE_SAMPLE_SPACING and LIGHT_TRIG_WINDOW set to what
+    no shipped configuration has: tests/golden/light_wvfm_edge_<case>.npz, each with the overridden constants by name and
+    value and `reach_*` counts of the branches the case is there for (asserted non-zero here and again by the tests)."""
+    _gen_lw_edge_triggers()
+    _gen_lw_edge_noise()
+    _gen_lw_edge_digitiser()
+
+
 def gen_light_export():
     """light_sim.export_to_hdf5 / export_light_trig_to_hdf5 / export_light_wvfm_to_hdf5 / zero_suppress_waveform_truth
     (light_sim.py:621-757) with h5py.File replaced by an in-memory sink: what lands in light_trig, light_wvfm and
@@ -1474,7 +1916,7 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     for s in a.sets.split(","):
         {"consts": gen_consts, "qd": gen_qd, "pixels": gen_pixels, "light": gen_light, "light_response": gen_light_response,
-         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_export": gen_light_export, "fee": gen_fee,
+         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_wvfm_edges": gen_light_wvfm_edges, "light_export": gen_light_export, "fee": gen_fee,
          "pixels_wide": lambda: gen_pixels_wide(a.jobs)}[s]()
     return 0
 

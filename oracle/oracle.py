@@ -449,7 +449,6 @@ def sim_triggers(signal, signal_op_channel_idx, signal_true_track_id, signal_tru
         signal = np.concatenate([signal, np.zeros((signal.shape[0], n1))], axis=-1)
         tid = np.concatenate([tid, np.full((tid.shape[0], n1, Mt), -1, dtype=np.int64)], axis=1)
         tph = np.concatenate([tph, np.zeros((tph.shape[0], n1, Mt))], axis=1)
-    sig_is_f4 = signal.dtype == np.float32
     noise_tab = np.asarray(light_det_noise, dtype=np.float64)
     if phases_signal is None:
         assert not np.any(noise_tab[sop]), "phases needed for a non-zero noise spectrum"
@@ -469,6 +468,8 @@ def sim_triggers(signal, signal_op_channel_idx, signal_true_track_id, signal_tru
         tph = np.concatenate([tph, np.zeros((missing.shape[0],) + tph.shape[1:])], axis=0)
         order = np.argsort(sop)
         signal, sop, tid, tph = signal[order], sop[order], tid[order], tph[order]
+    # the dtype digitize_signal sees: f4 only if nothing was padded (:578, :589) and no f8 noise rows were appended (:601)
+    sig_is_f4 = signal.dtype == np.float32
     sig = np.ascontiguousarray(signal, dtype=np.float64)
     tid = np.ascontiguousarray(tid); tph = np.ascontiguousarray(tph); sop = np.ascontiguousarray(sop)
     top = np.ascontiguousarray(np.broadcast_to(op_channel_idx, (ntrig, ndm)) if op_channel_idx.ndim == 1 else op_channel_idx)

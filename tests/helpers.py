@@ -201,6 +201,85 @@ def load_light_wvfm_case(name):
     return g
 
 
+LIGHT_WVFM_EDGE_TRIGGER_CASES = ("trig_sf1", "trig_sf7_allpad", "trig_sf8", "trig_sf13_tail", "trig_sf128", "trig_ratio_2p5",
+                                 "trig_ratio_3p5", "trig_tick_0p0007", "trig_mean_eq_thr", "trig_f4_cancel",
+                                 "trig_three_in_module", "trig_last_tick", "trig_2x2_group64")
+LIGHT_WVFM_EDGE_NOISE_CASES = ("noise_tiny", "noise_beyond_table", "noise_chunk")
+LIGHT_WVFM_EDGE_DIGIT_CASES = ("lerp_2p5", "lerp_order", "beyond_end", "all_rows_f4", "missing_rows_f4", "noisy_odd")
+
+
+def load_light_wvfm_edge_case(name):
+    """Constants of a tests/golden/light_wvfm_edge_<name>.npz case (oracle/gen_golden.py gen_light_wvfm_edges): the
+    configuration the fixture names with every constant it records set on ``consts`` (MC_TRUTH_THRESHOLD on sim, the others
+    on light).  Every ``reach_*`` count of the fixture -- how often the case got where it was sent -- must be non-zero.
+    Undo with ``load_cfg("module0")``."""
+    import json
+    g = gold(f"light_wvfm_edge_{name}.npz")
+    load_cfg(str(g["cfg"]))
+    for k, v in json.loads(str(g["const_json"])).items():
+        setattr(consts.sim if k == "MC_TRUTH_THRESHOLD" else consts.light, k, tuple(v) if isinstance(v, list) else v)
+    reach = [k for k in g.files if k.startswith("reach_")]
+    assert reach and all(int(g[k]) > 0 for k in reach), (name, {k: int(g[k]) for k in reach})
+    return g
+
+
+def light_wvfm_edge_phases(g, iset=0):
+    """(phases_signal, phases_missing) of the two noise calls sim_triggers makes for trigger set `iset` of a digitiser fixture
+    that records phase seeds: [rows, padded length // 2 + 1] each"""
+    m = int(g[f"padded_{iset}"][1]) // 2 + 1
+    seeds = g["phase_seeds"]
+    return (det_phases((g["signal"].shape[0], m), int(seeds[0])), det_phases((int(g["missing_rows"]), m), int(seeds[1])))
+
+
+def assert_light_wvfm_edge_triggers(g, get_triggers):
+    """get_triggers(signal, group_threshold, op_channel_idx, i_subbatch) against a trig_* fixture: trigger ticks, channels per
+    trigger and types exactly equal for every threshold set"""
+    for i, thr in enumerate(g["group_threshold"]):
+        trig, trig_op, trig_type = get_triggers(g["signal"], thr, g["op_channel"], 0)
+        print("thresholds", thr.tolist(), "triggers", np.asarray(trig).tolist(), "expected", g[f"trigger_idx_{i}"].tolist())
+        assert np.array_equal(trig, g[f"trigger_idx_{i}"])
+        assert np.array_equal(trig_op, g[f"trigger_op_channel_idx_{i}"])
+        assert np.array_equal(trig_type, g[f"trigger_type_{i}"])
+
+
+def assert_light_wvfm_edge_noise(g, noise):
+    """noise(shape, spectrum, phases) against a noise_* fixture: exactly equal (no value the reference rounded lies within
+    noise_tie_margin >= 1e-6 LSB of a tie)"""
+    assert (g["noise_tie_margin"] >= 1e-6).all()
+    for n, seed in zip(g["n_samples"], g["phase_seed"]):
+        ref = g[f"noise_{n}"]
+        got = noise(ref.shape, g["noise_spectrum"], det_phases((ref.shape[0], int(n) // 2 + 1), int(seed)))
+        print("n_samples", int(n), "differing values", int((got != ref).sum()), "of", ref.size, "largest |ref|", np.abs(ref).max())
+        assert np.array_equal(got, ref), int(n)
+
+
+def assert_light_wvfm_edge_digit(g, sim):
+    """sim(signal, signal_op_channel, true_id, true_photons, trigger_idx, op_channel_idx, digit_samples, noise_spectrum,
+    phases_signal, phases_missing) -> (digit, true ids, true photons) against a digitiser fixture, for every trigger set
+    (and every number of samples): digitised values and truth ids exactly equal, truth photons to rtol 1e-15"""
+    sig, sop = g["signal"], g["signal_op_channel"]
+    R, T = sig.shape
+    if "true_id" in g.files:
+        tid, tph = g["true_id"].astype('i8'), g["true_photons"]
+    else:
+        tid, tph = np.zeros((R, T, 0), dtype='i8'), np.zeros((R, T, 0))
+    all96 = np.arange(96, dtype='i4')
+    for i, trig in enumerate(g["trigger_sets"]):
+        top = np.stack([all96] * len(trig))
+        for ns in np.atleast_1d(g["digit_samples"]):
+            key = f"_{i}_{ns}" if g["digit_samples"].ndim else f"_{i}"
+            noisy = "noisy_set" in g.files and i == int(g["noisy_set"])        # the set that ran with the fixture's spectrum
+            tab = g["noise_spectrum"] if noisy else np.zeros((96, 9))
+            ph_sig, ph_mis = light_wvfm_edge_phases(g, i) if noisy else (None, None)
+            d, dt, dp = sim(sig, sop, tid, tph, trig, top, int(ns), tab, ph_sig, ph_mis)
+            ref = g["wvfm" + key]
+            print("triggers", trig.tolist(), "samples", int(ns), "differing values", int((d != ref).sum()), "of", ref.size)
+            assert np.array_equal(d, ref), (i, int(ns))
+            if tid.shape[-1]:
+                assert np.array_equal(dt, g["wvfm_true_id" + key])
+                np.testing.assert_allclose(dp, g["wvfm_true_photons" + key], rtol=1e-15, atol=0)
+
+
 FEE_SCAN_VARIANTS = ("default", "no_risetime", "long", "cap", "noisy")
 
 

@@ -249,6 +249,64 @@ def test_light_waveform_chain_golden(name):
     assert np.array_equal(d2, g["wvfm_noisy"])
 
 
+def _oracle_sim(sig, sop, tid, tph, trig, top, ns, tab, ph_sig, ph_mis):
+    return O.sim_triggers(sig, sop, tid, tph, trig, top, ns, tab, phases_signal=ph_sig, phases_missing=ph_mis)
+
+
+@pytest.mark.parametrize("name", H.LIGHT_WVFM_EDGE_TRIGGER_CASES)
+def test_light_wvfm_edge_triggers(name):
+    """The oracle's get_triggers against the reference's own (light_sim.py:380-477) at sample factors 1, 2, 3, 4, 7, 8, 13 and
+    128, ratios that round half to even, an all-padding block, a block mean equal to its threshold, an f4 group sum that
+    cancels, the re-slicing of a third trigger, a trigger on the last tick and groups of 64 rows across two modules
+    (oracle/gen_golden.py gen_light_wvfm_edges)."""
+    try:
+        g = H.load_light_wvfm_edge_case(name)
+        assert round(consts.light.LIGHT_DIGIT_SAMPLE_SPACING / consts.light.LIGHT_TICK_SIZE) == int(g["sample_factor"])
+        H.assert_light_wvfm_edge_triggers(g, O.get_triggers)
+    finally:
+        H.load_cfg("module0")
+
+
+@pytest.mark.parametrize("name", H.LIGHT_WVFM_EDGE_NOISE_CASES)
+def test_light_wvfm_edge_noise(name):
+    """The oracle's gen_light_detector_noise against the reference's own (light_sim.py:339-377) for 2..17 and 1026..1028
+    samples, desired frequencies that equal table frequencies, and a table that ends below most of them."""
+    try:
+        g = H.load_light_wvfm_edge_case(name)
+        H.assert_light_wvfm_edge_noise(g, O.gen_light_detector_noise)
+    finally:
+        H.load_cfg("module0")
+
+
+@pytest.mark.parametrize("name", H.LIGHT_WVFM_EDGE_DIGIT_CASES)
+def test_light_wvfm_edge_digitiser(name):
+    """The oracle's sim_triggers against the reference's sim_triggers / digitize_signal (light_sim.py:480-619) at a spacing
+    ratio of 2.5 and at tick 0.0007 (interp's lerp, truth photons interpolated between ticks, the next tick's slots
+    searched), sample ticks past the end, an odd padded length under noise, and f4 signals with and without appended
+    channels -- in the all-f64 mode and, where Numba's f4 typing cannot apply, in the numba_f32 mode too."""
+    try:
+        g = H.load_light_wvfm_edge_case(name)
+        H.assert_light_wvfm_edge_digit(g, _oracle_sim)
+        if name in ("all_rows_f4", "missing_rows_f4"):
+            O.lib().o_set_numba_f32(1)
+            try:
+                typed = _oracle_sim(g["signal"], g["signal_op_channel"], np.zeros(g["signal"].shape + (0,), dtype='i8'),
+                                    np.zeros(g["signal"].shape + (0,)), g["trigger_sets"][0], np.stack([np.arange(96)] * 2),
+                                    int(g["digit_samples"]), np.zeros((96, 9)), None, None)[0]
+            finally:
+                O.lib().o_set_numba_f32(0)
+            differ = int((typed != g["wvfm_0"]).sum())
+            print(name, "numba_f32 mode differs from the reference in", differ, "of", typed.size, "values")
+            if name == "missing_rows_f4":
+                # appending the missing channels made the reference's array f8 (light_sim.py:601): no f4 difference is left
+                assert differ == 0
+            else:
+                # the reference's run cannot type like Numba: this mode is pinned by the oracle alone; it must be another result
+                assert differ > 0
+    finally:
+        H.load_cfg("module0")
+
+
 @pytest.mark.parametrize("radius", H.WIDE_RADII)
 @pytest.mark.parametrize("cfg", H.WIDE_CFGS)
 def test_wide_neighbourhood_golden(cfg, radius):
