@@ -1,6 +1,6 @@
 // fee_record.h -- the set-up record of a chain launch's FEE stage: written by fee_setup_kernel, read by the pixel_adc kernels
-// (kernels_fee.hip) and, after the launch, by pixel_truth_kernel (kernels_pixtruth.hip), the pixel-waveform kernels
-// (kernels_pixwave.hip) and pixel_adc_universes_kernel (kernels_feeuni.hip).
+// (kernels_fee.hip) and, after the launch, through the one reader of fee_reader.h by pixel truth (kernels_pixtruth.hip), the
+// pixel waveforms (kernels_pixwave.hip) and the FEE and charge universes (kernels_feeuni.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

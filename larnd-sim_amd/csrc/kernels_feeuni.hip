@@ -2,7 +2,7 @@
 // (include/ldsim.h, "FEE universes"; the Python side: larndsim_amd/fee_universes.py).
 //
 // A sibling of kernels_pixtruth.hip and kernels_pixwave.hip: it reads what the launch left in HBM -- the per-pair current rows
-// (f32 [n_pairs][T]) and the FEE set-up record (fee_record.h) -- and changes nothing of the chain.  A launch spends its time on
+// (f32 [n_pairs][T]) and the FEE set-up record (fee_record.h, through fee_reader.h) -- and changes nothing of the chain.  A launch spends its time on
 // those rows; the front end (fee_setup_kernel + the pixel_adc kernels) only reads them, so a variation of the front end needs
 // no second launch.
 //
@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "launchers.h"
-#include "fee_record.h"
+#include "fee_reader.h"
 #include "fee_scan.h"
 #include "seg_charge.h"
 
@@ -40,7 +40,7 @@
 #define FU_WAVES 4
 #define FU_NT_MAX 4096   // ticks of S in LDS (32 KB)
 #define FU_A_MAX 64
-#define FU_M_MAX 64
+#define FU_M_MAX 64      // (fee_rec_header refuses a header with more slots)
 
 // one universe on the device: the constants the scan and the digitisation read, and what the pixel tables are transformed by
 struct FuUni {
@@ -51,16 +51,11 @@ struct FuUni {
 };
 
 struct FuArgs {
-  // the launch's record
-  const FeeHdr* hdr;
-  const unsigned long long* counts;         // [2] with lists, else NULL
-  const FeeSlot* slots;
-  const float* waves;
+  FeeRecArgs rec;                           // the launch's record
   const int32_t* upix;
-  int64_t U, n_pairs;
-  int32_t T, NT, M, A;
+  int32_t A;
   // the universes
-  int32_t n, pad;
+  int32_t n;
   const FuUni* uni;                         // [n]
   const double* tabs;                       // [n][128]: fee_tables_kernel's wtap[64] | G[64] of the universe's rise time
   const double* thr_table;                  // [n_pix_ids] or NULL, as the launch read them
@@ -87,27 +82,13 @@ __device__ __forceinline__ void fu_wave_sync() {      // (LDS traffic of one wav
   __builtin_amdgcn_wave_barrier();
 }
 
-// ---- the pixel of a workgroup, shared by the scan kernel and fu_dense_kernel ------------------------------------------------------
-// The pixel's header: header w, or (two lists) the w-th of list 0 followed by list 1 (kernels_pixwave.hip pw_pixel).  false: the
-// record does not describe the launch's buffers (nothing outside them is touched).
-__device__ __forceinline__ bool fu_header(const FuArgs& F, int64_t w, FeeHdr& H, int& n_slots) {
-  const int64_t U = F.U;
-  int64_t idx = w;
-  bool ok = true;
-  if (F.counts) {
-    const int64_t c0 = (int64_t)F.counts[0], c1 = (int64_t)F.counts[1];
-    ok = c0 >= 0 && c0 <= U && c1 >= 0 && c0 + c1 == U;
-    if (ok && w >= c0) idx = U + (w - c0);
-  }
-  H = FeeHdr{};
-  if (ok) H = F.hdr[idx];
-  n_slots = H.n_slots < F.M ? H.n_slots : F.M;
-  return ok && H.u >= 0 && H.u < U && n_slots >= 0 && n_slots <= FU_M_MAX && H.p0 >= 0 && H.p0 + n_slots <= F.n_pairs;
-}
-
+// ---- the pixel of a workgroup, in the scan kernel and in fu_dense_kernel: its header by fee_rec_header, its slots' windows by
+// fee_slot_window (fee_reader.h) into LDS ---------------------------------------------------------------------------------------
 // S[t] over the whole tick axis, by all 256 threads: each thread owns ticks tid, tid + 256, ... and adds the slots' rows in slot
 // order.  WEIGHTED: every sample times its slot's weight s_wt[k], the product rounded before it is added.  s_start / s_lo / s_hi
-// (and s_wt) may have been written just before the call: the first barrier orders them.
+// (and s_wt) may have been written just before the call: the first barrier orders them.  The workgroup-level LDS form of this
+// file: one row per trip to memory; pixel_adc_body's grouped row loads (fee_row_load, FEE_LG) and its LDS form are not shared
+// with it, which would change speed and wants a measurement of its own.
 template <bool WEIGHTED>
 __device__ __forceinline__ void fu_form_S(double* S, const float* waves, int64_t p0, int T, int NT, int n_slots, const int* s_start,
                                           const int* s_lo, const int* s_hi, const double* s_wt, int tid) {
@@ -126,13 +107,6 @@ __device__ __forceinline__ void fu_form_S(double* S, const float* waves, int64_t
   __syncthreads();
 }
 
-// a slot's window on the pixel's tick axis (pixel_adc_body: detsim.py:516-520; a row has T elements)
-__device__ __forceinline__ void fu_slot_window(const FeeSlot& sl, int T, int NT, int tid, int* s_start, int* s_lo, int* s_hi) {
-  s_start[tid] = sl.start;
-  s_lo[tid] = max(sl.start + max(sl.w0, 0), 0);
-  s_hi[tid] = min(sl.start + min(sl.w1, T), NT);
-}
-
 // WEIGHTED = false: the FEE universes of one S.  WEIGHTED = true (charge universes): the universes come in groups of equal
 // charge variation (F.grp: group g holds the universes order[gb[g]] .. order[gb[g + 1] - 1]); per group the workgroup forms S_g
 // from the rows times the group's segment weights, and wave w scans the group's universes w, w + 4, ...  Both barriers of a
@@ -145,33 +119,24 @@ __global__ void __launch_bounds__(FU_THREADS) pixel_adc_universes_kernel(FuArgs 
   __shared__ int s_start[FU_M_MAX], s_lo[FU_M_MAX], s_hi[FU_M_MAX];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int NT = F.NT, A = F.A, T = F.T;
-  const int64_t U = F.U;
-  // ---- the pixel's header (fu_header's text) ---------------------------------------------------------------------------------
+  const int NT = F.rec.NT, A = F.A, T = F.rec.T;
+  const int64_t U = F.rec.U;
   const int64_t w = blockIdx.x;
   if (w >= U) return;
-  int64_t idx = w;
-  bool ok = true;
-  if (F.counts) {
-    const int64_t c0 = (int64_t)F.counts[0], c1 = (int64_t)F.counts[1];
-    ok = c0 >= 0 && c0 <= U && c1 >= 0 && c0 + c1 == U;
-    if (ok && w >= c0) idx = U + (w - c0);
-  }
-  FeeHdr H{};
-  if (ok) H = F.hdr[idx];
-  const int64_t u = H.u, p0 = H.p0;
-  const int n_slots = H.n_slots < F.M ? H.n_slots : F.M;
-  ok = ok && u >= 0 && u < U && n_slots >= 0 && n_slots <= FU_M_MAX && p0 >= 0 && p0 + n_slots <= F.n_pairs;
-  if (!ok) {                                // (nothing outside the buffers is touched; the host refuses the result)
+  FeeHdr H;
+  int n_slots;
+  if (!fee_rec_header(F.rec, w, H, n_slots)) {      // (nothing outside the buffers is touched; the host refuses the result)
     if (tid == 0) *F.err = 1;
     return;
   }
+  const int64_t u = H.u, p0 = H.p0;
   [[maybe_unused]] int64_t my_seg = 0;      // WEIGHTED: the segment of slot tid, relative to the launch's range
   if (tid < n_slots) {
-    const FeeSlot sl = F.slots[p0 + tid];
-    s_start[tid] = sl.start;
-    s_lo[tid] = max(sl.start + max(sl.w0, 0), 0);       // (pixel_adc_body: detsim.py:516-520; a row has T elements)
-    s_hi[tid] = min(sl.start + min(sl.w1, T), NT);
+    const FeeSlot sl = F.rec.slots[p0 + tid];
+    const FeeWindow W = fee_slot_window(sl, T, NT);
+    s_start[tid] = W.st;
+    s_lo[tid] = W.lo;
+    s_hi[tid] = W.hi;
     if constexpr (WEIGHTED) my_seg = (int64_t)H.bfirst + sl.track;
   }
   if constexpr (WEIGHTED) {                 // a segment outside the launch's range: the record does not fit.  Nothing is indexed
@@ -202,7 +167,7 @@ __global__ void __launch_bounds__(FU_THREADS) pixel_adc_universes_kernel(FuArgs 
       j1 = F.grp[g + 1];
       if (tid < n_slots) s_wt[tid] = F.w[(int64_t)g * F.n_seg + my_seg];
     }
-    fu_form_S<WEIGHTED>(S, F.waves, p0, T, NT, n_slots, s_start, s_lo, s_hi, s_wt, tid);
+    fu_form_S<WEIGHTED>(S, F.rec.waves, p0, T, NT, n_slots, s_start, s_lo, s_hi, s_wt, tid);
     for (int j = j0 + wv; j < j1; j += FU_WAVES) {
       const int k = WEIGHTED ? F.grp[F.n_groups + 1 + j] : j;   // (results are written at the caller's universe index)
       const FuUni* V = F.uni + k;
@@ -215,9 +180,11 @@ __global__ void __launch_bounds__(FU_THREADS) pixel_adc_universes_kernel(FuArgs 
       const int ntap = rt > 0 ? (int)ceil(10 * rt / dt) : 0;  // floor(ic - 10*rt/dt) == ic - ceil(10*rt/dt)
       wtap[lane] = F.tabs[(int64_t)k * 128 + lane];
       fu_wave_sync();
-      // (two roundings each, as the same transformation of the tables on the host has)
-      const double thr = F.thr_table ? __dadd_rn(__dmul_rn(thr_pix, V->thr_scale), V->thr_offset) : V->threshold;
-      const double gain = F.gain_table ? __dmul_rn(gain_pix, V->gain_scale) : c->gain * (1e-3 * (1e-6 * 1.0)) / 1.0;   // GAIN * mV / e
+      // (two roundings each, as the same transformation of the tables on the host has; the tables are optional and marked
+      // unlikely: a non-null pointer counts as the likely side, and the path without tables then sits out of line, which cost
+      // 0.04 ms per universe and wave at 195 k pixels)
+      const double thr = __builtin_expect(F.thr_table != nullptr, 0) ? __dadd_rn(__dmul_rn(thr_pix, V->thr_scale), V->thr_offset) : V->threshold;
+      const double gain = __builtin_expect(F.gain_table != nullptr, 0) ? __dmul_rn(gain_pix, V->gain_scale) : c->gain * (1e-3 * (1e-6 * 1.0)) / 1.0;   // GAIN * mV / e
       int nd = 0, nh;
       // S holds every tick (s_lo = 0, s_hi = N_t); idle skipping by the header's [t_lo, t_hi) is adc_scan's own rule, per universe
       if (V->noisy) {
@@ -252,18 +219,22 @@ __global__ void __launch_bounds__(FU_THREADS) fu_dense_kernel(FuArgs F, const do
   __shared__ double s_wt[FU_M_MAX];
   const int tid = threadIdx.x;
   const int64_t w = blockIdx.x;
-  if (w >= F.U) return;
+  const int T = F.rec.T, NT = F.rec.NT;
+  if (w >= F.rec.U) return;
   FeeHdr H;
   int n_slots;
-  if (!fu_header(F, w, H, n_slots)) {
+  if (!fee_rec_header(F.rec, w, H, n_slots)) {
     if (tid == 0) *F.err = 1;
     return;
   }
   if (H.u < u_begin || H.u >= u_end) return;
   int64_t my_seg = 0;
   if (tid < n_slots) {
-    const FeeSlot sl = F.slots[H.p0 + tid];
-    fu_slot_window(sl, F.T, F.NT, tid, s_start, s_lo, s_hi);
+    const FeeSlot sl = F.rec.slots[H.p0 + tid];
+    const FeeWindow W = fee_slot_window(sl, T, NT);
+    s_start[tid] = W.st;
+    s_lo[tid] = W.lo;
+    s_hi[tid] = W.hi;
     my_seg = (int64_t)H.bfirst + sl.track;
   }
   if constexpr (WEIGHTED) {
@@ -273,8 +244,8 @@ __global__ void __launch_bounds__(FU_THREADS) fu_dense_kernel(FuArgs F, const do
     }
     if (tid < n_slots) s_wt[tid] = wts[my_seg];
   }
-  fu_form_S<WEIGHTED>(S, F.waves, H.p0, F.T, F.NT, n_slots, s_start, s_lo, s_hi, s_wt, tid);
-  for (int t = tid; t < F.NT; t += FU_THREADS) out[(H.u - u_begin) * (int64_t)F.NT + t] = S[t];
+  fu_form_S<WEIGHTED>(S, F.rec.waves, H.p0, T, NT, n_slots, s_start, s_lo, s_hi, s_wt, tid);
+  for (int t = tid; t < NT; t += FU_THREADS) out[(H.u - u_begin) * (int64_t)NT + t] = S[t];
 }
 
 // ---- charge universes: the segment weights ------------------------------------------------------------------------------------
@@ -348,17 +319,6 @@ __global__ void __launch_bounds__(256) fu_charge_kernel(const int32_t* __restric
   const int64_t o = off[u];
   for (int h = 0; h < nh && h < A; h++)
     if (o + h < n_rows) charge[o + h] = adc_list[u * A + h];
-}
-
-// a buffer of the pass; an allocation that fails leaves the buffer empty and the context usable
-static int fu_ensure(DevBuf& b, size_t need, const char* what) {
-  if (need <= b.bytes && b.p) return 0;
-  if (b.ensure(need)) {
-    (void)hipGetLastError();
-    ldsim_set_error("FEE universes: no device memory for %s (%zu bytes)", what, need);
-    return LDSIM_ENOMEM;
-  }
-  return 0;
 }
 
 static LdsimFeeVariation fu_nominal(const LdsimConsts& h) {
@@ -442,19 +402,10 @@ static int fu_validate(const ldsim_ctx* ctx, const LdsimFeeVariation* v, int32_t
 
 // the launch's record in the kernels' argument block
 static FuArgs fu_record_args(const ldsim_ctx* ctx, const ChainView& cv) {
-  const ldsim_ctx::FeeRecord& R = ctx->fee_rec;
   FuArgs F{};
-  F.hdr = cv.fee.hdr;
-  F.counts = cv.fee.counts;
-  F.slots = cv.fee_slots;
-  F.waves = cv.waves;
+  F.rec = fee_rec_args(ctx, cv);
   F.upix = cv.upix;
-  F.U = cv.U;
-  F.n_pairs = R.n_pairs;
-  F.T = R.T;
-  F.NT = R.NT;
-  F.M = R.M;
-  F.A = R.A;
+  F.A = ctx->fee_rec.A;
   return F;
 }
 
@@ -579,7 +530,7 @@ static int fu_run(ldsim_ctx* ctx, const LdsimFeeVariation* v, const LdsimChargeV
   }
   CK(fu_validate(ctx, v, n));
   if (charge) CK(cu_validate(charge, n));
-  CK(pt_need_launch(ctx, who));
+  CK(launch_need_record(ctx, who));
   // ---- charge universes: the state the replay needs, and the groups of byte-equal charge variations ---------------------------
   std::vector<int32_t> group_of, grp;        // [n]; group begins [G + 1] | universes ordered by group [n]
   std::vector<ChargeK> hk;
@@ -653,7 +604,7 @@ static int fu_run(ldsim_ctx* ctx, const LdsimFeeVariation* v, const LdsimChargeV
       return LDSIM_ESTATE;
     }
     const size_t need = cu_parts_of(nullptr, G, n, n_seg).bytes;
-    CK(fu_ensure(ctx->cu_w, need, "the segment weights"));
+    CK(pass_ensure(ctx->cu_w, need, "FEE universes", "the segment weights"));
     P = cu_parts_of(ctx->cu_w.p, G, n, n_seg);
     hipStream_t st0 = ctx->stream;
     HIPCHK(hipMemsetAsync(P.unw, 0, (size_t)G * 8 + 8, st0));
@@ -706,10 +657,10 @@ static int fu_run(ldsim_ctx* ctx, const LdsimFeeVariation* v, const LdsimChargeV
   const int A = R.A;
   // ---- every buffer of the dense result first: a result that does not fit is refused before anything is written ---------------
   const size_t plane = (size_t)n * (size_t)U * (size_t)A * 8;      // one of adc_list, adc_ticks, adc_digit
-  CK(fu_ensure(ctx->fu_dense, 3 * plane, "the per-universe ADC arrays"));
-  CK(fu_ensure(ctx->fu_cnt, fu_counts_bytes(n, U), "the hit counts"));
+  CK(pass_ensure(ctx->fu_dense, 3 * plane, "FEE universes", "the per-universe ADC arrays"));
+  CK(pass_ensure(ctx->fu_cnt, fu_counts_bytes(n, U), "FEE universes", "the hit counts"));
   const size_t b_uni = (((size_t)n * sizeof(FuUni)) + 15) & ~(size_t)15;
-  CK(fu_ensure(ctx->fu_uni, b_uni + (size_t)n * 128 * 8, "the universes' constants"));
+  CK(pass_ensure(ctx->fu_uni, b_uni + (size_t)n * 128 * 8, "FEE universes", "the universes' constants"));
   const FuCounts C = fu_counts_of(ctx->fu_cnt.p, n, U);
   double* d_tabs = (double*)((char*)ctx->fu_uni.p + b_uni);
   // ---- the universes' constants and tap tables ----------------------------------------------------------------------------
@@ -799,7 +750,7 @@ static int fu_run(ldsim_ctx* ctx, const LdsimFeeVariation* v, const LdsimChargeV
   }
   ctx->fu_row0[(size_t)n] = rows;
   // rows: [rows] 24-byte hit rows | [rows] f64 charges
-  CK(fu_ensure(ctx->fu_rows, (size_t)rows * 32 + 32, "the hit rows"));
+  CK(pass_ensure(ctx->fu_rows, (size_t)rows * 32 + 32, "FEE universes", "the hit rows"));
   char* d_rows = ctx->fu_rows.as<char>();
   double* d_chg = (double*)(d_rows + (size_t)rows * 24);
   for (int k = 0; k < n; k++) {
@@ -951,7 +902,7 @@ extern "C" int ldsim_chain_universe_waveforms_dense(ldsim_ctx* ctx, int32_t k, i
   LDSIM_ENTER(ctx);
   if (!ctx) { ldsim_set_error("null ctx"); return LDSIM_EINVAL; }
   CK(fu_need_pass(ctx, k));
-  CK(pt_need_launch(ctx, "ldsim_chain_universe_waveforms_dense"));
+  CK(launch_need_record(ctx, "ldsim_chain_universe_waveforms_dense"));
   const int64_t U = ctx->fu_U;
   if (u_begin < 0 || u_end < u_begin || u_end > U) {
     ldsim_set_error("rows [%lld, %lld) are no range of [0, %lld]", (long long)u_begin, (long long)u_end, (long long)U);
@@ -968,7 +919,7 @@ extern "C" int ldsim_chain_universe_waveforms_dense(ldsim_ctx* ctx, int32_t k, i
   }
   hipStream_t st = ctx->stream;
   const size_t bytes = (size_t)(u_end - u_begin) * (size_t)R.NT * 8;
-  CK(fu_ensure(ctx->cu_S, bytes, "the dense waveforms"));
+  CK(pass_ensure(ctx->cu_S, bytes, "FEE universes", "the dense waveforms"));
   HIPCHK(hipMemsetAsync(ctx->cu_S.p, 0, bytes, st));
   FuArgs F = fu_record_args(ctx, cv);
   const FuCounts C = fu_counts_of(ctx->fu_cnt.p, ctx->fu_n, U);

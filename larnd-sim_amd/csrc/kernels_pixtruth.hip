@@ -3,118 +3,72 @@
 //
 // Nothing of the reference is mirrored: its output ends in hits.  The pass reads the per-pair current rows once (f32
 // [n_pairs][T], the only large input) and the FEE set-up record (fee_record.h): per pixel a header, per slot its start tick,
-// written window and track.  A wave per pixel, four pixels per workgroup; lane k holds slot k's record (M <= 64 = the wave), so
-// the slot loops read it with readlane and nothing goes through LDS.
+// written window and track.  A wave per pixel, four pixels per workgroup; lane k holds slot k's window (fee_reader.h: FeeWavePixel,
+// M <= 64 = the wave), so the slot loops read it with readlane and nothing goes through LDS.
 //   pass A  per slot, the lanes stride over the slot's window (256 contiguous bytes per wave instruction) and a DPP wave sum
 //           follows: q_track, the read of the rows from HBM
 //   pass B  the pixel's ticks [t_lo, t_hi) in 64-tick chunks, every lane summing in slot order the slots that cover its tick:
-//           S[t] exactly as pixel_adc_body forms it, so q_induced and q_abs need no S array (the rows come from L2 now)
+//           S[t] by fee_wave_chunk_sum, as pixel_adc_body forms it, so q_induced and q_abs need no S array (the rows come from L2 now)
 // then a selection on the device (flags, two exclusive scans, a gather) into the compact form.
 #include "launchers.h"
-#include "fee_record.h"
-#include "wave_ops.h"
+#include "fee_reader.h"
 
 #define PT_WAVES 4       // pixels per workgroup
 
 __global__ void __launch_bounds__(64 * PT_WAVES) pixel_truth_kernel(
-    const FeeHdr* __restrict__ hdr /* [U], or [2][U] with counts */, const unsigned long long* __restrict__ counts /* [2] or NULL */,
-    const FeeSlot* __restrict__ slots, const float* __restrict__ waves, int64_t U, int64_t n_pairs, int T, int NT, int M, double dt,
-    double* __restrict__ q_induced, double* __restrict__ q_abs, double* __restrict__ q_track, int32_t* __restrict__ n_slots_out) {
+    FeeRecArgs R, double dt, double* __restrict__ q_induced, double* __restrict__ q_abs, double* __restrict__ q_track,
+    int32_t* __restrict__ n_slots_out) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * PT_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (w >= U) return;
-  // the w-th header: header w, or (two lists, the second behind the first's U places) the w-th of list 0 followed by list 1
-  int64_t idx = w;
-  if (counts) {
-    const int64_t c0 = (int64_t)counts[0];
-    if (w >= c0) {
-      if (w - c0 >= (int64_t)counts[1]) return;
-      idx = U + (w - c0);
-    }
-  }
-  const FeeHdr* H = hdr + idx;
-  const int64_t u = H->u, p0 = H->p0;
-  int n_slots = __builtin_amdgcn_readfirstlane(H->n_slots);
-  n_slots = n_slots < M ? n_slots : M;
   // (a record that is not this launch's is refused on the host; nothing outside the buffers is touched whatever it holds)
-  if (u < 0 || u >= U || n_slots < 0 || p0 < 0 || p0 + n_slots > n_pairs) return;
-  const int t_lo = __builtin_amdgcn_readfirstlane(max(H->t_lo, 0)), t_hi = __builtin_amdgcn_readfirstlane(min(H->t_hi, NT));
-
-  // slot k in lane k: the ticks [lo, hi) of the pixel's time axis its row is summed over (pixel_adc_body: detsim.py:516-520)
-  int st = 0, lo = 0, hi = 0;
-  if (lane < n_slots) {
-    const FeeSlot sl = slots[p0 + lane];
-    st = sl.start;
-    lo = max(st + max(sl.w0, 0), 0);
-    hi = min(st + min(sl.w1, T), NT);
-  }
+  FeeWavePixel P;
+  if (!fee_wave_pixel(R, w, lane, P)) return;
+  const float* __restrict__ waves = R.waves;
+  const int T = R.T, M = R.M;
   // ---- pass A: q_track ------------------------------------------------------------------------------------------------
   // A lane owns the ticks congruent to it mod 64, like the FEE sum, and adds them in rising order: the order of the sum is the
   // pixel's own, whatever else the launch holds (the same bits at any chunking of the batches).
   double q_mine = 0;
-  for (int k = 0; k < n_slots; k++) {
-    const int st_k = wave_lane_i32(st, k), lo_k = wave_lane_i32(lo, k), hi_k = wave_lane_i32(hi, k);
-    const int64_t row = (p0 + k) * (int64_t)T - st_k;          // element of tick 0 (the ticks [lo_k, hi_k) lie inside the row)
+  for (int k = 0; k < P.n_slots; k++) {
+    const int st_k = wave_lane_i32(P.win.st, k), lo_k = wave_lane_i32(P.win.lo, k), hi_k = wave_lane_i32(P.win.hi, k);
+    const int64_t row = (P.p0 + k) * (int64_t)T - st_k;        // element of tick 0 (the ticks [lo_k, hi_k) lie inside the row)
     double acc = 0;
     for (int t = lo_k + ((lane - lo_k) & 63); t < hi_k; t += 64) acc += (double)waves[row + t];
     acc = wave_add_f64(acc);
     if (lane == k) q_mine = acc * dt;
   }
-  // ---- pass B: S[t] over the pixel's ticks, slots added in slot order -------------------------------------------------------
+  // ---- pass B: S[t] over the pixel's ticks in 64-tick chunks (fee_wave_chunk_sum: slots added in slot order) ------------------
   double acc_i = 0, acc_a = 0;
-  for (int base = t_lo; base < t_hi; base += 64) {
-    const int t = base + lane;
-    double S = 0;
-    for (int k = 0; k < n_slots; k++) {
-      const int lo_k = wave_lane_i32(lo, k), hi_k = wave_lane_i32(hi, k);
-      if (hi_k <= base || lo_k >= base + 64) continue;         // (wave-uniform)
-      const int64_t row = (p0 + k) * (int64_t)T - wave_lane_i32(st, k);
-      if (t >= lo_k && t < hi_k) S += (double)waves[row + t];
-    }
+  for (int base = P.t_lo; base < P.t_hi; base += 64) {
+    const double S = fee_wave_chunk_sum(waves, P, T, base, lane);
     acc_i += S;
     acc_a += fabs(S);
   }
   acc_i = wave_add_f64(acc_i);
   acc_a = wave_add_f64(acc_a);
   if (lane == 0) {
-    q_induced[u] = acc_i * dt;
-    q_abs[u] = acc_a * dt;
-    n_slots_out[u] = n_slots;
+    q_induced[P.u] = acc_i * dt;
+    q_abs[P.u] = acc_a * dt;
+    n_slots_out[P.u] = P.n_slots;
   }
-  if (lane < M) q_track[u * M + lane] = q_mine;                // (0 behind the last slot)
+  if (lane < M) q_track[P.u * M + lane] = q_mine;              // (0 behind the last slot)
 }
 
 // the current samples pixel_truth_kernel's pass A sums (timing tools: the bytes it reads from the rows are 4 x that): a thread per
 // header, resolved and clipped as there; one atomic per workgroup
-__global__ void __launch_bounds__(256) pixel_truth_samples_kernel(const FeeHdr* __restrict__ hdr, const unsigned long long* __restrict__ counts,
-                                                                  const FeeSlot* __restrict__ slots, int64_t U, int64_t n_pairs, int T, int NT,
-                                                                  int M, unsigned long long* __restrict__ total) {
+__global__ void __launch_bounds__(256) pixel_truth_samples_kernel(FeeRecArgs R, unsigned long long* __restrict__ total) {
   __shared__ unsigned long long s_sum;
   if (threadIdx.x == 0) s_sum = 0;
   __syncthreads();
   const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
   unsigned long long mine = 0;
-  if (w < U) {
-    int64_t idx = w;
-    bool have = true;
-    if (counts) {
-      const int64_t c0 = (int64_t)counts[0];
-      if (w >= c0) {
-        have = w - c0 < (int64_t)counts[1];
-        idx = U + (w - c0);
-      }
+  FeeHdr H;
+  int n_slots;
+  if (w < R.U && fee_rec_header(R, w, H, n_slots))
+    for (int k = 0; k < n_slots; k++) {
+      const FeeWindow W = fee_slot_window(R.slots[H.p0 + k], R.T, R.NT);
+      if (W.hi > W.lo) mine += (unsigned long long)(W.hi - W.lo);
     }
-    if (have) {
-      const FeeHdr H = hdr[idx];
-      const int n_slots = H.n_slots < M ? H.n_slots : M;
-      if (n_slots > 0 && H.p0 >= 0 && H.p0 + n_slots <= n_pairs)
-        for (int k = 0; k < n_slots; k++) {
-          const FeeSlot sl = slots[H.p0 + k];
-          const int lo = max(sl.start + max(sl.w0, 0), 0), hi = min(sl.start + min(sl.w1, T), NT);
-          if (hi > lo) mine += (unsigned long long)(hi - lo);
-        }
-    }
-  }
   if (mine) atomicAdd(&s_sum, mine);
   __syncthreads();
   if (threadIdx.x == 0 && s_sum) atomicAdd(total, s_sum);
@@ -176,7 +130,7 @@ extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, in
     ldsim_set_error("pixel truth: min_abs_charge %g must be >= 0", min_abs_charge);
     return LDSIM_EINVAL;
   }
-  CK(pt_need_launch(ctx, "pixel truth"));
+  CK(launch_need_record(ctx, "pixel truth"));
   HIPCHK(hipSetDevice(ctx->device));
   const ChainView v = chain_view(ctx);      // (the pass grows its own buffers and SB_SORTTMP only)
   const int64_t U = v.U;
@@ -193,8 +147,7 @@ extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, in
   const PtDense D = pt_dense_of(ctx->pt_dense.p, U, R.M);
   HIPCHK(hipMemsetAsync(ctx->pt_dense.p, 0, D.bytes, st));
   hipLaunchKernelGGL(pixel_truth_kernel, dim3((unsigned)((U + PT_WAVES - 1) / PT_WAVES)), dim3(64 * PT_WAVES), 0, st,
-                     v.fee.hdr, v.fee.counts, v.fee_slots, v.waves, U, R.n_pairs, R.T, R.NT, R.M, R.dt, D.q_induced, D.q_abs,
-                     D.q_track, D.n_slots);
+                     fee_rec_args(ctx, v), R.dt, D.q_induced, D.q_abs, D.q_track, D.n_slots);
   HIPCHK(hipGetLastError());
   // ---- selection: flags, exclusive scans of the flags and of the kept pixels' slot counts, then the gather ------------------
   int32_t* keep = ctx->pt_sel.as<int32_t>();
@@ -232,44 +185,19 @@ extern "C" int ldsim_chain_pixel_truth(ldsim_ctx* ctx, double min_abs_charge, in
   return 0;
 }
 
-// the launch is intact and its set-up record describes its buffers (what the pass reads; kernels_pixwave.hip asks the same)
-int pt_need_launch(ldsim_ctx* ctx, const char* who) {
-  if (ctx->launch_stale) {
-    ldsim_set_error("%s reads what the last chain launch left in HBM, and it is gone: %s; run ldsim_charge_chain again", who,
-                    ctx->launch_stale);
-    return LDSIM_ESTATE;
-  }
-  const int64_t U = ctx->chain_U;
-  if (U == 0) return 0;
-  const ldsim_ctx::FeeRecord& R = ctx->fee_rec;
-  // all of the sizes the launch ran with (an intact launch has them; checked all the same)
-  const bool sized = R.U == U && R.M > 0 && R.M <= 64 && R.A > 0 && R.T > 0 && R.n_pairs > 0 &&
-                     ctx->scratch[SB_FEEHDR].bytes >= chain_view(ctx).fee.bytes && ctx->scratch[SB_FEESLOT].bytes >= (size_t)R.n_pairs * sizeof(FeeSlot) &&
-                     ctx->scratch[SB_WAVES].bytes >= (size_t)R.n_pairs * R.T * 4 && ctx->scratch[SB_UPIX].bytes >= (size_t)U * 4 &&
-                     ctx->scratch[SB_UBATCH].bytes >= (size_t)U * 4 && ctx->scratch[SB_ADC].bytes >= (size_t)U * R.A * 8 &&
-                     ctx->scratch[SB_TPM].bytes >= (size_t)U * R.M * 8 && ctx->scratch[SB_HITCNT].bytes >= hit_counts_bytes(U);
-  if (!sized) {
-    ldsim_set_error("pixel truth: the set-up record of the last chain launch does not describe its buffers");
-    return LDSIM_ESTATE;
-  }
-  return 0;
-}
-
 extern "C" int ldsim_chain_pixel_truth_row_samples(ldsim_ctx* ctx, int64_t* n_samples) {
   LDSIM_ENTER(ctx);
   if (!ctx || !n_samples) { ldsim_set_error("null argument"); return LDSIM_EINVAL; }
   *n_samples = 0;
-  CK(pt_need_launch(ctx, "ldsim_chain_pixel_truth_row_samples"));
+  CK(launch_need_record(ctx, "ldsim_chain_pixel_truth_row_samples"));
   const int64_t U = ctx->chain_U;
   if (U == 0) return 0;
   HIPCHK(hipSetDevice(ctx->device));
-  const ldsim_ctx::FeeRecord& R = ctx->fee_rec;
   CK(ctx->pt_sel.ensure((size_t)(4 * U + 4) * 4));
   unsigned long long* d_total = (unsigned long long*)(ctx->pt_sel.as<int32_t>() + 4 * U);      // (behind the scans; 16 U bytes in: 8-byte aligned)
   HIPCHK(hipMemsetAsync(d_total, 0, 8, ctx->stream));
-  const ChainView v = chain_view(ctx);
   hipLaunchKernelGGL(pixel_truth_samples_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, ctx->stream,
-                     v.fee.hdr, v.fee.counts, v.fee_slots, U, R.n_pairs, R.T, R.NT, R.M, d_total);
+                     fee_rec_args(ctx, chain_view(ctx)), d_total);
   HIPCHK(hipGetLastError());
   unsigned long long h = 0;
   HIPCHK(hipMemcpyAsync(&h, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));

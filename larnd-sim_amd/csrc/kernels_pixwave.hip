@@ -3,9 +3,9 @@
 //
 // A sibling of kernels_pixtruth.hip: it reads the same two things the launch left in HBM, the per-pair current rows (f32
 // [n_pairs][T]) and the FEE set-up record (fee_record.h), and changes nothing of the chain.  A wave per pixel, four pixels per
-// workgroup; lane k holds slot k's record (M <= 64 = the wave).  The pixel's time axis is cut into 64-tick words (word c: the ticks
-// [64 c, 64 c + 64)), lane l owning tick 64 c + l, and pw_chunk_sum forms S of a word exactly as pixel_truth_kernel's pass B and
-// pixel_adc_body do: f64, the slots' rows added in slot order.
+// workgroup; lane k holds slot k's window (fee_reader.h: FeeWavePixel, M <= 64 = the wave).  The pixel's time axis is cut into 64-tick words (word c: the ticks
+// [64 c, 64 c + 64)), lane l owning tick 64 c + l, and fee_wave_chunk_sum (fee_reader.h, pixel_truth_kernel's pass B too) forms S of a
+// word as pixel_adc_body does: f64, the slots' rows added in slot order.
 //   count  per word one 64-bit ballot of |S| > min_abs_current; the kept ticks of word c are the active ticks of the words
 //          c - 1, c, c + 1 dilated by pad_ticks <= 64; spans are the rising edges, samples the popcount: per pixel two counts
 //   scan   two exclusive 64-bit scans over the pixels (row order): a pixel's first span row and first sample
@@ -13,65 +13,9 @@
 //          are written as f32 at their places, and the lane behind a span's last tick writes its row
 // No atomics: every position is a function of the launch alone.
 #include "launchers.h"
-#include "fee_record.h"
-#include "wave_ops.h"
+#include "fee_reader.h"
 
 #define PW_WAVES 4       // pixels per workgroup
-
-// what a wave needs of its pixel: the header resolved and range-checked as pixel_truth_kernel does, slot k's window in lane k
-struct PwPixel {
-  int64_t u, p0;
-  int n_slots, t_lo, t_hi;      // (wave-uniform)
-  int st, lo, hi;               // lane k: slot k's start tick and the ticks [lo, hi) of the pixel's axis its row is summed over
-};
-
-// false: the wave has no pixel, or its record does not describe this launch's buffers (nothing outside them is touched)
-__device__ __forceinline__ bool pw_pixel(const FeeHdr* __restrict__ hdr, const unsigned long long* __restrict__ counts,
-                                         const FeeSlot* __restrict__ slots, int64_t U, int64_t n_pairs, int T, int NT, int M, int64_t w,
-                                         int lane, PwPixel& P) {
-  if (w >= U) return false;
-  // the w-th header: header w, or (two lists, the second behind the first's U places) the w-th of list 0 followed by list 1
-  int64_t idx = w;
-  if (counts) {
-    const int64_t c0 = (int64_t)counts[0];
-    if (c0 < 0 || c0 > U) return false;
-    if (w >= c0) {
-      if (w - c0 >= (int64_t)counts[1]) return false;
-      idx = U + (w - c0);
-    }
-  }
-  const FeeHdr* H = hdr + idx;
-  P.u = H->u;
-  P.p0 = H->p0;
-  int n_slots = __builtin_amdgcn_readfirstlane(H->n_slots);
-  n_slots = n_slots < M ? n_slots : M;
-  if (P.u < 0 || P.u >= U || n_slots < 0 || n_slots > 64 || P.p0 < 0 || P.p0 + n_slots > n_pairs) return false;
-  P.n_slots = n_slots;
-  P.t_lo = __builtin_amdgcn_readfirstlane(max(H->t_lo, 0));
-  P.t_hi = __builtin_amdgcn_readfirstlane(min(H->t_hi, NT));
-  P.st = P.lo = P.hi = 0;
-  if (lane < n_slots) {
-    const FeeSlot sl = slots[P.p0 + lane];
-    P.st = sl.start;
-    P.lo = max(sl.start + max(sl.w0, 0), 0);       // (pixel_adc_body: detsim.py:516-520)
-    P.hi = min(sl.start + min(sl.w1, T), NT);
-  }
-  return true;
-}
-
-// S[base + lane]: the slots that cover the tick, added in slot order in f64 (0 where no window reaches, and behind N_t).  The one
-// place S is formed: the count pass, the fill pass and the dense form all call it.
-__device__ __forceinline__ double pw_chunk_sum(const float* __restrict__ waves, const PwPixel& P, int T, int base, int lane) {
-  const int t = base + lane;
-  double S = 0;
-  for (int k = 0; k < P.n_slots; k++) {
-    const int lo_k = wave_lane_i32(P.lo, k), hi_k = wave_lane_i32(P.hi, k);
-    if (hi_k <= base || lo_k >= base + 64) continue;           // (wave-uniform)
-    const int64_t row = (P.p0 + k) * (int64_t)T - wave_lane_i32(P.st, k);      // element of tick 0 (the ticks [lo_k, hi_k) lie inside the row)
-    if (t >= lo_k && t < hi_k) S += (double)waves[row + t];
-  }
-  return S;
-}
 
 __device__ __forceinline__ unsigned long long pw_low_bits(int n) {      // the n lowest bits, 0 <= n <= 64
   return n >= 64 ? ~0ull : ((1ull << n) - 1ull);
@@ -79,7 +23,7 @@ __device__ __forceinline__ unsigned long long pw_low_bits(int n) {      // the n
 
 // The walk over one pixel's words, shared by the two passes.  FILL = false: counts only.
 template <bool FILL>
-__device__ __forceinline__ void pw_walk(const float* __restrict__ waves, const PwPixel& P, int T, int NT, int lane, double thr, int pad,
+__device__ __forceinline__ void pw_walk(const float* __restrict__ waves, const FeeWavePixel& P, int T, int NT, int lane, double thr, int pad,
                                         unsigned long long& n_spans, unsigned long long& n_samples,
                                         // fill: the pixel's first span row and first sample, the sizes of the two arrays, the row's identity
                                         unsigned long long span0, unsigned long long samp0, unsigned long long spans_cap,
@@ -94,7 +38,7 @@ __device__ __forceinline__ void pw_walk(const float* __restrict__ waves, const P
   unsigned long long a_prev = 0, a_cur = 0, a_next = 0;         // activity of the words c - 1, c, c + 1
   double s_cur = 0, s_next = 0;
   if (c_first >= c_lo) {
-    s_cur = pw_chunk_sum(waves, P, T, c_first << 6, lane);
+    s_cur = fee_wave_chunk_sum(waves, P, T, c_first << 6, lane);
     a_cur = __ballot(fabs(s_cur) > thr);
   }
   unsigned long long carry = 0;                                 // the last tick of the word before was kept
@@ -104,7 +48,7 @@ __device__ __forceinline__ void pw_walk(const float* __restrict__ waves, const P
     s_next = 0;
     a_next = 0;
     if (c + 1 >= c_lo && c + 1 < c_hi) {
-      s_next = pw_chunk_sum(waves, P, T, (c + 1) << 6, lane);
+      s_next = fee_wave_chunk_sum(waves, P, T, (c + 1) << 6, lane);
       a_next = __ballot(fabs(s_next) > thr);
     }
     // kept: an active tick within pad of this one, in this word or in a neighbour
@@ -161,64 +105,48 @@ __device__ __forceinline__ void pw_walk(const float* __restrict__ waves, const P
 
 // count[u] = the pixel's spans, count[U + 1 + u] = its samples (two arrays of U + 1 places, zeroed before; place U stays 0 so the
 // exclusive scans end in the totals)
-__global__ void __launch_bounds__(64 * PW_WAVES) pixel_wave_count_kernel(
-    const FeeHdr* __restrict__ hdr, const unsigned long long* __restrict__ counts, const FeeSlot* __restrict__ slots,
-    const float* __restrict__ waves, const int32_t* __restrict__ hit_count, int64_t U, int64_t n_pairs, int T, int NT, int M, double thr,
-    int pad, int hits_only, unsigned long long* __restrict__ count) {
+__global__ void __launch_bounds__(64 * PW_WAVES) pixel_wave_count_kernel(FeeRecArgs R, const int32_t* __restrict__ hit_count, double thr,
+                                                                         int pad, int hits_only, unsigned long long* __restrict__ count) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * PW_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  PwPixel P;
-  if (!pw_pixel(hdr, counts, slots, U, n_pairs, T, NT, M, w, lane, P)) return;
+  FeeWavePixel P;
+  if (!fee_wave_pixel(R, w, lane, P)) return;
   if (hits_only && hit_count[P.u] <= 0) return;
   unsigned long long n_spans, n_samples;
-  pw_walk<false>(waves, P, T, NT, lane, thr, pad, n_spans, n_samples, 0, 0, 0, 0, 0, 0, nullptr, nullptr);
+  pw_walk<false>(R.waves, P, R.T, R.NT, lane, thr, pad, n_spans, n_samples, 0, 0, 0, 0, 0, 0, nullptr, nullptr);
   if (lane == 0) {
     count[P.u] = n_spans;
-    count[U + 1 + P.u] = n_samples;
+    count[R.U + 1 + P.u] = n_samples;
   }
 }
 
 __global__ void __launch_bounds__(64 * PW_WAVES) pixel_wave_fill_kernel(
-    const FeeHdr* __restrict__ hdr, const unsigned long long* __restrict__ counts, const FeeSlot* __restrict__ slots,
-    const float* __restrict__ waves, const int32_t* __restrict__ upix, const int32_t* __restrict__ ubatch, int64_t U, int64_t n_pairs,
-    int T, int NT, int M, double thr, int pad, const unsigned long long* __restrict__ count, const unsigned long long* __restrict__ first,
-    unsigned long long spans_cap, unsigned long long samples_cap, LdsimPixelWaveSpan* __restrict__ spans, float* __restrict__ samples) {
+    FeeRecArgs R, const int32_t* __restrict__ upix, const int32_t* __restrict__ ubatch, double thr, int pad,
+    const unsigned long long* __restrict__ count, const unsigned long long* __restrict__ first, unsigned long long spans_cap,
+    unsigned long long samples_cap, LdsimPixelWaveSpan* __restrict__ spans, float* __restrict__ samples) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * PW_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  PwPixel P;
-  if (!pw_pixel(hdr, counts, slots, U, n_pairs, T, NT, M, w, lane, P)) return;
+  FeeWavePixel P;
+  if (!fee_wave_pixel(R, w, lane, P)) return;
   if (count[P.u] == 0) return;                                  // (nothing kept, or not selected: a kept tick makes a span)
   unsigned long long n_spans, n_samples;
-  pw_walk<true>(waves, P, T, NT, lane, thr, pad, n_spans, n_samples, first[P.u], first[U + 1 + P.u], spans_cap, samples_cap, upix[P.u],
-                ubatch[P.u], spans, samples);
+  pw_walk<true>(R.waves, P, R.T, R.NT, lane, thr, pad, n_spans, n_samples, first[P.u], first[R.U + 1 + P.u], spans_cap, samples_cap,
+                upix[P.u], ubatch[P.u], spans, samples);
 }
 
 // the dense form of the rows [u_begin, u_end): (float)S[t] into out [u_end - u_begin][NT], zeroed before
-__global__ void __launch_bounds__(64 * PW_WAVES) pixel_wave_dense_kernel(
-    const FeeHdr* __restrict__ hdr, const unsigned long long* __restrict__ counts, const FeeSlot* __restrict__ slots,
-    const float* __restrict__ waves, int64_t U, int64_t n_pairs, int T, int NT, int M, int64_t u_begin, int64_t u_end,
-    float* __restrict__ out) {
+__global__ void __launch_bounds__(64 * PW_WAVES) pixel_wave_dense_kernel(FeeRecArgs R, int64_t u_begin, int64_t u_end,
+                                                                         float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * PW_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  PwPixel P;
-  if (!pw_pixel(hdr, counts, slots, U, n_pairs, T, NT, M, w, lane, P)) return;
+  FeeWavePixel P;
+  if (!fee_wave_pixel(R, w, lane, P)) return;
   if (P.u < u_begin || P.u >= u_end) return;
-  float* row = out + (P.u - u_begin) * (int64_t)NT;
+  float* row = out + (P.u - u_begin) * (int64_t)R.NT;
   for (int base = (P.t_lo >> 6) << 6; base < P.t_hi; base += 64) {
-    const double S = pw_chunk_sum(waves, P, T, base, lane);
-    if (base + lane < NT) row[base + lane] = (float)S;
+    const double S = fee_wave_chunk_sum(R.waves, P, R.T, base, lane);
+    if (base + lane < R.NT) row[base + lane] = (float)S;
   }
-}
-
-// a buffer of the pass; an allocation that fails leaves the buffer empty and the context usable
-static int pw_ensure(DevBuf& b, size_t need, const char* what) {
-  if (need <= b.bytes && b.p) return 0;
-  if (b.ensure(need)) {
-    (void)hipGetLastError();
-    ldsim_set_error("pixel waveforms: no device memory for %s (%zu bytes)", what, need);
-    return LDSIM_ENOMEM;
-  }
-  return 0;
 }
 
 extern "C" int ldsim_chain_pixel_waveforms(ldsim_ctx* ctx, double min_abs_current, int32_t pad_ticks, int32_t hits_only, int64_t sizes[3]) {
@@ -233,7 +161,7 @@ extern "C" int ldsim_chain_pixel_waveforms(ldsim_ctx* ctx, double min_abs_curren
     ldsim_set_error("pixel waveforms: pad_ticks %d must lie in [0, 64]", (int)pad_ticks);
     return LDSIM_EINVAL;
   }
-  CK(pt_need_launch(ctx, "ldsim_chain_pixel_waveforms"));
+  CK(launch_need_record(ctx, "ldsim_chain_pixel_waveforms"));
   HIPCHK(hipSetDevice(ctx->device));
   const ChainView v = chain_view(ctx);      // (the pass grows its own buffers and SB_SORTTMP only)
   const int64_t U = v.U;
@@ -245,17 +173,18 @@ extern "C" int ldsim_chain_pixel_waveforms(ldsim_ctx* ctx, double min_abs_curren
     return 0;
   }
   const ldsim_ctx::FeeRecord& R = ctx->fee_rec;
+  const FeeRecArgs F = fee_rec_args(ctx, v);
   hipStream_t st = ctx->stream;
   const size_t n_cnt = 2 * ((size_t)U + 1);
-  CK(pw_ensure(ctx->pw_sel, 2 * n_cnt * 8, "the counts"));
+  CK(pass_ensure(ctx->pw_sel, 2 * n_cnt * 8, "pixel waveforms", "the counts"));
   unsigned long long *count = ctx->pw_sel.as<unsigned long long>(), *first = count + n_cnt;
   HIPCHK(hipMemsetAsync(count, 0, n_cnt * 8, st));
   const dim3 grid((unsigned)((U + PW_WAVES - 1) / PW_WAVES)), block(64 * PW_WAVES);
   for (int k = 0; k < 4; k++) CK(ctx->pw_ev[k].ensure());
   ctx->pw_filled = false;
   HIPCHK(hipEventRecord(ctx->pw_ev[0], st));
-  hipLaunchKernelGGL(pixel_wave_count_kernel, grid, block, 0, st, v.fee.hdr, v.fee.counts, v.fee_slots, v.waves, v.hit_count, U,
-                     R.n_pairs, R.T, R.NT, R.M, min_abs_current, (int)pad_ticks, (int)(hits_only != 0), count);
+  hipLaunchKernelGGL(pixel_wave_count_kernel, grid, block, 0, st, F, v.hit_count, min_abs_current, (int)pad_ticks,
+                     (int)(hits_only != 0), count);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->pw_ev[1], st));
   // 64-bit from the start: the samples of a launch can pass 2^31.  Place U of each array is 0, so first[U] is the total.
@@ -272,12 +201,11 @@ extern "C" int ldsim_chain_pixel_waveforms(ldsim_ctx* ctx, double min_abs_curren
     return LDSIM_ESTATE;
   }
   const size_t b_spans = (size_t)total[0] * sizeof(LdsimPixelWaveSpan);
-  CK(pw_ensure(ctx->pw_out, b_spans + (size_t)total[1] * 4, "the spans and samples"));
+  CK(pass_ensure(ctx->pw_out, b_spans + (size_t)total[1] * 4, "pixel waveforms", "the spans and samples"));
   if (total[0]) {
     HIPCHK(hipEventRecord(ctx->pw_ev[2], st));
-    hipLaunchKernelGGL(pixel_wave_fill_kernel, grid, block, 0, st, v.fee.hdr, v.fee.counts, v.fee_slots, v.waves, v.upix, v.ubatch, U,
-                       R.n_pairs, R.T, R.NT, R.M, min_abs_current, (int)pad_ticks, count, first, total[0], total[1],
-                       (LdsimPixelWaveSpan*)ctx->pw_out.p, (float*)((char*)ctx->pw_out.p + b_spans));
+    hipLaunchKernelGGL(pixel_wave_fill_kernel, grid, block, 0, st, F, v.upix, v.ubatch, min_abs_current, (int)pad_ticks, count, first,
+                       total[0], total[1], (LdsimPixelWaveSpan*)ctx->pw_out.p, (float*)((char*)ctx->pw_out.p + b_spans));
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->pw_ev[3], st));
     ctx->pw_filled = true;
@@ -333,7 +261,7 @@ extern "C" int ldsim_chain_pixel_waveforms_ms(ldsim_ctx* ctx, double* count_ms, 
 extern "C" int ldsim_chain_pixel_waveforms_dense(ldsim_ctx* ctx, int64_t u_begin, int64_t u_end, float* S) {
   LDSIM_ENTER(ctx);
   if (!ctx) { ldsim_set_error("null ctx"); return LDSIM_EINVAL; }
-  CK(pt_need_launch(ctx, "ldsim_chain_pixel_waveforms_dense"));
+  CK(launch_need_record(ctx, "ldsim_chain_pixel_waveforms_dense"));
   const int64_t U = ctx->chain_U;
   if (u_begin < 0 || u_end < u_begin || u_end > U) {
     ldsim_set_error("pixel waveforms: rows [%lld, %lld) are not a range of the launch's %lld unique pixels", (long long)u_begin,
@@ -347,10 +275,10 @@ extern "C" int ldsim_chain_pixel_waveforms_dense(ldsim_ctx* ctx, int64_t u_begin
   const ldsim_ctx::FeeRecord& R = ctx->fee_rec;
   hipStream_t st = ctx->stream;
   const size_t bytes = (size_t)(u_end - u_begin) * (size_t)R.NT * 4;
-  CK(pw_ensure(ctx->pw_dense, bytes, "the dense rows"));
+  CK(pass_ensure(ctx->pw_dense, bytes, "pixel waveforms", "the dense rows"));
   HIPCHK(hipMemsetAsync(ctx->pw_dense.p, 0, bytes, st));
-  hipLaunchKernelGGL(pixel_wave_dense_kernel, dim3((unsigned)((U + PW_WAVES - 1) / PW_WAVES)), dim3(64 * PW_WAVES), 0, st, v.fee.hdr,
-                     v.fee.counts, v.fee_slots, v.waves, U, R.n_pairs, R.T, R.NT, R.M, u_begin, u_end, ctx->pw_dense.as<float>());
+  hipLaunchKernelGGL(pixel_wave_dense_kernel, dim3((unsigned)((U + PW_WAVES - 1) / PW_WAVES)), dim3(64 * PW_WAVES), 0, st,
+                     fee_rec_args(ctx, v), u_begin, u_end, ctx->pw_dense.as<float>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(S, ctx->pw_dense.p, bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

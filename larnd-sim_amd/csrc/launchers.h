@@ -78,9 +78,12 @@ int fee_launch_adc_dense(ldsim_ctx* ctx, const double* ps, const double* pts, in
                          double* ticks, double* frac);
 int fee_launch_digitize(ldsim_ctx* ctx, const double* q, const double* gain, double* out, int64_t n);
 
-// ---- kernels_pixtruth.hip ----------------------------------------------------------------------------------------------
+// ---- the passes that read a chain launch afterwards (pixel truth, pixel waveforms, FEE and charge universes): ldsim_abi.hip -----
 // 0 while the scratch buffers hold the last chain launch and its set-up record describes them; else LDSIM_ESTATE, `who` named
-int pt_need_launch(ldsim_ctx* ctx, const char* who);
+int launch_need_record(ldsim_ctx* ctx, const char* who);
+// a buffer of the pass `pass`, named in the message with `what`; an allocation that fails leaves the buffer empty and the context
+// usable (LDSIM_ENOMEM)
+int pass_ensure(DevBuf& b, size_t need, const char* pass, const char* what);
 
 // ---- kernels_rng.hip ---------------------------------------------------------------------------------------------------
 int rng_ensure_states(ldsim_ctx* ctx, int64_t n);

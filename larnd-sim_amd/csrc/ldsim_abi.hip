@@ -1802,6 +1802,40 @@ extern "C" int ldsim_charge_chain(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg
   return rc;
 }
 
+// the launch is intact and its set-up record describes its buffers: what every pass that reads the launch afterwards asks first
+int launch_need_record(ldsim_ctx* ctx, const char* who) {
+  if (ctx->launch_stale) {
+    ldsim_set_error("%s reads what the last chain launch left in HBM, and it is gone: %s; run ldsim_charge_chain again", who,
+                    ctx->launch_stale);
+    return LDSIM_ESTATE;
+  }
+  const int64_t U = ctx->chain_U;
+  if (U == 0) return 0;
+  const ldsim_ctx::FeeRecord& R = ctx->fee_rec;
+  const DevBuf* sb = ctx->scratch;
+  // all of the sizes the launch ran with (an intact launch has them; checked all the same)
+  const bool sized = R.U == U && R.M > 0 && R.M <= 64 && R.A > 0 && R.T > 0 && R.n_pairs > 0 &&
+                     sb[SB_FEEHDR].bytes >= chain_view(ctx).fee.bytes && sb[SB_FEESLOT].bytes >= (size_t)R.n_pairs * sizeof(FeeSlot) &&
+                     sb[SB_WAVES].bytes >= (size_t)R.n_pairs * R.T * 4 && sb[SB_UPIX].bytes >= (size_t)U * 4 &&
+                     sb[SB_UBATCH].bytes >= (size_t)U * 4 && sb[SB_ADC].bytes >= (size_t)U * R.A * 8 &&
+                     sb[SB_TPM].bytes >= (size_t)U * R.M * 8 && sb[SB_HITCNT].bytes >= hit_counts_bytes(U);
+  if (!sized) {
+    ldsim_set_error("%s: the set-up record of the last chain launch does not describe its buffers", who);
+    return LDSIM_ESTATE;
+  }
+  return 0;
+}
+
+int pass_ensure(DevBuf& b, size_t need, const char* pass, const char* what) {
+  if (need <= b.bytes && b.p) return 0;
+  if (b.ensure(need)) {
+    (void)hipGetLastError();
+    ldsim_set_error("%s: no device memory for %s (%zu bytes)", pass, what, need);
+    return LDSIM_ENOMEM;
+  }
+  return 0;
+}
+
 // the dense fractions array of the current output set, complete (entries the FEE kernel did not write: zero)
 static int fractions_complete(ldsim_ctx* ctx) {
   if (ctx->frac_clean_gen == ctx->out_gen) return 0;
