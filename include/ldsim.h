@@ -333,6 +333,40 @@ int ldsim_light_detector_response(ldsim_ctx* ctx, const float* light_sample_inc,
  * uniform for a mean below 30 PE per tick, one float32 normal above.  The generator is third-party and unpinned. */
 int ldsim_stat_fluctuations(ldsim_ctx* ctx, const float* light_sample_inc, int32_t n_det, int32_t n_ticks,
                             float* light_sample_inc_disc);
+
+/* ---- SiPM correlated noise in the fluctuation stage (DESIGN.md "SiPM correlated noise") --------------------------------------
+ * Mirrors nothing in the reference, whose only statistical model of the light leg is the Poisson draw above.  Opt-in, off by
+ * default; keyed mode only.  While enabled, the fluctuation stage of ldsim_dev_light_response and ldsim_dev_light_universes (and
+ * ldsim_sipm_stat_fluctuations below) counts avalanches per element (idet, itick) of the rate array x [PE / us], with
+ * tick = LIGHT_TICK_SIZE and the element's keyed stream (stage tag 2, key_mix(key_mix(call key, idet), itick)); "Poisson(m, i)" is
+ * the sampler above on draw i (m <= 0: 0; m < 30: inversion on uniform i; else (long long)(normal i * sqrt(m) + m) clamped at 0):
+ *   n_p = Poisson(x * tick, 0)                                   primaries: the draw of the stage with the noise off
+ *   n_d = Poisson(dark_rate * tick, 1)                           dark counts, also where x <= 0
+ *   g_0 = n_p + n_d, g_{k+1} = Poisson(crosstalk * g_k, 2 + k)   prompt cross-talk by generations, until g_k = 0 or k = 31
+ *   N = sum of g_k
+ *   n_ap = Binomial(N, afterpulse)                               the charge statistics' sampler on normal 34 and uniform 35
+ *   after-pulse j lands on tick itick + 1 + floor(-afterpulse_tau * log((double)u_j) / tick), u_j = uniform 64 + j (f64); it has
+ *   full amplitude, starts no cross-talk and no after-pulse, and is dropped at or beyond n_ticks (it never reaches the next row)
+ *   count[idet][t] = N of the element + the after-pulses that landed on it (int32)
+ *   out = (float)(1 / tick * (double)count)
+ * With the four constants 0 the output equals the plain keyed stage's bit for bit.  Dark counts exist only inside the tick window
+ * of a fluctuated array; truth slots are untouched.
+ * Ranges (LDSIM_EINVAL, the message names the field; a refused call changes nothing): 0 <= crosstalk <= 0.5,
+ * 0 <= afterpulse <= 0.5, afterpulse_tau finite and > 0 when afterpulse > 0, dark_rate finite, >= 0 and dark_rate * tick < 30.
+ * The values are kept when enable = 0 (noise may then be NULL).  A fluctuation while enabled outside keyed mode: LDSIM_ESTATE. */
+typedef struct {
+  double crosstalk;        /* mean number of secondary avalanches per avalanche */
+  double afterpulse;       /* probability of one after-pulse per avalanche */
+  double afterpulse_tau;   /* [us] mean delay of an after-pulse */
+  double dark_rate;        /* [avalanches / us] per detector row */
+} LdsimSipmNoise;
+int ldsim_set_sipm_noise(ldsim_ctx* ctx, int32_t enable, const LdsimSipmNoise* noise);
+int ldsim_get_sipm_noise(ldsim_ctx* ctx, int32_t* enable, LdsimSipmNoise* noise);
+/* The fluctuation stage on a host array under the current call key (ldsim_rng_set_call_key): rate, out [n_det][n_ticks] f4; rows
+ * are keyed by their index in this call.  Keyed mode only (LDSIM_ESTATE).  With the noise enabled, counts (or NULL) receives the
+ * int32 avalanche counts; with it disabled the plain keyed stage runs and counts must be NULL (LDSIM_ESTATE). */
+int ldsim_sipm_stat_fluctuations(ldsim_ctx* ctx, const float* rate, int32_t n_det, int32_t n_ticks, float* out,
+                                 int32_t* counts);
 /* light_sim.get_triggers(signal, group_threshold, op_channel_idx, i_subbatch), LIGHT_TRIG_MODE 0 branch
  *                                                                         -- larndsim/light_sim.py:339-411
  * signal [n_det][n_ticks] f4 (NULL: the resident response of ldsim_dev_light_response), group_threshold [n_grp] with

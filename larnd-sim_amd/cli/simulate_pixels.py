@@ -83,6 +83,15 @@ def _parser():
                          "keyed streams (larndsim_amd/charge_stats.py) instead of mean values; needs --rng keyed")
     ap.add_argument("--fano_factor", type=float, default=None,
                     help="Fano factor of the ion-pair count under --charge_statistics (default 0.107)")
+    ap.add_argument("--sipm_crosstalk", type=float, default=None,
+                    help="SiPM correlated noise in the light fluctuations (larndsim_amd/sipm_noise.py; any --sipm_* flag enables "
+                         "it; needs --rng keyed): mean number of prompt cross-talk avalanches per avalanche, 0 .. 0.5 (default 0)")
+    ap.add_argument("--sipm_afterpulse", type=float, default=None,
+                    help="SiPM noise: probability of one after-pulse per avalanche, 0 .. 0.5 (default 0)")
+    ap.add_argument("--sipm_afterpulse_tau", type=float, default=None,
+                    help="SiPM noise: mean delay of an after-pulse [us] (default 0.1)")
+    ap.add_argument("--sipm_dark_rate", type=float, default=None,
+                    help="SiPM noise: dark counts per us and light detector inside a simulated sub-batch's window (default 0)")
     ap.add_argument("--pixel_truth", action="store_true",
                     help="also store the true induced charge per pixel and per (pixel, segment) of every chain launch "
                          "(datasets pixel_truth and pixel_truth_tracks, larndsim_amd/pixel_truth.py); one GPU only")
@@ -152,6 +161,28 @@ LIGHT_UNIVERSES_NEED_LIGHT = "--light_universes varies the light simulation, and
 
 CHARGE_STATISTICS_NEEDS_KEYED = ("--charge_statistics draws from keyed random streams (one per segment, whatever the "
                                  "chunking or rank count): give --rng keyed as well")
+SIPM_NOISE_NEEDS_KEYED = ("--sipm_crosstalk, --sipm_afterpulse, --sipm_afterpulse_tau and --sipm_dark_rate draw from keyed random "
+                          "streams (one per light detector and tick, whatever the chunking or rank count): give --rng keyed as "
+                          "well")
+
+
+def sipm_noise_of(crosstalk, afterpulse, afterpulse_tau, dark_rate):
+    """the four constants of the SiPM noise from the --sipm_* options (None where one is absent: its default), or None when
+    none is given (the feature stays off); ValueError names a flag out of range"""
+    if crosstalk is None and afterpulse is None and afterpulse_tau is None and dark_rate is None:
+        return None
+    # (standard library only: the parent of --n_gpus N parses the options too.  The ranges are ldsim_set_sipm_noise's; the bound
+    # of the dark rate that depends on LIGHT_TICK_SIZE is left to it)
+    p = dict(crosstalk=float(crosstalk or 0.0), afterpulse=float(afterpulse or 0.0),
+             afterpulse_tau=0.1 if afterpulse_tau is None else float(afterpulse_tau), dark_rate=float(dark_rate or 0.0))
+    for name in ("crosstalk", "afterpulse"):
+        if not 0 <= p[name] <= 0.5:
+            raise ValueError(f"--sipm_{name} {p[name]:g} must lie in [0, 0.5]")
+    if p["afterpulse"] > 0 and not 0 < p["afterpulse_tau"] < float("inf"):
+        raise ValueError(f"--sipm_afterpulse_tau {p['afterpulse_tau']:g} us must be finite and > 0 when --sipm_afterpulse > 0")
+    if not 0 <= p["dark_rate"] < float("inf"):
+        raise ValueError(f"--sipm_dark_rate {p['dark_rate']:g} per us must be finite and >= 0")
+    return p
 
 
 def _parse_args(argv=None):
@@ -164,6 +195,12 @@ def _parse_args(argv=None):
         ap.error(CHARGE_STATISTICS_NEEDS_KEYED)
     if a.fano_factor is not None and not (0 <= a.fano_factor < float("inf")):
         ap.error("--fano_factor must be finite and >= 0")
+    try:
+        sipm = sipm_noise_of(a.sipm_crosstalk, a.sipm_afterpulse, a.sipm_afterpulse_tau, a.sipm_dark_rate)
+    except ValueError as e:
+        ap.error(str(e))
+    if sipm is not None and a.rng != "keyed":
+        ap.error(SIPM_NOISE_NEEDS_KEYED)
     if a.pixel_truth_min_charge is not None and not a.pixel_truth:
         ap.error("--pixel_truth_min_charge sets the selection of --pixel_truth: give --pixel_truth as well")
     if a.pixel_truth_min_charge is not None and not (0 <= a.pixel_truth_min_charge < float("inf")):
@@ -476,7 +513,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                    numba_f32="auto", n_gpus=None, force_dist=False, rng="table", field_map=None, charge_statistics=False,
                    fano_factor=None, pixel_truth=False, pixel_truth_min_charge=None, light_lut_interpolation="nearest",
                    pixel_waveforms=False, pixel_waveforms_threshold=None, pixel_waveforms_pad=None, pixel_waveforms_hits_only=False,
-                   fee_universes=None, charge_universes=None, light_universes=None, **ignored):
+                   fee_universes=None, charge_universes=None, light_universes=None, sipm_crosstalk=None, sipm_afterpulse=None,
+                   sipm_afterpulse_tau=None, sipm_dark_rate=None, **ignored):
     rank, world = launch.dist_mode(n_gpus, force_dist)
     if world is not None and "WORLD_SIZE" not in os.environ:
         raise RuntimeError(f"--n_gpus {n_gpus}: run_simulation runs one rank; start the ranks with main() (simulate_pixels.py "
@@ -510,6 +548,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         for k, (name, _, fee_changes) in enumerate(lcu.read(charge_universes)):   # (the file's keys, before anything is simulated)
             if lfu.changes_noisy(fee_changes) and rng != "keyed":
                 raise ValueError(CHARGE_UNIVERSES_NEED_KEYED.format(f"{k} ({name})"))
+    sipm = sipm_noise_of(sipm_crosstalk, sipm_afterpulse, sipm_afterpulse_tau, sipm_dark_rate)
+    if sipm is not None and rng != "keyed":
+        raise ValueError(SIPM_NOISE_NEEDS_KEYED)
     if light_universes is not None:
         if world is not None and world > 1:
             raise ValueError(LIGHT_UNIVERSES_NO_MULTI_GPU)
@@ -667,6 +708,9 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
     fano = charge_stats.FANO_DEFAULT if fano_factor is None else float(fano_factor)
     print("Charge statistics:", f"on (--charge_statistics, Fano factor {fano:g})" if charge_statistics
           else "off (mean-value charge)")
+    print("SiPM noise:", "off (Poisson fluctuations only)" if sipm is None else
+          f"on (--sipm_crosstalk {sipm['crosstalk']:g}, --sipm_afterpulse {sipm['afterpulse']:g}, --sipm_afterpulse_tau "
+          f"{sipm['afterpulse_tau']:g} us, --sipm_dark_rate {sipm['dark_rate']:g} per us)")
     truth_min = None if not pixel_truth else float(pixel_truth_min_charge or 0.0)
     if pixel_truth:                     # (without the flag the header, like the file, is what it was)
         print("Pixel charge truth:", f"on (--pixel_truth, --pixel_truth_min_charge {truth_min:g} e)")
@@ -716,6 +760,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
                 chain.set_field_map(field_maps)
             if charge_statistics:
                 chain.set_charge_statistics(True, fano)
+            if sipm is not None:
+                chain.set_sipm_noise(**sipm)
             if not rng_seeded:
                 # create_xoroshiro128p_states(1024*256, seed) (:396), once; rank r of a sharded run seeds rand_seed + r.
                 # Keyed mode: every rank seeds rand_seed (the streams follow the identity of what is simulated)
@@ -817,6 +863,8 @@ def run_simulation(input_filename, output_filename, config="module0", mod2mod_va
         lib.set_option("light_lut_interp", 0)
         if charge_statistics:                                       # (the ctx is process-wide: leave it as it was found)
             lib.check(lib.load().ldsim_set_charge_statistics(lib.context(refresh_consts=False), 0, 0))
+        if sipm is not None:
+            lib.check(lib.load().ldsim_set_sipm_noise(lib.context(refresh_consts=False), 0, None))
     print(f"simulated {totals['n_segments']} segments in {totals['n_batches']} batches -> {totals['n_hits']} hits, "
           f"{totals['n_packets']} packets" + (f", {totals['n_light_triggers']} light triggers" if light_simulated else ""))
     print("Output saved in:", output_filename)

@@ -223,27 +223,7 @@ __global__ void __launch_bounds__(256) quench_drift_map_kernel(SegStore s, const
 }
 
 // ---- charge statistics: keyed binomial recombination and attachment ------------------------------
-// Binomial(n, p) from one normal draw z and one uniform draw u, n a whole number held in a double.  Design constants:
-// BINOM_NORMAL_MIN = 30 (n * min(p, 1 - p) from which the rounded normal is drawn) and BINOM_WALK_MAX = 256 (where the
-// inversion walk stops).  Below 30: inversion on the minority outcome at the centre u - 2^-25 of the uniform's 24-bit cell,
-// P(0) = exp(n log1p(-pm)), P(j + 1) = P(j) (n - j) / (j + 1) * (pm / (1 - pm)), j = the first running sum >= the centre.
-// larndsim_amd/charge_stats.py restates this operation for operation.
-#define BINOM_NORMAL_MIN 30.0
-#define BINOM_WALK_MAX 256.0
-__device__ __forceinline__ double binomial_draw(double n, double p, float z, float u) {
-  if (!(n > 0) || !(p > 0)) return 0;
-  if (p >= 1) return n;
-  const double pm = fmin(p, 1 - p);
-  if (n * pm >= BINOM_NORMAL_MIN) return fmin(fmax(rint(n * p + sqrt(n * p * (1 - p)) * (double)z), 0.0), n);
-  const double centre = (double)u - 0x1p-25, ratio = pm / (1 - pm), jmax = fmin(n, BINOM_WALK_MAX);
-  double q = exp(n * log1p(-pm)), sum = q, j = 0;
-  while (sum < centre && j < jmax) {
-    q = q * (n - j) / (j + 1) * ratio;
-    j += 1;
-    sum += q;
-  }
-  return p <= 0.5 ? j : n - j;
-}
+// binomial_draw: seg_charge.h (the light leg's SiPM after-pulses draw with it too)
 
 // drift_at without n_electrons: widths and times written, the drift time returned
 __device__ __forceinline__ double drift_times_at(SegStore& s, const LdsimConsts* __restrict__ c, int32_t plane, int64_t i,

@@ -111,6 +111,7 @@ int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const
                           int Mt, const double* weights, int C, const double* gain, float* out, int64_t* out_tid,
                           double* out_tph);
 int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick);
+int light_sipm_check(const LdsimSipmNoise& v, double tick);
 // light universes: out = (float)((double)x * scale); K tables over one input by light_conv_universes_kernel (a stage's plain sum
 // under each, bit-equal to light_conv_kernel's)
 int light_universes_scale(ldsim_ctx* ctx, const float* x, int64_t n, double scale, float* out);

@@ -629,6 +629,27 @@ extern "C" int ldsim_get_charge_statistics(ldsim_ctx* ctx, int32_t* enable, doub
   return 0;
 }
 
+// ---- SiPM correlated noise of the light fluctuation stage (light_wvfm.hip) ----------------------------------------------------
+extern "C" int ldsim_set_sipm_noise(ldsim_ctx* ctx, int32_t enable, const LdsimSipmNoise* noise) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  if (enable) {
+    NEED(noise, "SiPM noise: enabling needs the four constants");
+    CK(light_sipm_check(*noise, ctx->h_consts.light_tick_size));
+    ctx->sipm = *noise;
+  }
+  ctx->sipm_on = enable ? 1 : 0;
+  return 0;
+}
+
+extern "C" int ldsim_get_sipm_noise(ldsim_ctx* ctx, int32_t* enable, LdsimSipmNoise* noise) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  if (enable) *enable = ctx->sipm_on;
+  if (noise) *noise = ctx->sipm;
+  return 0;
+}
+
 // ---- drift-field maps ----------------------------------------------------------------------------------------------------
 static int fmap_upload_desc(ldsim_ctx* ctx) {
   CK(ctx->d_fmap.ensure(sizeof(ctx->h_fmap)));

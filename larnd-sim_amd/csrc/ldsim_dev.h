@@ -406,6 +406,11 @@ struct ldsim_ctx {
   int drift_stat_on = -1;                // setting of the quench_drift whose results the store holds (-1: none since the upload)
   double drift_stat_fano = 0;
   DevBuf d_stat_first;                   // [batches of the upload] i32 first segment index of every batch over the whole store
+  // SiPM correlated noise (ldsim_set_sipm_noise): cross-talk, after-pulses and dark counts in the keyed fluctuation stage
+  // (light_sipm_count_kernel, light_wvfm.hip)
+  int sipm_on = 0;
+  LdsimSipmNoise sipm = {0, 0, 0.1, 0};
+  DevBuf sipm_counts;                    // i32 avalanche counts of the array being fluctuated (zeroed, summed by atomics, converted)
   // multi-GPU exchange (comm.hip): RCCL communicator, rows accumulated over the chain calls of a pass, gathered rows
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 0;

@@ -1,6 +1,7 @@
 // light_wvfm.hip -- second half of the light chain: from the photo-electron rate per (channel, tick) to the
 // digitised waveforms the reference writes as light_wvfm.
 //   light_sim.calc_stat_fluctuations        larndsim/light_sim.py:186-238   light_stat_fluct_kernel
+//     (no counterpart in the reference: SiPM cross-talk, after-pulses, dark counts)   light_sipm_count_kernel + light_sipm_convert_kernel
 //   light_sim.get_triggers                  :339-443                       light_trig_mask_kernel + the host scan below
 //   light_sim.gen_light_detector_noise      :445-478                       light_noise_spec_kernel + light_idft_kernel
 //   light_sim.sim_triggers / digitize_signal :480-619                      light_sample_kernel + light_digitize_kernel
@@ -17,6 +18,7 @@
 
 #include "launchers.h"
 #include "rng.h"
+#include "seg_charge.h"
 
 // ---- calc_stat_fluctuations ----------------------------------------------------------------------------------------------
 // xoroshiro128p_poisson_int32 (:186-216): inversion with one float32 uniform below a mean of 30, else a normal truncated at 0
@@ -78,8 +80,113 @@ __global__ void __launch_bounds__(256) light_stat_fluct_keyed_kernel(const float
   }
 }
 
+// ---- SiPM correlated noise (ldsim_set_sipm_noise; include/ldsim.h states the model, larndsim_amd/sipm_noise.py restates it) -----
+// Draw indices of an element's stream: 0 primaries, 1 dark counts, 2 + k cross-talk generation k (k < SIPM_MAX_GEN), 34 / 35 the
+// normal / uniform of the after-pulse binomial, 64 + j the delay of after-pulse j (four to a Philox call).
+#define SIPM_MAX_GEN 32
+enum : uint32_t { SIPM_DRAW_PRIMARY = 0, SIPM_DRAW_DARK = 1, SIPM_DRAW_CASCADE = 2, SIPM_DRAW_AP_Z = 34, SIPM_DRAW_AP_U = 35,
+                  SIPM_DRAW_DELAY = 64 };
+struct KeyedPoissonAt {          // poisson_int32's source on draw i of a keyed stream
+  uint64_t seed, key;
+  uint32_t i;
+};
+__device__ inline float rng_uniform_f32(const KeyedPoissonAt& k) { return keyed_uniform(k.seed, RNG_TAG_LIGHT_FLUCT, k.key, k.i); }
+__device__ inline float rng_normal_f32(const KeyedPoissonAt& k) { return keyed_normal(k.seed, RNG_TAG_LIGHT_FLUCT, k.key, k.i); }
+
+// One thread per element: primaries, dark counts, the cross-talk cascade and the after-pulses of its avalanches, added into the
+// zeroed int32 counts (the element's own tick and, for after-pulses, later ticks of its row: integer atomics, so the sums do not
+// depend on the order of arrival).  Elements that can fire nothing (x <= 0 without dark counts) leave at once.
+__global__ void __launch_bounds__(256) light_sipm_count_kernel(const float* __restrict__ inc, int32_t* __restrict__ count,
+                                                               uint64_t seed, uint64_t call_key, int64_t n, int64_t ntick,
+                                                               double tick, LdsimSipmNoise k) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const float x = inc[e];
+  const double dark_mean = k.dark_rate * tick;
+  if (!(x > 0) && !(dark_mean > 0)) return;
+  const int64_t idet = e / ntick, itick = e - idet * ntick;
+  KeyedPoissonAt src{seed, key_mix(key_mix(call_key, (uint64_t)idet), (uint64_t)itick), SIPM_DRAW_PRIMARY};
+  int g = x > 0 ? poisson_int32((double)x * tick, src) : 0;
+  src.i = SIPM_DRAW_DARK;
+  g += poisson_int32(dark_mean, src);
+  int total = g;
+  for (uint32_t gen = 0; gen < SIPM_MAX_GEN && g > 0; gen++) {
+    src.i = SIPM_DRAW_CASCADE + gen;
+    g = poisson_int32(k.crosstalk * (double)g, src);
+    total += g;
+  }
+  if (total == 0) return;
+  atomicAdd(&count[e], total);
+  const double room = (double)(ntick - 1 - itick);       // an after-pulse delayed by fewer whole ticks than this stays in the row
+  if (!(k.afterpulse > 0) || !(room > 0)) return;
+  const int n_ap = (int)binomial_draw((double)total, k.afterpulse,
+                                      keyed_normal(seed, RNG_TAG_LIGHT_FLUCT, src.key, SIPM_DRAW_AP_Z),
+                                      keyed_uniform(seed, RNG_TAG_LIGHT_FLUCT, src.key, SIPM_DRAW_AP_U));
+  for (int j0 = 0; j0 < n_ap; j0 += 4) {
+    uint32_t w[4];
+    keyed_block(seed, RNG_TAG_LIGHT_FLUCT, src.key, (SIPM_DRAW_DELAY + (uint32_t)j0) >> 2, w);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (j0 + q < n_ap) {
+        const double d = floor(-k.afterpulse_tau * log((double)keyed_u01(w[q])) / tick);
+        if (d < room) atomicAdd(&count[e + 1 + (int64_t)d], 1);     // (d >= 0; a NaN compares false and is dropped)
+      }
+    }
+  }
+}
+
+// counts -> rate, the conversion of light_stat_fluct_keyed_kernel
+__global__ void __launch_bounds__(256) light_sipm_convert_kernel(const int32_t* __restrict__ count, float* __restrict__ out,
+                                                                 int64_t n, double tick) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  out[e] = (float)(1. / tick * (double)count[e]);
+}
+
+// the ranges of ldsim_set_sipm_noise; tick <= 0 (light constants not set yet): dark_rate * tick is checked at the launch
+int light_sipm_check(const LdsimSipmNoise& v, double tick) {
+  if (!(v.crosstalk >= 0 && v.crosstalk <= 0.5)) {
+    ldsim_set_error("SiPM noise: crosstalk %g must lie in [0, 0.5]", v.crosstalk);
+    return LDSIM_EINVAL;
+  }
+  if (!(v.afterpulse >= 0 && v.afterpulse <= 0.5)) {
+    ldsim_set_error("SiPM noise: afterpulse %g must lie in [0, 0.5]", v.afterpulse);
+    return LDSIM_EINVAL;
+  }
+  if (v.afterpulse > 0 && !(std::isfinite(v.afterpulse_tau) && v.afterpulse_tau > 0)) {
+    ldsim_set_error("SiPM noise: afterpulse_tau %g us must be finite and > 0 when afterpulse > 0", v.afterpulse_tau);
+    return LDSIM_EINVAL;
+  }
+  if (!(std::isfinite(v.dark_rate) && v.dark_rate >= 0) || (tick > 0 && !(v.dark_rate * tick < 30))) {
+    ldsim_set_error("SiPM noise: dark_rate %g per us must be finite, >= 0 and below 30 per tick of %g us", v.dark_rate, tick);
+    return LDSIM_EINVAL;
+  }
+  return 0;
+}
+
+static int light_launch_sipm_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick) {
+  if (!ctx->rng_keyed) {
+    ldsim_set_error("SiPM noise draws from keyed random streams (one per detector row and tick): call ldsim_rng_keyed_seed, or "
+                    "ldsim_set_sipm_noise(ctx, 0, ...) first");
+    return LDSIM_ESTATE;
+  }
+  const double tick = ctx->h_consts.light_tick_size;
+  CK(light_sipm_check(ctx->sipm, tick));                 // (the tick may have changed since the setter)
+  CK(ctx->sipm_counts.ensure((size_t)n * 4));
+  int32_t* count = ctx->sipm_counts.as<int32_t>();
+  HIPCHK(hipMemsetAsync(count, 0, (size_t)n * 4, ctx->stream));
+  const dim3 grid((unsigned)((n + 255) / 256));
+  hipLaunchKernelGGL(light_sipm_count_kernel, grid, dim3(256), 0, ctx->stream, inc, count, ctx->rng_seed, ctx->rng_call_key, n,
+                     ntick, tick, ctx->sipm);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(light_sipm_convert_kernel, grid, dim3(256), 0, ctx->stream, (const int32_t*)count, out, n, tick);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick) {
   if (n == 0) return 0;
+  if (ctx->sipm_on) return light_launch_sipm_fluct(ctx, inc, out, n, ntick);
   if (ctx->rng_keyed) {
     hipLaunchKernelGGL(light_stat_fluct_keyed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, inc, out,
                        ctx->rng_seed, ctx->rng_call_key, n, ntick, ctx->h_consts.light_tick_size);
@@ -704,6 +811,36 @@ extern "C" int ldsim_stat_fluctuations(ldsim_ctx* ctx, const float* light_sample
   HIPCHK(hipMemcpyAsync(din.p, light_sample_inc, n * 4, hipMemcpyHostToDevice, ctx->stream));
   CK(light_launch_stat_fluct(ctx, din.as<float>(), dout.as<float>(), (int64_t)n, n_ticks));
   HIPCHK(hipMemcpyAsync(light_sample_inc_disc, dout.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+// the fluctuation stage under the current call key, SiPM noise included when it is enabled (rows keyed by their index)
+extern "C" int ldsim_sipm_stat_fluctuations(ldsim_ctx* ctx, const float* rate, int32_t n_det, int32_t n_ticks, float* out,
+                                            int32_t* counts) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && rate && out && n_det >= 0 && n_ticks >= 0, "bad argument");
+  NEED(ctx->h_consts.light_tick_size > 0, "light constants not set");
+  if (!ctx->rng_keyed) {
+    ldsim_set_error("ldsim_sipm_stat_fluctuations keys its rows by the call key and their index: call ldsim_rng_keyed_seed first "
+                    "(table mode: ldsim_stat_fluctuations)");
+    return LDSIM_ESTATE;
+  }
+  if (counts && !ctx->sipm_on) {
+    ldsim_set_error("ldsim_sipm_stat_fluctuations: avalanche counts exist only while the SiPM noise is enabled "
+                    "(ldsim_set_sipm_noise)");
+    return LDSIM_ESTATE;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t n = (size_t)n_det * n_ticks;
+  if (n == 0) return 0;
+  DevBuf din, dout;
+  CK(din.ensure(n * 4));
+  CK(dout.ensure(n * 4));
+  HIPCHK(hipMemcpyAsync(din.p, rate, n * 4, hipMemcpyHostToDevice, ctx->stream));
+  CK(light_launch_stat_fluct(ctx, din.as<float>(), dout.as<float>(), (int64_t)n, n_ticks));
+  HIPCHK(hipMemcpyAsync(out, dout.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (counts) HIPCHK(hipMemcpyAsync(counts, ctx->sipm_counts.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
 }

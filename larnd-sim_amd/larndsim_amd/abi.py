@@ -77,6 +77,11 @@ class LdsimLightVariation(C.Structure):
                 ("gain_scale", C.c_double), ("response_time", C.c_double), ("oscillation_period", C.c_double)]
 
 
+class LdsimSipmNoise(C.Structure):
+    """include/ldsim.h LdsimSipmNoise (ldsim_set_sipm_noise): 32 bytes"""
+    _fields_ = [("crosstalk", C.c_double), ("afterpulse", C.c_double), ("afterpulse_tau", C.c_double), ("dark_rate", C.c_double)]
+
+
 FEE_UNIVERSES_MAX = 64      # include/ldsim.h LDSIM_FEE_UNIVERSES_MAX
 LIGHT_UNIVERSES_MAX = 64    # include/ldsim.h LDSIM_LIGHT_UNIVERSES_MAX
 

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import consts, lib
-from .abi import LdsimChainStats
+from .abi import LdsimChainStats, LdsimSipmNoise
 from .layout import make_layout
 
 
@@ -24,6 +24,7 @@ class ChargeChain:
             lib.set_response(response, self.ctx)
         self.clear_field_map()          # the ctx is process-wide: a fresh chain starts with the uniform field
         self.set_charge_statistics(False)                         # ... and with mean-value charge
+        self.set_sipm_noise(enable=False)                         # ... and with the plain Poisson light fluctuations
 
     def set_field_map(self, maps):
         """Drift-field maps (``field_map``: {tpc: {"origin", "spacing", "E" / "dx" / "dy" / "dz"}}, or the path of an .npz),
@@ -64,6 +65,20 @@ class ChargeChain:
         on, f = C.c_int32(), C.c_double()
         lib.check(lib.load().ldsim_get_charge_statistics(self.ctx, C.byref(on), C.byref(f)))
         return bool(on.value), f.value
+
+    def set_sipm_noise(self, crosstalk=0.0, afterpulse=0.0, afterpulse_tau=0.1, dark_rate=0.0, enable=True):
+        """SiPM correlated noise (``sipm_noise``) in the fluctuation stage of ``light_response`` and ``light_universes``: prompt
+        cross-talk (``crosstalk`` secondary avalanches per avalanche, 0 .. 0.5), after-pulses (probability ``afterpulse`` per
+        avalanche, 0 .. 0.5, mean delay ``afterpulse_tau`` us) and dark counts (``dark_rate`` per us and detector row).  Needs
+        ``seed_keyed``; ``enable=False`` switches it off and keeps the context's values."""
+        v = LdsimSipmNoise(float(crosstalk), float(afterpulse), float(afterpulse_tau), float(dark_rate))
+        lib.check(lib.load().ldsim_set_sipm_noise(self.ctx, C.c_int32(int(bool(enable))), C.byref(v) if enable else None))
+
+    def sipm_noise(self):
+        """(enabled, {crosstalk, afterpulse, afterpulse_tau, dark_rate}) as the context holds them"""
+        on, v = C.c_int32(), LdsimSipmNoise()
+        lib.check(lib.load().ldsim_get_sipm_noise(self.ctx, C.byref(on), C.byref(v)))
+        return bool(on.value), {f: getattr(v, f) for f, _ in LdsimSipmNoise._fields_}
 
     def seed_rng(self, seed, n_states=1024 * 256):
         """``create_xoroshiro128p_states(1024*256, seed=rand_seed)`` of the driver (cli/simulate_pixels.py:396): needed before

@@ -51,6 +51,7 @@ EXPORTS = [
     "ldsim_rng_seed", "ldsim_rng_states_download", "ldsim_rng_clear", "ldsim_rng_extend", "ldsim_rng_count",
     "ldsim_rng_keyed_seed", "ldsim_rng_is_keyed", "ldsim_chain_set_batch_keys", "ldsim_rng_set_call_key",
     "ldsim_rng_keyed_normals", "ldsim_rng_keyed_uniforms",
+    "ldsim_set_sipm_noise", "ldsim_get_sipm_noise", "ldsim_sipm_stat_fluctuations",
     "ldsim_stat_fluctuations", "ldsim_light_triggers", "ldsim_light_detector_noise", "ldsim_sim_triggers",
     "ldsim_dev_light_response", "ldsim_dev_light_response_download", "ldsim_light_response_ms",
     "ldsim_light_variation_nominal", "ldsim_dev_light_universes", "ldsim_dev_light_universe_download",
