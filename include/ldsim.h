@@ -835,6 +835,73 @@ int ldsim_dev_light_universe_waveforms(ldsim_ctx* ctx, int32_t k, const int32_t*
                                        const double* phases_signal, const double* phases_missing, double* digit_signal);
 int ldsim_light_universes_ms(ldsim_ctx* ctx, double* scint_ms, double* fluct_ms, double* response_ms);
 
+/* ---- light LUT builder: keyed photon transport in a TPC box (csrc/kernels_lutbuild.hip) --------------------------------------
+ * The producer of the table ldsim_set_light_lut loads: scintillation photons walked from every voxel of a box to rectangular
+ * detectors on its walls under Rayleigh scattering, bulk absorption and diffuse wall reflection.  larndsim_amd/lut_builder.py
+ * restates the walk in numpy (trace_twin) and turns the tallies into the table (to_lut).
+ * Frame: the box [0, box[0]] x [0, box[1]] x [0, box[2]] cm (axes u, v, w) with a grid (nx, ny, nz); voxel (i, j, k) spans
+ * [i, i + 1) * box[0] / nx and likewise, linear index (i * ny + j) * nz + k.  A detector is an axis-aligned rectangle on wall
+ * 0..5 = u0, u1, v0, v1, w0, w1 (u0: u = 0, u1: u = box[0]); lo / hi are in the wall's two in-plane coordinates in cyclic axis
+ * order (u walls: (v, w); v walls: (w, u); w walls: (u, v)); a point belongs to it when lo <= point < hi in both.  Its index in
+ * the list is the LUT's detector index.  Rectangles of one wall must not overlap.
+ * All geometry is f64.  Uniforms are keyed_uniform values (csrc/rng.h; f32 in (0, 1], widened exactly) of the stream
+ * (seed, stage tag 6, key_mix(key_mix(RNG_KEY_ROOT, voxel linear index), photon index)), indexed serially; an index whose
+ * branch is not taken stays unused.  The seed is the call's own argument: the context need not be in keyed mode.
+ * Emission: draws 0, 1, 2: p = voxel_lo + u * voxel_size, clamped into the box (emit_mode 1: the voxel's centre, the three
+ * indices unused); draws 3, 4: mu = 1 - 2 u3, phi = 2 pi u4, d = (sqrt(1 - mu^2) cos phi, sqrt(1 - mu^2) sin phi, mu).
+ * Step s = 0, 1, ... uses draws a, b, c, e = 5 + 4s .. 8 + 4s.  lambda_t = 1 / (1 / rayleigh + 1 / absorption);
+ * l = -lambda_t ln(u_a) (inf when lambda_t is); d_wall = the smallest distance to a wall along d (never negative; on a tie the
+ * lowest axis).  If l < d_wall: p += l d, path += l; with u_b <= lambda_t / absorption the photon is absorbed in the bulk, else
+ * it Rayleigh-scatters: q = 4 u_c - 2, A = cbrt(q + sqrt(q^2 + 1)), mu = A - 1 / A (the exact inverse of the (1 + mu^2) law),
+ * phi = 2 pi u_e, and with st = sqrt(1 - mu^2), den = sqrt(1 - d_z^2):
+ *   d' = (st (d_x d_z cos phi - d_y sin phi) / den + d_x mu, st (d_y d_z cos phi + d_x sin phi) / den + d_y mu,
+ *         -st cos phi den + d_z mu), or (st cos phi, st sin phi, sign(d_z) mu) where |d_z| > 0.99999; d' is renormalised.
+ * Otherwise: path += d_wall, p is put on the wall; the first rectangle of that wall (lowest index) holding the point detects the
+ * photon; if none does, with u_b <= wall_reflectivity[wall] it is re-emitted Lambertian about the inward normal
+ * (cos theta = sqrt(u_c), phi = 2 pi u_e; the in-plane components (sin theta cos phi, sin theta sin phi) in cyclic axis order),
+ * else it is absorbed at the wall.  After max_steps steps the photon is truncated.  Every photon has exactly one fate.
+ * Tallies (integers, so independent of order): per (voxel, detector) count u32; hist[nprof] u32, bin min(floor(t), nprof - 1)
+ * of t = path / group_velocity in ns (late photons land in the last bin); tmin = the least (float)t (+inf where count is 0);
+ * tsum u64 = sum of llrint(1024 t).  Per voxel three u64 fate counters: absorbed in the bulk, absorbed at a wall, truncated;
+ * sum(count) + the three == n_photons.
+ * ldsim_light_lut_build fills the host arrays for the voxels [voxel_begin, voxel_end) only (counts [nv][ndet],
+ * hist [nv][ndet][nprof], tmin [nv][ndet], tsum [nv][ndet], fates [nv][3]): a table can be built in slices, or on several GPUs
+ * by separate processes, and concatenated -- the same integers at any slicing, any lut_build_group_photons (ldsim_set_option:
+ * photons one workgroup walks, 64 .. 2^20, default 4096) and either tally path (option lut_build_lds_tile 0 sends every
+ * arrival to global atomics, as happens by itself when ndet * nprof does not fit the workgroup's LDS tile).
+ * ldsim_light_lut_trace writes, for photons [photon_begin, photon_end) of one voxel: fate (the detector index, or -1 absorbed
+ * in the bulk, -2 absorbed at a wall, -3 truncated), the steps taken, the arrival time path / group_velocity and the end point
+ * [n][3].  ldsim_light_lut_build_ms: HIP-event time of the last build's kernel.
+ * LDSIM_EINVAL (with a message): ndet outside 1 .. 1024, nprof outside 1 .. 512, n_photons outside 1 .. 2^31 - 1, a zero-sized
+ * box, grid or rectangle, a rectangle outside its wall or on an unknown wall, overlapping rectangles, lengths <= 0, a
+ * reflectivity outside [0, 1), a range outside the grid. */
+#define LDSIM_LUT_MAX_DETECTORS 1024
+#define LDSIM_LUT_MAX_NPROF 512
+typedef struct LdsimLutBuildParams {   /* 112 bytes */
+  double box[3];                 /* offset 0: extents of the box, cm */
+  double rayleigh_cm;            /* 24: Rayleigh scattering length, > 0, inf allowed */
+  double absorption_cm;          /* 32: bulk absorption length, > 0, inf allowed */
+  double group_velocity_cm_ns;   /* 40: 13.4 is a literature value for 128 nm in LAr */
+  double wall_reflectivity[6];   /* 48: u0 u1 v0 v1 w0 w1, each in [0, 1) */
+  int32_t emit_mode;             /* 96: 0 uniformly in the voxel, 1 at its centre */
+  int32_t max_steps;             /* 100 */
+  int32_t nprof;                 /* 104: 1 ns bins of the arrival-time histogram */
+  int32_t reserved;              /* 108 */
+} LdsimLutBuildParams;
+typedef struct LdsimLutDetector {      /* 40 bytes */
+  int32_t wall;                  /* 0..5 = u0 u1 v0 v1 w0 w1 */
+  int32_t pad;
+  double lo[2];
+  double hi[2];
+} LdsimLutDetector;
+int ldsim_light_lut_build(ldsim_ctx* ctx, const LdsimLutBuildParams* params, const LdsimLutDetector* detectors, int32_t ndet,
+                          int32_t nx, int32_t ny, int32_t nz, int64_t voxel_begin, int64_t voxel_end, int64_t n_photons,
+                          uint64_t seed, uint32_t* counts, uint32_t* hist, float* tmin, uint64_t* tsum, uint64_t* fates);
+int ldsim_light_lut_trace(ldsim_ctx* ctx, const LdsimLutBuildParams* params, const LdsimLutDetector* detectors, int32_t ndet,
+                          int32_t nx, int32_t ny, int32_t nz, int64_t voxel, int64_t photon_begin, int64_t photon_end,
+                          uint64_t seed, int32_t* fate, int32_t* steps, double* time, double* end);
+int ldsim_light_lut_build_ms(ldsim_ctx* ctx, double* ms);
+
 /* ---- multi-GPU: the one exchange step of the batch-sharded path, RCCL over xGMI -------------------------------
  * One process per GPU; (event, TPC-group) batches are sharded over the ranks and never share a pixel, so the only
  * collective reassembles the output: row counts (all-gather), then the 24-byte hit rows (all-gather-v). */

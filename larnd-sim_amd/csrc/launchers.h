@@ -17,6 +17,14 @@ int seg_launch_get_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int radius, int3
                           int32_t* nrad, int P, double* n_list, const int32_t* radius_b, int32_t batch0);
 int seg_launch_time_intervals(ldsim_ctx* ctx, int64_t b, int64_t e, double* starts, int32_t* tmax);
 
+// ---- kernels_lutbuild.hip (the entry points of ldsim_abi.hip hand their arguments through) ----------------------------------
+int lutbuild_build(ldsim_ctx* ctx, const LdsimLutBuildParams* P, const LdsimLutDetector* dets, int32_t ndet, int32_t nx,
+                   int32_t ny, int32_t nz, int64_t voxel_begin, int64_t voxel_end, int64_t n_photons, uint64_t seed,
+                   uint32_t* counts, uint32_t* hist, float* tmin, uint64_t* tsum, uint64_t* fates);
+int lutbuild_trace(ldsim_ctx* ctx, const LdsimLutBuildParams* P, const LdsimLutDetector* dets, int32_t ndet, int32_t nx,
+                   int32_t ny, int32_t nz, int64_t voxel, int64_t photon_begin, int64_t photon_end, uint64_t seed, int32_t* fate,
+                   int32_t* steps, double* time, double* end);
+
 // ---- sort.hip ----------------------------------------------------------------------------------------------------------
 int sort_make_keys(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
                    int64_t n_entries, unsigned long long* keys, int32_t* vals, unsigned long long* counters);

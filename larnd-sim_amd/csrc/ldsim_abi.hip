@@ -218,6 +218,14 @@ extern "C" int ldsim_set_option(ldsim_ctx* ctx, const char* name, double value) 
     if (!(value == 1 || value == 2 || value == 3 || value == 4)) { ldsim_set_error("light_universes_nu must be 1, 2, 3 or 4"); return LDSIM_EINVAL; }
     ctx->lu_nu = (int)value;
   }
+  else if (!strcmp(name, "lut_build_group_photons")) {
+    if (!(value >= 64 && value <= 1048576 && value == (double)(int)value)) { ldsim_set_error("lut_build_group_photons must be an integer in [64, 1048576]"); return LDSIM_EINVAL; }
+    ctx->lb_group = (int)value;
+  }
+  else if (!strcmp(name, "lut_build_lds_tile")) {
+    if (!(value == 0 || value == 1)) { ldsim_set_error("lut_build_lds_tile must be 0 or 1"); return LDSIM_EINVAL; }
+    ctx->lb_tile = (int)value;
+  }
   else if (!strcmp(name, "light_sum_no_list")) ctx->light_sum_no_list = value != 0;
   else if (!strcmp(name, "light_sum_async")) {
     CK(light_join(ctx));
@@ -647,6 +655,32 @@ extern "C" int ldsim_get_sipm_noise(ldsim_ctx* ctx, int32_t* enable, LdsimSipmNo
   NEED(ctx, "null ctx");
   if (enable) *enable = ctx->sipm_on;
   if (noise) *noise = ctx->sipm;
+  return 0;
+}
+
+// ---- light LUT builder (kernels_lutbuild.hip) ------------------------------------------------------------------------------
+extern "C" int ldsim_light_lut_build(ldsim_ctx* ctx, const LdsimLutBuildParams* params, const LdsimLutDetector* detectors,
+                                     int32_t ndet, int32_t nx, int32_t ny, int32_t nz, int64_t voxel_begin, int64_t voxel_end,
+                                     int64_t n_photons, uint64_t seed, uint32_t* counts, uint32_t* hist, float* tmin,
+                                     uint64_t* tsum, uint64_t* fates) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return lutbuild_build(ctx, params, detectors, ndet, nx, ny, nz, voxel_begin, voxel_end, n_photons, seed, counts, hist, tmin,
+                        tsum, fates);
+}
+
+extern "C" int ldsim_light_lut_trace(ldsim_ctx* ctx, const LdsimLutBuildParams* params, const LdsimLutDetector* detectors,
+                                     int32_t ndet, int32_t nx, int32_t ny, int32_t nz, int64_t voxel, int64_t photon_begin,
+                                     int64_t photon_end, uint64_t seed, int32_t* fate, int32_t* steps, double* time, double* end) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return lutbuild_trace(ctx, params, detectors, ndet, nx, ny, nz, voxel, photon_begin, photon_end, seed, fate, steps, time, end);
+}
+
+extern "C" int ldsim_light_lut_build_ms(ldsim_ctx* ctx, double* ms) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && ms, "null argument");
+  *ms = ctx->ms_lb;
   return 0;
 }
 

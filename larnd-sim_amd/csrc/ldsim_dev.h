@@ -378,6 +378,15 @@ struct ldsim_ctx {
   int lu_nu = 4;                 // option light_universes_nu: tables per launch of light_conv_universes_kernel (1: light_conv_kernel per table)
   Event lu_ev[4];                // around the scintillation, fluctuation and response stages of the last pass
   double ms_lu[3] = {0, 0, 0};
+  // light LUT builder (ldsim_light_lut_build / _trace, kernels_lutbuild.hip): staged rectangles, the tallies of the last build's
+  // voxel range, the last trace's photons
+  DevBuf lb_dets;                // LutRect [ndet] grouped by wall | i32 [ndet] their indices in the caller's list
+  DevBuf lb_counts, lb_hist, lb_tmin, lb_tsum, lb_fates;   // u32 [nv][ndet] | u32 [nv][ndet][nprof] | f32 bits [nv][ndet] | u64 [nv][ndet] | u64 [nv][3]
+  DevBuf lb_trace;               // fate i32 [n] | steps i32 [n] | time f64 [n] | end f64 [n][3]
+  int lb_group = 4096;           // option lut_build_group_photons: photons a workgroup walks
+  int lb_tile = 1;               // option lut_build_lds_tile: 0 sends every arrival to global atomics (the path of a tile too big for LDS)
+  Event lb_ev[2];                // around lut_build_kernel of the last build (ldsim_light_lut_build_ms)
+  double ms_lb = 0;
   // random streams (kernels_rng.hip): numba-style table of xoroshiro128p states, grown on demand
   DevBuf d_rng;
   int64_t rng_n = 0;

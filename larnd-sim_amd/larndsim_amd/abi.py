@@ -82,6 +82,20 @@ class LdsimSipmNoise(C.Structure):
     _fields_ = [("crosstalk", C.c_double), ("afterpulse", C.c_double), ("afterpulse_tau", C.c_double), ("dark_rate", C.c_double)]
 
 
+class LdsimLutBuildParams(C.Structure):
+    """include/ldsim.h LdsimLutBuildParams (ldsim_light_lut_build): 112 bytes"""
+    _fields_ = [("box", C.c_double * 3), ("rayleigh_cm", C.c_double), ("absorption_cm", C.c_double),
+                ("group_velocity_cm_ns", C.c_double), ("wall_reflectivity", C.c_double * 6), ("emit_mode", C.c_int32),
+                ("max_steps", C.c_int32), ("nprof", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LdsimLutDetector(C.Structure):
+    """include/ldsim.h LdsimLutDetector: 40 bytes; wall 0..5 = u0 u1 v0 v1 w0 w1, lo / hi in the wall's in-plane coordinates"""
+    _fields_ = [("wall", C.c_int32), ("pad", C.c_int32), ("lo", C.c_double * 2), ("hi", C.c_double * 2)]
+
+
+LUT_MAX_DETECTORS = 1024    # include/ldsim.h LDSIM_LUT_MAX_DETECTORS
+LUT_MAX_NPROF = 512         # include/ldsim.h LDSIM_LUT_MAX_NPROF
 FEE_UNIVERSES_MAX = 64      # include/ldsim.h LDSIM_FEE_UNIVERSES_MAX
 LIGHT_UNIVERSES_MAX = 64    # include/ldsim.h LDSIM_LIGHT_UNIVERSES_MAX
 

@@ -51,7 +51,33 @@ def maybe_create_rng_states(n, seed=0, rng_states=None, ctx=None):
 # numbers at any chunking, rank count or event subset.
 MASK64 = (1 << 64) - 1
 KEY_ROOT = 0x6A09E667F3BCC909
-TAG_FEE, TAG_LIGHT_FLUCT, TAG_LIGHT_NOISE, TAG_MC, TAG_CHARGE = 1, 2, 3, 4, 5
+TAG_FEE, TAG_LIGHT_FLUCT, TAG_LIGHT_NOISE, TAG_MC, TAG_CHARGE, TAG_LUT = 1, 2, 3, 4, 5, 6
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 in numpy (csrc/rng.h philox4x32_10): ctr [..][4], key [..][2] -> [..][4] uint32"""
+    c = [np.asarray(ctr, dtype=np.uint64)[..., i].copy() for i in range(4)]
+    k0 = np.asarray(key, dtype=np.uint64)[..., 0].copy()
+    k1 = np.asarray(key, dtype=np.uint64)[..., 1].copy()
+    m32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & m32, p1 & m32, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & m32, p0 & m32]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & m32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & m32
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def keyed_block_uniforms(seed, tag, keys, m):
+    """the four uniforms of Philox block ``m`` of each keyed stream (draws 4m .. 4m + 3; csrc/rng.h keyed_block, keyed_u01),
+    [..][4] float32 in (0, 1], on the host"""
+    keys, m = np.broadcast_arrays(np.asarray(keys, dtype=np.uint64), np.asarray(m, dtype=np.uint64))
+    seed = int(seed) & MASK64
+    ctr = np.stack([m, keys & np.uint64(0xFFFFFFFF), keys >> np.uint64(32), np.full(keys.shape, tag, dtype=np.uint64)], -1)
+    key = np.broadcast_to(np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64), keys.shape + (2,))
+    x = philox4x32_10(ctr, key)
+    return ((x >> np.uint32(8)) + np.uint32(1)).astype(np.float32) * np.float32(2.0 ** -24)
 
 
 def _fin(z):
