@@ -175,11 +175,12 @@ int ldsim_set_light_lut(ldsim_ctx* ctx, const float* vis, const float* t0, const
  * writes what they read -- segment upload / reset / quench-drift, incidence, LUT, channel tables, constants -- or reads their array
  * -- ldsim_dev_light_download, ldsim_dev_light_response, ldsim_synchronize -- waits for them first; default 0),
  * "light_truth_lds" (the truth slots of ldsim_scintillation_effect / ldsim_light_detector_response / ldsim_dev_light_response, at most
- * 64 of them: 1 (default) = by light_truth_lds_kernel, a wave's 64 output rows in LDS beside the plain sum; 0 = inside light_conv_kernel
- * on slot-major copies of the rows in memory -- same bits for rows of distinct ids in front of their first -1, and the only path
- * that follows light_sim.py:331-335 literally for other rows is the default),
- * "light_universes_nu" (ldsim_dev_light_universes: weight tables that share an input go through light_conv_universes_kernel
- * this many at a time, 2, 3 or 4 (default); 1 = one light_conv_kernel launch per table; same bits at every value),
+ * 64 of them: 1 (default) = by light_truth_lds_kernel, a wave's 64 output rows in LDS; 0 = by light_truth_rows_kernel on slot-major
+ * copies of the rows in memory, what more than 64 slots always take -- same bits for rows of distinct ids in front of their first
+ * -1, and the only path that follows light_sim.py:331-335 literally for other rows is the default; the plain sum is
+ * light_plain_kernel's at either value),
+ * "light_universes_nu" (ldsim_dev_light_universes: weight tables that share an input go through light_plain_kernel this many at
+ * a time, 1 to 4 (default 4); same bits at every value),
  * "numba_f32" (1 = the sub-expressions Numba types float32 for f4 record fields are evaluated in float, detsim.py:74-79,
  * 116-118,141,387; 0 = all-f64, what the reference computes for f8 records and what the goldens pin; default 0),
  * "mc_current" (1 = the fused chain takes its induced currents from tracks_current_mc like the reference driver does;
@@ -810,7 +811,7 @@ int ldsim_light_response_ms(ldsim_ctx* ctx, double* scint_ms, double* fluct_ms, 
  * before anything is touched, the message naming the universe and the field (LDSIM_EINVAL); a refused call leaves the earlier
  * result in place.  Universes with byte-equal photon_scale share one input; within it equal (singlet_fraction, tau_s, tau_t)
  * share one scint and one disc; per disc equal (gain_scale, response_time, oscillation_period) share one response: no stage
- * runs twice on the same input with the same table, and tables that share an input go through light_conv_universes_kernel
+ * runs twice on the same input with the same table, and tables that share an input go through light_plain_kernel
  * together.  resp_k stays resident for every k, scint_k and disc_k only with keep_stages != 0.  The launch's own arrays
  * (ldsim_dev_light_response), its truth arrays and the call key are left as they were.  The result is invalidated by the next
  * ldsim_dev_sum_light, ldsim_dev_light_response, ldsim_segments_upload and ldsim_segments_reset.

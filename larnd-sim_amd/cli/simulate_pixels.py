@@ -1336,17 +1336,21 @@ def main(argv=None):
         # CPU rehearsal of the launch path (tests/test_cpu_multirank.py): the ranks meet over the ncclUniqueId hand-out and stop
         # before anything touches a GPU; LDSIM_CLI_REHEARSAL_FAIL_RANK=r makes rank r exit non-zero before the rendezvous
         from larndsim_amd import comm as lcomm
-        print(f"rehearsal: rank {rank} of {world} started (pid {os.getpid()})", flush=True)
+
+        def say(line):          # (the ranks share the launcher's stdout and print together: line and newline in one write, or an
+            print(line + "\n", end="", flush=True)          # unbuffered stdout lets the other rank's line in between)
+
+        say(f"rehearsal: rank {rank} of {world} started (pid {os.getpid()})")
         if a["field_map"] is not None:
-            print(f"rehearsal: rank {rank} field_map {a['field_map']}", flush=True)
+            say(f"rehearsal: rank {rank} field_map {a['field_map']}")
         if a["light_lut_interpolation"] != "nearest":
-            print(f"rehearsal: rank {rank} light_lut_interpolation {a['light_lut_interpolation']}", flush=True)
+            say(f"rehearsal: rank {rank} light_lut_interpolation {a['light_lut_interpolation']}")
         if os.environ.get("LDSIM_CLI_REHEARSAL_FAIL_RANK") == str(rank):
             raise SystemExit(f"rank {rank}: asked to fail (test of the launcher's error path)")
         got = lcomm.exchange_id(bytes(range(128)) if rank == 0 else b"", rank, world, timeout=120.0)
         if got != bytes(range(128)):
             raise SystemExit(f"rank {rank}: rendezvous payload differs")
-        print(f"rehearsal: rank {rank} of {world} met", flush=True)
+        say(f"rehearsal: rank {rank} of {world} met")
         return
     run_simulation(**a)
 

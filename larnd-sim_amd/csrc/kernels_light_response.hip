@@ -6,26 +6,194 @@
 // term -- the f4 store after every term, in ascending j, is part of the result and is kept.  w depends on i-j only, so the
 // host tabulates it once per call with the reference's expressions (ldsim_abi.hip) and the kernels never call exp/sin.
 //
-// One thread per (row, tick), a workgroup = 256 consecutive ticks of one row.  The j range of the workgroup is walked in
-// chunks of JCHUNK: the chunk of x and the weights it can meet are staged in LDS; inside a chunk all lanes read the same
-// x[j] (broadcast) and consecutive weights (conflict-free).  Truth slots (optional) follow the reference literally; a
-// per-tick bound on the slots' photons (light_truth_max_kernel) lets a pair (i, j) skip its slot walk when none can pass.
+// The file, in order:
+//   * light_plain_kernel<RESPONSE, NU, ACCUMULATE>: the f4 sum itself and the only code that forms it -- for the launch and the stage API
+//     (NU = 1, accumulating into the caller's `out`) and for the light universes (up to four weight tables over one input row);
+//   * light_truth_rows_kernel<RESPONSE>: the optional truth slots on the rows in memory, literally -- more than 64 slots, or
+//     option light_truth_lds 0;
+//   * light_truth_lds_kernel<RESPONSE>: the truth slots with a wave's 64 output rows in LDS (at most 64 slots, the default);
+//   * the host side: light_plain_launch (widen pass, tables NU at a time), light_response_launch = the plain sum, then the truth
+//     rows by one of the two truth kernels.
+// The plain and the rows-in-memory kernels share a geometry: one thread per (row, tick), a workgroup = 256 consecutive ticks of
+// one row.  The j range of the workgroup is walked in chunks of JCHUNK: the chunk of x and the weights it can meet are staged in
+// LDS; inside a chunk all lanes read the same x[j] (broadcast) and consecutive weights (conflict-free).
 #include "launchers.h"
 #include "wave_ops.h"
 
 #define LR_THREADS 256
 #define JCHUNK 1024
 
-template <bool RESPONSE>
-__global__ void __launch_bounds__(LR_THREADS) light_conv_kernel(
-    const float* __restrict__ inc, const int64_t* __restrict__ tid, const double* __restrict__ tph, int D, int T, int Mt,
-    const double* __restrict__ weights /* [C+1] */, int C, const double* __restrict__ gain /* [D] or NULL */,
-    double truth_threshold, float* __restrict__ out, int64_t* __restrict__ out_tid /* [D][Mt][T]: slot-major working copy */,
-    double* __restrict__ out_tph /* [D][Mt][T] */,
-    const double* __restrict__ truth_max /* [D][T]: light_truth_max_kernel, or NULL when Mt == 0 */,
-    const int64_t* __restrict__ tid_sm /* RESPONSE: the input ids slot-major, [D][Mt][T] (read at the OUTPUT tick) */,
+// ---- the plain sum: NU weight tables (1 .. 4) over one shared input row ----------------------------------------------------------
+// The chunk of the input row is staged once (f4 for the ballot and the bit-scan form, doubles for the unrolled blocks), each table
+// has its own weight tile in LDS and each thread NU f4 accumulators, every one updated in ascending j as
+// acc = (float)((double)acc + w * x), so output u is the same bits whatever NU it is computed under.  The non-zero ballot, the
+// sample fetch and the block bookkeeping are paid once per block for all NU tables, and the NU dependent cvt -> mul -> add -> cvt
+// chains of a term interleave.  RESPONSE (the SiPM stage): the weights are staged as gain_u[d] * w_u, the product the reference
+// forms first (:320); zero samples are skipped in the scintillation stage only (:166).
+template <int NU>
+struct LightPlainArgs {
+  const double* w[NU];          // [C + 1]
+  const double* gain[NU];       // [D] (RESPONSE)
+  float* out[NU];               // [D][T]
+};
+
+// eight consecutive input ticks for all NU tables: weight of tick e at s_w[u][wo - e]; per table the sums stay in ascending-tick order
+template <int NU>
+__device__ __forceinline__ void light_plain_terms8(float (&acc)[NU], const double (*s_w)[JCHUNK + LR_THREADS], int wo,
+                                                   const double (&x8)[8]) {
+  double w8[NU][8];
+#pragma unroll
+  for (int u = 0; u < NU; u++)
+#pragma unroll
+    for (int e = 0; e < 8; e++) w8[u][e] = s_w[u][wo - e];
+#pragma unroll
+  for (int e = 0; e < 8; e++)
+#pragma unroll
+    for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + w8[u][e] * x8[e]);
+}
+
+// ACCUMULATE: start from what `out` holds (the launch, the stage API; NU = 1 only) or from zero without reading it (the universes' pools)
+template <bool RESPONSE, int NU, bool ACCUMULATE>
+__global__ void __launch_bounds__(LR_THREADS) light_plain_kernel(
+    const float* __restrict__ inc, int D, int T, int C, LightPlainArgs<NU> A,
     const double* __restrict__ inc_f64 /* [D][T]: `inc` widened (light_widen_kernel), or NULL */) {
+  static_assert(NU == 1 || !ACCUMULATE, "light_plain_launch accumulates table by table");
   __shared__ float s_x[JCHUNK];
+  __shared__ double s_xd[JCHUNK];
+  __shared__ double s_w[NU][JCHUNK + LR_THREADS];
+  const int d = blockIdx.y;
+  const int i0 = blockIdx.x * LR_THREADS;
+  const int i = i0 + threadIdx.x;
+  const bool live = i < T;
+  const int i_last = min(i0 + LR_THREADS, T) - 1;          // last tick of this workgroup
+  const int j_begin = max(i0 - C, 0);                       // first j any of its ticks can reach
+  const float* x = inc + (int64_t)d * T;
+  const int my_j0 = max(i - C, 0);
+  float acc[NU];
+  double g[NU];
+#pragma unroll
+  for (int u = 0; u < NU; u++) {
+    acc[u] = (ACCUMULATE && live) ? A.out[u][(int64_t)d * T + i] : 0.f;
+    g[u] = RESPONSE ? A.gain[u][d] : 1.0;
+  }
+  // One j loop for the whole wave (a thread's own range [i - C, i] is a predicate), the chunk walked 64 input ticks at a time: lane l
+  // fetches the sample of tick jb + l once, the loops over the 64 ticks take it from there with v_readlane (three LDS reads per term
+  // were what the plain convolution ran at: the LDS, shared by the CU's four SIMDs, was its limit), and which ticks are zero is a
+  // ballot -- a block of zeros skips the wave as a whole.
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int jc = j_begin; jc <= i_last; jc += JCHUNK) {
+    const int nj = min(JCHUNK, i_last - jc + 1);
+    // weights this chunk can meet: n = i - j in [i0 - (jc + nj - 1), i_last - jc], at most LR_THREADS + JCHUNK - 1 of them
+    const int n_lo = max(i0 - (jc + nj - 1), 0), n_hi = min(i_last - jc, C);
+    __syncthreads();
+    for (int k = threadIdx.x; k < nj; k += LR_THREADS) {
+      const float xv = x[jc + k];
+      s_x[k] = xv;
+      s_xd[k] = (double)xv;
+    }
+#pragma unroll
+    for (int u = 0; u < NU; u++)
+      for (int k = threadIdx.x; k <= n_hi - n_lo; k += LR_THREADS) s_w[u][k] = RESPONSE ? g[u] * A.w[u][n_lo + k] : A.w[u][n_lo + k];
+    __syncthreads();
+    for (int jb = jc; jb <= jc + nj - 1; jb += 64) {
+      const int nb64 = min(64, jc + nj - jb);
+      const float x_l = lane < nb64 ? s_x[jb - jc + lane] : 0.f;
+      const unsigned long long m_nz = RESPONSE ? ~0ull : __ballot(x_l != 0.f);
+      unsigned long long todo = (nb64 == 64 ? ~0ull : ((1ull << nb64) - 1ull)) & m_nz;
+      const int w_i0 = i0 + (wv << 6);
+      const bool inside = w_i0 + 63 < T && jb >= max(w_i0 + 63 - C, 0) && jb + nb64 - 1 <= w_i0;
+      if (inside) {          // a block inside every lane's own range [i - C, i] (most blocks): the bare convolution, no predicate
+        const int wo = (i - jb) - n_lo;          // weight of tick jb + t: s_w[u][wo - t]
+        if (todo == ~0ull) {
+          // all 64 ticks of the block (the SiPM stage, and lit stretches of the scintillation stage): lane numbers and weight
+          // offsets are constants -- no bit scan, no address arithmetic per term; what is left is the sample, the weight and the
+          // three dependent operations of the f4 sum (5-6 instructions per term instead of ~12).  Eight ticks at a time; NU = 1
+          // unrolls the loop over them, NU >= 2 keeps it rolled: unrolled over all 64 the NU x 64 weight reads are hoisted in front
+          // of the sums and the kernel runs out of registers (512 at NU = 2, scratch at NU = 4).
+          constexpr int unroll8 = NU == 1 ? 8 : 1;
+          // the sample arrives as a double -- no v_cvt_f64_f32 per term (the conversions are the slow instructions of the term: with
+          // it gone the SiPM stage of a 2x2 batch runs 15.6 -> 11.8 ms).  With a widened copy (the SiPM stage: every block is of
+          // this kind) from memory at a wave-uniform address: scalar loads, eight doubles per request straight into scalar
+          // registers -- no vector instruction and no LDS read for the sample.  Without one, SiPM stage: lane t holds tick jb + t's
+          // sample widened once, two v_readlane per term; from LDS by a broadcast read instead the stage is bound by the LDS (13.5
+          // ms: two 8-byte reads per term and lane).  Scintillation stage (few such blocks): the broadcast read, 1.82 against 1.91 ms.
+          const double* xd = s_xd + (jb - jc);
+          const double xd_l = (double)x_l;
+          if (inc_f64) {
+            const double* xg = inc_f64 + (int64_t)d * T + jb;
+#pragma unroll unroll8
+            for (int t8 = 0; t8 < 64; t8 += 8) {
+              double x8[8];
+#pragma unroll
+              for (int e = 0; e < 8; e++) x8[e] = xg[t8 + e];
+              light_plain_terms8<NU>(acc, s_w, wo - t8, x8);
+            }
+          } else {
+#pragma unroll unroll8
+            for (int t8 = 0; t8 < 64; t8 += 8) {
+              double x8[8];
+#pragma unroll
+              for (int e = 0; e < 8; e++) x8[e] = RESPONSE ? wave_lane_f64(xd_l, t8 + e) : xd[t8 + e];
+              light_plain_terms8<NU>(acc, s_w, wo - t8, x8);
+            }
+          }
+          continue;
+        }
+        for (; todo; todo &= todo - 1) {          // the ticks that are not zero, by bit scan
+          const int t = __ffsll((long long)todo) - 1;
+          const double xv = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
+#pragma unroll
+          for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + s_w[u][wo - t] * xv);
+        }
+        continue;
+      }
+      for (; todo; todo &= todo - 1) {          // a block at the edge of some lane's range: the same under the lane's predicate
+        const int t = __ffsll((long long)todo) - 1;
+        const int j = jb + t;
+        const double xv = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
+        if (live && j >= my_j0 && j <= i) {
+#pragma unroll
+          for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + s_w[u][(i - j) - n_lo] * xv);          // :169, :320
+        }
+      }
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int u = 0; u < NU; u++) A.out[u][(int64_t)d * T + i] = acc[u];
+  }
+}
+
+// x_k = (float)((double)x * scale): one rounding (exact at scale 1.0, which the host does not launch)
+__global__ void light_scale_kernel(const float* __restrict__ x, int64_t n, double scale, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) out[e] = (float)((double)x[e] * scale);
+}
+
+int light_universes_scale(ldsim_ctx* ctx, const float* x, int64_t n, double scale, float* out) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(light_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x, n, scale, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+__global__ void light_widen_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ xd) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) xd[e] = (double)x[e];
+}
+
+// ---- the truth slots on the rows in memory (more than 64 slots, or option light_truth_lds 0) -------------------------------------
+// The truth rows of a stage (Mt > 0 slots), following the reference literally (light_sim.py:171-184 / :323-337) over the pairs
+// (i, j) light_plain_kernel sums; the plain sum itself is not formed here.  A per-tick bound on the slots' photons
+// (light_truth_max_kernel) lets a pair skip its slot walk when none can pass.
+template <bool RESPONSE>
+__global__ void __launch_bounds__(LR_THREADS) light_truth_rows_kernel(
+    const float* __restrict__ inc, const int64_t* __restrict__ tid, const double* __restrict__ tph, int D, int T, int Mt,
+    const double* __restrict__ weights /* [C+1] */, int C, double truth_threshold,
+    int64_t* __restrict__ out_tid /* [D][Mt][T]: slot-major working copy */, double* __restrict__ out_tph /* [D][Mt][T] */,
+    const double* __restrict__ truth_max /* [D][T]: light_truth_max_kernel */,
+    const int64_t* __restrict__ tid_sm /* RESPONSE: the input ids slot-major, [D][Mt][T] (read at the OUTPUT tick) */) {
+  __shared__ float s_x[JCHUNK];          // (scintillation stage: a zero sample skips its truth, :166)
   __shared__ double s_w[JCHUNK + LR_THREADS];
   // largest photon count (RESPONSE: magnitude) among the filled truth slots of input tick j, -1 when it has none: a pair
   // (i, j) whose weight times this stays below the threshold cannot pass the per-slot test (rounding is monotone), so its
@@ -40,8 +208,6 @@ __global__ void __launch_bounds__(LR_THREADS) light_conv_kernel(
   const int i_last = min(i0 + LR_THREADS, T) - 1;          // last tick of this workgroup
   const int j_begin = max(i0 - C, 0);                       // first j any of its ticks can reach
   const float* x = inc + (int64_t)d * T;
-  float acc = live ? out[(int64_t)d * T + i] : 0.f;
-  const double g = RESPONSE ? gain[d] : 1.0;
   const int my_j0 = max(i - C, 0);
   // the output's truth rows live slot-major while the kernel works ([detector][slot][tick]: the wave's 64 ticks of one slot are
   // one 512-byte run; in the reference's [detector][tick][slot] every lane's row is 8 Mt bytes from its neighbour's and each
@@ -64,7 +230,7 @@ __global__ void __launch_bounds__(LR_THREADS) light_conv_kernel(
     word_sel = (h >> 62);
     return 1ull << ((h >> 56) & 63ull);
   };
-  if (!RESPONSE && Mt > 0 && live) {
+  if (!RESPONSE && live) {
     prefix_ok = true;
     bool seen_empty = false;
     for (int b = 0; b < Mt; b++) {
@@ -79,7 +245,7 @@ __global__ void __launch_bounds__(LR_THREADS) light_conv_kernel(
   }
   int row_f = Mt;
   bool row_unique = false;
-  if (RESPONSE && Mt > 0 && live) {
+  if (RESPONSE && live) {
     for (int b = 0; b < Mt; b++)
       if (tid_sm[O(b)] == -1) { row_f = b; break; }
     row_unique = true;
@@ -97,206 +263,126 @@ __global__ void __launch_bounds__(LR_THREADS) light_conv_kernel(
     __syncthreads();
     for (int k = threadIdx.x; k < nj; k += LR_THREADS) {
       s_x[k] = x[jc + k];
-      // (without truth slots the bound's place holds the samples as doubles: the unrolled blocks below read them from there)
-      s_tmax[k] = Mt > 0 ? truth_max[(int64_t)d * T + jc + k] : (double)x[jc + k];
+      s_tmax[k] = truth_max[(int64_t)d * T + jc + k];
     }
-    // (SiPM stage without truth slots: the weights staged as LIGHT_GAIN[row] * w, the product the reference forms first, :320)
-    const bool premul = RESPONSE && Mt <= 0;
-    for (int k = threadIdx.x; k <= n_hi - n_lo; k += LR_THREADS) s_w[k] = premul ? g * weights[n_lo + k] : weights[n_lo + k];
+    for (int k = threadIdx.x; k <= n_hi - n_lo; k += LR_THREADS) s_w[k] = weights[n_lo + k];
     __syncthreads();
-    // One j loop for the whole wave (a thread's own range [i - C, i] is a predicate): the input tick's sample and bound are
-    // broadcast LDS reads, a zero sample or a tick without truth skips the wave as a whole, and when some lane's product can
-    // pass the threshold the wave stages the tick's <= 64 truth slots in LDS with one coalesced read -- the walk over them
-    // (the bulk of the truth leg: one dependent L2 round trip per slot and pair before) then runs on LDS broadcasts.
-    // The chunk is walked 64 input ticks at a time: lane l fetches sample and bound of tick jb + l once, the loop over the 64 ticks
-    // takes them from there with v_readlane (three LDS reads per term were what the plain convolution ran at: the LDS, shared by
-    // the CU's four SIMDs, was its limit), and which ticks are zero / without truth is two ballots.
+    // One j loop for the whole wave (a thread's own range [i - C, i] is a predicate), like light_plain_kernel's: lane l fetches
+    // sample and bound of tick jb + l once, which ticks are zero / without truth is two ballots (either skips the wave as a whole),
+    // and when some lane's product can pass the threshold the wave stages the tick's <= 64 truth slots in LDS with one coalesced
+    // read -- the walk over them (the bulk of the truth leg: one dependent L2 round trip per slot and pair before) then runs on LDS
+    // broadcasts.
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int jb = jc; jb <= jc + nj - 1; jb += 64) {
       const int nb64 = min(64, jc + nj - jb);
       const float x_l = lane < nb64 ? s_x[jb - jc + lane] : 0.f;
-      const double t_l = (Mt > 0 && lane < nb64) ? s_tmax[jb - jc + lane] : -1.0;
+      const double t_l = lane < nb64 ? s_tmax[jb - jc + lane] : -1.0;
       const unsigned long long m_nz = RESPONSE ? ~0ull : __ballot(x_l != 0.f);
       const unsigned long long m_truth = __ballot(t_l >= 0.0);
-      unsigned long long todo = (nb64 == 64 ? ~0ull : ((1ull << nb64) - 1ull)) & m_nz;
-      // a block inside every lane's own range [i - C, i] (most blocks) and without truth: the bare convolution, no predicate
-      const int w_i0 = i0 + (wv << 6);
-      const bool inside = w_i0 + 63 < T && jb >= max(w_i0 + 63 - C, 0) && jb + nb64 - 1 <= w_i0;
-      if (inside && !m_truth) {
-        const double* wl = s_w + (i - jb) - n_lo;
-        if (todo == ~0ull) {
-          // all 64 ticks of the block (the SiPM stage, and lit stretches of the scintillation stage): lane numbers and weight
-          // offsets are constants -- no bit scan, no address arithmetic per term; what is left is the sample, the weight and the
-          // three dependent operations of the f4 sum (5-6 instructions per term instead of ~12)
-          if (Mt <= 0) {
-            // the sample arrives as a double -- no v_cvt_f64_f32 per term (the conversions are the slow instructions of the term: with
-            // it gone the SiPM stage of a 2x2 batch runs 15.6 -> 11.8 ms).  SiPM stage (every block is of this kind): lane t holds
-            // tick jb + t's sample widened once, two v_readlane per term; from LDS by a broadcast read instead the stage is bound by
-            // the LDS (13.5 ms: two 8-byte reads per term and lane).  Scintillation stage (few such blocks): the broadcast read,
-            // 1.82 against 1.91 ms.
-            const double* xd = s_tmax + (jb - jc);
-            const double xd_l = (double)x_l;
-            if (inc_f64) {
-              // (the widened samples from memory at a wave-uniform address: scalar loads, eight doubles per request straight into
-              // scalar registers -- no vector instruction and no LDS read for the sample)
-              const double* xg = inc_f64 + (int64_t)d * T + jb;
-#pragma unroll
-              for (int t8 = 0; t8 < 64; t8 += 8) {
-                double w8[8], x8[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) w8[u] = wl[-(t8 + u)];
-#pragma unroll
-                for (int u = 0; u < 8; u++) x8[u] = xg[t8 + u];
-#pragma unroll
-                for (int u = 0; u < 8; u++) acc = (float)((double)acc + w8[u] * x8[u]);
-              }
-              continue;
-            }
-#pragma unroll
-            for (int t8 = 0; t8 < 64; t8 += 8) {
-              double w8[8], x8[8];
-#pragma unroll
-              for (int u = 0; u < 8; u++) w8[u] = wl[-(t8 + u)];
-#pragma unroll
-              for (int u = 0; u < 8; u++) x8[u] = RESPONSE ? wave_lane_f64(xd_l, t8 + u) : xd[t8 + u];
-#pragma unroll
-              for (int u = 0; u < 8; u++) acc = (float)((double)acc + w8[u] * x8[u]);
-            }
-            continue;
+      unsigned long long todo = (nb64 == 64 ? ~0ull : ((1ull << nb64) - 1ull)) & m_nz & m_truth;
+      for (; todo; todo &= todo - 1) {
+        const int t = __ffsll((long long)todo) - 1;
+        const int j = jb + t;
+        const bool mine = live && j >= my_j0 && j <= i;
+        const double w = mine ? s_w[(i - j) - n_lo] : 0.0;
+        const double bound = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t_l), t), __builtin_amdgcn_readlane(__double2loint(t_l), t));
+        const bool walk = mine && !(RESPONSE ? (fabs(w) * bound < truth_threshold) : (w >= 0.0 && w * bound < truth_threshold));
+        if (!__ballot(walk)) continue;
+        const int64_t src = ((int64_t)d * T + j) * Mt;
+        const bool staged = Mt <= 64;
+        // the slots some lane's product can pass on: lane a holds slot a while it stages it, so with the largest weight among the
+        // walking lanes this is one ballot -- the walk visits those slots only, in ascending order, instead of all filled ones
+        unsigned long long cand = ~0ull;
+        if (staged) {
+          __builtin_amdgcn_wave_barrier();
+          int64_t my_id = -1;
+          double my_ph = 0.0;
+          if (lane < Mt) {
+            my_id = tid[src + lane];
+            my_ph = tph[src + lane];
+            s_sid[wv][lane] = my_id;
+            s_sph[wv][lane] = my_ph;
           }
-#pragma unroll
-          for (int t8 = 0; t8 < 64; t8 += 8) {
-            double w8[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) w8[u] = wl[-(t8 + u)];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-              const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t8 + u));
-              if (RESPONSE && !premul) acc = (float)((double)acc + g * w8[u] * (double)xv);
-              else acc = (float)((double)acc + w8[u] * (double)xv);
-            }
-          }
-          continue;
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          const unsigned long long empty = __ballot(lane < Mt && my_id == -1);
+          const int nfill = empty ? __ffsll((long long)empty) - 1 : Mt;          // (the walk stops at the first empty slot)
+          const double wmax = wave_max_f64(walk ? fabs(w) : 0.0);
+          if (RESPONSE) cand = __ballot(lane < nfill && !(wmax * fabs(my_ph) < truth_threshold));
+          else if (__ballot(walk && w < 0.0)) cand = nfill >= 64 ? ~0ull : ((1ull << nfill) - 1ull);
+          else cand = __ballot(lane < nfill && !(my_ph >= 0.0 ? wmax * my_ph < truth_threshold : truth_threshold > 0.0));
         }
-        for (; todo; todo &= todo - 1) {
-          const int t = __ffsll((long long)todo) - 1;
-          const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
-          const double w = wl[-t];
-          if (RESPONSE && !premul) acc = (float)((double)acc + g * w * (double)xv);
-          else acc = (float)((double)acc + w * (double)xv);
-        }
-        continue;
-      }
-    for (; todo; todo &= todo - 1) {
-      const int t = __ffsll((long long)todo) - 1;
-      const int j = jb + t;
-      const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
-      const bool mine = live && j >= my_j0 && j <= i;
-      const double w = mine ? s_w[(i - j) - n_lo] : 0.0;
-      if (mine) {
-        if (RESPONSE && !premul) acc = (float)((double)acc + g * w * (double)xv);          // :320  LIGHT_GAIN[idet] * tick_weight * x
-        else acc = (float)((double)acc + w * (double)xv);                       // :169 (and :320 with the gain already in w)
-      }
-      if (!((m_truth >> t) & 1ull)) continue;
-      const double bound = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t_l), t), __builtin_amdgcn_readlane(__double2loint(t_l), t));
-      const bool walk = mine && !(RESPONSE ? (fabs(w) * bound < truth_threshold) : (w >= 0.0 && w * bound < truth_threshold));
-      if (!__ballot(walk)) continue;
-      const int64_t src = ((int64_t)d * T + j) * Mt;
-      const bool staged = Mt <= 64;
-      // the slots some lane's product can pass on: lane a holds slot a while it stages it, so with the largest weight among the
-      // walking lanes this is one ballot -- the walk visits those slots only, in ascending order, instead of all filled ones
-      unsigned long long cand = ~0ull;
-      if (staged) {
-        __builtin_amdgcn_wave_barrier();
-        int64_t my_id = -1;
-        double my_ph = 0.0;
-        if (lane < Mt) {
-          my_id = tid[src + lane];
-          my_ph = tph[src + lane];
-          s_sid[wv][lane] = my_id;
-          s_sph[wv][lane] = my_ph;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const unsigned long long empty = __ballot(lane < Mt && my_id == -1);
-        const int nfill = empty ? __ffsll((long long)empty) - 1 : Mt;          // (the walk stops at the first empty slot)
-        const double wmax = wave_max_f64(walk ? fabs(w) : 0.0);
-        if (RESPONSE) cand = __ballot(lane < nfill && !(wmax * fabs(my_ph) < truth_threshold));
-        else if (__ballot(walk && w < 0.0)) cand = nfill >= 64 ? ~0ull : ((1ull << nfill) - 1ull);
-        else cand = __ballot(lane < nfill && !(my_ph >= 0.0 ? wmax * my_ph < truth_threshold : truth_threshold > 0.0));
-      }
-      if (walk) {
-        for (int a0 = 0; a0 < Mt; a0++) {
-          int a = a0;
-          if (staged) {
-            if (!cand) break;
-            a = __ffsll((long long)cand) - 1;
-            cand &= cand - 1;
-          }
-          const int64_t ida_src = staged ? s_sid[wv][a] : tid[src + a];
-          if (ida_src == -1) break;
-          const double ph = staged ? s_sph[wv][a] : tph[src + a];
-          if (RESPONSE ? (fabs(w * ph) < truth_threshold) : (w * ph < truth_threshold)) continue;
-          if (RESPONSE && row_unique) {
-            const int b = a < row_f ? a : row_f;
-            if (b < Mt) {
-              out_tid[O(b)] = tid_sm[O(a)];
-              out_tph[O(b)] += w * ph;
+        if (walk) {
+          for (int a0 = 0; a0 < Mt; a0++) {
+            int a = a0;
+            if (staged) {
+              if (!cand) break;
+              a = __ffsll((long long)cand) - 1;
+              cand &= cand - 1;
             }
-            continue;
-          }
-          if (!RESPONSE && prefix_ok) {
-            const int64_t id = ida_src;
-            unsigned long long ws;
-            const unsigned long long bit = sig_bit(id, ws);
-            const unsigned long long word = ws == 0 ? sig0 : (ws == 1 ? sig1 : (ws == 2 ? sig2 : sig3));
-            if (id != -1 && !(word & bit)) {             // certainly not stored yet
-              if (filled < Mt) {
-                out_tid[O(filled)] = id;
-                out_tph[O(filled)] += w * ph;
-                filled++;
-                if (ws == 0) sig0 |= bit; else if (ws == 1) sig1 |= bit; else if (ws == 2) sig2 |= bit; else sig3 |= bit;
-              }
-              continue;
-            }
-            for (int b = 0; b < Mt; b++) {              // maybe stored: the literal search (an insert extends the prefix)
-              const int64_t cur = out_tid[O(b)];
-              if (cur == id || cur == -1) {
-                out_tid[O(b)] = id;
+            const int64_t ida_src = staged ? s_sid[wv][a] : tid[src + a];
+            if (ida_src == -1) break;
+            const double ph = staged ? s_sph[wv][a] : tph[src + a];
+            if (RESPONSE ? (fabs(w * ph) < truth_threshold) : (w * ph < truth_threshold)) continue;
+            if (RESPONSE && row_unique) {
+              const int b = a < row_f ? a : row_f;
+              if (b < Mt) {
+                out_tid[O(b)] = tid_sm[O(a)];
                 out_tph[O(b)] += w * ph;
-                if (cur == -1 && id != -1) {
-                  filled = b + 1;
+              }
+              continue;
+            }
+            if (!RESPONSE && prefix_ok) {
+              const int64_t id = ida_src;
+              unsigned long long ws;
+              const unsigned long long bit = sig_bit(id, ws);
+              const unsigned long long word = ws == 0 ? sig0 : (ws == 1 ? sig1 : (ws == 2 ? sig2 : sig3));
+              if (id != -1 && !(word & bit)) {             // certainly not stored yet
+                if (filled < Mt) {
+                  out_tid[O(filled)] = id;
+                  out_tph[O(filled)] += w * ph;
+                  filled++;
                   if (ws == 0) sig0 |= bit; else if (ws == 1) sig1 |= bit; else if (ws == 2) sig2 |= bit; else sig3 |= bit;
                 }
-                break;
+                continue;
               }
+              for (int b = 0; b < Mt; b++) {              // maybe stored: the literal search (an insert extends the prefix)
+                const int64_t cur = out_tid[O(b)];
+                if (cur == id || cur == -1) {
+                  out_tid[O(b)] = id;
+                  out_tph[O(b)] += w * ph;
+                  if (cur == -1 && id != -1) {
+                    filled = b + 1;
+                    if (ws == 0) sig0 |= bit; else if (ws == 1) sig1 |= bit; else if (ws == 2) sig2 |= bit; else sig3 |= bit;
+                  }
+                  break;
+                }
+              }
+              continue;
             }
-            continue;
-          }
-          for (int b = 0; b < Mt; b++) {
-            if (RESPONSE) {
-              // :331-335 literally: the slot test reads the INPUT ids at [idet, itick], not the output's
-              const int64_t idb = tid_sm[O(b)], ida = tid_sm[O(a)];
-              if (idb == ida || idb == -1) {
-                out_tid[O(b)] = ida;
-                out_tph[O(b)] += w * ph;
-                break;
-              }
-            } else {
-              const int64_t id = ida_src;
-              if (out_tid[O(b)] == id || out_tid[O(b)] == -1) {           // :180-183
-                out_tid[O(b)] = id;
-                out_tph[O(b)] += w * ph;
-                break;
+            for (int b = 0; b < Mt; b++) {
+              if (RESPONSE) {
+                // :331-335 literally: the slot test reads the INPUT ids at [idet, itick], not the output's
+                const int64_t idb = tid_sm[O(b)], ida = tid_sm[O(a)];
+                if (idb == ida || idb == -1) {
+                  out_tid[O(b)] = ida;
+                  out_tph[O(b)] += w * ph;
+                  break;
+                }
+              } else {
+                const int64_t id = ida_src;
+                if (out_tid[O(b)] == id || out_tid[O(b)] == -1) {           // :180-183
+                  out_tid[O(b)] = id;
+                  out_tph[O(b)] += w * ph;
+                  break;
+                }
               }
             }
           }
         }
       }
     }
-    }
   }
-  if (live) out[(int64_t)d * T + i] = acc;
 }
 
 // truth_max[d][j] = max over the filled slots a of tph[d][j][a] (RESPONSE: |tph|), -1 when slot 0 is empty
@@ -318,10 +404,9 @@ __global__ void light_truth_max_kernel(const int64_t* __restrict__ tid, const do
 }
 
 // ---- the truth slots on their own: a wave's 64 output rows in LDS (round 4) ----------------------------------------------------
-// The 2x2 batch of tools/light_wvfm_profile.py accepts ~10^9 (output tick, input tick, slot) terms per stage; in light_conv_kernel
-// every one is a read-modify-write of the output slot through L2 (and a search of the output row through L2 in the scintillation
-// stage), and a 64-tick block of input ticks that holds any truth takes the predicated path for the plain sum as well.  Here the
-// plain sum is left to light_conv_kernel (called without truth: its unrolled blocks) and one wave owns the truth rows of 64
+// The 2x2 batch of tools/light_wvfm_profile.py accepts ~10^9 (output tick, input tick, slot) terms per stage; in
+// light_truth_rows_kernel every one is a read-modify-write of the output slot through L2 (and a search of the output row through L2
+// in the scintillation stage).  Here one wave owns the truth rows of 64
 // consecutive output ticks of a detector, in LDS as [slot][tick] (stride LT_S words: lane = tick reads and adds without a bank
 // conflict whatever the slot, and the transposed load / store of the reference's [tick][slot] rows is conflict-free too):
 //   * the input ticks are screened 64 at a time -- lane l holds tick jb + l: its bound (light_truth_max_kernel) times the largest
@@ -771,43 +856,66 @@ __global__ void __launch_bounds__(256) light_truth_transpose_kernel(const unsign
   }
 }
 
-__global__ void light_widen_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ xd) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) xd[e] = (double)x[e];
+template <bool RESPONSE, int NU>
+static void light_plain_launch_nu(hipStream_t st, const float* inc, int D, int T, int C, const double* const* w,
+                                  const double* const* gain, float* const* out, bool accumulate, const double* xd) {
+  LightPlainArgs<NU> A;
+  for (int u = 0; u < NU; u++) {
+    A.w[u] = w[u];
+    A.gain[u] = RESPONSE ? gain[u] : nullptr;
+    A.out[u] = out[u];
+  }
+  dim3 grid((unsigned)((T + LR_THREADS - 1) / LR_THREADS), (unsigned)D);
+  if (NU == 1 && accumulate)          // (light_plain_launch accumulates table by table: no NU >= 2 instance carries the read of `out`)
+    hipLaunchKernelGGL((light_plain_kernel<RESPONSE, 1, true>), grid, dim3(LR_THREADS), 0, st, inc, D, T, C,
+                       LightPlainArgs<1>{{A.w[0]}, {A.gain[0]}, {A.out[0]}}, xd);
+  else
+    hipLaunchKernelGGL((light_plain_kernel<RESPONSE, NU, false>), grid, dim3(LR_THREADS), 0, st, inc, D, T, C, A, xd);
 }
 
-// the plain sum of a stage (no truth slots) on `st`
-int light_response_plain(ldsim_ctx* ctx, hipStream_t st, bool response, const float* inc, int D, int T, const double* weights,
-                                      int C, const double* gain, float* out) {
-  if (D <= 0 || T <= 0) return 0;
-  dim3 grid((unsigned)((T + LR_THREADS - 1) / LR_THREADS), (unsigned)D), block(LR_THREADS);
-  const double thr = ctx->h_consts.mc_truth_threshold;
+// The plain sum of a stage under K tables (w[k]: [C + 1]; response: gain[k]: [D]) over the one input `inc`, on the ctx's stream:
+// out[k] = (accumulate: out[k] +) the sum under table k, by light_plain_kernel over ctx->lu_nu tables at a time (the same bits at
+// every grouping; an accumulating pass, which no caller asks for more than one table, goes table by table).  light_xd is shared by every caller: all on the one stream, so a pass is through with it before the next widens.
+static int light_plain_launch(ldsim_ctx* ctx, bool response, const float* inc, int D, int T, int C, int K, const double* const* w,
+                              const double* const* gain, float* const* out, bool accumulate) {
+  if (D <= 0 || T <= 0 || K <= 0) return 0;
+  static constexpr decltype(&light_plain_launch_nu<false, 1>) by_nu[2][4] = {
+      {light_plain_launch_nu<false, 1>, light_plain_launch_nu<false, 2>, light_plain_launch_nu<false, 3>, light_plain_launch_nu<false, 4>},
+      {light_plain_launch_nu<true, 1>, light_plain_launch_nu<true, 2>, light_plain_launch_nu<true, 3>, light_plain_launch_nu<true, 4>}};
+  hipStream_t st = ctx->stream;
   const double* xd = nullptr;
-  if (response) {          // (the SiPM stage's blocks of 64 input ticks all take part: the samples once more as doubles)
+  if (response) {          // (the SiPM stage's blocks of 64 input ticks all take part: the samples once more as doubles, for all K)
     const int64_t n = (int64_t)D * T;
-    int rc = ctx->light_xd.ensure((size_t)n * 8 + 64);
-    if (rc) return rc;
+    CK(ctx->light_xd.ensure((size_t)n * 8 + 64));
     hipLaunchKernelGGL(light_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, inc, n, (double*)ctx->light_xd.p);
     xd = (const double*)ctx->light_xd.p;
   }
-  if (response)
-    hipLaunchKernelGGL(light_conv_kernel<true>, grid, block, 0, st, inc, (const int64_t*)nullptr, (const double*)nullptr, D, T, 0, weights,
-                       C, gain, thr, out, (int64_t*)nullptr, (double*)nullptr, (const double*)nullptr, (const int64_t*)nullptr, xd);
-  else
-    hipLaunchKernelGGL(light_conv_kernel<false>, grid, block, 0, st, inc, (const int64_t*)nullptr, (const double*)nullptr, D, T, 0, weights,
-                       C, gain, thr, out, (int64_t*)nullptr, (double*)nullptr, (const double*)nullptr, (const int64_t*)nullptr, xd);
-  HIPCHK(hipGetLastError());
+  for (int k = 0; k < K;) {
+    const int nu = accumulate ? 1 : (K - k < ctx->lu_nu ? K - k : ctx->lu_nu);
+    by_nu[response ? 1 : 0][nu - 1](st, inc, D, T, C, w + k, response ? gain + k : nullptr, out + k, accumulate, xd);
+    HIPCHK(hipGetLastError());
+    k += nu;
+  }
   return 0;
 }
 
-// can the truth slots of a stage go by light_truth_lds_kernel?
-bool light_truth_in_lds(const ldsim_ctx* ctx, int Mt) { return Mt > 0 && Mt <= 64 && ctx->light_truth_lds; }
+// the plain sum of a stage, added to what `out` holds
+static int light_response_plain(ldsim_ctx* ctx, bool response, const float* inc, int D, int T, const double* weights, int C,
+                                const double* gain, float* out) {
+  return light_plain_launch(ctx, response, inc, D, T, C, 1, &weights, &gain, &out, true);
+}
 
-// the truth slots of a stage (light_truth_in_lds) on `st`: bounds, weight envelopes, light_truth_lds_kernel.  The scintillation and the
-// SiPM stage of one call share the bound and envelope buffers: both on the same stream.
-int light_response_truth(ldsim_ctx* ctx, hipStream_t st, bool response, const float* inc, const int64_t* tid, const double* tph,
-                                      int D, int T, int Mt, const double* weights, int C, int64_t* out_tid, double* out_tph) {
-  if (D <= 0 || T <= 0) return 0;
+// the plain sums of the light universes: into pool buffers that hold an earlier pass's values, which are not read
+int light_universes_conv(ldsim_ctx* ctx, bool response, const float* inc, int D, int T, int C, int K, const double* const* w,
+                         const double* const* gain, float* const* out) {
+  return light_plain_launch(ctx, response, inc, D, T, C, K, w, gain, out, false);
+}
+
+// the truth slots of a stage, rows in LDS (at most 64 slots): bounds, weight envelopes, light_truth_lds_kernel.  The scintillation and
+// the SiPM stage of one call share the bound and envelope buffers: both on the same stream.
+static int light_response_truth(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid, const double* tph, int D, int T,
+                                int Mt, const double* weights, int C, int64_t* out_tid, double* out_tph) {
+  hipStream_t st = ctx->stream;
   const double thr = ctx->h_consts.mc_truth_threshold;
   const int nblk = (T + 63) / 64, nq = (C + 63) / 64 + 1;
   const int64_t n = (int64_t)D * T;
@@ -839,258 +947,53 @@ int light_response_truth(ldsim_ctx* ctx, hipStream_t st, bool response, const fl
   return 0;
 }
 
-int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid,
-                                       const double* tph, int D, int T, int Mt, const double* weights, int C,
-                                       const double* gain, float* out, int64_t* out_tid, double* out_tph) {
-  if (D <= 0 || T <= 0) return 0;
-  if (light_truth_in_lds(ctx, Mt)) {
-    // the plain sum by light_conv_kernel without truth, the truth slots by light_truth_lds_kernel (rows in LDS: no slot-major copies)
-    int rc = light_response_plain(ctx, ctx->stream, response, inc, D, T, weights, C, gain, out);
-    if (rc) return rc;
-    return light_response_truth(ctx, ctx->stream, response, inc, tid, tph, D, T, Mt, weights, C, out_tid, out_tph);
-  }
-  dim3 grid((unsigned)((T + LR_THREADS - 1) / LR_THREADS), (unsigned)D), block(LR_THREADS);
-  const double thr = ctx->h_consts.mc_truth_threshold;
-  double* tmax = nullptr;
-  if (Mt > 0) {
-    const int64_t n = (int64_t)D * T;
-    int rc = ctx->light_tmax.ensure((size_t)n * 8);
-    if (rc) return rc;
-    tmax = (double*)ctx->light_tmax.p;
-    hipLaunchKernelGGL(light_truth_max_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, tid, tph, n, Mt,
-                       response ? 1 : 0, tmax);
-    HIPCHK(hipGetLastError());
-  }
-  // (more than 64 slots, or "light_truth_lds" 0:) the output's truth rows to slot-major, through light_conv_kernel, and back (2 x 2
-  // passes over [D][T][Mt]: a few ms at 2.5 GB each)
-  int64_t* w_tid = nullptr;
-  int64_t* in_sm = nullptr;
-  double* w_tph = nullptr;
-  if (Mt > 0) {
-    const size_t bt = (size_t)D * T * Mt;
-    int rc = ctx->light_wtid.ensure(bt * 8 + 16);
-    if (rc) return rc;
-    if ((rc = ctx->light_wtph.ensure(bt * 8 + 16))) return rc;
-    w_tid = (int64_t*)ctx->light_wtid.p;
-    w_tph = (double*)ctx->light_wtph.p;
-    dim3 tg((unsigned)((T + TR_TICKS - 1) / TR_TICKS), (unsigned)D);
-    hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), (size_t)TR_TICKS * (Mt + 1) * 8, ctx->stream,
-                       (const unsigned long long*)out_tid, (unsigned long long*)w_tid, T, Mt);
-    hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), (size_t)TR_TICKS * (Mt + 1) * 8, ctx->stream,
-                       (const unsigned long long*)out_tph, (unsigned long long*)w_tph, T, Mt);
-    if (response) {        // the SiPM stage compares ids of the INPUT row at the output tick (light_sim.py:331-335): slot-major too
-      if ((rc = ctx->light_wtid2.ensure(bt * 8 + 16))) return rc;
-      in_sm = (int64_t*)ctx->light_wtid2.p;
-      hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), (size_t)TR_TICKS * (Mt + 1) * 8, ctx->stream,
-                         (const unsigned long long*)tid, (unsigned long long*)in_sm, T, Mt);
-    }
-    HIPCHK(hipGetLastError());
-  }
-  if (response)
-    hipLaunchKernelGGL(light_conv_kernel<true>, grid, block, 0, ctx->stream, inc, tid, tph, D, T, Mt, weights, C, gain, thr,
-                       out, w_tid, w_tph, tmax, in_sm, (const double*)nullptr);
-  else
-    hipLaunchKernelGGL(light_conv_kernel<false>, grid, block, 0, ctx->stream, inc, tid, tph, D, T, Mt, weights, C, gain,
-                       thr, out, w_tid, w_tph, tmax, (const int64_t*)nullptr, (const double*)nullptr);
-  HIPCHK(hipGetLastError());
-  if (Mt > 0) {
-    dim3 tg((unsigned)((T + TR_TICKS - 1) / TR_TICKS), (unsigned)D);
-    hipLaunchKernelGGL(light_truth_transpose_kernel<false>, tg, dim3(256), (size_t)TR_TICKS * (Mt + 1) * 8, ctx->stream,
-                       (const unsigned long long*)w_tid, (unsigned long long*)out_tid, T, Mt);
-    hipLaunchKernelGGL(light_truth_transpose_kernel<false>, tg, dim3(256), (size_t)TR_TICKS * (Mt + 1) * 8, ctx->stream,
-                       (const unsigned long long*)w_tph, (unsigned long long*)out_tph, T, Mt);
-    HIPCHK(hipGetLastError());
-  }
-  return 0;
-}
-
-// ---- light universes: up to NU weight tables over one shared input row --------------------------------------------------------
-// light_conv_kernel without truth slots (its Mt == 0 path) for NU tables at once: the chunk of the input row is staged once (f4 for
-// the ballots and the bit-scan form, doubles for the unrolled blocks), each table has its own weight tile in LDS and each thread NU
-// f4 accumulators, updated in the same ascending-j order with the same rounding, so output u equals light_conv_kernel's under table
-// u bit for bit.  The non-zero ballot, the sample fetch and the block bookkeeping are paid once per block for all NU tables, and
-// the NU dependent cvt -> mul -> add -> cvt chains of a term interleave.  RESPONSE: the weights are staged as gain_u[d] * w_u.
-template <int NU>
-struct LightUniArgs {
-  const double* w[NU];          // [C + 1]
-  const double* gain[NU];       // [D] (RESPONSE)
-  float* out[NU];               // [D][T]
-};
-
-// eight consecutive input ticks for all NU tables: weight of tick e at s_w[u][wo - e]; per table the sums stay in ascending-tick order
-template <int NU>
-__device__ __forceinline__ void light_uni_terms8(float (&acc)[NU], const double (*s_w)[JCHUNK + LR_THREADS], int wo,
-                                                 const double (&x8)[8]) {
-  double w8[NU][8];
-#pragma unroll
-  for (int u = 0; u < NU; u++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) w8[u][e] = s_w[u][wo - e];
-#pragma unroll
-  for (int e = 0; e < 8; e++)
-#pragma unroll
-    for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + w8[u][e] * x8[e]);
-}
-
-template <bool RESPONSE, int NU>
-__global__ void __launch_bounds__(LR_THREADS) light_conv_universes_kernel(
-    const float* __restrict__ inc, int D, int T, int C, LightUniArgs<NU> A,
-    const double* __restrict__ inc_f64 /* [D][T]: `inc` widened (light_widen_kernel), or NULL */) {
-  __shared__ float s_x[JCHUNK];
-  __shared__ double s_xd[JCHUNK];
-  __shared__ double s_w[NU][JCHUNK + LR_THREADS];
-  const int d = blockIdx.y;
-  const int i0 = blockIdx.x * LR_THREADS;
-  const int i = i0 + threadIdx.x;
-  const bool live = i < T;
-  const int i_last = min(i0 + LR_THREADS, T) - 1;          // last tick of this workgroup
-  const int j_begin = max(i0 - C, 0);                       // first j any of its ticks can reach
-  const float* x = inc + (int64_t)d * T;
-  const int my_j0 = max(i - C, 0);
-  float acc[NU];
-  double g[NU];
-#pragma unroll
-  for (int u = 0; u < NU; u++) {
-    acc[u] = 0.f;
-    g[u] = RESPONSE ? A.gain[u][d] : 1.0;
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int jc = j_begin; jc <= i_last; jc += JCHUNK) {
-    const int nj = min(JCHUNK, i_last - jc + 1);
-    // weights this chunk can meet: n = i - j in [i0 - (jc + nj - 1), i_last - jc], at most LR_THREADS + JCHUNK - 1 of them
-    const int n_lo = max(i0 - (jc + nj - 1), 0), n_hi = min(i_last - jc, C);
-    __syncthreads();
-    for (int k = threadIdx.x; k < nj; k += LR_THREADS) {
-      const float xv = x[jc + k];
-      s_x[k] = xv;
-      s_xd[k] = (double)xv;
-    }
-#pragma unroll
-    for (int u = 0; u < NU; u++)
-      for (int k = threadIdx.x; k <= n_hi - n_lo; k += LR_THREADS) s_w[u][k] = RESPONSE ? g[u] * A.w[u][n_lo + k] : A.w[u][n_lo + k];
-    __syncthreads();
-    for (int jb = jc; jb <= jc + nj - 1; jb += 64) {
-      const int nb64 = min(64, jc + nj - jb);
-      const float x_l = lane < nb64 ? s_x[jb - jc + lane] : 0.f;
-      const unsigned long long m_nz = RESPONSE ? ~0ull : __ballot(x_l != 0.f);
-      unsigned long long todo = (nb64 == 64 ? ~0ull : ((1ull << nb64) - 1ull)) & m_nz;
-      const int w_i0 = i0 + (wv << 6);
-      const bool inside = w_i0 + 63 < T && jb >= max(w_i0 + 63 - C, 0) && jb + nb64 - 1 <= w_i0;
-      if (inside) {
-        const int wo = (i - jb) - n_lo;          // weight of tick jb + t: s_w[u][wo - t]
-        if (todo == ~0ull) {
-          const double* xd = s_xd + (jb - jc);
-          const double xd_l = (double)x_l;
-          // eight ticks at a time, the loop over them kept rolled: unrolled over all 64 the NU x 64 weight reads are hoisted in
-          // front of the sums and the kernel runs out of registers (512 at NU = 2, scratch at NU = 4)
-          if (inc_f64) {
-            const double* xg = inc_f64 + (int64_t)d * T + jb;
-#pragma unroll 1
-            for (int t8 = 0; t8 < 64; t8 += 8) {
-              double x8[8];
-#pragma unroll
-              for (int e = 0; e < 8; e++) x8[e] = xg[t8 + e];
-              light_uni_terms8<NU>(acc, s_w, wo - t8, x8);
-            }
-          } else {
-#pragma unroll 1
-            for (int t8 = 0; t8 < 64; t8 += 8) {
-              double x8[8];
-#pragma unroll
-              for (int e = 0; e < 8; e++) x8[e] = RESPONSE ? wave_lane_f64(xd_l, t8 + e) : xd[t8 + e];
-              light_uni_terms8<NU>(acc, s_w, wo - t8, x8);
-            }
-          }
-          continue;
-        }
-        for (; todo; todo &= todo - 1) {
-          const int t = __ffsll((long long)todo) - 1;
-          const double xv = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
-#pragma unroll
-          for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + s_w[u][wo - t] * xv);
-        }
-        continue;
-      }
-      for (; todo; todo &= todo - 1) {
-        const int t = __ffsll((long long)todo) - 1;
-        const int j = jb + t;
-        const double xv = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x_l), t));
-        if (live && j >= my_j0 && j <= i) {
-#pragma unroll
-          for (int u = 0; u < NU; u++) acc[u] = (float)((double)acc[u] + s_w[u][(i - j) - n_lo] * xv);
-        }
-      }
-    }
-  }
-  if (live) {
-#pragma unroll
-    for (int u = 0; u < NU; u++) A.out[u][(int64_t)d * T + i] = acc[u];
-  }
-}
-
-// x_k = (float)((double)x * scale): one rounding (exact at scale 1.0, which the host does not launch)
-__global__ void light_scale_kernel(const float* __restrict__ x, int64_t n, double scale, float* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) out[e] = (float)((double)x[e] * scale);
-}
-
-int light_universes_scale(ldsim_ctx* ctx, const float* x, int64_t n, double scale, float* out) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(light_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x, n, scale, out);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <bool RESPONSE, int NU>
-static void light_universes_launch_nu(hipStream_t st, dim3 grid, const float* inc, int D, int T, int C, const double* const* w,
-                                      const double* const* gain, float* const* out, const double* xd) {
-  LightUniArgs<NU> A;
-  for (int u = 0; u < NU; u++) {
-    A.w[u] = w[u];
-    A.gain[u] = RESPONSE ? gain[u] : nullptr;
-    A.out[u] = out[u];
-  }
-  hipLaunchKernelGGL((light_conv_universes_kernel<RESPONSE, NU>), grid, dim3(LR_THREADS), 0, st, inc, D, T, C, A, xd);
-}
-
-// K tables (w[k]: [C + 1]; response: gain[k]: [D]) over the one input `inc`, out[k] = the stage's plain sum under table k, on the
-// ctx's stream: light_conv_universes_kernel over ctx->lu_nu tables at a time, light_conv_kernel for a single one (into zeros)
-int light_universes_conv(ldsim_ctx* ctx, bool response, const float* inc, int D, int T, int C, int K, const double* const* w,
-                         const double* const* gain, float* const* out) {
-  if (D <= 0 || T <= 0 || K <= 0) return 0;
+// the truth slots of a stage on the rows in memory: the output's truth rows to slot-major, through light_truth_rows_kernel, and back
+// (2 x 2 passes over [D][T][Mt]: a few ms at 2.5 GB each)
+static int light_response_truth_rows(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid, const double* tph, int D,
+                                     int T, int Mt, const double* weights, int C, int64_t* out_tid, double* out_tph) {
   hipStream_t st = ctx->stream;
-  dim3 grid((unsigned)((T + LR_THREADS - 1) / LR_THREADS), (unsigned)D), block(LR_THREADS);
-  const double* xd = nullptr;
-  if (response) {          // (the SiPM stage's blocks of 64 input ticks all take part: the samples once more as doubles, for all K)
-    const int64_t n = (int64_t)D * T;
-    CK(ctx->lu_xd.ensure((size_t)n * 8 + 64));
-    hipLaunchKernelGGL(light_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, inc, n, (double*)ctx->lu_xd.p);
-    xd = (const double*)ctx->lu_xd.p;
-  }
   const double thr = ctx->h_consts.mc_truth_threshold;
-  for (int k = 0; k < K;) {
-    const int nu = K - k < ctx->lu_nu ? K - k : ctx->lu_nu;
-    if (nu == 1) {
-      HIPCHK(hipMemsetAsync(out[k], 0, (size_t)D * T * 4, st));
-      if (response)
-        hipLaunchKernelGGL(light_conv_kernel<true>, grid, block, 0, st, inc, (const int64_t*)nullptr, (const double*)nullptr, D, T, 0,
-                           w[k], C, gain[k], thr, out[k], (int64_t*)nullptr, (double*)nullptr, (const double*)nullptr,
-                           (const int64_t*)nullptr, xd);
-      else
-        hipLaunchKernelGGL(light_conv_kernel<false>, grid, block, 0, st, inc, (const int64_t*)nullptr, (const double*)nullptr, D, T, 0,
-                           w[k], C, (const double*)nullptr, thr, out[k], (int64_t*)nullptr, (double*)nullptr, (const double*)nullptr,
-                           (const int64_t*)nullptr, xd);
-    } else if (response) {
-      if (nu == 2) light_universes_launch_nu<true, 2>(st, grid, inc, D, T, C, w + k, gain + k, out + k, xd);
-      else if (nu == 3) light_universes_launch_nu<true, 3>(st, grid, inc, D, T, C, w + k, gain + k, out + k, xd);
-      else light_universes_launch_nu<true, 4>(st, grid, inc, D, T, C, w + k, gain + k, out + k, xd);
-    } else {
-      if (nu == 2) light_universes_launch_nu<false, 2>(st, grid, inc, D, T, C, w + k, gain, out + k, xd);
-      else if (nu == 3) light_universes_launch_nu<false, 3>(st, grid, inc, D, T, C, w + k, gain, out + k, xd);
-      else light_universes_launch_nu<false, 4>(st, grid, inc, D, T, C, w + k, gain, out + k, xd);
-    }
-    HIPCHK(hipGetLastError());
-    k += nu;
+  const int64_t n = (int64_t)D * T;
+  const size_t bt = (size_t)n * Mt, lds = (size_t)TR_TICKS * (Mt + 1) * 8;
+  CK(ctx->light_tmax.ensure((size_t)n * 8));
+  CK(ctx->light_wtid.ensure(bt * 8 + 16));
+  CK(ctx->light_wtph.ensure(bt * 8 + 16));
+  if (response) CK(ctx->light_wtid2.ensure(bt * 8 + 16));
+  double* tmax = (double*)ctx->light_tmax.p;
+  int64_t* w_tid = (int64_t*)ctx->light_wtid.p;
+  double* w_tph = (double*)ctx->light_wtph.p;
+  int64_t* in_sm = response ? (int64_t*)ctx->light_wtid2.p : nullptr;
+  hipLaunchKernelGGL(light_truth_max_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tid, tph, n, Mt, response ? 1 : 0, tmax);
+  dim3 tg((unsigned)((T + TR_TICKS - 1) / TR_TICKS), (unsigned)D), grid((unsigned)((T + LR_THREADS - 1) / LR_THREADS), (unsigned)D);
+  hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), lds, st, (const unsigned long long*)out_tid,
+                     (unsigned long long*)w_tid, T, Mt);
+  hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), lds, st, (const unsigned long long*)out_tph,
+                     (unsigned long long*)w_tph, T, Mt);
+  if (response) {        // the SiPM stage compares ids of the INPUT row at the output tick (light_sim.py:331-335): slot-major too
+    hipLaunchKernelGGL(light_truth_transpose_kernel<true>, tg, dim3(256), lds, st, (const unsigned long long*)tid,
+                       (unsigned long long*)in_sm, T, Mt);
+    hipLaunchKernelGGL(light_truth_rows_kernel<true>, grid, dim3(LR_THREADS), 0, st, inc, tid, tph, D, T, Mt, weights, C, thr, w_tid, w_tph,
+                       (const double*)tmax, (const int64_t*)in_sm);
+  } else {
+    hipLaunchKernelGGL(light_truth_rows_kernel<false>, grid, dim3(LR_THREADS), 0, st, inc, tid, tph, D, T, Mt, weights, C, thr, w_tid, w_tph,
+                       (const double*)tmax, (const int64_t*)nullptr);
   }
+  hipLaunchKernelGGL(light_truth_transpose_kernel<false>, tg, dim3(256), lds, st, (const unsigned long long*)w_tid,
+                     (unsigned long long*)out_tid, T, Mt);
+  hipLaunchKernelGGL(light_truth_transpose_kernel<false>, tg, dim3(256), lds, st, (const unsigned long long*)w_tph,
+                     (unsigned long long*)out_tph, T, Mt);
+  HIPCHK(hipGetLastError());
   return 0;
 }
+
+// a response stage: the plain sum, then the truth slots -- rows in LDS where a wave can hold them and option light_truth_lds is on
+int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid, const double* tph, int D, int T,
+                          int Mt, const double* weights, int C, const double* gain, float* out, int64_t* out_tid,
+                          double* out_tph) {
+  if (D <= 0 || T <= 0) return 0;
+  CK(light_response_plain(ctx, response, inc, D, T, weights, C, gain, out));
+  if (Mt <= 0) return 0;
+  if (Mt <= 64 && ctx->light_truth_lds) return light_response_truth(ctx, response, inc, tid, tph, D, T, Mt, weights, C, out_tid, out_tph);
+  return light_response_truth_rows(ctx, response, inc, tid, tph, D, T, Mt, weights, C, out_tid, out_tph);
+}
+

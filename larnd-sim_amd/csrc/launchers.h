@@ -115,13 +115,15 @@ int light_launch_sum(ldsim_ctx* ctx, int64_t seg0, int64_t n, const int32_t* vox
 int light_launch_reset_cells(ldsim_ctx* ctx, int64_t n_rec, int64_t n_ticks, int max_truth, float* out, int64_t* true_id,
                              double* true_ph);
 int light_check_emit_overflow(ldsim_ctx* ctx);
+// a response stage on the ctx's stream: the plain sum added to `out` (light_plain_kernel), then the Mt truth slots
+// (light_truth_lds_kernel, or light_truth_rows_kernel for more than 64 slots / option light_truth_lds 0)
 int light_response_launch(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid, const double* tph, int D, int T,
                           int Mt, const double* weights, int C, const double* gain, float* out, int64_t* out_tid,
                           double* out_tph);
 int light_launch_stat_fluct(ldsim_ctx* ctx, const float* inc, float* out, int64_t n, int64_t ntick);
 int light_sipm_check(const LdsimSipmNoise& v, double tick);
-// light universes: out = (float)((double)x * scale); K tables over one input by light_conv_universes_kernel (a stage's plain sum
-// under each, bit-equal to light_conv_kernel's)
+// light universes: out = (float)((double)x * scale); K tables over one input by light_plain_kernel (out[k] = a stage's plain sum
+// under table k, the launch's bits; what out[k] held is not read)
 int light_universes_scale(ldsim_ctx* ctx, const float* x, int64_t n, double scale, float* out);
 int light_universes_conv(ldsim_ctx* ctx, bool response, const float* inc, int D, int T, int C, int K, const double* const* w,
                          const double* const* gain, float* const* out);

@@ -1427,6 +1427,24 @@ static double sipm_response_model(int64_t n, const double* impulse, int64_t n_im
   return v;
 }
 
+// the weight tables w[0 .. C] of the two stages under the constants `h`
+static void scintillation_table(const LdsimConsts& h, int64_t C, double* w) {
+  for (int64_t n = 0; n <= C; n++) w[n] = scintillation_model(n, h);
+}
+static void sipm_table(const LdsimConsts& h, const double* impulse, int64_t n_impulse, int64_t C, double* w) {
+  for (int64_t n = 0; n <= C; n++) w[n] = sipm_response_model(n, impulse, n_impulse, h);
+}
+
+// the light constants the stages of an entry point read (`scint`, `sipm`: which of the two it runs), conv_ticks in *C
+static int light_stage_consts(const LdsimConsts& h, bool scint, bool sipm, const double* impulse_model, int32_t n_impulse, int64_t* C) {
+  NEED(h.light_tick_size > 0 && (!scint || (h.tau_s > 0 && h.tau_t > 0)), "light constants not set");
+  NEED(!sipm || h.sipm_response_model == 0 || (h.sipm_response_model == 1 && impulse_model && n_impulse > 0 && h.impulse_tick_size > 0),
+       "SIPM_RESPONSE_MODEL 1 needs IMPULSE_MODEL and IMPULSE_TICK_SIZE");
+  *C = conv_ticks(h);
+  NEED(*C >= 0 && *C < (1 << 24), "LIGHT_WINDOW / LIGHT_TICK_SIZE out of range");
+  return 0;
+}
+
 static int light_response_stage(ldsim_ctx* ctx, bool response, const float* inc, const int64_t* tid, const double* tph,
                                 int32_t n_det, int32_t n_ticks, int32_t max_truth, const std::vector<double>& weights,
                                 const double* gain, float* out, int64_t* out_tid, double* out_tph) {
@@ -1466,12 +1484,10 @@ extern "C" int ldsim_scintillation_effect(ldsim_ctx* ctx, const float* light_sam
   NEED(ctx && light_sample_inc && scint && n_det >= 0 && n_ticks >= 0 && max_truth >= 0, "bad argument");
   NEED(max_truth == 0 || (true_track_id && true_photons && scint_true_track_id && scint_true_photons),
        "truth arrays missing");
-  const LdsimConsts& h = ctx->h_consts;
-  NEED(h.light_tick_size > 0 && h.tau_s > 0 && h.tau_t > 0, "light constants not set");
-  const int64_t C = conv_ticks(h);
-  NEED(C >= 0 && C < (1 << 24), "LIGHT_WINDOW / LIGHT_TICK_SIZE out of range");
+  int64_t C;
+  CK(light_stage_consts(ctx->h_consts, true, false, nullptr, 0, &C));
   std::vector<double> w((size_t)C + 1);
-  for (int64_t n = 0; n <= C; n++) w[(size_t)n] = scintillation_model(n, h);
+  scintillation_table(ctx->h_consts, C, w.data());
   return light_response_stage(ctx, false, light_sample_inc, true_track_id, true_photons, n_det, n_ticks, max_truth, w,
                               nullptr, scint, scint_true_track_id, scint_true_photons);
 }
@@ -1485,14 +1501,10 @@ extern "C" int ldsim_light_detector_response(ldsim_ctx* ctx, const float* light_
   NEED(ctx && light_sample_inc && response && light_gain && n_det >= 0 && n_ticks >= 0 && max_truth >= 0, "bad argument");
   NEED(max_truth == 0 || (true_track_id && true_photons && response_true_track_id && response_true_photons),
        "truth arrays missing");
-  const LdsimConsts& h = ctx->h_consts;
-  NEED(h.light_tick_size > 0, "light constants not set");
-  NEED(h.sipm_response_model == 0 || (h.sipm_response_model == 1 && impulse_model && n_impulse > 0 && h.impulse_tick_size > 0),
-       "SIPM_RESPONSE_MODEL 1 needs IMPULSE_MODEL and IMPULSE_TICK_SIZE");
-  const int64_t C = conv_ticks(h);
-  NEED(C >= 0 && C < (1 << 24), "LIGHT_WINDOW / LIGHT_TICK_SIZE out of range");
+  int64_t C;
+  CK(light_stage_consts(ctx->h_consts, false, true, impulse_model, n_impulse, &C));
   std::vector<double> w((size_t)C + 1);
-  for (int64_t n = 0; n <= C; n++) w[(size_t)n] = sipm_response_model(n, impulse_model, n_impulse, h);
+  sipm_table(ctx->h_consts, impulse_model, n_impulse, C, w.data());
   return light_response_stage(ctx, true, light_sample_inc, true_track_id, true_photons, n_det, n_ticks, max_truth, w,
                               light_gain, response, response_true_track_id, response_true_photons);
 }
@@ -1507,21 +1519,16 @@ extern "C" int ldsim_dev_light_response(ldsim_ctx* ctx, const double* light_gain
   NEED(ctx->light_sum_ndet > 0, "no resident photon sum (ldsim_dev_sum_light)");
   CK(light_join(ctx));
   const LdsimConsts& h = ctx->h_consts;
-  NEED(h.light_tick_size > 0 && h.tau_s > 0 && h.tau_t > 0, "light constants not set");
-  NEED(h.sipm_response_model == 0 || (h.sipm_response_model == 1 && impulse_model && n_impulse > 0 && h.impulse_tick_size > 0),
-       "SIPM_RESPONSE_MODEL 1 needs IMPULSE_MODEL and IMPULSE_TICK_SIZE");
-  const int64_t C = conv_ticks(h);
-  NEED(C >= 0 && C < (1 << 24), "LIGHT_WINDOW / LIGHT_TICK_SIZE out of range");
+  int64_t C;
+  CK(light_stage_consts(h, true, true, impulse_model, n_impulse, &C));
   HIPCHK(hipSetDevice(ctx->device));
   const int D = ctx->light_sum_ndet, T = ctx->light_sum_nticks, Mt = ctx->light_sum_truth;
   const size_t bo = (size_t)D * T, bt = bo * (size_t)Mt;
   ctx->light_resp_valid = 0;
   ctx->lu_valid = 0;
   std::vector<double> w0((size_t)C + 1), w1((size_t)C + 1);
-  for (int64_t n = 0; n <= C; n++) {
-    w0[(size_t)n] = scintillation_model(n, h);
-    w1[(size_t)n] = sipm_response_model(n, impulse_model, n_impulse, h);
-  }
+  scintillation_table(h, C, w0.data());
+  sipm_table(h, impulse_model, n_impulse, C, w1.data());
   hipStream_t st = ctx->stream;
   CK(ctx->light_w[0].ensure(w0.size() * 8));
   CK(ctx->light_w[1].ensure(w1.size() * 8));
@@ -1648,11 +1655,8 @@ extern "C" int ldsim_dev_light_universes(ldsim_ctx* ctx, const LdsimLightVariati
     return LDSIM_EINVAL;
   }
   const LdsimConsts& h = ctx->h_consts;
-  NEED(h.light_tick_size > 0 && h.tau_s > 0 && h.tau_t > 0, "light constants not set");
-  NEED(h.sipm_response_model == 0 || (h.sipm_response_model == 1 && impulse_model && n_impulse > 0 && h.impulse_tick_size > 0),
-       "SIPM_RESPONSE_MODEL 1 needs IMPULSE_MODEL and IMPULSE_TICK_SIZE");
-  const int64_t C = conv_ticks(h);
-  NEED(C >= 0 && C < (1 << 24), "LIGHT_WINDOW / LIGHT_TICK_SIZE out of range");
+  int64_t C;
+  CK(light_stage_consts(h, true, true, impulse_model, n_impulse, &C));
   for (int k = 0; k < n; k++) CK(light_variation_check(v[k], k, h));
   if (ctx->light_sum_ndet <= 0) {
     ldsim_set_error("light universes: no resident photon sum (ldsim_dev_sum_light)");
@@ -1707,12 +1711,12 @@ extern "C" int ldsim_dev_light_universes(ldsim_ctx* ctx, const LdsimLightVariati
   for (size_t s = 0; s < n_sc; s++) {
     LdsimConsts hc = h;
     hc.singlet_fraction = sc_keys[s].c[0]; hc.tau_s = sc_keys[s].c[1]; hc.tau_t = sc_keys[s].c[2];
-    for (int64_t m = 0; m <= C; m++) tab[s * W + (size_t)m] = scintillation_model(m, hc);
+    scintillation_table(hc, C, &tab[s * W]);
   }
   for (size_t r = 0; r < n_rs; r++) {
     LdsimConsts hc = h;
     hc.light_response_time = rs_keys[r].c[1]; hc.light_oscillation_period = rs_keys[r].c[2];
-    for (int64_t m = 0; m <= C; m++) tab[(n_sc + r) * W + (size_t)m] = sipm_response_model(m, impulse_model, n_impulse, hc);
+    sipm_table(hc, impulse_model, n_impulse, C, &tab[(n_sc + r) * W]);
     for (int d = 0; d < D; d++) tab[(n_sc + n_rs) * W + r * (size_t)D + (size_t)d] = light_gain[d] * rs_keys[r].c[0];
   }
   CK(ctx->lu_tab.ensure(tab.size() * 8 + 8));

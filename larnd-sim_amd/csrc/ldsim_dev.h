@@ -261,9 +261,9 @@ struct ldsim_ctx {
   // overlapped download of the chain's results (ldsim_chain_download_async): a second stream copies launch k's per-pixel
   // arrays to the host while launch k + 1 computes into the other set of output buffers
   DevBuf light_wtid, light_wtph, light_wtid2;            // slot-major working copies of a response stage's output truth rows
-  DevBuf light_xd;                           // the SiPM stage's input samples widened to doubles (light_widen_kernel)
+  DevBuf light_xd;                           // a SiPM stage's input samples widened to doubles (light_widen_kernel): the launch's and the universes' passes, one after the other on the stream
   DevBuf light_env;                          // per offset of a wave's first tick from an input tick: the largest weight its 64 ticks meet it with (light_env_kernel)
-  int light_truth_lds = 1;                   // truth slots of the light response stages by light_truth_lds_kernel (0: inside light_conv_kernel, slot-major copies)
+  int light_truth_lds = 1;                   // truth slots of the light response stages by light_truth_lds_kernel (0, or more than 64 slots: light_truth_rows_kernel, slot-major copies in memory)
   DevBuf light_tmax;                         // per (detector, tick) bound on the truth slots' photons (light_truth_max_kernel)
   DevBuf out_alt[7];                         // the other set of SB_UPIX, SB_UBATCH, SB_ADC, SB_TICKS, SB_DIGIT, SB_TPM, SB_FRAC
   int async_out = 0;                         // alternate the output buffers from launch to launch (set by the first async download)
@@ -369,13 +369,12 @@ struct ldsim_ctx {
   DevBuf lu_scint, lu_disc;      // distinct scintillation profiles and their fluctuated counts (lu_disc unused without fluctuations)
   DevBuf lu_resp;                // distinct detector responses
   DevBuf lu_tab;                 // weight tables f64 [n_sc + n_rs][C + 1] | row gains f64 [n_rs][lu_D]
-  DevBuf lu_xd;                  // a response pass's input widened to doubles (light_widen_kernel)
   DevBuf lu_digit;               // waveforms of the last ldsim_dev_light_universe_waveforms, f64 [n_trig][n_det_trig][samples]
   int lu_valid = 0, lu_keep = 0, lu_fluct = 0;
   int32_t lu_n = 0, lu_D = 0, lu_T = 0;
   size_t lu_bo = 0;
   std::vector<int32_t> lu_in, lu_sc, lu_rs;
-  int lu_nu = 4;                 // option light_universes_nu: tables per launch of light_conv_universes_kernel (1: light_conv_kernel per table)
+  int lu_nu = 4;                 // option light_universes_nu: tables per launch of light_plain_kernel, 1 .. 4
   Event lu_ev[4];                // around the scintillation, fluctuation and response stages of the last pass
   double ms_lu[3] = {0, 0, 0};
   // light LUT builder (ldsim_light_lut_build / _trace, kernels_lutbuild.hip): staged rectangles, the tallies of the last build's

@@ -26,7 +26,7 @@ CLI = os.path.join(REPO, "larnd-sim_amd", "cli", "simulate_pixels.py")
 CALL_KEY = lrng.call_key(1, 3, 0, 0)
 WINDOW = (0.2, 1.5)
 T_MAIN, T_SHORT = 1531, 1003
-NU = 4                                     # tables per launch of light_conv_universes_kernel (option light_universes_nu)
+NU = 4                                     # tables per launch of light_plain_kernel (option light_universes_nu)
 
 
 @pytest.fixture(autouse=True)
@@ -235,7 +235,10 @@ def _grouping_universes(nominal):
 def test_grouping_gives_each_universe_what_it_gives_alone():
     """n = 1, NU, NU + 1, 9 and 64 universes with inputs, scintillation keys and response keys interleaved (groups of 1, NU and
     NU + 1 distinct tables at both stages): every universe byte-equal to itself run alone, duplicates byte-equal to each other; the
-    same bits at every setting of the option light_universes_nu"""
+    same bits at every setting of the option light_universes_nu.  The settings select instances of one kernel (light_plain_kernel
+    <RESPONSE, NU>, which the launch runs at NU = 1 too), so this sweep checks the grouping and that a pass does not read what the pool
+    buffers held, not the sum itself: the plain sum is pinned independently by the golden files and the oracle tests of
+    test_gpu_parity.py and by the Python twin of the universes in this file."""
     ch, opc, nt = _launch(model=0)
     nominal = LU.nominal()
     vs = _grouping_universes(nominal)

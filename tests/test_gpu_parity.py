@@ -1024,13 +1024,17 @@ def _truth_rows(rng, D, T, M, density, kind):
 
 
 @pytest.mark.parametrize("M,T,kind,win", [(3, 200, 0, 150.3), (50, 330, 0, 150.3), (50, 200, 2, 150.3), (64, 130, 1, 150.3),
-                                          (7, 330, 2, 150.3), (20, 330, 3, 150.3), (1, 70, 0, 2.5), (5, 40, 2, 0.0)])
+                                          (7, 330, 2, 150.3), (20, 330, 3, 150.3), (1, 70, 0, 2.5), (5, 40, 2, 0.0),
+                                          (65, 130, 0, 150.3)])
 def test_light_truth_rows_in_lds_vs_oracle(M, T, kind, win):
     """The truth slots of both response stages by `light_truth_lds_kernel` (a wave's 64 output rows in LDS, the default) against the
-    oracle's literal walk, bit for bit, and against `light_conv_kernel`'s rows in memory (option light_truth_lds 0) where that path
-    is literal: a window shorter than the waveform (the bound max(itick - conv_ticks, 0)), a waveform that is no multiple of 64 ticks,
-    zero samples (the scintillation stage skips their truth, :166), negative photons in the SiPM stage's magnitude test, rows that
-    fill up and drop ids, and -- `kind` 1, 2 -- input rows with repeated ids / holes and output rows that arrive partly filled."""
+    oracle's literal walk, bit for bit, and against `light_truth_rows_kernel`'s rows in memory (option light_truth_lds 0) where that
+    path is literal: a window shorter than the waveform (the bound max(itick - conv_ticks, 0)), a waveform that is no multiple of 64
+    ticks, zero samples (the scintillation stage skips their truth, :166), negative photons in the SiPM stage's magnitude test, rows
+    that fill up and drop ids, and -- `kind` 1, 2 -- input rows with repeated ids / holes and output rows that arrive partly filled.
+    65 slots: more than a wave can stage, both option values take the rows in memory.  At the smallest shape the scintillation stage
+    runs once more under option 0 into an `out` of ones: the plain sum accumulates into what the caller put there, beside the truth
+    rows in memory."""
     import ctypes as C
     H.load_cfg("module0")
     light, sim = consts.light, consts.sim
@@ -1069,6 +1073,17 @@ def test_light_truth_rows_in_lds_vs_oracle(M, T, kind, win):
                 for k, name in enumerate(("scint", "ids", "photons")):
                     assert np.array_equal(got[mode][k], ref[k]), f"scintillation stage, light_truth_lds {mode}, {name} (filled {filled})"
             assert (ref[1][:, :, -1] != -1).any() or M > 10 or win < 3          # (small M: rows fill up and drop ids)
+            if (M, T, kind) == (3, 200, 0):
+                o1 = [np.ones((D, T), dtype='f4'), s0[1].copy(), s0[2].copy()]
+                ref1 = [a.copy() for a in o1]
+                O.lib().o_scintillation_effect(O._p(inc), O._p(tid), O._p(tph), C.c_int32(D), C.c_int32(T), C.c_int32(M), O._p(ref1[0]),
+                                               O._p(ref1[1]), O._p(ref1[2]), C.byref(O._consts()))
+                lib.set_option("light_truth_lds", 0)
+                light_sim.calc_scintillation_effect[grid[0], grid[1]](inc, tid, tph, o1[0], o1[1], o1[2])
+                lib.set_option("light_truth_lds", 1)
+                for k, name in enumerate(("scint", "ids", "photons")):
+                    assert np.array_equal(o1[k], ref1[k]), f"scintillation stage into ones, light_truth_lds 0, {name}"
+                assert (ref1[0] != ref[0]).all()
             assert (ref[1] != s0[1]).any()
             # SiPM stage on the scintillation stage's output (negative photons added: the magnitude test), literal rows in `tid`
             s_in, s_id, s_ph = ref[0], ref[1].copy(), ref[2].copy()

@@ -3,8 +3,8 @@ driver's sizes: module0 (96 rows) and 2x2_no_modvar (384 rows x 16 000 ticks), 5
 
 For K = 1, 2, 4 and 8 distinct tables at a stage -- K scintillation tables over the one photon sum (universes that differ in TAU_T),
 K response tables over the one fluctuated array (universes that differ in LIGHT_GAIN_SCALE) -- the HIP-event time of that stage
-(ldsim_light_universes_ms) with light_conv_universes_kernel over 2, 3 and 4 tables at a time, against K launches of
-light_conv_kernel in the same session (option light_universes_nu 1: the single-table kernel, the yardstick).  Then a typical
+(ldsim_light_universes_ms) with light_plain_kernel over 2, 3 and 4 tables at a time, against K launches of its single-table
+instance in the same session (option light_universes_nu 1: what the launch itself runs, the yardstick).  Then a typical
 9-universe file (nominal and +- one knob each: PHOTON_SCALE, TAU_T, SINGLET_FRACTION, LIGHT_GAIN_SCALE) against nine times the
 launch's own light_response_ms.  Medians of the repeats after 2 warm-ups, with the spread min .. max.
 python tools/light_universes_timing.py [cfg ...] [--segments N] [--repeats R]"""
@@ -81,7 +81,7 @@ def main(cfgs, n_seg, reps):
                 lib.set_option("light_universes_nu", 4)
                 res["stages"].append(row)
                 base = row["by_nu"][1]["median"]
-                print(f"  K = {K} {label}: K launches of light_conv_kernel {spread(row['by_nu'][1]['all'])}"
+                print(f"  K = {K} {label}: K launches of one table {spread(row['by_nu'][1]['all'])}"
                       + "".join(f"; {nu} at a time {spread(row['by_nu'][nu]['all'])} = {row['by_nu'][nu]['median'] / base:.2f} x"
                                 for nu in (2, 3, 4) if nu in row["by_nu"]), flush=True)
         nine = [nominal]

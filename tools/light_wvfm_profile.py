@@ -1,6 +1,7 @@
 """Time of the device-resident light waveform chain per (event, TPC group) batch at the reference driver's sizes:
 photon sum -> scintillation -> Poisson -> SiPM response -> triggers -> digitised waveforms (with a noise spectrum).
-usage: python tools/light_wvfm_profile.py [cfg] [n_segments] [max_truth]"""
+usage: python tools/light_wvfm_profile.py [cfg] [n_segments] [max_truth] [light_truth_lds]
+light_truth_lds 0: the truth slots of the response stages on the rows in memory (light_truth_rows_kernel) instead of in LDS."""
 import os
 import sys
 import time
@@ -9,7 +10,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', 'larnd-sim_amd'
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', 'tests'))
 import numpy as np  # noqa: E402
 import helpers as H  # noqa: E402
-from larndsim_amd import batching, consts, light_sim, synth  # noqa: E402
+from larndsim_amd import batching, consts, lib, light_sim, synth  # noqa: E402
 from larndsim_amd.chain import ChargeChain  # noqa: E402
 
 cfg = sys.argv[1] if len(sys.argv) > 1 else "2x2_no_modvar"
@@ -24,6 +25,8 @@ bid, order, table = batching.assign_batches(seg)
 seg, bid = np.ascontiguousarray(seg[order]), bid[order]
 lut = synth.make_lut((14, 26, 8), 48, 100, 3)
 ch = ChargeChain()
+if len(sys.argv) > 4:
+    lib.set_option("light_truth_lds", int(sys.argv[4]))
 ch.upload(seg, bid)
 ch.quench_drift(consts.physics.BIRKS)
 ch.light_incidence(lut)
