@@ -903,6 +903,39 @@ int ldsim_light_lut_trace(ldsim_ctx* ctx, const LdsimLutBuildParams* params, con
                           uint64_t seed, int32_t* fate, int32_t* steps, double* time, double* end);
 int ldsim_light_lut_build_ms(ldsim_ctx* ctx, double* ms);
 
+/* ---- field-response builder: pixel induction tables by Shockley-Ramo (csrc/kernels_respbuild.hip) ---------------------------
+ * The producer of the table ldsim_set_response loads.  The anode is the plane z = 0; the pixel is a square pad of side pad_size
+ * centred on its pitch cell, everything else in the plane is grounded, the cathode is far away, the drift field uniform: an
+ * electron at transverse offset (x, y) from the pad centre moves straight down at v_drift.  The pad's weighting potential is the
+ * solid angle it subtends over 2 pi:
+ *   phi(x, y, z) = 1 / (2 pi) sum_{sx = -1, +1} sum_{sy = -1, +1} sx sy atan2(X Y, z sqrt(X^2 + Y^2 + z^2)),
+ *   X = x + sx a, Y = y + sy a, a = pad_size / 2        (z = 0: 1 over the pad, 0 off it, 1/2 on an edge, 1/4 on a corner).
+ * Tick edges m = 0 .. n_k: z_e(m) = v_drift max(0, (arrival_tick + 1/2) sampling - (m - 1/2) sampling): the charge reaches the
+ * plane at the upper edge of tick arrival_tick.  phibar(i, j, m) = the sum over p = 0 .. n_sub - 1 (outer), q = 0 .. n_sub - 1
+ * (inner) of phi(x, y, z_e(m)) at x = (i + (p + 1/2) / n_sub) bin_size, y = (j + (q + 1/2) / n_sub) bin_size, divided by n_sub^2;
+ * table[i][j][k] = (phibar(i, j, k + 1) - phibar(i, j, k)) / sampling: the tick average of the induced current per unit charge
+ * (Ramo), exact, without a derivative.  Entries after arrival_tick are exactly 0; a bin's entries sum to
+ * (phibar(z = 0) - phibar(z_e(0))) / sampling.  All arithmetic is f64 in one fixed order: the same bytes at any n_i, n_j, n_k.
+ * ldsim_response_build fills the host array table [n_i][n_j][n_k]; ldsim_response_build_ms: HIP-event time of the last build's
+ * kernel.  The kernel keeps a row's n_k + 1 edges in the workgroup's LDS: n_k <= LDSIM_RESPONSE_BUILD_MAX_K.
+ * LDSIM_EINVAL (with a message naming the entry): pad_size, bin_size, v_drift or sampling not finite and > 0, n_i, n_j or n_k < 1,
+ * n_k > LDSIM_RESPONSE_BUILD_MAX_K, n_sub outside 1 .. LDSIM_RESPONSE_BUILD_MAX_NSUB, arrival_tick outside [0, n_k), more than
+ * 2^31 - 1 rows. */
+#define LDSIM_RESPONSE_BUILD_MAX_K 7679
+#define LDSIM_RESPONSE_BUILD_MAX_NSUB 16
+typedef struct LdsimResponseBuildParams {   /* 56 bytes */
+  double pad_size;               /* offset 0: side of the square pad, cm */
+  double bin_size;               /* 8: transverse bin of the table, cm (RESPONSE_BIN_SIZE) */
+  double v_drift;                /* 16: cm / us */
+  double sampling;               /* 24: tick of the table, us (RESPONSE_SAMPLING) */
+  int32_t n_i, n_j, n_k;         /* 32, 36, 40: shape of the table */
+  int32_t n_sub;                 /* 44: sub-samples per bin and axis */
+  int32_t arrival_tick;          /* 48 */
+  int32_t _pad;                  /* 52 */
+} LdsimResponseBuildParams;
+int ldsim_response_build(ldsim_ctx* ctx, const LdsimResponseBuildParams* params, double* table);
+int ldsim_response_build_ms(ldsim_ctx* ctx, double* ms);
+
 /* ---- multi-GPU: the one exchange step of the batch-sharded path, RCCL over xGMI -------------------------------
  * One process per GPU; (event, TPC-group) batches are sharded over the ranks and never share a pixel, so the only
  * collective reassembles the output: row counts (all-gather), then the 24-byte hit rows (all-gather-v). */

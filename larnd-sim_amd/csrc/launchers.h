@@ -25,6 +25,9 @@ int lutbuild_trace(ldsim_ctx* ctx, const LdsimLutBuildParams* P, const LdsimLutD
                    int32_t ny, int32_t nz, int64_t voxel, int64_t photon_begin, int64_t photon_end, uint64_t seed, int32_t* fate,
                    int32_t* steps, double* time, double* end);
 
+// ---- kernels_respbuild.hip ---------------------------------------------------------------------------------------------------
+int respbuild_build(ldsim_ctx* ctx, const LdsimResponseBuildParams* P, double* table);
+
 // ---- sort.hip ----------------------------------------------------------------------------------------------------------
 int sort_make_keys(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
                    int64_t n_entries, unsigned long long* keys, int32_t* vals, unsigned long long* counters);

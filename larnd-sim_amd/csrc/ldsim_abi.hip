@@ -684,6 +684,20 @@ extern "C" int ldsim_light_lut_build_ms(ldsim_ctx* ctx, double* ms) {
   return 0;
 }
 
+// ---- field-response builder (kernels_respbuild.hip) ------------------------------------------------------------------------
+extern "C" int ldsim_response_build(ldsim_ctx* ctx, const LdsimResponseBuildParams* params, double* table) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return respbuild_build(ctx, params, table);
+}
+
+extern "C" int ldsim_response_build_ms(ldsim_ctx* ctx, double* ms) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && ms, "null argument");
+  *ms = ctx->ms_rb;
+  return 0;
+}
+
 // ---- drift-field maps ----------------------------------------------------------------------------------------------------
 static int fmap_upload_desc(ldsim_ctx* ctx) {
   CK(ctx->d_fmap.ensure(sizeof(ctx->h_fmap)));

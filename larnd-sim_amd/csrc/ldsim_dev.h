@@ -386,6 +386,10 @@ struct ldsim_ctx {
   int lb_tile = 1;               // option lut_build_lds_tile: 0 sends every arrival to global atomics (the path of a tile too big for LDS)
   Event lb_ev[2];                // around lut_build_kernel of the last build (ldsim_light_lut_build_ms)
   double ms_lb = 0;
+  // field-response builder (ldsim_response_build, kernels_respbuild.hip): the last build's table
+  DevBuf rb_table;               // f64 [n_i][n_j][n_k]
+  Event rb_ev[2];                // around response_build_kernel of the last build (ldsim_response_build_ms)
+  double ms_rb = 0;
   // random streams (kernels_rng.hip): numba-style table of xoroshiro128p states, grown on demand
   DevBuf d_rng;
   int64_t rng_n = 0;

@@ -94,6 +94,15 @@ class LdsimLutDetector(C.Structure):
     _fields_ = [("wall", C.c_int32), ("pad", C.c_int32), ("lo", C.c_double * 2), ("hi", C.c_double * 2)]
 
 
+class LdsimResponseBuildParams(C.Structure):
+    """include/ldsim.h LdsimResponseBuildParams (ldsim_response_build): 56 bytes"""
+    _fields_ = [("pad_size", C.c_double), ("bin_size", C.c_double), ("v_drift", C.c_double), ("sampling", C.c_double),
+                ("n_i", C.c_int32), ("n_j", C.c_int32), ("n_k", C.c_int32), ("n_sub", C.c_int32), ("arrival_tick", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
+RESPONSE_BUILD_MAX_K = 7679       # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_K
+RESPONSE_BUILD_MAX_NSUB = 16      # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_NSUB
 LUT_MAX_DETECTORS = 1024    # include/ldsim.h LDSIM_LUT_MAX_DETECTORS
 LUT_MAX_NPROF = 512         # include/ldsim.h LDSIM_LUT_MAX_NPROF
 FEE_UNIVERSES_MAX = 64      # include/ldsim.h LDSIM_FEE_UNIVERSES_MAX
