@@ -118,6 +118,10 @@ int ldsim_host_free(void* p);
 /* test seam: device buffers, streams and events the library holds in this process, over all contexts (page-locked host memory
  * is not counted).  All three are 0 once every context is destroyed. */
 int ldsim_debug_live_objects(int64_t counts[3]);
+/* test seam (host arithmetic, no device): the key bits the chain's pair-list sort looks at for a largest pixel id and a batch
+ * count.  ranges = {e0, b1, e1}: a stable LSD sort over [0, e0), then one over [b1, e1) if e1 > b1 (else none).  Every key
+ * batch << 36 | pixel << 4 | ring code with pixel <= pixel_max and batch < n_batches is zero outside them. */
+int ldsim_debug_sort_key_ranges(uint64_t pixel_max, int64_t n_batches, int32_t ranges[3]);
 int ldsim_set_consts(ldsim_ctx* ctx, const LdsimConsts* consts);
 /* cp.load(response_file) (cli/simulate_pixels.py:436): f64 table [ni][nj][nk], host pointer */
 int ldsim_set_response(ldsim_ctx* ctx, const double* response, int32_t ni, int32_t nj, int32_t nk);

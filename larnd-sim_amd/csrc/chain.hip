@@ -159,10 +159,12 @@ int chain_tracks_current(ldsim_ctx* ctx, const int32_t* d_pixels, int P, float* 
   int rc = run_tracks_current(ctx, a, ctx->seg.n, counters, &split_timed);
   ctx->mc_current = keep_mc;
   if (rc) return rc;
-  unsigned long long h_cnt[ST_N], h_raw[STAT_WORDS];
-  HIPCHK(hipMemcpyAsync(h_raw, counters, STAT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  unsigned long long h_cnt[ST_N];
+  CK(ctx->readback.ensure(sizeof(ChainReadback)));
+  ChainReadback* rb = ctx->readback.as<ChainReadback>();
+  HIPCHK(hipMemcpyAsync(rb->raw, counters, STAT_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  stat_sum(h_raw, h_cnt);
+  stat_sum(rb->raw, h_cnt);
   stats_from_counters(ctx->stage_stats, h_cnt);
   return 0;
 }
@@ -198,12 +200,6 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   hipStream_t st = ctx->stream;
   HIPCHK(hipEventRecord(ctx->ev[0], st));
 
-  // ---- misc block (ChainMisc) -------------------------------------------------------------------------------------------
-  CK(ctx->scratch[SB_MISC].ensure(MISC_BYTES));
-  ChainMisc* misc = ctx->scratch[SB_MISC].as<ChainMisc>();
-  unsigned long long* counters = misc->counters;
-  HIPCHK(hipMemsetAsync(misc, 0, offsetof(ChainMisc, tail), st));
-
   // batch id range of this call: the non-negative ids are non-decreasing (checked at upload against the host copy kept
   // in the ctx), so the first and the last one are the range; negative = not simulated
   int32_t b_first = 0, b_last = 0;
@@ -237,39 +233,44 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
     return LDSIM_EINVAL;
   }
 
-  // ---- a8 time_intervals per batch, and the per-batch max tran_diff that sets max_radius -------------------------------
-  CK(ctx->scratch[SB_STARTS].ensure((size_t)n * 8));
-  CK(ctx->scratch[SB_BATCH].ensure(batch_block_bytes(n_batches)));
-  const BatchBlock bb = batch_block(ctx->scratch[SB_BATCH].p, n_batches);
+  // ---- misc block (ChainMisc) and, behind it, the per-batch block: one memset clears both ------------------------------------
+  CK(ctx->scratch[SB_MISC].ensure(MISC_BYTES + batch_block_bytes(n_batches)));
+  ChainMisc* misc = ctx->scratch[SB_MISC].as<ChainMisc>();
+  unsigned long long* counters = misc->counters;
+  const BatchBlock bb = batch_block((char*)misc + MISC_BYTES, n_batches);
   int32_t *d_tmax_b = bb.tmax, *d_first_b = bb.first, *d_radius_b = bb.radius;
   unsigned long long* d_tran_b = bb.tran;
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_BATCH].p, 0, batch_block_bytes(n_batches), st));
-  double* d_starts = ctx->scratch[SB_STARTS].as<double>();
-  CK(sort_tmax_batch(ctx, seg_begin, n, batch0, d_starts, d_tmax_b, d_tran_b));
-  CK(sort_batch_first(ctx, seg_begin, n, batch0, d_first_b));
+  HIPCHK(hipMemsetAsync(misc, 0, MISC_BYTES + batch_block_bytes(n_batches), st));
+  // the words the launch reads back between its stages land in page-locked memory of the context (nothing is in flight here:
+  // every launch ends with a synchronisation)
+  CK(ctx->readback.ensure(chain_readback_bytes(n_batches)));
+  ChainReadback* rb = ctx->readback.as<ChainReadback>();
+  const ChainReadbackBatch rbb = chain_readback_batch(rb, n_batches);
 
-  // ---- a5 max_pixels (cli/simulate_pixels.py:918-928) ---------------------------------------------------------------------
-  CK(seg_launch_max_pixels(ctx, seg_begin, seg_end, &misc->nmax, &misc->tran_bits));
-  int32_t nmax = 0;
-  std::vector<unsigned long long> h_tran(n_batches);
-  std::vector<int32_t> h_radius(n_batches);
-  HIPCHK(hipMemcpyAsync(&nmax, &misc->nmax, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h_tran.data(), d_tran_b, n_batches * 8, hipMemcpyDeviceToHost, st));
+  // ---- the segment front in one pass: a8 time_intervals per batch, the batches' first segments, a5 max_pixels
+  // (cli/simulate_pixels.py:918-928) and the per-batch max tran_diff that sets max_radius ------------------------------------------
+  CK(ctx->scratch[SB_STARTS].ensure((size_t)n * 8));
+  double* d_starts = ctx->scratch[SB_STARTS].as<double>();
+  CK(seg_launch_front(ctx, seg_begin, seg_end, batch0, d_starts, &misc->nmax, d_tmax_b, d_first_b, d_tran_b));
+  // read-back 1: nmax and the batches' tran_diff size P, and with it every buffer of the pixel stages
+  HIPCHK(hipMemcpyAsync(&rb->nmax, &misc->nmax, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(rbb.tran, d_tran_b, n_batches * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  const int32_t nmax = rb->nmax;
   int radius = 0;
   for (int64_t b = 0; b < n_batches; b++) {
     double mt;
-    memcpy(&mt, &h_tran[b], 8);
-    h_radius[b] = (int32_t)ceil(mt * 5 / h.pixel_pitch);      // max_radius of the batch
-    radius = h_radius[b] > radius ? h_radius[b] : radius;
+    memcpy(&mt, &rbb.tran[b], 8);
+    rbb.radius[b] = (int32_t)ceil(mt * 5 / h.pixel_pitch);      // max_radius of the batch
+    radius = rbb.radius[b] > radius ? rbb.radius[b] : radius;
   }
-  HIPCHK(hipMemcpyAsync(d_radius_b, h_radius.data(), n_batches * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_radius_b, rbb.radius, n_batches * 4, hipMemcpyHostToDevice, st));
   const int P = (2 * radius + 1) * nmax + (1 + 2 * radius) * radius * 2;
   ctx->stats.max_active = nmax;
   ctx->stats.max_neigh = P;
   if (nmax == 0 || P == 0) return 0;
 
-  // ---- a6 get_pixels -----------------------------------------------------------------------------------------------------
+  // ---- a6 get_pixels (the kernel writes every slot of its rows, the empty ones as -1) ------------------------------------------------
   const int64_t n_entries = n * P;
   if (n_entries >= 0x7fffffffLL) {
     ldsim_set_error("chain call too large: %lld (segment, pixel) slots; split the segment range", (long long)n_entries);
@@ -278,15 +279,15 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   CK(ctx->scratch[SB_ACTIVE].ensure((size_t)n * nmax * 4));
   CK(ctx->scratch[SB_NEIGH].ensure((size_t)n_entries * 4));
   CK(ctx->scratch[SB_NRAD].ensure((size_t)n_entries * 4));
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_ACTIVE].p, 0xFF, (size_t)n * nmax * 4, st));
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_NEIGH].p, 0xFF, (size_t)n_entries * 4, st));
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_NRAD].p, 0xFF, (size_t)n_entries * 4, st));
   int32_t* d_neigh = ctx->scratch[SB_NEIGH].as<int32_t>();
   int32_t* d_nrad = ctx->scratch[SB_NRAD].as<int32_t>();
   CK(seg_launch_get_pixels(ctx, seg_begin, seg_end, radius, ctx->scratch[SB_ACTIVE].as<int32_t>(), nmax, d_neigh, d_nrad,
                            P, nullptr, d_radius_b, batch0));
 
   // ---- a7 unique pixels: stable radix sort of (batch, pixel, ring code) --------------------------------------------------------
+  // The empty slots (three quarters of the entries of the module0 bench) never become keys: one stable selection forms the key of
+  // every entry where it reads it and keeps the valid (key, entry index) pairs -- equal keys keep the order of their entries -- and
+  // the count comes back with the per-batch tick counts, before the sort instead of after it.
   CK(ctx->scratch[SB_KEYS].ensure((size_t)n_entries * 8));
   CK(ctx->scratch[SB_KEYS2].ensure((size_t)n_entries * 8));
   CK(ctx->scratch[SB_VALS].ensure((size_t)n_entries * 4));
@@ -295,53 +296,43 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   unsigned long long* d_keys2 = ctx->scratch[SB_KEYS2].as<unsigned long long>();
   int32_t* d_vals = ctx->scratch[SB_VALS].as<int32_t>();
   int32_t* d_vals2 = ctx->scratch[SB_VALS2].as<int32_t>();
-  CK(sort_make_keys(ctx, d_neigh, d_nrad, seg_begin, batch0, P, n_entries, d_keys, d_vals, counters));
-  // The empty slots (key ~0: three quarters of the entries of the module0 bench) are dropped before the sort -- a stable compaction, so
-  // equal keys keep the order of their entries -- and the count comes back with the per-batch tick counts, before the sort instead
-  // of after it.
-  CK(sort_compact_valid(ctx, d_keys, n_entries, d_keys2, d_vals2, &misc->n_compact));      // (its count: a word of its own; the launch uses counters[ST_VALID_PAIRS])
-  unsigned long long n_valid_ull = 0;
-  std::vector<int32_t> h_tmax(n_batches);
-  HIPCHK(hipMemcpyAsync(&n_valid_ull, &counters[ST_VALID_PAIRS], 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h_tmax.data(), d_tmax_b, n_batches * 4, hipMemcpyDeviceToHost, st));
+  CK(sort_select_pairs(ctx, d_neigh, d_nrad, seg_begin, batch0, P, n_entries, d_keys, d_vals, &counters[ST_VALID_PAIRS]));
+  // read-back 2: the valid pairs size the sort and everything per pair; the tick counts size the current rows
+  HIPCHK(hipMemcpyAsync(&rb->n_valid, &counters[ST_VALID_PAIRS], 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(rbb.tmax, d_tmax_b, n_batches * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  const int64_t n_valid = (int64_t)rb->n_valid;
   {
-    // key = batch << 36 | pixel << 4 | ring code: the sort stops above the launch's batch count (20 batches: 41 bits, six 8-bit passes
-    // instead of eight)
-    int bb = 0;
-    while ((1ll << bb) < n_batches) bb++;
-    CK(sort_pairs_bits(ctx, d_keys2, d_keys, d_vals2, d_vals, (int64_t)n_valid_ull, 0, 36 + bb));
-    std::swap(d_keys, d_keys2);         // (d_keys2 / d_vals2: the sorted list, as below)
-    std::swap(d_vals, d_vals2);
+    // key = batch << 36 | pixel << 4 | ring code.  The sort looks at the bits that can differ only (sort_key_ranges): up to the top of
+    // the largest pixel id these constants allow, and the launch's batch bits (module0, 20 batches: 24 + 5 bits, four 8-bit passes
+    // where [0, 41) takes six)
+    int kr[3];
+    sort_key_ranges((unsigned long long)h.n_pixels[0] * h.n_pixels[1] * h.n_tpc - 1, n_batches, kr);
+    CK(sort_pairs_bits(ctx, d_keys, d_keys2, d_vals, d_vals2, n_valid, 0, kr[0]));
+    if (kr[2] > kr[1]) {
+      CK(sort_pairs_bits(ctx, d_keys2, d_keys, d_vals2, d_vals, n_valid, kr[1], kr[2]));
+      std::swap(d_keys, d_keys2);
+      std::swap(d_vals, d_vals2);
+    }
+    // (d_keys2 / d_vals2: the sorted list, as below)
   }
-  const int64_t n_valid = (int64_t)n_valid_ull;
   ctx->stats.n_pairs = n_valid;
   int32_t T = 0;
-  for (auto v : h_tmax) T = v > T ? v : T;
+  for (int64_t b = 0; b < n_batches; b++) T = rbb.tmax[b] > T ? rbb.tmax[b] : T;
   ctx->stats.max_length = T;
   if (n_valid == 0 || T == 0) return 0;
 
+  // a pair's unique-pixel index: the exclusive scan of the head flags.  The last index and the last flag give the number of unique
+  // pixels U; nothing in the current stage needs it (CurArgs carries no per-pixel array), so their copies are only queued here and
+  // read behind the synchronisation the current stage makes anyway (read-back 3, below)
   CK(ctx->scratch[SB_HEADS].ensure((size_t)n_valid * 4 + 16));
   CK(ctx->scratch[SB_UIDX].ensure((size_t)n_valid * 4 + 16));
   int32_t* d_heads = ctx->scratch[SB_HEADS].as<int32_t>();
   int32_t* d_uidx = ctx->scratch[SB_UIDX].as<int32_t>();
   CK(sort_heads(ctx, d_keys2, n_valid, d_heads));
   CK(sort_exclusive_scan_i32(ctx, d_heads, d_uidx, n_valid));
-  int32_t last_idx = 0, last_head = 0;
-  HIPCHK(hipMemcpyAsync(&last_idx, d_uidx + (n_valid - 1), 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&last_head, d_heads + (n_valid - 1), 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const int64_t U = (int64_t)last_idx + last_head;
-  ctx->stats.n_unique = U;
-  ctx->chain_U = U;
-
-  CK(ctx->scratch[SB_UPIX].ensure((size_t)U * 4));
-  CK(ctx->scratch[SB_UBATCH].ensure((size_t)U * 4));
-  CK(ctx->scratch[SB_PIXOFF].ensure((size_t)(U + 1) * 8));
-  int32_t* d_upix = ctx->scratch[SB_UPIX].as<int32_t>();
-  int32_t* d_ubatch = ctx->scratch[SB_UBATCH].as<int32_t>();
-  int64_t* d_uoff = ctx->scratch[SB_PIXOFF].as<int64_t>();
-  CK(sort_fill_unique(ctx, d_keys2, d_heads, d_uidx, n_valid, batch0, d_upix, d_ubatch, d_uoff, U));
+  HIPCHK(hipMemcpyAsync(&rb->last_idx, d_uidx + (n_valid - 1), 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&rb->last_head, d_heads + (n_valid - 1), 4, hipMemcpyDeviceToHost, st));
 
   // ---- a9-a12 induced current per sorted pair -------------------------------------------------------------------------------------
   CK(ctx->scratch[SB_WAVES].ensure((size_t)n_valid * T * 4));
@@ -368,6 +359,20 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   bool split_timed = false, win_used = false;
   CK(run_tracks_current(ctx, a, n, counters, &split_timed, &win_used));
   HIPCHK(hipEventRecord(ctx->ev[2], st));
+
+  // ---- the unique pixels (read-back 3: U, queued before the current stage) ---------------------------------------------------------------
+  // gform_launch has synchronised behind that copy for its pool size; every other current path gets a synchronisation here
+  if (!ctx->gform_rec.valid) HIPCHK(hipStreamSynchronize(st));
+  const int64_t U = (int64_t)rb->last_idx + rb->last_head;
+  ctx->stats.n_unique = U;
+  ctx->chain_U = U;
+  CK(ctx->scratch[SB_UPIX].ensure((size_t)U * 4));
+  CK(ctx->scratch[SB_UBATCH].ensure((size_t)U * 4));
+  CK(ctx->scratch[SB_PIXOFF].ensure((size_t)(U + 1) * 8));
+  int32_t* d_upix = ctx->scratch[SB_UPIX].as<int32_t>();
+  int32_t* d_ubatch = ctx->scratch[SB_UBATCH].as<int32_t>();
+  int64_t* d_uoff = ctx->scratch[SB_PIXOFF].as<int64_t>();
+  CK(sort_fill_unique(ctx, d_keys2, d_heads, d_uidx, n_valid, batch0, d_upix, d_ubatch, d_uoff, U));
 
   // ---- a13-a16 per-pixel sum, trigger scan, digitise ---------------------------------------------------------------------------------
   CK(ctx->scratch[SB_ADC].ensure((size_t)U * A * 8));
@@ -441,11 +446,12 @@ int chain_run(ldsim_ctx* ctx, int64_t seg_begin, int64_t seg_end, int want_fract
   CK(ctx->scratch[SB_HITS].ensure((size_t)U * A * 24 + 24));
   CK(sort_compact_hits(ctx, d_upix, d_ubatch, d_hitcnt, d_hitoff, F.adc_digit, F.adc_ticks, A, U,
                        ctx->scratch[SB_HITS].as<int32_t>()));
-  unsigned long long h_cnt[ST_N], h_raw[STAT_WORDS];
-  HIPCHK(hipMemcpyAsync(h_raw, counters, STAT_BYTES, hipMemcpyDeviceToHost, st));
+  // read-back 4: the launch counters, with the launch's last synchronisation
+  unsigned long long h_cnt[ST_N];
+  HIPCHK(hipMemcpyAsync(rb->raw, counters, STAT_BYTES, hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(ctx->ev[4], st));
   HIPCHK(hipStreamSynchronize(st));
-  stat_sum(h_raw, h_cnt);
+  stat_sum(rb->raw, h_cnt);
   if (ctx->debug_gform & 128)       // timing tools: cycle stamps of gcorr_kernel's waves (kernels_gcorr.hip)
     fprintf(stderr, "gcorr stamps (shader cycles, summed over waves): info %llu stage %llu G %llu P %llu edges %llu tail %llu life %llu\n",
             h_cnt[ST_GCORR_INFO], h_cnt[ST_GCORR_STAGE], h_cnt[ST_GCORR_G], h_cnt[ST_GCORR_P], h_cnt[ST_GCORR_EDGES],

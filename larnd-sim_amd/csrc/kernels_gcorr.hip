@@ -1085,7 +1085,9 @@ __global__ void __launch_bounds__(GT, GFUSED_WAVES) gcorr_fused_kernel(GArgs GA,
 __global__ void __launch_bounds__(256) gbig_list_kernel(GInfo* __restrict__ gi, int64_t n, int TT, int b0, int b1, int M,
                                                         int32_t* __restrict__ lists /* [2][n] */,
                                                         unsigned long long* __restrict__ counts /* [2] */, int fused,
-                                                        int32_t* __restrict__ fused_lists /* [2][n] */, unsigned long long* __restrict__ fused_counts /* [2] */) {
+                                                        int32_t* __restrict__ fused_lists /* [2][n] */, unsigned long long* __restrict__ fused_counts /* [2] */,
+                                                        const unsigned long long* __restrict__ off /* [n] */, unsigned long long* __restrict__ total,
+                                                        unsigned long long* __restrict__ total_stat) {
   __shared__ unsigned s_cnt[4][GL_ITEMS * 4 + 1];      // [list][chunk of 256 pairs][wave]: listed pairs, then their exclusive prefix
   __shared__ unsigned long long s_base[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1095,6 +1097,11 @@ __global__ void __launch_bounds__(256) gbig_list_kernel(GInfo* __restrict__ gi, 
   for (int k = 0; k < GL_ITEMS; k++) {
     const int64_t i = i0 + k * 256;
     int l = 0;
+    if (i < n) {      // record offset: the exclusive scan of the sizes pair_setup_kernel wrote; the pool's size from the last pair
+      const unsigned long long o = off[i];
+      gi[i].off = o;
+      if (i == n - 1) *total = *total_stat = o + gi[i].size;
+    }
     if (i < n && gi[i].status == 1) {
       const int ncol = gi[i].ncol, NJ = gi[i].NJ, NU = gi[i].NU, NB = gi[i].NB, NQ = gi[i].NQ;
       l = g_lds_class(ncol, NJ, NU, TT, b0, b1, M);
@@ -1138,20 +1145,6 @@ __global__ void __launch_bounds__(256) gbig_list_kernel(GInfo* __restrict__ gi, 
   }
 }
 
-// ---- record offsets: exclusive scan of the sizes pair_setup_kernel wrote ------------------------------------------------------------
-__global__ void __launch_bounds__(256) gsize_gather_kernel(const GInfo* __restrict__ gi, int64_t n, unsigned long long* __restrict__ sz) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) sz[i] = gi[i].size;
-}
-__global__ void __launch_bounds__(256) goff_scatter_kernel(GInfo* __restrict__ gi, int64_t n, const unsigned long long* __restrict__ off,
-                                                           unsigned long long* __restrict__ total) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
-    gi[i].off = off[i];
-    if (i == n - 1) *total = off[i] + gi[i].size;
-  }
-}
-
 // M of the form for these constants, 0 = configuration not covered (caller uses the monolithic kernel)
 int gform_M(const ldsim_ctx* ctx, const CurArgs& args) {
   const LdsimConsts& h = ctx->h_consts;
@@ -1182,20 +1175,18 @@ int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters,
   if ((rc = ctx->scratch[SB_PPAR].ensure(qpair_params_bytes(n)))) return rc;
   if ((rc = ctx->scratch[SB_GINFO].ensure((size_t)n * sizeof(GInfo)))) return rc;
   if ((rc = ctx->scratch[SB_GFLAGS].ensure((size_t)(n + 16) * 4))) return rc;
-  if ((rc = ctx->scratch[SB_GSIZES].ensure((size_t)(2 * n + 8) * 8 + (size_t)(7 * n + 2) * 4))) return rc;      // sizes | offsets | total, 2 class counts, n_wg, n_flagged, n_w2, 2 fused counts | 2 class lists | wg list | flagged list | wide-wave list | 2 fused lists
+  if ((rc = ctx->scratch[SB_GSIZES].ensure((size_t)(n + 8) * 8 + (size_t)(7 * n + 2) * 4))) return rc;      // offsets | total, 2 class counts, n_wg, n_flagged, n_w2, 2 fused counts | 2 class lists | wg list | flagged list | wide-wave list | 2 fused lists
   SplitArgs S{};
   S.c = a;
   GInfo* gi = ctx->scratch[SB_GINFO].as<GInfo>();
   if ((rc = ctx->scratch[SB_GMAPS].ensure((size_t)n * G_MAPB))) return rc;      // the wave tables kernel's maps (gform.h)
   if ((rc = qpair_setup_launch(ctx, S, M, ctx->scratch[SB_PPAR].p, gi, ctx->scratch[SB_GMAPS].p))) return rc;
-  unsigned long long* d_sz = ctx->scratch[SB_GSIZES].as<unsigned long long>();
-  unsigned long long* d_off = d_sz + n;
+  // record offsets: the exclusive scan of GInfo::size, read from the GInfo array by the scan; gbig_list_kernel below puts them
+  // into the GInfo and the pool's size into d_total[0] and the statistics slot of the split paths (doubles)
+  unsigned long long* d_off = ctx->scratch[SB_GSIZES].as<unsigned long long>();
   unsigned long long* d_total = d_off + n;
   const unsigned g0 = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(gsize_gather_kernel, dim3(g0), dim3(256), 0, st, gi, n, d_sz);
-  if ((rc = sort_exclusive_scan_u64(ctx, d_sz, d_off, n))) return rc;
-  hipLaunchKernelGGL(goff_scatter_kernel, dim3(g0), dim3(256), 0, st, gi, n, d_off, d_total);
-  HIPCHK(hipGetLastError());
+  if ((rc = sort_scan_record_sizes(ctx, gi, d_off, n))) return rc;
   GArgs GA{};
   if ((rc = resp_pad_ensure(ctx, a, &GA.k_lo, &GA.k_hi, &GA.nkp))) return rc;
   {
@@ -1230,15 +1221,16 @@ int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters,
   const bool fused_on = GW == 2 && M == 1 && !(ctx->debug_gform & (131072 | 4096 | 65536));
   const bool fused_list = fused_on && !(ctx->debug_gform & 262144);
   int32_t* d_fused = d_big + 5 * n;                // [2][n], behind the wide-wave list
-  hipLaunchKernelGGL(gbig_list_kernel, dim3((unsigned)((n + GL_ITEMS * 256 - 1) / (GL_ITEMS * 256))), dim3(256), 0, st, gi, n, TT, b0, b1, Mz, d_big, d_total + 1, fused_list ? 1 : 0, d_fused, d_total + 6);
+  hipLaunchKernelGGL(gbig_list_kernel, dim3((unsigned)((n + GL_ITEMS * 256 - 1) / (GL_ITEMS * 256))), dim3(256), 0, st, gi, n, TT, b0, b1, Mz, d_big, d_total + 1, fused_list ? 1 : 0, d_fused, d_total + 6, d_off, d_total, &counters[ST_POOL_CURSOR]);
   HIPCHK(hipGetLastError());
   GA.gi = gi;
   GA.dbg = (ctx->debug_gform & ~64) | (ctx->gform_wave_tables ? 0 : 64);
   GA.c.n_pairs = n;
   int32_t* d_w2 = d_wg + 2 * n;                    // (d_wg + n: the flagged list)
   if ((rc = gtables_list_launch(ctx, GA, d_wg, d_total + 3, d_w2, d_total + 5))) return rc;
-  unsigned long long h_tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  HIPCHK(hipMemcpyAsync(h_tot, d_total, 64, hipMemcpyDeviceToHost, st));
+  if ((rc = ctx->readback.ensure(sizeof(ChainReadback)))) return rc;      // (the chain has sized it already: kept, with what is queued into it)
+  const unsigned long long* h_tot = ctx->readback.as<ChainReadback>()->gform_tot;
+  HIPCHK(hipMemcpyAsync(ctx->readback.as<ChainReadback>()->gform_tot, d_total, 64, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const unsigned long long total = h_tot[0], n_wg = h_tot[3], n_w2 = h_tot[5];
   const unsigned long long n_fused[2] = {fused_on ? h_tot[6] : 0, fused_on ? h_tot[7] : 0};
@@ -1276,7 +1268,6 @@ int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters,
             s_nu / n1, s_nq / n1, small, mid);
   }
   if ((rc = ctx->scratch[SB_GREC].ensure((size_t)(total + 16) * 8))) return rc;
-  HIPCHK(hipMemsetAsync(&counters[ST_POOL_CURSOR], 0, 8, st));
   GA.c = a;
   GA.pp = ctx->scratch[SB_PPAR].as<const PairParams>();
   GA.gi = gi;
@@ -1342,8 +1333,6 @@ int gform_launch(ldsim_ctx* ctx, const CurArgs& a, unsigned long long* counters,
       if ((rc = corr(cls, 0, (int64_t)n_cls[cls]))) return rc;
   }
   HIPCHK(hipEventRecord(ctx->ev[6], st));
-  // the pool's size in the statistics slot of the split paths (doubles)
-  HIPCHK(hipMemcpyAsync(&counters[ST_POOL_CURSOR], d_total, 8, hipMemcpyDeviceToDevice, st));
   *flags_out = GA.flags;
   hipLaunchKernelGGL(gflag_list_kernel, dim3(g0), dim3(256), 0, st, GA.flags, n, d_wg + n, d_total + 4);
   HIPCHK(hipGetLastError());

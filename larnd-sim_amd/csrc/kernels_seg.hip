@@ -4,6 +4,7 @@
 #include "launchers.h"
 #include "rng.h"
 #include "seg_charge.h"   // recomb_at, fmap_eval
+#include "wave_ops.h"
 
 // ---- AoS <-> SoA ------------------------------------------------------------------------------------------
 __device__ __forceinline__ double load_field(const unsigned char* rec, int off, int code) {
@@ -397,6 +398,56 @@ __global__ void __launch_bounds__(256) max_pixels_kernel(SegStore s, const Ldsim
   }
 }
 
+// The chain's front in one pass over the segment columns of [begin, begin + n): a8 time_intervals per batch (starts; the batch's
+// largest tick count by atomic max), the first relative segment index of every batch, a5 max_pixels over every segment of the
+// range, and the batch's largest tran_diff (sets its max_radius, cli/simulate_pixels.py:918) as order-preserving float bits.
+// n_max and the per-batch words are zeroed by the caller.
+// Segments are sorted by batch, so nearly every wave holds one batch: one atomic per wave instead of one per segment on
+// the few per-batch cells (50 k contended atomics cost 0.7 ms per launch).
+__global__ void __launch_bounds__(256) seg_front_kernel(SegStore s, const LdsimConsts* __restrict__ c, int64_t begin, int64_t n,
+                                                        int32_t batch0, double* __restrict__ starts, int32_t* __restrict__ n_max,
+                                                        int32_t* __restrict__ tmax_b, int32_t* __restrict__ first_b,
+                                                        unsigned long long* __restrict__ tran_b) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int32_t b = -1, len_i = 0, k = 0;
+  double td = 0;
+  if (r < n) {
+    const int64_t i = begin + r;
+    double t_end = py_round((s.f[LDSIM_T_END][i] + 1) / c->time_sampling) * c->time_sampling;
+    double t_start = py_round((s.f[LDSIM_T_START][i] - c->time_padding) / c->time_sampling) * c->time_sampling;
+    starts[r] = t_start;
+    b = s.batch[i];
+    if (b >= 0) {
+      double len = ceil((t_end - t_start) / c->time_sampling);
+      if (len > 0 && len < 2.0e9) len_i = (int32_t)len;
+      td = s.f[LDSIM_TRAN_DIFF][i];
+      if (!(td > 0)) td = 0;
+      if (r == 0 || s.batch[i - 1] != b) first_b[b - batch0] = (int32_t)r;
+    }
+    Walk w;
+    if (walk_init(s, c, i, w)) k = (int32_t)walk_pixels(c, w, nullptr, 0);
+  }
+  const int km = wave_max_i32(k);
+  if (lane == 0 && km > 0) atomicMax(n_max, km);
+  const unsigned long long act = __ballot(b >= 0);
+  if (act == 0) return;
+  const int first = __ffsll((long long)act) - 1;
+  const int bref = __builtin_amdgcn_readlane(b, first);
+  if (__ballot(b >= 0 && b != bref) == 0) {
+    const int m = wave_max_i32(len_i);
+    const double tm = wave_max_f64(td);
+    if (lane == first) {
+      if (m > 0) atomicMax(&tmax_b[bref - batch0], m);
+      if (tm > 0) atomicMax(&tran_b[bref - batch0], (unsigned long long)__double_as_longlong(tm));
+    }
+    return;
+  }
+  if (b < 0) return;
+  if (len_i > 0) atomicMax(&tmax_b[b - batch0], len_i);
+  if (td > 0) atomicMax(&tran_b[b - batch0], (unsigned long long)__double_as_longlong(td));
+}
+
 __device__ __forceinline__ int32_t ring_code(int x_r, int y_r) {  // pixels_from_track.py:246-269
   int dx = abs(x_r), dy = abs(y_r), dmax = max(dx, dy), dmin = min(dx, dy), dsum = dmax + dmin;
   if (dsum > 4) return -1;
@@ -407,55 +458,81 @@ __device__ __forceinline__ int32_t ring_code(int x_r, int y_r) {  // pixels_from
 }
 
 // a6 get_pixels: active pixel ids (walk order, -1 gaps), first-seen-unique neighbour union, ring codes.
-// Outputs must be pre-filled with -1 (the reference's cp.full(..., -1)).
-__global__ void __launch_bounds__(128) get_pixels_kernel(SegStore s, const LdsimConsts* __restrict__ c, int64_t begin,
+// The kernel writes every slot of its rows, the empty ones (-1, the reference's cp.full(..., -1)) too: the active rows of a
+// workgroup's segments are cleared before the walk, which leaves gaps, and the slots of the neighbour and ring-code rows behind
+// a segment's count are written after it -- by the whole workgroup, whose rows are one contiguous range.  No slot of
+// [0, n * max_active) and [0, n * P) keeps what an earlier launch left in the buffers.
+#define GP_THREADS 128
+__global__ void __launch_bounds__(GP_THREADS) get_pixels_kernel(SegStore s, const LdsimConsts* __restrict__ c, int64_t begin,
                                                          int64_t end, int radius, int32_t* __restrict__ active,
                                                          int max_active, int32_t* __restrict__ neigh,
                                                          int32_t* __restrict__ nrad, int P,
                                                          double* __restrict__ n_list,
                                                          const int32_t* __restrict__ radius_b, int32_t batch0) {
-  int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t i = begin + r;
-  if (i >= end) return;
-  // the reference derives max_radius per batch from max(tran_diff) (cli/simulate_pixels.py:918)
-  if (radius_b) {
-    int32_t b = s.batch[i];
-    radius = b >= 0 ? radius_b[b - batch0] : 0;
+  __shared__ int s_count[GP_THREADS];
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * GP_THREADS;
+  const int64_t left = end - begin - r0;
+  const unsigned rows = (unsigned)(left < GP_THREADS ? left : GP_THREADS);      // (the grid covers the range: rows >= 1)
+  {
+    int32_t* a0 = active + r0 * max_active;
+    const unsigned na = rows * (unsigned)max_active;
+    for (unsigned e = tid; e < na; e += GP_THREADS) a0[e] = -1;
   }
-  int32_t* act = active + r * max_active;
-  int32_t* ng = neigh + r * P;
-  int32_t* nr = nrad + r * P;
-  Walk w;
-  if (!walk_init(s, c, i, w)) {
-    if (n_list) n_list[r] = 0;
-    return;
-  }
-  walk_pixels(c, w, act, max_active);
+  __syncthreads();
+  const int64_t r = r0 + tid;
+  const int64_t i = begin + r;
   int count = 0;
-  for (int p = 0; p < max_active; p++) {
-    int32_t a = act[p];
-    if (a == -1) continue;
-    int64_t ax, ay, pl;
-    id2pixel(c, a, ax, ay, pl);
-    for (int x_r = -radius; x_r <= radius; x_r++)
-      for (int y_r = -radius; y_r <= radius; y_r++) {
-        int64_t nx = ax + x_r, ny = ay + y_r;
-        if (!pix_in_range(c, nx, ny, pl)) continue;
-        int32_t np_ = (int32_t)pixel2id(c, nx, ny, pl);
-        bool uniq = true;
-        for (int q = 0; q < count; q++)  // entries >= count are still -1 and np_ >= 0
-          if (ng[q] == np_) {
-            uniq = false;
-            break;
+  Walk w;
+  if (i < end && walk_init(s, c, i, w)) {
+    // the reference derives max_radius per batch from max(tran_diff) (cli/simulate_pixels.py:918)
+    if (radius_b) {
+      int32_t b = s.batch[i];
+      radius = b >= 0 ? radius_b[b - batch0] : 0;
+    }
+    int32_t* act = active + r * max_active;
+    int32_t* ng = neigh + r * P;
+    int32_t* nr = nrad + r * P;
+    walk_pixels(c, w, act, max_active);
+    for (int p = 0; p < max_active; p++) {
+      int32_t a = act[p];
+      if (a == -1) continue;
+      int64_t ax, ay, pl;
+      id2pixel(c, a, ax, ay, pl);
+      for (int x_r = -radius; x_r <= radius; x_r++)
+        for (int y_r = -radius; y_r <= radius; y_r++) {
+          int64_t nx = ax + x_r, ny = ay + y_r;
+          if (!pix_in_range(c, nx, ny, pl)) continue;
+          int32_t np_ = (int32_t)pixel2id(c, nx, ny, pl);
+          bool uniq = true;
+          for (int q = 0; q < count; q++)  // (entries >= count are not read)
+            if (ng[q] == np_) {
+              uniq = false;
+              break;
+            }
+          if (uniq && count < P) {
+            ng[count] = np_;
+            nr[count] = ring_code(x_r, y_r);
+            count++;
           }
-        if (uniq && count < P) {
-          ng[count] = np_;
-          nr[count] = ring_code(x_r, y_r);
-          count++;
         }
-      }
+    }
   }
-  if (n_list) n_list[r] = (double)count;
+  if (i < end && n_list) n_list[r] = (double)count;
+  s_count[tid] = count;
+  __syncthreads();
+  {
+    int32_t* g0 = neigh + r0 * P;
+    int32_t* d0 = nrad + r0 * P;
+    const unsigned ne = rows * (unsigned)P;
+    for (unsigned e = tid; e < ne; e += GP_THREADS) {
+      const unsigned row = e / (unsigned)P;
+      if ((int)(e - row * (unsigned)P) >= s_count[row]) {
+        g0[e] = -1;
+        d0[e] = -1;
+      }
+    }
+  }
 }
 
 // a8 time_intervals (detsim.py:18-40); max_length per launch via atomic max
@@ -524,11 +601,19 @@ int seg_launch_max_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int32_t* d_nmax,
   HIPCHK(hipGetLastError());
   return 0;
 }
+int seg_launch_front(ldsim_ctx* ctx, int64_t b, int64_t e, int32_t batch0, double* starts, int32_t* d_nmax, int32_t* tmax_b,
+                     int32_t* first_b, unsigned long long* tran_b) {
+  if (e <= b) return 0;
+  hipLaunchKernelGGL(seg_front_kernel, dim3(nblk(e - b, 256)), dim3(256), 0, ctx->stream, charge_store(ctx),
+                     ctx->d_consts.as<LdsimConsts>(), b, e - b, batch0, starts, d_nmax, tmax_b, first_b, tran_b);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 int seg_launch_get_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int radius, int32_t* active, int max_active,
                           int32_t* neigh, int32_t* nrad, int P, double* n_list, const int32_t* radius_b,
                           int32_t batch0) {
   if (e <= b) return 0;
-  hipLaunchKernelGGL(get_pixels_kernel, dim3(nblk(e - b, 128)), dim3(128), 0, ctx->stream, charge_store(ctx), ctx->d_consts.as<LdsimConsts>(),
+  hipLaunchKernelGGL(get_pixels_kernel, dim3(nblk(e - b, GP_THREADS)), dim3(GP_THREADS), 0, ctx->stream, charge_store(ctx), ctx->d_consts.as<LdsimConsts>(),
                      b, e, radius, active, max_active, neigh, nrad, P, n_list, radius_b, batch0);
   HIPCHK(hipGetLastError());
   return 0;

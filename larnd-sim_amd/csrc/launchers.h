@@ -13,6 +13,8 @@ int seg_launch_quench_drift(ldsim_ctx* ctx, int mode, int do_q, int do_d, int* d
 int seg_launch_quench_drift_map(ldsim_ctx* ctx, int mode, int* d_err);
 int seg_launch_quench_drift_stat(ldsim_ctx* ctx, int mode, bool map, const int32_t* d_first, int32_t batch0, int* d_err);
 int seg_launch_max_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int32_t* d_nmax, unsigned long long* d_tranbits);
+int seg_launch_front(ldsim_ctx* ctx, int64_t b, int64_t e, int32_t batch0, double* starts, int32_t* d_nmax, int32_t* tmax_b,
+                     int32_t* first_b, unsigned long long* tran_b);
 int seg_launch_get_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int radius, int32_t* active, int max_active, int32_t* neigh,
                           int32_t* nrad, int P, double* n_list, const int32_t* radius_b, int32_t batch0);
 int seg_launch_time_intervals(ldsim_ctx* ctx, int64_t b, int64_t e, double* starts, int32_t* tmax);
@@ -29,24 +31,23 @@ int lutbuild_trace(ldsim_ctx* ctx, const LdsimLutBuildParams* P, const LdsimLutD
 int respbuild_build(ldsim_ctx* ctx, const LdsimResponseBuildParams* P, double* table);
 
 // ---- sort.hip ----------------------------------------------------------------------------------------------------------
-int sort_make_keys(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
-                   int64_t n_entries, unsigned long long* keys, int32_t* vals, unsigned long long* counters);
+int sort_select_pairs(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
+                      int64_t n_entries, unsigned long long* keys_out, int32_t* vals_out, unsigned long long* d_count);
+void sort_key_ranges(unsigned long long pixel_max, int64_t n_batches, int r[3]);
 int sort_pairs(ldsim_ctx* ctx, unsigned long long* keys_in, unsigned long long* keys_out, int32_t* vals_in, int32_t* vals_out,
                int64_t n);
 int sort_pairs_bits(ldsim_ctx* ctx, unsigned long long* keys_in, unsigned long long* keys_out, int32_t* vals_in,
                     int32_t* vals_out, int64_t n, int begin_bit, int end_bit);
 int sort_pairs_u32_u64(ldsim_ctx* ctx, unsigned* keys_in, unsigned* keys_out, unsigned long long* vals_in,
                        unsigned long long* vals_out, int64_t n, int bits);
-int sort_compact_valid(ldsim_ctx* ctx, const unsigned long long* keys_in, int64_t n, unsigned long long* keys_out,
-                       int32_t* vals_out, unsigned int* d_count);
 int sort_exclusive_scan_i32(ldsim_ctx* ctx, const int32_t* in, int32_t* out, int64_t n);
 int sort_exclusive_scan_u64(ldsim_ctx* ctx, const unsigned long long* in, unsigned long long* out, int64_t n);
 int sort_heads(ldsim_ctx* ctx, const unsigned long long* keys, int64_t n_valid, int32_t* heads);
 int sort_fill_unique(ldsim_ctx* ctx, const unsigned long long* keys, const int32_t* heads, const int32_t* uidx, int64_t n_valid,
                      int32_t batch0, int32_t* upix, int32_t* ubatch, int64_t* uoff, int64_t U);
+struct GInfo;   // gform.h
+int sort_scan_record_sizes(ldsim_ctx* ctx, const GInfo* gi, unsigned long long* off, int64_t n);
 int sort_batch_first(ldsim_ctx* ctx, int64_t seg_begin, int64_t n, int32_t batch0, int32_t* first);
-int sort_tmax_batch(ldsim_ctx* ctx, int64_t seg_begin, int64_t n, int32_t batch0, double* starts, int32_t* tmax_b,
-                    unsigned long long* tran_b);
 int sort_compact_hits(ldsim_ctx* ctx, const int32_t* upix, const int32_t* ubatch, const int32_t* hit_count,
                       const int32_t* hit_off, const double* digit, const double* ticks, int A, int64_t U, int32_t* rows);
 

@@ -29,6 +29,14 @@ extern "C" int ldsim_device_count(void) {
   return n;
 }
 
+extern "C" int ldsim_debug_sort_key_ranges(uint64_t pixel_max, int64_t n_batches, int32_t ranges[3]) {
+  NEED(ranges && n_batches >= 1, "bad sort_key_ranges arguments");
+  int r[3];
+  sort_key_ranges(pixel_max, n_batches, r);
+  for (int k = 0; k < 3; k++) ranges[k] = r[k];
+  return 0;
+}
+
 // device buffers, streams and events the library holds in this process (the owner types of ldsim_dev.h count them)
 std::atomic<int64_t> ldsim_live[3];
 extern "C" int ldsim_debug_live_objects(int64_t counts[3]) {
@@ -851,9 +859,7 @@ extern "C" int ldsim_get_pixels(ldsim_ctx* ctx, const void* tracks, int64_t n, c
   CK(ctx->scratch[SB_NEIGH].ensure(bn));
   CK(ctx->scratch[SB_NRAD].ensure(bn));
   CK(ctx->scratch[SB_NLIST].ensure((size_t)n * 8));
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_ACTIVE].p, 0xFF, ba, ctx->stream));
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_NEIGH].p, 0xFF, bn, ctx->stream));
-  HIPCHK(hipMemsetAsync(ctx->scratch[SB_NRAD].p, 0xFF, bn, ctx->stream));
+  // (the kernel writes every slot of the three arrays, the empty ones as -1)
   CK(seg_launch_get_pixels(ctx, 0, n, radius, ctx->scratch[SB_ACTIVE].as<int32_t>(), max_active,
                            ctx->scratch[SB_NEIGH].as<int32_t>(), ctx->scratch[SB_NRAD].as<int32_t>(), P,
                            ctx->scratch[SB_NLIST].as<double>(), nullptr, 0));

@@ -54,7 +54,7 @@ struct ChainMisc {
   int32_t nmax, pad1;               // max_pixels: most active pixels of a segment
   unsigned long long tran_bits;     // max_pixels: bits of the largest tran_diff
   int32_t time_max, pad2[9];        // time_intervals stage call: largest tick count
-  unsigned int n_compact;           // sort_compact_valid's own count (the launch reads counters[ST_VALID_PAIRS])
+  unsigned int n_compact;           // unused (the stage calls clear the words before it)
   int32_t pad3[47];
   unsigned long long counters[STAT_WORDS];
   char tail[256];
@@ -69,7 +69,8 @@ static_assert(offsetof(ChainMisc, counters) == 256, "misc block layout");
 static_assert(sizeof(ChainMisc) == MISC_BYTES, "misc block layout");
 
 // ---- blocks inside a slot ---------------------------------------------------------------------------------------------
-// SB_BATCH, per batch of a launch: tmax i32 [nb] | first i32 [nb] | (16-byte aligned) tran u64 [nb] | radius i32 [nb]
+// SB_MISC behind the ChainMisc (one memset clears both), per batch of a launch:
+// tmax i32 [nb] | first i32 [nb] | (16-byte aligned) tran u64 [nb] | radius i32 [nb]
 struct BatchBlock {
   int32_t *tmax, *first;
   unsigned long long* tran;
@@ -82,6 +83,28 @@ static inline BatchBlock batch_block(void* p, int64_t nb) {
   b.first = b.tmax + nb;
   b.tran = (unsigned long long*)((char*)p + ((nb * 8 + 15) / 16) * 16);
   b.radius = (int32_t*)(b.tran + nb);
+  return b;
+}
+// ---- the words a chain launch reads back between its stages (ctx->readback, page-locked) ---------------------------------------
+// One copy per word and synchronisation, straight into this block.  Behind it, per batch: tran u64 [nb] | tmax i32 [nb] |
+// radius i32 [nb] (the last one goes the other way: the radii the host derives from tran).
+struct ChainReadback {
+  int32_t nmax, pad;                       // max_pixels
+  int32_t last_idx, last_head;             // last entries of the head scan and of the heads: their sum is the unique pixels
+  unsigned long long n_valid;              // counters[ST_VALID_PAIRS]
+  unsigned long long gform_tot[8];         // gform_launch: pool size and list counts
+  unsigned long long raw[STAT_WORDS];      // the launch counters
+};
+struct ChainReadbackBatch {
+  unsigned long long* tran;
+  int32_t *tmax, *radius;
+};
+static inline size_t chain_readback_bytes(int64_t nb) { return sizeof(ChainReadback) + (size_t)nb * 16; }
+static inline ChainReadbackBatch chain_readback_batch(void* p, int64_t nb) {
+  ChainReadbackBatch b;
+  b.tran = (unsigned long long*)((char*)p + sizeof(ChainReadback));
+  b.tmax = (int32_t*)(b.tran + nb);
+  b.radius = b.tmax + nb;
   return b;
 }
 // SB_HITCNT: hit_count i32 [U] | hit_off i32 [U] (the exclusive scan of the counts)

@@ -175,6 +175,34 @@ struct DevBuf {
   T* as() const { return (T*)p; }
 };
 
+// Page-locked host memory that device-to-host copies of a few words land in (a copy into pageable memory is staged by the
+// runtime).  Host memory: not one of the ldsim_live counts.  Grown like a DevBuf, contents lost; no copy may be in flight then.
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { reset(); }
+  void reset() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  int ensure(size_t need) {
+    if (need <= bytes && p) return 0;
+    reset();
+    const size_t want = need + need / 8 + 256;
+    void* q = nullptr;
+    HIPCHK(hipHostMalloc(&q, want, hipHostMallocDefault));
+    p = q;
+    bytes = want;
+    return 0;
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+
 struct Stream {
   hipStream_t s = nullptr;
   Stream() = default;
@@ -322,6 +350,7 @@ struct ldsim_ctx {
   DevBuf raw;          // AoS staging (H2D/D2H)
   LdsimTrackLayout seg_layout{};
   DevBuf scratch[40];  // named scratch buffers, grown on demand
+  PinnedBuf readback;  // the words a launch reads back from the device between its stages (ChainReadback, ldsim_args.h)
   std::vector<int32_t> h_batch;   // host copy of the resident segments' batch ids (validated non-decreasing at upload)
   int seg_owner = 0;   // who filled the segment store last: 1 = ldsim_segments_upload (resident chain), 2 = a host-buffer stage call
   // device-resident light leg (ldsim_dev_light_incidence / ldsim_dev_sum_light)
@@ -499,8 +528,10 @@ struct ldsim_ctx {
 // fee_record.h (fee_hdr_view), and chain_view (ldsim_args.h) gives what a chain launch left as typed pointers.
 enum {
   SB_ACTIVE = 0, SB_NEIGH, SB_NRAD,
-  SB_NLIST, SB_BATCH = SB_NLIST,     // get_pixels stage call: n_list f64 [n] | chain: the per-batch block (batch_block)
-  SB_STARTS, SB_MISC, SB_KEYS, SB_KEYS2, SB_VALS, SB_VALS2, SB_SORTTMP,
+  SB_NLIST,                          // get_pixels stage call: n_list f64 [n]
+  SB_STARTS,
+  SB_MISC,                           // ChainMisc, and behind it the chain's per-batch block (batch_block)
+  SB_KEYS, SB_KEYS2, SB_VALS, SB_VALS2, SB_SORTTMP,
   SB_PIXOFF,                         // uoff i64 [U + 1]: a unique pixel's first pair in the sorted list
   SB_HITCNT,                         // hit_count i32 [U] | hit_off i32 [U] (hit_counts)
   SB_HEADS,
@@ -509,7 +540,7 @@ enum {
   // shifted-window split path | node-separable form (gform_launch):
   SB_ITEMS, SB_GFLAGS = SB_ITEMS,    //   items                | fallback flags i32 [n]
   SB_HDR, SB_GINFO = SB_HDR,         //   pair headers         | GInfo [n]
-  SB_CORR, SB_GSIZES = SB_CORR,      //   corrections          | record sizes, offsets, class counts and lists
+  SB_CORR, SB_GSIZES = SB_CORR,      //   corrections          | record offsets, class counts and lists
   SB_WBUF, SB_GREC = SB_WBUF,        //   weight pool          | table records
   SB_NOISE, SB_NDRAWS, SB_PPAR, SB_CPT, SB_CPO, SB_WIN,
   SB_FEEHDR,                         // FEE set-up record: headers (fee_hdr_view)

@@ -7,39 +7,33 @@
 #include <rocprim/rocprim.hpp>
 
 #include "launchers.h"
-#include "wave_ops.h"
+#include "gform.h"
 
-// key = batch(24) | pixel(32) | ringcode(4, 15 = invalid) ; invalid pairs get ~0 and sort last
-// (n_entries < 2^31, checked by the chain: 32-bit index arithmetic; the valid count goes to its counter once per workgroup -- one
-// atomic per wave on the same address had made this kernel 0.34 ms per 100 k segments)
-__global__ void __launch_bounds__(256) make_keys_kernel(const int32_t* __restrict__ neigh, const int32_t* __restrict__ nrad,
-                                 const int32_t* __restrict__ batch, int64_t seg_begin, int32_t batch0, int P,
-                                 int64_t n_entries, unsigned long long* __restrict__ keys, int32_t* __restrict__ vals,
-                                 unsigned long long* __restrict__ counters) {
-  __shared__ int s_cnt[4];
-  int valid = 0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)n_entries; i += gridDim.x * 256u) {
-    int32_t pix = neigh[i];
-    const unsigned r = i / (unsigned)P;
-    int32_t b = batch[seg_begin + r];
+// key = batch(24) | pixel(32) | ringcode(4, 15 = invalid); an empty slot (no pixel, or a segment that is not simulated) has no key
+// (n_entries < 2^31, checked by the chain: 32-bit index arithmetic).  The keys are formed where the selection reads its input
+// (sort_select_pairs below): the entries are never written as a list of their own.
+namespace {
+typedef rocprim::tuple<unsigned long long, int32_t> KeyedEntry;      // (key, entry index r * P + slot)
+struct EntryKey {
+  const int32_t *neigh, *nrad, *batch;      // batch: of the launch's first segment on
+  int32_t batch0;
+  unsigned P;
+  __device__ KeyedEntry operator()(unsigned i) const {
+    const int32_t pix = neigh[i];
+    const int32_t b = batch[i / P];
     unsigned long long key = ~0ull;
     if (pix >= 0 && b >= 0) {
-      int32_t d = nrad[i];
-      unsigned long long dn = (d < 0 || d > 14) ? 15ull : (unsigned long long)d;
+      const int32_t d = nrad[i];
+      const unsigned long long dn = (d < 0 || d > 14) ? 15ull : (unsigned long long)d;
       key = ((unsigned long long)(uint32_t)(b - batch0) << 36) | ((unsigned long long)(uint32_t)pix << 4) | dn;
-      valid++;
     }
-    keys[i] = key;
-    vals[i] = (int32_t)i;
+    return KeyedEntry(key, (int32_t)i);
   }
-  const int wsum = wave_lane_i32(wave_scan_i32(valid, 0, [](int a, int b) { return a + b; }), 63);
-  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = wsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    if (c) atomicAdd(&counters[ST_VALID_PAIRS], (unsigned long long)c);
-  }
-}
+};
+struct EntryValid {
+  __device__ bool operator()(const KeyedEntry& e) const { return rocprim::get<0>(e) != ~0ull; }
+};
+}  // namespace
 
 __global__ void heads_kernel(const unsigned long long* __restrict__ keys, int64_t n_valid, int32_t* __restrict__ heads) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,46 +64,6 @@ __global__ void batch_first_kernel(const int32_t* __restrict__ batch, int64_t se
   if (r == 0 || batch[seg_begin + r - 1] != b) first[b - batch0] = (int32_t)r;
 }
 
-__global__ void tmax_batch_kernel(SegStore s, const LdsimConsts* __restrict__ c, int64_t begin, int64_t n, int32_t batch0,
-                                  double* __restrict__ starts, int32_t* __restrict__ tmax_b,
-                                  unsigned long long* __restrict__ tran_b) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  int32_t b = -1, len_i = 0;
-  double td = 0;
-  if (r < n) {
-    const int64_t i = begin + r;
-    double t_end = py_round((s.f[LDSIM_T_END][i] + 1) / c->time_sampling) * c->time_sampling;
-    double t_start = py_round((s.f[LDSIM_T_START][i] - c->time_padding) / c->time_sampling) * c->time_sampling;
-    starts[r] = t_start;
-    b = s.batch[i];
-    if (b >= 0) {
-      double len = ceil((t_end - t_start) / c->time_sampling);
-      if (len > 0 && len < 2.0e9) len_i = (int32_t)len;
-      td = s.f[LDSIM_TRAN_DIFF][i];
-      if (!(td > 0)) td = 0;
-    }
-  }
-  // segments are sorted by batch, so nearly every wave holds one batch: one atomic per wave instead of one per segment on
-  // the few per-batch cells (50 k contended atomics cost 0.7 ms per launch)
-  const unsigned long long act = __ballot(b >= 0);
-  if (act == 0) return;
-  const int first = __ffsll((long long)act) - 1;
-  const int bref = __builtin_amdgcn_readlane(b, first);
-  if (__ballot(b >= 0 && b != bref) == 0) {
-    const int m = wave_max_i32(len_i);
-    const double tm = wave_max_f64(td);
-    if (lane == first) {
-      if (m > 0) atomicMax(&tmax_b[bref - batch0], m);
-      if (tran_b && tm > 0) atomicMax(&tran_b[bref - batch0], (unsigned long long)__double_as_longlong(tm));
-    }
-    return;
-  }
-  if (b < 0) return;
-  if (len_i > 0) atomicMax(&tmax_b[b - batch0], len_i);
-  if (tran_b && td > 0) atomicMax(&tran_b[b - batch0], (unsigned long long)__double_as_longlong(td));
-}
-
 // compact hit rows for the multi-GPU all-gather: {batch i32, pixel i32, adc i32, tick f64-bits hi/lo}
 __global__ void compact_hits_kernel(const int32_t* __restrict__ upix, const int32_t* __restrict__ ubatch,
                                     const int32_t* __restrict__ hit_count, const int32_t* __restrict__ hit_off,
@@ -132,16 +86,6 @@ __global__ void compact_hits_kernel(const int32_t* __restrict__ upix, const int3
 
 static inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
-int sort_make_keys(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
-                   int64_t n_entries, unsigned long long* keys, int32_t* vals, unsigned long long* counters) {
-  if (n_entries == 0) return 0;
-  const int64_t nb = nblk(n_entries, 256);
-  hipLaunchKernelGGL(make_keys_kernel, dim3((unsigned)(nb < 8192 ? nb : 8192)), dim3(256), 0, ctx->stream, neigh, nrad,
-                     ctx->seg.batch, seg_begin, batch0, P, n_entries, keys, vals, counters);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 int sort_pairs(ldsim_ctx* ctx, unsigned long long* keys_in, unsigned long long* keys_out, int32_t* vals_in,
                int32_t* vals_out, int64_t n) {
   if (n == 0) return 0;
@@ -154,35 +98,48 @@ int sort_pairs(ldsim_ctx* ctx, unsigned long long* keys_in, unsigned long long* 
   return 0;
 }
 
-// The valid entries of make_keys_kernel's arrays (key != ~0) in their order of appearance: keys -> keys_out, their indices ->
-// vals_out, their number -> *d_count (a device word).  Two stable rocPRIM selects; the pair-list sort then runs over the valid
-// entries only (a quarter of the (segment, neighbour slot) entries of the module0 bench) and equal keys keep the entry order they
-// had among all entries.
-namespace {
-struct KeyValid {
-  __device__ bool operator()(const unsigned long long& k) const { return k != ~0ull; }
-};
-struct KeyFlag {
-  __device__ unsigned char operator()(const unsigned long long& k) const { return k != ~0ull ? 1 : 0; }
-};
-}  // namespace
-int sort_compact_valid(ldsim_ctx* ctx, const unsigned long long* keys_in, int64_t n, unsigned long long* keys_out, int32_t* vals_out,
-                       unsigned int* d_count) {
-  if (n == 0) return 0;
-  auto flags = rocprim::make_transform_iterator(keys_in, KeyFlag());
-  rocprim::counting_iterator<int32_t> idx(0);
-  size_t t1 = 0, t2 = 0;
-  HIPCHK(rocprim::select(nullptr, t1, keys_in, keys_out, d_count, (size_t)n, KeyValid(), ctx->stream));
-  HIPCHK(rocprim::select(nullptr, t2, idx, flags, vals_out, d_count, (size_t)n, ctx->stream));
-  int rc = ctx->scratch[SB_SORTTMP].ensure(t1 > t2 ? t1 : t2);
+// The valid (segment, neighbour slot) entries of get_pixels' arrays in their order of appearance: their keys -> keys_out, their indices ->
+// vals_out, their number -> *d_count (a device word, overwritten).  One stable rocPRIM select over (key, index) pairs made by a transform
+// iterator: the pair-list sort then runs over the valid entries only (a quarter of the entries of the module0 bench) and equal keys keep
+// the entry order they had among all entries.
+int sort_select_pairs(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
+                      int64_t n_entries, unsigned long long* keys_out, int32_t* vals_out, unsigned long long* d_count) {
+  if (n_entries == 0) return 0;
+  auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(0),
+                                             EntryKey{neigh, nrad, ctx->seg.batch + seg_begin, batch0, (unsigned)P});
+  auto out = rocprim::make_zip_iterator(rocprim::make_tuple(keys_out, vals_out));
+  size_t tmp = 0;
+  HIPCHK(rocprim::select(nullptr, tmp, in, out, d_count, (size_t)n_entries, EntryValid(), ctx->stream));
+  int rc = ctx->scratch[SB_SORTTMP].ensure(tmp);
   if (rc) return rc;
-  t1 = t2 = ctx->scratch[SB_SORTTMP].bytes;
-  HIPCHK(rocprim::select(ctx->scratch[SB_SORTTMP].p, t1, keys_in, keys_out, d_count, (size_t)n, KeyValid(), ctx->stream));
-  HIPCHK(rocprim::select(ctx->scratch[SB_SORTTMP].p, t2, idx, flags, vals_out, d_count, (size_t)n, ctx->stream));
+  HIPCHK(rocprim::select(ctx->scratch[SB_SORTTMP].p, tmp, in, out, d_count, (size_t)n_entries, EntryValid(), ctx->stream));
   return 0;
 }
 
-// the same over the key bits [begin_bit, end_bit) only (a pass per 8 bits)
+// The bit ranges the pair-list sort has to look at.  key = batch << 36 | pixel << 4 | ring code, and the pixel field cannot use its 32
+// bits: the largest id is n_pixels[0] * n_pixels[1] * n_tpc - 1 (pixel_max).  The bits between the top of that id and bit 36 are zero
+// in every key, so two stable passes of the LSD sort -- [0, r[0]) and then [r[1], r[2]) -- leave the order, equal keys included, that
+// one pass over [0, 36 + bb) leaves.  The two ranges are chosen only where they save a pass of SORT_RADIX_BITS bits; else
+// r = {36 + bb, 0, 0}, the single range.  (One batch: bb = 0 and no second range at all.)
+#define SORT_RADIX_BITS 8      // (rocPRIM's digit for 64-bit keys with 32-bit values: a pass per 8 bits, read off the trace)
+void sort_key_ranges(unsigned long long pixel_max, int64_t n_batches, int r[3]) {
+  int bb = 0, pb = 0;
+  while ((1ll << bb) < n_batches) bb++;
+  while (pb < 32 && (pixel_max >> pb) != 0) pb++;
+  const int single = 36 + bb, lo = 4 + pb;
+  auto passes = [](int bits) { return (bits + SORT_RADIX_BITS - 1) / SORT_RADIX_BITS; };
+  r[0] = single;
+  r[1] = r[2] = 0;
+  if (passes(lo) + passes(bb) < passes(single)) {
+    r[0] = lo;
+    if (bb > 0) {
+      r[1] = 36;
+      r[2] = 36 + bb;
+    }
+  }
+}
+
+// sort_pairs over the key bits [begin_bit, end_bit) only (a pass per 8 bits)
 int sort_pairs_bits(ldsim_ctx* ctx, unsigned long long* keys_in, unsigned long long* keys_out, int32_t* vals_in, int32_t* vals_out,
                     int64_t n, int begin_bit, int end_bit) {
   if (n == 0) return 0;
@@ -221,6 +178,25 @@ int sort_exclusive_scan_i32(ldsim_ctx* ctx, const int32_t* in, int32_t* out, int
   return 0;
 }
 
+// record offsets of the node-separable form: the exclusive scan of GInfo::size, read from the pairs' GInfo by the scan itself
+// (gbig_list_kernel, which reads every GInfo anyway, puts the offsets into them)
+namespace {
+struct RecordSize {
+  __device__ unsigned long long operator()(const GInfo& g) const { return g.size; }
+};
+}  // namespace
+int sort_scan_record_sizes(ldsim_ctx* ctx, const GInfo* gi, unsigned long long* off, int64_t n) {
+  if (n == 0) return 0;
+  auto sizes = rocprim::make_transform_iterator(gi, RecordSize());
+  size_t tmp = 0;
+  HIPCHK(rocprim::exclusive_scan(nullptr, tmp, sizes, off, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), ctx->stream));
+  int rc = ctx->scratch[SB_SORTTMP].ensure(tmp);
+  if (rc) return rc;
+  HIPCHK(rocprim::exclusive_scan(ctx->scratch[SB_SORTTMP].p, tmp, sizes, off, 0ull, (size_t)n,
+                                 rocprim::plus<unsigned long long>(), ctx->stream));
+  return 0;
+}
+
 int sort_exclusive_scan_u64(ldsim_ctx* ctx, const unsigned long long* in, unsigned long long* out, int64_t n) {
   if (n == 0) return 0;
   size_t tmp = 0;
@@ -251,15 +227,6 @@ int sort_batch_first(ldsim_ctx* ctx, int64_t seg_begin, int64_t n, int32_t batch
   if (n == 0) return 0;
   hipLaunchKernelGGL(batch_first_kernel, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, ctx->seg.batch, seg_begin, n,
                      batch0, first);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int sort_tmax_batch(ldsim_ctx* ctx, int64_t seg_begin, int64_t n, int32_t batch0, double* starts, int32_t* tmax_b,
-                    unsigned long long* tran_b) {
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(tmax_batch_kernel, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, charge_store(ctx), ctx->d_consts.as<LdsimConsts>(),
-                     seg_begin, n, batch0, starts, tmax_b, tran_b);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -26,7 +26,7 @@ _ctx_device = None
 
 EXPORTS = [
     "ldsim_last_error", "ldsim_abi_version", "ldsim_device_count", "ldsim_ctx_create", "ldsim_ctx_destroy",
-    "ldsim_host_alloc", "ldsim_host_free", "ldsim_debug_live_objects",
+    "ldsim_host_alloc", "ldsim_host_free", "ldsim_debug_live_objects", "ldsim_debug_sort_key_ranges",
     "ldsim_set_consts", "ldsim_set_response", "ldsim_set_light_channels", "ldsim_set_light_lut", "ldsim_set_option",
     "ldsim_set_pixel_thresholds", "ldsim_set_pixel_gains", "ldsim_clear_pixel_tables",
     "ldsim_synchronize", "ldsim_quench", "ldsim_drift", "ldsim_max_pixels", "ldsim_get_pixels",
