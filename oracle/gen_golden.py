@@ -19,7 +19,7 @@ Faithfulness rules (Numba types arithmetic as f64; NumPy-2 scalars do not):
   * between stages the mutated float fields are rounded through f4 (the HDF5 schema);
   * FEE noise constants are 0 (the Numba RNG stream is third-party and unpinned).
 
-Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,pixels_wide,chain,sampled,light,light_response,light_wvfm,light_wvfm_edges,fee] [--jobs 8]
+Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,pixels_wide,chain,sampled,light,light_response,light_wvfm,light_wvfm_edges,fee,mc] [--jobs 8]
 """
 import argparse
 import importlib
@@ -56,6 +56,7 @@ class _State:
     pos = (0, 0, 0)
     size = (1, 1, 1)
     z_only = None       # optional iterable restricting the 3rd grid axis (sampled ticks)
+    x_only = None       # optional iterable restricting the 1st grid axis (one segment per worker; the grid size stays)
 
 
 def _tup3(v):
@@ -76,7 +77,7 @@ class _Kernel:
         def launch(*args):
             _State.size = size
             zs = range(size[2]) if _State.z_only is None else [z for z in _State.z_only if z < size[2]]
-            for x in range(size[0]):
+            for x in (range(size[0]) if _State.x_only is None else [x for x in _State.x_only if x < size[0]]):
                 for y in range(size[1]):
                     for z in zs:
                         _State.pos = (x, y, z)
@@ -1905,6 +1906,245 @@ def gen_fee():
               f"{os.path.getsize(path)} bytes {time.time() - t_begin:.1f} s")
 
 
+# --------------------------------------------------------------------------
+# mc: tracks_current_mc on the table streams this project defines
+# --------------------------------------------------------------------------
+MC_SEED = 20261020
+MC_FRAGILE_MARGIN = 8.0      # spacings of float32 at the draw's Box-Muller radius (tests/test_gpu_mc_current.py)
+MC_FRAGILE_CAP = 0.01
+# end points: (x, y) in pixel pitches from the low corner of TPC 0's pixel plane, depth in cm from its anode (negative: from the
+# cathode).  diag: the z_start < z_end branch, diag_swapped the other; steep: 3.5 cm along the drift, hundreds of steps; inside:
+# ~300 um, wholly inside the impact circle (s_minus 0, s_plus 1, a few steps); tiny: round(length / MIN_STEP_SIZE) is 0 and the
+# max(.., 1) acts; anode: the first ~1850 ticks have time_tick < 0; cathode: the longest drift, the last ticks of the window.
+# No segment runs exactly along z: l == 0 divides by zero in the pure-Python run (the device's "no signal" there is the
+# HIP-vs-oracle tests' business).
+MC_SEGMENTS = {
+    "diag": ((60.30, 120.40, 15.0), (60.90, 120.80, 15.4)),
+    "diag_swapped": ((60.90, 120.80, 15.4), (60.30, 120.40, 15.0)),
+    "steep": ((70.45, 130.50, 10.0), (70.62, 130.58, 13.5)),
+    "inside": ((80.50, 140.50, 20.00), (80.55, 140.53, 20.02)),
+    "tiny": ((85.500, 145.500, 18.000), (85.505, 145.503, 18.002)),
+    "anode": ((90.30, 150.60, 0.4), (90.70, 150.35, 1.0)),
+    "cathode": ((95.40, 155.30, -0.6), (95.65, 155.60, -0.2)),
+    "short_a": ((60.50, 120.50, 25.00), (60.53, 120.52, 25.02)),
+    "short_b": ((64.40, 124.45, 27.03), (64.47, 124.40, 27.00)),
+}
+MC_CASES = (
+    ("module0_plain", "module0", "survey", {"MIN_STEP_SIZE": 0.01, "MC_SAMPLE_MULTIPLIER": 1},
+     ("diag", "diag_swapped", "steep", "inside", "tiny", "anode", "cathode")),
+    ("module0_multi", "module0", "golden", {"MIN_STEP_SIZE": 0.001, "MC_SAMPLE_MULTIPLIER": 3}, ("short_a", "short_b")),
+    ("ndlar_plain", "ndlar", "golden", {"MIN_STEP_SIZE": 0.01, "MC_SAMPLE_MULTIPLIER": 1},
+     ("diag", "diag_swapped", "steep", "anode")),
+)
+
+
+def mc_segments(det, names):
+    from larndsim_amd.layout import segments_dtype
+    B = np.asarray(det.TPC_BORDERS)[0]
+    sgn = np.sign(B[2, 1] - B[2, 0])
+    depth_max = abs(B[2, 1] - B[2, 0])
+    seg = np.zeros(len(names), dtype=segments_dtype)
+    for i, name in enumerate(names):
+        for end, (px, py, depth) in zip(("start", "end"), MC_SEGMENTS[name]):
+            seg["x_" + end][i] = B[0, 0] + px * det.PIXEL_PITCH
+            seg["y_" + end][i] = B[1, 0] + py * det.PIXEL_PITCH
+            seg["z_" + end][i] = B[2, 0] + sgn * (depth if depth >= 0 else depth_max + depth)
+    if "diag" in names:     # whatever the sign of the drift axis, `diag` is the one with z_start < z_end
+        i, j = names.index("diag"), names.index("diag_swapped")
+        if not seg["z_start"][i] < seg["z_end"][i]:
+            seg[[i, j]] = seg[[j, i]]
+    for ax in "xyz":
+        seg[ax] = 0.5 * (seg[ax + "_start"].astype(np.float64) + seg[ax + "_end"])
+    d = np.stack([seg[ax + "_end"].astype(np.float64) - seg[ax + "_start"] for ax in "xyz"])
+    seg["dx"] = np.sqrt((d * d).sum(axis=0))
+    seg["dEdx"] = 2.1 + 0.2 * np.arange(len(names))
+    seg["dE"] = seg["dEdx"].astype(np.float64) * seg["dx"]
+    seg["segment_id"] = np.arange(len(names))
+    return seg
+
+
+def _mc_far_pixel(det, r, pid, impact):
+    """a pixel of the plane of `pid` whose centre lies farther than `impact` from the line of segment record r (in x, y)"""
+    N0, N1 = int(det.N_PIXELS[0]), int(det.N_PIXELS[1])
+    plane, py0, px0 = pid // (N0 * N1), (pid // N0) % N1, pid % N0
+    B = np.asarray(det.TPC_BORDERS)[plane]
+    a = np.array([r["x_start"], r["y_start"]])
+    v = np.array([r["x_end"], r["y_end"]]) - a
+    v /= np.linalg.norm(v)
+    for dx, dy in ((9, 0), (0, 9), (-9, 9), (9, 9), (-9, 0), (0, -9), (14, -7), (-7, 14)):
+        px, py = px0 + dx, py0 + dy
+        if not (0 <= px < N0 and 0 <= py < N1):
+            continue
+        p = np.array([px * det.PIXEL_PITCH + B[0, 0] + det.PIXEL_PITCH / 2, py * det.PIXEL_PITCH + B[1, 0] + det.PIXEL_PITCH / 2]) - a
+        if abs(p[0] * v[1] - p[1] * v[0]) > 1.2 * impact:
+            return px + N0 * (py + N1 * plane)
+    raise AssertionError("no far pixel found")
+
+
+def _mc_stream_state(ORC, states, index, it):
+    """mc_stream_words (csrc/kernels_mc.hip) of table state `index` and tick `it`, restated: SplitMix64's output function of the
+    two words offset by the tick"""
+    M = (1 << 64) - 1
+
+    def fin(z):
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+        return z ^ (z >> 31)
+    z0 = fin((int(states["s0"][index]) + 0x9E3779B97F4A7C15 * (it + 1)) & M)
+    z1 = fin(int(states["s1"][index]) ^ ((0xD1B54A32D192ED03 * (it + 1)) & M))
+    if (z0 | z1) == 0:
+        z0 = 1
+    st = np.zeros(1, dtype=ORC.RNG_DTYPE)
+    st["s0"], st["s1"] = z0, z1
+    return st
+
+
+def _mc_job(args):
+    case, cfg, kind, over, r, pixels, T, itrk, bound = args
+    from larndsim_amd import synth
+    try:
+        from oracle import oracle as ORC
+    except ImportError:
+        import oracle as ORC
+    S, P = pixels.shape
+    states = ORC.rng_create_states(S * P, MC_SEED)
+    counts = np.zeros((P, T), dtype=np.int64)
+    cur = {"pos": None, "buf": None, "d": 0}
+
+    def normal(rng_state, index):
+        # the state argument is ignored: draw d of thread (itrk, ipix, it) is draw d of the table-mode stream of that entry,
+        # all fetched at the thread's first draw.  A Python float: Numba types f32 * f64 as f64.
+        pos = _State.pos
+        if pos != cur["pos"]:
+            cur["pos"], cur["d"] = pos, 0
+            cur["buf"] = ORC.rng_normals(_mc_stream_state(ORC, states, pos[0] + S * pos[1], pos[2]), 0, bound)
+        v = float(cur["buf"][cur["d"]])
+        cur["d"] += 1
+        counts[pos[1], pos[2]] = cur["d"]
+        return v
+    ref = Ref(cfg, noise_zero=False, normal=normal)
+    for k, v in over.items():
+        setattr(ref.sim, k, v)
+    response = synth.make_response(kind, response_sampling=ref.detector.RESPONSE_SAMPLING)
+    # census of the look-ups: how many samples reached get_closest_waveform, how many of them past the table's last tick
+    seen = {"lookups": 0, "k_past_end": 0}
+    inner = ref.detsim.get_closest_waveform
+
+    def counted(x, y, t, resp):
+        seen["lookups"] += 1
+        seen["k_past_end"] += round(t / ref.detector.RESPONSE_SAMPLING) >= resp.shape[2]
+        return inner(x, y, t, resp)
+    ref.detsim.get_closest_waveform = counted
+    signals = np.zeros((S, P, T))
+    _State.x_only = [itrk]
+    ref.detsim.tracks_current_mc[(S, P, T), (1, 1, 1)](signals, pixels, r, response, states)
+    _State.x_only = None
+    return itrk, signals[itrk], counts, seen
+
+
+def gen_mc(jobs):
+    """detsim.tracks_current_mc (detsim.py:258-348) run thread by thread on hand-placed segments, its normals the draws of the
+    table-mode streams (one per (segment, pixel, tick): csrc/kernels_mc.hip) -> tests/golden/mc_<case>.npz: the records after the
+    reference's quench and drift, the pixel rows (get_pixels at radius 1, then per segment a pixel farther than the impact
+    radius and a -1), T, seed, constants, the f64 signals and the draw count of every entry.  One census line per segment."""
+    import time
+    try:
+        from oracle import oracle as ORC
+    except ImportError:
+        import oracle as ORC
+    from larndsim_amd import consts as my_consts, synth
+    for case, cfg, kind, over, names in MC_CASES:
+        t_begin = time.time()
+        ref = Ref(cfg, noise_zero=False)
+        det = ref.detector
+        for k, v in over.items():
+            setattr(ref.sim, k, v)
+        seg = mc_segments(det, list(names))
+        r = run_quench_drift(ref, to_ref(seg), ref.physics.BIRKS)
+        S = r.shape[0]
+        assert (r["pixel_plane"] != det.DEFAULT_PLANE_INDEX).all()
+        mp = np.array([0])
+        ref.pixels_from_track.max_pixels[1, 128](r, mp)
+        nmax = int(mp[0])
+        P0 = 3 * nmax + 6                                                      # cli/simulate_pixels.py:928 at radius 1
+        active = np.full((S, nmax), -1, dtype=np.int32)
+        neigh = np.full((S, P0), -1, dtype=np.int32)
+        nrad = np.full((S, P0), -1, dtype=np.int32)
+        ref.pixels_from_track.get_pixels[1, 128](r, active, neigh, nrad, np.zeros(S), 1)
+        shape = (45, 45)
+        impact = np.sqrt(shape[0] ** 2 + shape[1] ** 2) * det.RESPONSE_BIN_SIZE
+        far = np.array([_mc_far_pixel(det, r[i], int(neigh[i][neigh[i] >= 0][0]), impact) for i in range(S)], dtype=np.int32)
+        pixels = np.concatenate([neigh, far[:, None], np.full((S, 1), -1, dtype=np.int32)], axis=1)
+        P = pixels.shape[1]
+        starts, tmax = np.empty(S), np.array([0])
+        ref.detsim.time_intervals[1, 128](starts, tmax, r)
+        T = int(tmax[0])
+        length = np.sqrt((r["x_end"] - r["x_start"]) ** 2 + (r["y_end"] - r["y_start"]) ** 2 + (r["z_end"] - r["z_start"]) ** 2)
+        mult = int(ref.sim.MC_SAMPLE_MULTIPLIER)
+        bound = [3 * mult * (max(int(round(L / ref.sim.MIN_STEP_SIZE)), 1) + 1) for L in length]
+        with Pool(min(jobs, S)) as pool:
+            res = pool.map(_mc_job, [(case, cfg, kind, over, r, pixels, T, i, bound[i]) for i in range(S)], chunksize=1)
+        signals = np.zeros((S, P, T))
+        n_draws = np.zeros((S, P, T), dtype=np.int64)
+        seen = {}
+        for itrk, s, c, sn in res:
+            signals[itrk], n_draws[itrk], seen[itrk] = s, c, sn
+        # ---- the oracle on the same streams: margins (the share of fragile entries) ----
+        my_consts.load_snapshot(cfg)
+        for k, v in over.items():
+            setattr(my_consts.sim, k, v)
+        resp = synth.make_response(kind, response_sampling=det.RESPONSE_SAMPLING)
+        assert resp.shape[:2] == shape
+        o = ORC.tracks_current_mc_detail(r, pixels, T, resp, ORC.rng_create_states(S * P, MC_SEED))
+        nz = signals != 0
+        fragile = float((o["margin"][nz] < MC_FRAGILE_MARGIN).mean())
+        assert fragile <= MC_FRAGILE_CAP, f"mc {case}: {fragile:.4f} of the non-zero entries are fragile: reshape the case"
+        # ---- census: what each segment reached, from the reference's signals and draw counts ----
+        for i, name in enumerate(names):
+            real = np.flatnonzero(pixels[i, :P0] >= 0)
+            cnt = n_draws[i]
+            assert not cnt[P0].any() and not signals[i, P0].any() and cnt[real].any(), (case, name, "rr > impact row")
+            assert not cnt[P0 + 1].any() and not cnt[:P0][pixels[i, :P0] < 0].any(), (case, name, "-1 slots")
+            drew = cnt[real] > 0
+            # a row's samples per tick: its all-one-draw ticks (the last ticks of T lie past every sample's window)
+            nsamp = np.array([row[row > 0].min() if (row > 0).any() else 0 for row in cnt[real]])
+            assert (cnt[real] <= 3 * nsamp[:, None]).all() and (nsamp % mult == 0).all()
+            nstep = nsamp // mult
+            first = drew.argmax(axis=1)[drew.any(axis=1)]
+            one = int((drew & (cnt[real] == nsamp[:, None])).sum())
+            three = int((drew & (cnt[real] == 3 * nsamp[:, None])).sum())
+            mixed = int(drew.sum()) - one - three
+            swapped = not r["z_start"][i] < r["z_end"][i]
+            print(f"mc {case:14s} {name:13s} T {T} swapped {int(swapped)} rows {len(real)} nstep {nstep[nstep > 0].min()}"
+                  f"..{nstep.max()} ticks before time 0 {first.min()}..{first.max()} entries with 1 draw/sample {one} with 3 {three} "
+                  f"mixed {mixed} non-zero {int(nz[i].sum())} look-ups {seen[i]['lookups']} past the table's end "
+                  f"{seen[i]['k_past_end']} draws {int(cnt.sum())} far pixel {pixels[i, P0]}")
+            assert T > 256 and first.min() > 0 and one > 0 and three > 0
+            if name == "diag":
+                assert not swapped
+            if name == "diag_swapped":
+                assert swapped
+            if name == "tiny":
+                assert nstep.max() == 1
+            if name == "inside":
+                assert 2 <= nstep.max() <= 5 and nstep[nstep > 0].min() == nstep.max()
+            if name == "steep":
+                assert nstep.max() > 256
+            if name == "anode":
+                assert first.min() > 1500
+        out = dict(case=np.array(case), cfg=np.array(cfg), response_kind=np.array(kind), segment_names=np.array(names),
+                   segments_in=seg, tracks=r, pixels=pixels, n_neigh=np.int64(P0), T=np.int64(T), seed=np.int64(MC_SEED),
+                   const_names=np.array(sorted(over)), const_values=np.array([float(over[k]) for k in sorted(over)]),
+                   track_starts=starts, fragile_share=np.float64(fragile))
+        out.update(sparse_fields("signals", signals))
+        out.update(sparse_fields("n_draws", n_draws))
+        path = os.path.join(GOLD, f"mc_{case}.npz")
+        save_npz_fixed(path, out)
+        print(f"mc {case}: S {S} P {P} T {T} non-zero {int(nz.sum())} draws {int(n_draws.sum())} largest count {int(n_draws.max())} "
+              f"share of non-zero entries with margin < {MC_FRAGILE_MARGIN:g}: {fragile:.5f} (cap {MC_FRAGILE_CAP}) "
+              f"{os.path.getsize(path)} bytes {time.time() - t_begin:.1f} s")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="consts,qd,pixels,light,sampled,chain")
@@ -1917,7 +2157,7 @@ def main():
     for s in a.sets.split(","):
         {"consts": gen_consts, "qd": gen_qd, "pixels": gen_pixels, "light": gen_light, "light_response": gen_light_response,
          "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_wvfm_edges": gen_light_wvfm_edges, "light_export": gen_light_export, "fee": gen_fee,
-         "pixels_wide": lambda: gen_pixels_wide(a.jobs)}[s]()
+         "pixels_wide": lambda: gen_pixels_wide(a.jobs), "mc": lambda: gen_mc(a.jobs)}[s]()
     return 0
 
 

@@ -543,7 +543,9 @@ float o_rng_normal_f32(ORng* st) {
 /* ---- 8f row 1: tracks_current_mc (detsim.py:258-348), overlapping_segment (:220-256) ------------------------------------------
  * The reference's 64 tick threads race on rng_states[itrk + ntrk*ipix]; like the HIP kernel this restatement gives every
  * (segment, pixel, tick) its own stream derived from that state (SplitMix64 finaliser of the words offset by the tick):
- * reproducible, statistically equivalent, unpinned.  `states` has S*P entries; each is stepped once at the end. */
+ * reproducible, statistically equivalent.  Given those streams the loop is pinned: the reference's own tracks_current_mc, run on
+ * them thread by thread (oracle/gen_golden.py gen_mc), gives the sums of this one to 1e-12 with the same draw counts
+ * (tests/test_oracle_golden.py).  `states` has S*P entries; each is stepped once at the end. */
 static void mc_stream(const ORng* b, uint32_t it, ORng* o) {
   uint64_t z0 = b->s0 + 0x9E3779B97F4A7C15ULL * (uint64_t)(it + 1u);
   uint64_t z1 = b->s1 ^ (0xD1B54A32D192ED03ULL * (uint64_t)(it + 1u));
@@ -553,9 +555,58 @@ static void mc_stream(const ORng* b, uint32_t it, ORng* o) {
   o->s0 = z0;
   o->s1 = z1;
 }
-int o_tracks_current_mc(float* signals, const int32_t* pixels, const OTrack* tr, int64_t S, int64_t P, int64_t T,
-                        const double* response, int64_t ni, int64_t nj, int64_t nk, const LdsimConsts* c, ORng* states) {
-#pragma omp parallel for schedule(dynamic, 1)
+/* one normal of the xoroshiro128p stream with its Box-Muller radius (o_rng_normal_f32 split in two; same bits) */
+static float rng_normal_radius_f32(ORng* st, float* radius) {
+  float u1 = o_rng_uniform_f32(st), u2 = o_rng_uniform_f32(st);
+  *radius = sqrtf(-2.0f * logf(u1));
+  return *radius * cosf(6.28318530717958647692f * u2);
+}
+void o_rng_normals_fill(ORng* st, int64_t n, float* out) {
+  for (int64_t i = 0; i < n; i++) out[i] = o_rng_normal_f32(st);
+}
+/* spacing(float32(r)): the distance from r to the next float32 above it (numpy.spacing); not finite -> +inf */
+static double f32_spacing(float r) {
+  r = fabsf(r);
+  if (!isfinite(r)) return INFINITY;
+  return (double)nextafterf(r, INFINITY) - (double)r;
+}
+/* The normal source of one (segment, pixel, tick) entry: the table stream, or row `entry` of normals[S*P*T][D] (radii: the
+ * Box-Muller radius of each supplied normal, or NULL: the margin then takes spacing(|normal|), a lower bound of the radius's). */
+typedef struct {
+  ORng rs;
+  const float* normals;
+  const float* radii;
+  int64_t D, n;
+  int overrun;
+} McSource;
+static double mc_draw(McSource* q, double* spacing) {
+  float r, v;
+  if (q->normals) {
+    if (q->n >= q->D) { q->overrun = 1; q->n++; *spacing = INFINITY; return 0.0; }
+    v = q->normals[q->n];
+    r = q->radii ? q->radii[q->n] : v;
+  } else {
+    v = rng_normal_radius_f32(&q->rs, &r);
+  }
+  q->n++;
+  *spacing = f32_spacing(r);
+  return (double)v;
+}
+static double half_integer_distance(double a) { return fabs(a - floor(a) - 0.5); }
+
+/* The loop of tracks_current_mc with its normal source.  states != NULL: the table streams (every state stepped once at the end);
+ * else draw d of entry e is normals[e*D + d].  Optional outputs (NULL: not wanted): signals64 [S][P][T] the unrounded sums,
+ * n_draws [S][P][T] the normals each entry drew, margin [S][P][T]: the smallest amount by which one draw of the entry would have
+ * to move to change a decision (the two edges of the time window, the two reach cuts, the half-integers of the roundings for
+ * i, j and k), in units of spacing(float32(r)) of that draw's Box-Muller radius r; +inf where no decision depends on a draw.
+ * Returns -1 when an entry needs more than D supplied normals. */
+static int mc_core(float* signals, double* signals64, int32_t* n_draws, double* margin, const int32_t* pixels, const OTrack* tr,
+                   int64_t S, int64_t P, int64_t T, const double* response, int64_t ni, int64_t nj, int64_t nk,
+                   const LdsimConsts* c, ORng* states, const float* normals, const float* radii, int64_t D) {
+  int overrun = 0;
+  if (margin)
+    for (int64_t e = 0; e < S * P * T; e++) margin[e] = INFINITY;
+#pragma omp parallel for schedule(dynamic, 1) reduction(| : overrun)
   for (int64_t pr = 0; pr < S * P; pr++) {
     const int64_t itrk = pr / P, ipix = pr % P;
     const OTrack* t = &tr[itrk];
@@ -604,34 +655,96 @@ int o_tracks_current_mc(float* signals, const int32_t* pixels, const OTrack* tr,
     double step = sublen / nstep;
     double charge = t->n_electrons * (sublen / length) / ((double)nstep * c->mc_sample_multiplier);
     double z_anode = c->tpc_borders[t->pixel_plane][2][0];
-    const ORng* base = &states[itrk + S * ipix];
+    const double bin = c->response_bin_size, sL = t->long_diff, sT = t->tran_diff;
+    /* a move of the z draw by one unit moves t0 by sL / v_drift; of the x or y draw, the distance by sT */
+    const double per_t = sL > 0 ? c->v_drift / sL : INFINITY, per_xy = sT > 0 ? 1.0 / sT : INFINITY;
     for (int64_t it = 0; it < T; it++) {
       double time_tick = t_start + it * c->time_sampling;
       if (time_tick < 0) continue;
-      ORng rs;
-      mc_stream(base, (uint32_t)it, &rs);
-      double total = 0;
+      McSource q = {{0, 0}, NULL, NULL, D, 0, 0};
+      if (states) mc_stream(&states[itrk + S * ipix], (uint32_t)it, &q.rs);
+      else {
+        q.normals = normals + (pr * T + it) * D;
+        q.radii = radii ? radii + (pr * T + it) * D : NULL;
+      }
+      double total = 0, mg = INFINITY;
+#define MC_MARGIN(dist, per, spc)                                  \
+  do {                                                             \
+    double m_ = (per) == INFINITY ? INFINITY : (dist) * (per) / (spc); \
+    if (m_ < mg) mg = m_;                                          \
+  } while (0)
       for (int64_t istep = 0; istep < nstep; istep++)
         for (int m = 0; m < c->mc_sample_multiplier; m++) {
           double x = ns[0] + step * (istep + 0.5) * dir[0], y = ns[1] + step * (istep + 0.5) * dir[1];
           double z = ns[2] + step * (istep + 0.5) * dir[2];
-          z += (double)o_rng_normal_f32(&rs) * t->long_diff;
+          double spz, spx, spy;
+          z += mc_draw(&q, &spz) * t->long_diff;
           double t0 = fabs(z - z_anode) / c->v_drift - c->time_window;
+          MC_MARGIN(fabs(time_tick - t0), per_t, spz);
+          MC_MARGIN(fabs(t0 + c->time_window - time_tick), per_t, spz);
           if (!(t0 < time_tick && time_tick < t0 + c->time_window)) continue;
-          x += (double)o_rng_normal_f32(&rs) * t->tran_diff;
-          y += (double)o_rng_normal_f32(&rs) * t->tran_diff;
+          x += mc_draw(&q, &spx) * t->tran_diff;
+          y += mc_draw(&q, &spy) * t->tran_diff;
           double xd = fabs(x_p - x), yd = fabs(y_p - y);
-          if (xd > c->response_bin_size * ni) continue;
-          if (yd > c->response_bin_size * nj) continue;
-          int64_t i = (int64_t)py_round(xd / c->response_bin_size - 0.5), j = (int64_t)py_round(yd / c->response_bin_size - 0.5);
+          MC_MARGIN(fabs(xd - bin * ni), per_xy, spx);
+          if (xd > bin * ni) continue;
+          MC_MARGIN(fabs(yd - bin * nj), per_xy, spy);
+          if (yd > bin * nj) continue;
+          MC_MARGIN(half_integer_distance(xd / bin - 0.5) * bin, per_xy, spx);
+          MC_MARGIN(half_integer_distance(yd / bin - 0.5) * bin, per_xy, spy);
+          MC_MARGIN(half_integer_distance((time_tick - t0) / c->response_sampling) * c->response_sampling, per_t, spz);
+          int64_t i = (int64_t)py_round(xd / bin - 0.5), j = (int64_t)py_round(yd / bin - 0.5);
           int64_t k = (int64_t)py_round((time_tick - t0) / c->response_sampling);
           if (i >= 0 && i < ni && j >= 0 && j < nj && k >= 0 && k < nk) total += charge * response[(i * nj + j) * nk + k];
         }
+#undef MC_MARGIN
       out[it] = (float)total;
+      if (signals64) signals64[pr * T + it] = total;
+      if (n_draws) n_draws[pr * T + it] = (int32_t)q.n;
+      if (margin) margin[pr * T + it] = mg;
+      overrun |= q.overrun;
     }
   }
-  for (int64_t i = 0; i < S * P; i++) o_rng_next(&states[i]);
-  return 0;
+  if (states)
+    for (int64_t i = 0; i < S * P; i++) o_rng_next(&states[i]);
+  return overrun ? -1 : 0;
+}
+int o_tracks_current_mc(float* signals, const int32_t* pixels, const OTrack* tr, int64_t S, int64_t P, int64_t T,
+                        const double* response, int64_t ni, int64_t nj, int64_t nk, const LdsimConsts* c, ORng* states) {
+  return mc_core(signals, NULL, NULL, NULL, pixels, tr, S, P, T, response, ni, nj, nk, c, states, NULL, NULL, 0);
+}
+/* the same with the optional outputs of mc_core; the states are stepped once */
+int o_tracks_current_mc_ex(float* signals, double* signals64, int32_t* n_draws, double* margin, const int32_t* pixels,
+                           const OTrack* tr, int64_t S, int64_t P, int64_t T, const double* response, int64_t ni, int64_t nj,
+                           int64_t nk, const LdsimConsts* c, ORng* states) {
+  return mc_core(signals, signals64, n_draws, margin, pixels, tr, S, P, T, response, ni, nj, nk, c, states, NULL, NULL, 0);
+}
+/* supplied normals: normals[S*P*T][D] f32 (radii: the same shape or NULL) */
+int o_tracks_current_mc_normals(float* signals, double* signals64, int32_t* n_draws, double* margin, const int32_t* pixels,
+                                const OTrack* tr, int64_t S, int64_t P, int64_t T, const double* response, int64_t ni,
+                                int64_t nj, int64_t nk, const LdsimConsts* c, const float* normals, const float* radii,
+                                int64_t D) {
+  return mc_core(signals, signals64, n_draws, margin, pixels, tr, S, P, T, response, ni, nj, nk, c, NULL, normals, radii, D);
+}
+/* the first count[e] (NULL: D) normals of the table stream of every entry of segments [itrk0, itrk1), e = ((itrk - itrk0)*P + ipix)*T
+ * + it, with their radii (NULL: not wanted): what o_tracks_current_mc draws there among S segments, as arrays for
+ * o_tracks_current_mc_normals.  The states are not stepped. */
+void o_mc_table_normals(const ORng* states, int64_t S, int64_t P, int64_t T, int64_t itrk0, int64_t itrk1, int64_t D,
+                        const int32_t* count, float* normals, float* radii) {
+#pragma omp parallel for schedule(static)
+  for (int64_t e = 0; e < (itrk1 - itrk0) * P * T; e++) {
+    const int64_t pr = e / T, it = e % T, itrk = itrk0 + pr / P, ipix = pr % P;
+    int64_t n = count ? count[e] : D;
+    if (n > D) n = D;
+    if (n <= 0) continue;
+    ORng rs;
+    mc_stream(&states[itrk + S * ipix], (uint32_t)it, &rs);
+    for (int64_t d = 0; d < n; d++) {
+      float r;
+      normals[e * D + d] = rng_normal_radius_f32(&rs, &r);
+      if (radii) radii[e * D + d] = r;
+    }
+  }
 }
 
 int o_get_adc_values_rng(const double* pixels_signals, const double* pixels_signals_tracks, const double* time_ticks,

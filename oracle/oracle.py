@@ -197,7 +197,73 @@ def tracks_current_mc(tracks, pixels, T, response, rng_states):
     return sig
 
 
-RNG_DTYPE = np.dtype([("s0", "<u8"), ("s1", "<u8")])     # numba.cuda.random.xoroshiro128p_dtype
+def _mc_outputs(S, P, T, want):
+    sig = np.zeros((S, P, T), dtype=np.float32)
+    out = {"signals": sig}
+    if want:
+        out.update(signals64=np.zeros((S, P, T)), n_draws=np.zeros((S, P, T), dtype=np.int32), margin=np.zeros((S, P, T)))
+    return out
+
+
+def tracks_current_mc_detail(tracks, pixels, T, response, rng_states):
+    """``tracks_current_mc`` (same streams, same bits in ``signals``, the states stepped once) with what the loop knows besides:
+    dict(signals f32, signals64 the unrounded sums, n_draws i4 the normals each (segment, pixel, tick) drew, margin f8: the
+    smallest move of one of its draws that changes a decision -- an edge of the time window, a reach cut, a half-integer of the
+    roundings for i, j, k -- in spacings of float32 at that draw's Box-Muller radius; +inf where nothing was decided)."""
+    o = to_oracle(tracks)
+    c = _consts(noise_zero=False)
+    S, P = pixels.shape
+    out = _mc_outputs(S, P, T, True)
+    resp = np.ascontiguousarray(response, dtype=np.float64)
+    pix = np.ascontiguousarray(pixels, dtype=np.int32)
+    assert rng_states.dtype == RNG_DTYPE and len(rng_states) >= S * P
+    lib().o_tracks_current_mc_ex(_p(out["signals"]), _p(out["signals64"]), _p(out["n_draws"]), _p(out["margin"]), _p(pix), _p(o),
+                                 C.c_int64(S), C.c_int64(P), C.c_int64(T), _p(resp), C.c_int64(resp.shape[0]),
+                                 C.c_int64(resp.shape[1]), C.c_int64(resp.shape[2]), C.byref(c), _p(rng_states))
+    return out
+
+
+def tracks_current_mc_normals(tracks, pixels, T, response, normals, radii=None):
+    """The loop of ``tracks_current_mc`` on supplied normals: draw d of entry (itrk, ipix, it) is ``normals[itrk, ipix, it, d]``
+    (f32 [S][P][T][D]; D at least the largest count an entry needs, else ValueError).  ``radii``: the Box-Muller radius of
+    each normal, for the margin (None: the margin takes the spacing at |normal|, which is not above the radius's).  Returns
+    the dict of ``tracks_current_mc_detail``."""
+    o = to_oracle(tracks)
+    c = _consts(noise_zero=False)
+    S, P = pixels.shape
+    nrm = np.ascontiguousarray(normals, dtype=np.float32)
+    assert nrm.shape[:3] == (S, P, T), (nrm.shape, (S, P, T))
+    rad = None if radii is None else np.ascontiguousarray(radii, dtype=np.float32)
+    assert rad is None or rad.shape == nrm.shape
+    out = _mc_outputs(S, P, T, True)
+    resp = np.ascontiguousarray(response, dtype=np.float64)
+    pix = np.ascontiguousarray(pixels, dtype=np.int32)
+    rc = lib().o_tracks_current_mc_normals(_p(out["signals"]), _p(out["signals64"]), _p(out["n_draws"]), _p(out["margin"]),
+                                           _p(pix), _p(o), C.c_int64(S), C.c_int64(P), C.c_int64(T), _p(resp),
+                                           C.c_int64(resp.shape[0]), C.c_int64(resp.shape[1]), C.c_int64(resp.shape[2]),
+                                           C.byref(c), _p(nrm), _p(rad), C.c_int64(nrm.shape[3]))
+    if rc:
+        raise ValueError(f"tracks_current_mc_normals: an entry needs more than the {nrm.shape[3]} normals supplied per entry")
+    return out
+
+
+def mc_stream_normals(rng_states, S, P, T, D, segments=None, count=None, want_radii=False):
+    """The normals ``tracks_current_mc`` draws in table mode among S segments, as arrays for the segments ``(begin, end)``
+    (None: all): draws 0 .. D-1 (``count`` i4 [n][P][T]: only the first count[entry]; the rest stay 0) of the stream of every
+    (itrk, ipix, it) -- ``mc_stream_words(states[itrk + S*ipix], it)`` then the xoroshiro128p Box-Muller normals.
+    f32 [n][P][T][D], with the radii when asked.  The states are not stepped."""
+    assert rng_states.dtype == RNG_DTYPE and len(rng_states) >= S * P
+    b, e = (0, S) if segments is None else segments
+    nrm = np.zeros((e - b, P, T, D), dtype=np.float32)
+    rad = np.zeros((e - b, P, T, D), dtype=np.float32) if want_radii else None
+    cnt = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+    assert cnt is None or cnt.shape == (e - b, P, T)
+    lib().o_mc_table_normals(_p(rng_states), C.c_int64(S), C.c_int64(P), C.c_int64(T), C.c_int64(b), C.c_int64(e), C.c_int64(D),
+                             _p(cnt), _p(nrm), _p(rad))
+    return (nrm, rad) if want_radii else nrm
+
+
+RNG_DTYPE =np.dtype([("s0", "<u8"), ("s1", "<u8")])     # numba.cuda.random.xoroshiro128p_dtype
 
 
 def rng_create_states(n, seed):
@@ -209,12 +275,9 @@ def rng_create_states(n, seed):
 
 def rng_normals(states, index, count):
     """`count` successive xoroshiro128p_normal_float32(states, index) draws (advances states[index])."""
-    l = lib()
-    l.o_rng_normal_f32.restype = C.c_float
     out = np.zeros(count, dtype=np.float32)
     ptr = C.c_void_p(states.ctypes.data + int(index) * RNG_DTYPE.itemsize)
-    for i in range(count):
-        out[i] = l.o_rng_normal_f32(ptr)
+    lib().o_rng_normals_fill(ptr, C.c_int64(int(count)), _p(out))
     return out
 
 

@@ -316,6 +316,85 @@ def assert_fee_scan_matches(g, adc, ticks, frac, digit, noisy):
     assert np.array_equal((ticks > float(g["time_ticks_stop"])).sum(axis=1), g["expect_beyond_end"])
 
 
+MC_CASES = ("module0_plain", "module0_multi", "ndlar_plain")
+MC_FRAGILE_MARGIN = 8.0      # below it an entry may differ between device and host normals (tests/test_gpu_mc_current.py)
+MC_FRAGILE_CAP = 0.01        # the share of the non-zero entries that may lie below it
+_mc = {}
+
+
+def dense_field(g, name, dtype=np.float64):
+    """the dense array of a sparse field (oracle/gen_golden.py sparse_fields)"""
+    shape, idx, val = sparse_field(g, name)
+    a = np.zeros(int(np.prod(shape)), dtype=dtype)
+    a[idx] = val
+    return a.reshape(shape)
+
+
+def load_mc_case(case):
+    """Constants and arrays of tests/golden/mc_<case>.npz (oracle/gen_golden.py gen_mc): the configuration the fixture names
+    with MIN_STEP_SIZE and MC_SAMPLE_MULTIPLIER as the reference ran with them (noise constants as shipped).  Returns a dict:
+    tracks (the records after the reference's quench and drift), segments_in, pixels i4 [S][P], T, seed, response, signals f8
+    [S][P][T] (the reference's unrounded sums), n_draws i8 [S][P][T], names.  The arrays are loaded once and read-only.
+    Undo with ``load_cfg("module0")``."""
+    if case not in _mc:
+        g = gold(f"mc_{case}.npz")
+        d = dict(cfg=str(g["cfg"]), kind=str(g["response_kind"]), names=[str(n) for n in g["segment_names"]],
+                 tracks=g["tracks"], segments_in=g["segments_in"], pixels=g["pixels"], n_neigh=int(g["n_neigh"]), T=int(g["T"]),
+                 seed=int(g["seed"]), track_starts=g["track_starts"], fragile_share=float(g["fragile_share"]),
+                 consts={str(k): float(v) for k, v in zip(g["const_names"], g["const_values"])},
+                 signals=dense_field(g, "signals"), n_draws=dense_field(g, "n_draws", np.int64))
+        for v in d.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _mc[case] = d
+    d = dict(_mc[case])
+    load_cfg(d["cfg"], noise_zero=False)
+    for k, v in d["consts"].items():
+        setattr(consts.sim, k, int(v) if k == "MC_SAMPLE_MULTIPLIER" else v)
+    d["response"] = response_for(d["kind"])
+    return d
+
+
+_mc_oracle = {}
+
+
+def mc_oracle(case):
+    """the oracle's tracks_current_mc on a mc_<case> fixture (table streams of the fixture's seed), computed once per case:
+    (fixture dict, dict of oracle.tracks_current_mc_detail, the states after the call).  Leaves the case's constants loaded."""
+    from oracle import oracle as O
+    m = load_mc_case(case)
+    if case not in _mc_oracle:
+        S, P = m["pixels"].shape
+        st = O.rng_create_states(S * P, m["seed"])
+        d = O.tracks_current_mc_detail(m["tracks"], m["pixels"], m["T"], m["response"], st)
+        for v in d.values():
+            v.setflags(write=False)
+        st.setflags(write=False)
+        _mc_oracle[case] = d, st
+    return (m,) + _mc_oracle[case]
+
+
+def mc_bar(got, ref, margin=None):
+    """The project's bar on Monte-Carlo currents, |d| <= 1e-5 |ref| + 1e-7 peak(row), and the zero pattern, on the entries
+    whose margin is at least MC_FRAGILE_MARGIN (all when ``margin`` is None).  The zero pattern is compared where the
+    float32 of ``ref`` is zero or a normal number: a subnormal float32 output may be flushed by the cast.  Returns the
+    number of entries compared."""
+    ref = np.asarray(ref, dtype=np.float64)
+    got = np.asarray(got, dtype=np.float64)
+    keep = np.ones(ref.shape, dtype=bool) if margin is None else margin >= MC_FRAGILE_MARGIN
+    peak = np.abs(ref).max(axis=-1, keepdims=True)
+    tol = 1e-5 * np.abs(ref) + 1e-7 * peak
+    bad = keep & ~(np.abs(got - ref) <= tol)
+    if bad.any():
+        i = np.unravel_index(np.argmax(np.where(bad, np.abs(got - ref) - tol, -1.0)), ref.shape)
+        raise AssertionError(f"{int(bad.sum())} of {int(keep.sum())} entries out of tolerance; worst at {i}: got {got[i]!r} "
+                             f"ref {ref[i]!r} row peak {peak[i[:-1]]}" + ("" if margin is None else f" margin {margin[i]}"))
+    r32 = ref.astype(np.float32)
+    sure = keep & ((r32 == 0) | (np.abs(r32) >= np.finfo(np.float32).tiny))
+    assert np.array_equal((got != 0)[sure], (r32 != 0)[sure]), "zero pattern differs"
+    return int(keep.sum())
+
+
 def det_phases(shape, seed):
     """The golden generator's stand-in for cp.random.uniform(size=shape) (oracle/gen_golden.py det_phases): a
     multiplicative hash of (row, column, seed) in [0, 1), so the fixtures need not store the phases."""

@@ -1876,7 +1876,8 @@ def test_tracks_current_mc_vs_oracle_and_closure():
     has its own stream here (the reference's tick threads race on one state), so parity is (a) with the oracle's
     restatement of the same rule: the table states end bit-identical and the currents agree except where a float32 normal's
     last bit moves a sample across a response-cell edge; (b) statistical closure with the deterministic integral
-    tracks_current: the same charge is induced."""
+    tracks_current: the same charge is induced.  tests/test_gpu_mc_current.py compares the kernel with the reference's own
+    source entry by entry, and the keyed instantiation on the device's own normals."""
     H.load_cfg("module0")
     seg = synth.make_segments(4, seed=17, segs_per_event=4)
     batching.swap_coordinates(seg)

@@ -346,3 +346,81 @@ def test_wide_neighbourhood_golden(cfg, radius):
         assert no_slot.any() == (radius >= 3) and not ps[no_slot].any()
         if tag:
             assert ((tpm >= 0).sum(axis=1) == M).any() and ovf.any()
+
+
+@pytest.mark.parametrize("case", H.MC_CASES)
+def test_mc_oracle_against_reference(case):
+    """The oracle's tracks_current_mc against the reference's own (detsim.py:220-348, oracle/gen_golden.py gen_mc), both on the
+    table streams this project defines (one per (segment, pixel, tick)): every entry of the unrounded sums to rtol 1e-12 and
+    1e-12 of the case's largest entry (same host normals, same order of sums; libm's sqrt alone separates them), the same
+    number of normals drawn by every entry, the same zero pattern.  The cases reach the z_start < z_end swap and its
+    opposite, both clamps of overlapping_segment, nstep 1 / 3 / hundreds, MC_SAMPLE_MULTIPLIER 3, M = 2 (ndlar), time_tick < 0,
+    an rr > impact row and a -1 slot per segment, and ticks past 256.  Not reached: k >= nk (TIME_WINDOW / RESPONSE_SAMPLING is
+    below the tables' length: the generator counts 0 such look-ups) and a segment exactly along z (l == 0 divides by zero in
+    the reference's pure-Python run; the kernel's "no signal" there is compared with the oracle alone)."""
+    try:
+        m, d, st = H.mc_oracle(case)
+        S, P = m["pixels"].shape
+        ref = m["signals"]
+        assert np.array_equal(d["n_draws"], m["n_draws"])
+        assert np.array_equal(d["signals64"] != 0, ref != 0) and (ref != 0).sum() > 500
+        np.testing.assert_allclose(d["signals64"], ref, rtol=1e-12, atol=1e-12 * np.abs(ref).max())
+        # the unchanged entry point: the same bits, the float32 of the sums, every state stepped once
+        st2 = O.rng_create_states(S * P, m["seed"])
+        sig = O.tracks_current_mc(m["tracks"], m["pixels"], m["T"], m["response"], st2)
+        assert np.array_equal(sig, d["signals"]) and np.array_equal(sig, d["signals64"].astype(np.float32))
+        assert np.array_equal(st2.view("u8"), st.view("u8"))
+        # the appended columns: a pixel beyond the impact radius and a -1, per segment
+        assert (m["pixels"][:, -1] == -1).all() and (m["pixels"][:, -2] >= 0).all()
+        assert not ref[:, -2:].any() and not m["n_draws"][:, -2:].any()
+        nstep = {n: m["n_draws"][i][m["n_draws"][i] > 0].min() for i, n in enumerate(m["names"])}
+        if case == "module0_plain":
+            assert nstep["tiny"] == 1 and nstep["inside"] == 3 and nstep["steep"] > 256
+            i, j = m["names"].index("diag"), m["names"].index("diag_swapped")
+            assert m["tracks"]["z_start"][i] < m["tracks"]["z_end"][i] and m["tracks"]["z_start"][j] > m["tracks"]["z_end"][j]
+        if case == "module0_multi":
+            assert consts.sim.MC_SAMPLE_MULTIPLIER == 3 and all(v % 3 == 0 for v in nstep.values())
+        if case == "ndlar_plain":
+            assert round(consts.detector.TIME_SAMPLING / consts.detector.RESPONSE_SAMPLING) == 2
+    finally:
+        H.load_cfg("module0")
+
+
+@pytest.mark.parametrize("case", H.MC_CASES)
+def test_mc_oracle_supplied_normals(case):
+    """The supplied-normals entry fed the table streams' normals as arrays (segment by segment: the steep one draws up to 1050
+    per entry) returns the table entry point's signals, sums and draw counts bit for bit, and with the radii its margins."""
+    try:
+        m, d, st = H.mc_oracle(case)
+        S, P = m["pixels"].shape
+        T = m["T"]
+        states = O.rng_create_states(S * P, m["seed"])
+        for i in range(S):
+            cnt = d["n_draws"][i:i + 1]
+            D = int(cnt.max())
+            nrm, rad = O.mc_stream_normals(states, S, P, T, D, segments=(i, i + 1), count=cnt, want_radii=True)
+            got = O.tracks_current_mc_normals(m["tracks"][i:i + 1], m["pixels"][i:i + 1], T, m["response"], nrm, rad)
+            for k in ("signals", "signals64", "n_draws", "margin"):
+                assert np.array_equal(got[k][0], d[k][i]), (m["names"][i], k)
+            if D > 1:
+                with pytest.raises(ValueError, match="more than the"):
+                    O.tracks_current_mc_normals(m["tracks"][i:i + 1], m["pixels"][i:i + 1], T, m["response"], nrm[..., :D - 1])
+    finally:
+        H.load_cfg("module0")
+
+
+@pytest.mark.parametrize("case", H.MC_CASES)
+def test_mc_fragile_entries_are_few(case):
+    """At most 1 % of a case's non-zero entries may have a decision (window edge, reach cut, rounding of i, j, k) within 8
+    float32 spacings of a draw's Box-Muller radius: those are the entries the device's normals may legitimately move (the
+    GPU test leaves them out).  Shares: module0_plain 0.00061, module0_multi 0.00082, ndlar_plain 0.00129."""
+    try:
+        m, d, st = H.mc_oracle(case)
+        nz = m["signals"] != 0
+        fragile = float((d["margin"][nz] < H.MC_FRAGILE_MARGIN).mean())
+        print(case, "share of non-zero entries with margin below", H.MC_FRAGILE_MARGIN, ":", fragile)
+        assert fragile == m["fragile_share"]
+        assert fragile <= H.MC_FRAGILE_CAP
+        assert np.isinf(d["margin"][m["n_draws"] == 0]).all() and (d["margin"][m["n_draws"] > 0] < np.inf).all()
+    finally:
+        H.load_cfg("module0")
