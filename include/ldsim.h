@@ -298,7 +298,9 @@ int ldsim_get_adc_values(ldsim_ctx* ctx, const double* pixels_signals, const dou
 /* fee.digitize(integral_list, gain)                   -- larndsim/fee.py:499-515; gain NULL = GAIN*mV/e */
 int ldsim_digitize(ldsim_ctx* ctx, const double* integral_list, int64_t n, const double* gain_list, double* adcs);
 /* lightLUT.calculate_light_incidence[bpg,tpb](tracks, lut, light_incidence, voxel)
- *                                                     -- larndsim/lightLUT.py:65-136 */
+ *                                                     -- larndsim/lightLUT.py:65-136
+ * The three arrays are read and written: rows of segments outside every TPC, and t0_det in trigger mode 1, come back as
+ * they were passed (the reference does not touch them); under option "light_lut_interp" they come back zero. */
 int ldsim_light_incidence(ldsim_ctx* ctx, const void* tracks, int64_t n, const LdsimTrackLayout* layout,
                           int32_t n_out_channels, float* n_photons_det, float* t0_det, int32_t* voxel);
 /* light_sim.sum_light_signals[...](segments, segment_voxel, segment_track_id, light_inc, op_channel, lut,

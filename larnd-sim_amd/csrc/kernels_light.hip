@@ -676,7 +676,12 @@ __global__ void light_fill_ordered_kernel(LightSum L, const int32_t* __restrict_
 // ---- round 4, resident sum: only the (detector, segment) pairs that carry photons are ordered, and a wave emits a pair's records ----
 // A segment lights the detectors of its own TPC: 1 in 8 (2x2) to 1 in 70 (ndlar) of the n_det x n pairs hold photons.  The pairs
 // that do are compacted (any order: the sort that follows orders them, their keys are distinct) ...
-#define LIGHT_SPARE 2                 // record slots of a pair beyond its profile bins (a bin at a window edge can deposit into two ticks: ~1e-10 per bin)
+// record slots of a pair beyond its profile bins.  A bin at a window edge can deposit into two ticks: ~1e-10 per bin for times
+// off the tick grid only.  Times ON the grid (t0 = k / 1000 in f64 with start_time = -1.0: whole nanoseconds, what an event
+// generator writes) meet an edge with every bin: of the 2048 arrivals of tests/golden/light_edge_grid_smear.npz the reference's
+// expressions put 976 into no tick, 443 into one and 629 into two.  No pair of the on-grid fixtures needs more than bins + 1 records
+// (their reach_records_per_pair_max, asserted <= bins + LIGHT_SPARE when they are generated and loaded).
+#define LIGHT_SPARE 2
 #define LIGHT_NONE 0xFFFFFFFFu        // key of an unused record slot: sorts behind every (detector, tick) cell (those use <= 31 bits)
 __global__ void __launch_bounds__(256) light_active_pairs_kernel(LightSum L, unsigned long long* __restrict__ keys,
                                                                 int32_t* __restrict__ vals, unsigned* __restrict__ count) {
@@ -707,7 +712,8 @@ __global__ void __launch_bounds__(256) light_active_pairs_kernel(LightSum L, uns
 // expressions can admit two ticks, both are emitted, tick ascending) are ranked by ballot and written side by side; the slots
 // left over carry LIGHT_NONE.  No count pass, no scan, no read-back of the record count, and the stores are coalesced (a thread per
 // pair wrote its ~100 records alone: 0.63 ms per 2x2 batch).  cap = bins + LIGHT_SPARE; a pair that would need more (three window-edge
-// coincidences in one pair: ~1e-24) raises *overflow and the sum fails loudly.
+// coincidences in one pair: ~1e-24 for times off the tick grid; on the grid the two-tick bins are many, but none of the on-grid
+// fixtures of tests/test_gpu_light_edges.py needs more than bins + 1) raises *overflow and the sum fails loudly.
 __global__ void __launch_bounds__(256) light_emit_wave_kernel(LightSum L, const int32_t* __restrict__ order, int64_t n_act, int cap,
                                                              int tick_bits, unsigned* __restrict__ keys,
                                                              unsigned long long* __restrict__ vals, unsigned* __restrict__ overflow) {

@@ -1060,9 +1060,20 @@ extern "C" int ldsim_light_incidence(ldsim_ctx* ctx, const void* tracks, int64_t
   DevBuf dn, dt, dv;
   size_t bc = (size_t)n * n_out * 4;
   CK(dn.ensure(bc)); CK(dt.ensure(bc)); CK(dv.ensure((size_t)n * 12));
-  HIPCHK(hipMemsetAsync(dn.p, 0, bc, ctx->stream));
-  HIPCHK(hipMemsetAsync(dt.p, 0, bc, ctx->stream));
-  HIPCHK(hipMemsetAsync(dv.p, 0, (size_t)n * 12, ctx->stream));
+  // the kernels write into the caller's arrays like the reference: rows of segments outside every TPC, and t0_det in trigger
+  // mode 1, keep what they hold (lightLUT.py:98,134).  Option light_lut_interp has no reference: its contract is the numpy twin's,
+  // which returns zeros there.
+  if (ctx->light_lut_interp) {
+    HIPCHK(hipMemsetAsync(dn.p, 0, bc, ctx->stream));
+    HIPCHK(hipMemsetAsync(dt.p, 0, bc, ctx->stream));
+    HIPCHK(hipMemsetAsync(dv.p, 0, (size_t)n * 12, ctx->stream));
+  } else {
+    if (bc) {
+      HIPCHK(hipMemcpyAsync(dn.p, nph, bc, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(dt.p, t0det, bc, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (n) HIPCHK(hipMemcpyAsync(dv.p, voxel, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+  }
   CK(light_launch_incidence(ctx, 0, n, n_out, dn.as<float>(), dt.as<float>(), dv.as<int32_t>(), 0));
   if (bc) {
     HIPCHK(hipMemcpyAsync(nph, dn.p, bc, hipMemcpyDeviceToHost, ctx->stream));

@@ -231,7 +231,13 @@ def set_light(lut=None, ctx=None):
     c2t = np.ascontiguousarray(consts.light.OP_CHANNEL_TO_TPC, dtype=np.int32)
     check(lib.ldsim_set_light_channels(ctx, ptr(eff), ptr(c2t), C.c_int32(len(eff))))
     if lut is not None:
-        tok = _token(lut, lut['vis'].ravel()[::97].sum())
+        sample = lut['vis'].ravel()[::97].sum()
+        if lut.nbytes <= (1 << 20):
+            # a small table (a test's, a hand-made one): every value of every field counts -- tables built one after another
+            # land on the same address with the same shape, and the strided sample of vis sees one value of a table of < 97
+            import zlib
+            sample = zlib.crc32(np.ascontiguousarray(lut).view(np.uint8))
+        tok = _token(lut, sample)
         if tok == _lut_token:
             return
         _lut_token = tok

@@ -15,14 +15,19 @@ def _ensure_lut(lut):
 @kernel
 def calculate_light_incidence(tracks, lut, light_incidence, voxel):
     """``calculate_light_incidence[bpg, tpb](tracks, lut, light_incidence, voxel)``; ``light_incidence`` is the
-    structured array with ``n_photons_det`` / ``t0_det`` (f4) the reference driver allocates."""
+    structured array with ``n_photons_det`` / ``t0_det`` (f4) the reference driver allocates.  Like the reference the call
+    writes into what the caller passed: rows of segments outside every TPC, and ``t0_det`` in trigger mode 1, keep their values
+    (under the context option ``light_lut_interp`` they read zero, like the numpy twin's)."""
     lay = make_layout(tracks.dtype)
     n, n_out = light_incidence.shape
     lib.context()
     _ensure_lut(lut)
-    nph = np.zeros((n, n_out), dtype=np.float32)
-    t0d = np.zeros((n, n_out), dtype=np.float32)
-    vox = np.zeros((n, 3), dtype=np.int32)
+    nph = np.array(light_incidence['n_photons_det'], dtype=np.float32, order='C')
+    t0d = (np.array(light_incidence['t0_det'], dtype=np.float32, order='C') if 't0_det' in light_incidence.dtype.names
+           else np.zeros((n, n_out), dtype=np.float32))
+    vox = np.array(voxel, dtype=np.int32, order='C')
+    if vox.shape != (n, 3):
+        raise ValueError("voxel must be [n_tracks, 3]")
     lib.check(lib.load().ldsim_light_incidence(lib.context(refresh_consts=False), lib.ptr(tracks), C.c_int64(n),
                                                C.byref(lay), C.c_int32(n_out), lib.ptr(nph), lib.ptr(t0d),
                                                lib.ptr(vox)))

@@ -19,7 +19,7 @@ Faithfulness rules (Numba types arithmetic as f64; NumPy-2 scalars do not):
   * between stages the mutated float fields are rounded through f4 (the HDF5 schema);
   * FEE noise constants are 0 (the Numba RNG stream is third-party and unpinned).
 
-Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,pixels_wide,chain,sampled,light,light_response,light_wvfm,light_wvfm_edges,fee,mc] [--jobs 8]
+Usage:  python oracle/gen_golden.py [--sets consts,qd,pixels,pixels_wide,chain,sampled,light,light_response,light_wvfm,light_wvfm_edges,light_edges,fee,mc] [--jobs 8]
 """
 import argparse
 import importlib
@@ -1424,6 +1424,547 @@ def gen_light_wvfm_edges():
     _gen_lw_edge_digitiser()
 
 
+# --------------------------------------------------------------------------
+# light_edges: lightLUT.calculate_light_incidence, light_sim.get_nticks and light_sim.sum_light_signals where the kernels that
+# stand for them are delicate: arrival times on the tick grid, truth-slot rules, voxel faces and clamps, channel slices, LUTs of
+# 6 detectors, trigger mode 1, efficiencies that are zero / negative / NaN.  A fixture is a list of runs r0, r1, ...; the inputs
+# travel in it in the form the stage reads (records, LUT, efficiencies, op_channel, sorted_indices, track ids).
+# --------------------------------------------------------------------------
+LE_MAX_BYTES = 256 * 1024
+LE_SENT_NPH, LE_SENT_T0, LE_SENT_VOX = 123.0, -7.0, -5          # what the incidence outputs hold before the call
+LE_INC8 = [('segment_id', 'u4'), ('n_photons_det', 'f8'), ('t0_det', 'f8')]      # f8 mirrors: Numba's f64 arithmetic
+LE_INC4 = [('segment_id', 'u4'), ('n_photons_det', 'f4'), ('t0_det', 'f4')]
+LE_REC_FIELDS = ("x", "y", "z", "t0", "n_photons", "pixel_plane")
+
+
+def _le_ref(cfg, over):
+    """The reference loaded for `cfg` with the constants of `over` set by name (MC_TRUTH_THRESHOLD on sim, the others on light;
+    a list is an array)."""
+    ref = Ref(cfg)
+    for k, v in over.items():
+        setattr(ref.sim if k == "MC_TRUTH_THRESHOLD" else ref.light, k, np.array(v, dtype=float) if isinstance(v, list) else v)
+    return ref
+
+
+def _le_lut(shape, ndet, n_prof, salt=0):
+    """A hand-made LUT whose every value is dyadic: vis and time_dist powers of two, t0 and t0_avg whole nanoseconds; every
+    voxel and detector differs from its neighbours."""
+    nx, ny, nz = shape
+    lut = np.zeros((nx, ny, nz, ndet), dtype=[('vis', 'f4'), ('t0', 'f4'), ('t0_avg', 'f4'), ('time_dist', 'f4', (n_prof,))])
+    i, j, k, d = np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), np.arange(ndet), indexing='ij')
+    h = i * 5 + j * 3 + k * 7 + d + salt
+    lut['vis'] = 2.0 ** -(1 + h % 4)
+    lut['t0'] = (h * 3) % 5
+    lut['t0_avg'] = (h * 7) % 12
+    lut['time_dist'] = 2.0 ** -(1 + (h[..., None] + np.arange(n_prof)) % 4)
+    return lut
+
+
+def _le_lut8(lut):
+    n_prof = lut['time_dist'].shape[-1]
+    lut8 = np.zeros(lut.shape, dtype=[('vis', 'f8'), ('t0', 'f8'), ('t0_avg', 'f8'), ('time_dist', 'f8', (n_prof,))])
+    for f in lut.dtype.names:
+        lut8[f] = lut[f]
+    return lut8
+
+
+def _le_records(n):
+    return np.zeros(n, dtype=REF_DTYPE)
+
+
+def _le_inside(det, itpc, m, n):
+    """a point well inside TPC `itpc`, different for every m of n"""
+    b = det.TPC_BORDERS[itpc]
+    u = np.array([((m * 7 + 3) % n + 0.37) / n, ((m * 11 + 1) % n + 0.61) / n, ((m * 5 + 2) % n + 0.23) / n])
+    return [float(f4(b[a][0] + (b[a][1] - b[a][0]) * (0.05 + 0.9 * u[a]))) for a in range(3)]
+
+
+def _le_incidence(ref, rec, lut, n_out):
+    """The reference's calculate_light_incidence into arrays that hold the sentinels: (n_photons_det f4, t0_det f4, voxel i4)"""
+    n = len(rec)
+    inc8 = np.zeros((n, n_out), dtype=LE_INC8)
+    inc8['n_photons_det'] = LE_SENT_NPH
+    inc8['t0_det'] = LE_SENT_T0
+    voxel = np.full((n, 3), LE_SENT_VOX, dtype='i4')
+    with np.errstate(invalid='ignore'):
+        ref.lightLUT.calculate_light_incidence[max(1, -(-n // 256)), 256](rec, _le_lut8(lut), inc8, voxel)
+    return inc8['n_photons_det'].astype('f4'), inc8['t0_det'].astype('f4'), voxel
+
+
+def _le_nticks(ref, nph, t0d):
+    inc = np.zeros(nph.shape, dtype=LE_INC4)
+    inc['n_photons_det'] = nph
+    inc['t0_det'] = t0d
+    n_ticks, start = ref.light_sim.get_nticks(inc)
+    return int(n_ticks), float(start)          # (Numba types the scalar argument f64)
+
+
+def _le_voxel_unclamped(ref, rec, shape):
+    """get_voxel's three indices before the clamp and its fractions times n (lightLUT.py:39-57) for the records inside a TPC:
+    (rows, int indices [m, 3], fractions [m, 3])"""
+    rows, idx, fr = [], [], []
+    for m, r in enumerate(rec):
+        itpc = int(r['pixel_plane'])
+        if itpc == ref.detector.DEFAULT_PLANE_INDEX:
+            continue
+        b = ref.detector.TPC_BORDERS[itpc]
+        is_even = b[2][1] > b[2][0]
+        x_min, x_max = b[0][0] - 2e-2, b[0][1] + 2e-2
+        y_min, y_max = b[1][0] - 2e-2, b[1][1] + 2e-2
+        z_min, z_max = b[2][0] - 2e-2, b[2][1] + 2e-2
+        f = [(r['x'] - x_min) / (x_max - x_min) * shape[0] if is_even else (x_max - r['x']) / (x_max - x_min) * shape[0],
+             (y_max - r['y']) / (y_max - y_min) * shape[1], (r['z'] - z_min) / (z_max - z_min) * shape[2]]
+        rows.append(m); idx.append([int(v) for v in f]); fr.append(f)
+    return np.array(rows), np.array(idx).reshape(-1, 3), np.array(fr).reshape(-1, 3)
+
+
+def _le_save(case, cfg, over, out, bounds=None):
+    """One fixture: arrays, configuration name, overridden constants as JSON.  Every `reach_*` count is non-zero, or at least the
+    bound given for it."""
+    out = dict(out)
+    bounds = bounds or {}
+    for k, v in out.items():
+        if k.startswith("reach_"):
+            assert int(v) >= bounds.get(k, 1), (case, k, int(v))
+            out[k] = np.int64(v)
+    out["cfg"] = np.array(cfg)
+    out["const_json"] = np.array(json.dumps({k: (list(v) if isinstance(v, tuple) else v) for k, v in over.items()}, sort_keys=True))
+    path = os.path.join(GOLD, f"light_edge_{case}.npz")
+    save_npz_fixed(path, out)
+    size = os.path.getsize(path)
+    assert size < LE_MAX_BYTES, (case, size)
+    reach = " ".join(f"{k[6:]}={int(v)}" for k, v in sorted(out.items()) if k.startswith("reach_"))
+    print(f"light_edge {case:24s} {size:7d} bytes  {reach}")
+
+
+def _le_put_records(out, pre, rec):
+    for f in LE_REC_FIELDS:
+        out[pre + f] = rec[f].copy()
+
+
+def _le_put_lut(out, pre, lut):
+    for f in lut.dtype.names:
+        out[pre + "lut_" + f] = np.ascontiguousarray(lut[f])
+
+
+def _le_incidence_run(ref, out, k, rec, lut, n_out, lut_key=None):
+    """run k of an incidence fixture: records, LUT (or the key of a LUT stored once), output width, what the reference wrote and
+    get_nticks of it.  Returns (n_photons_det, t0_det, voxel)."""
+    assert len(rec) <= 64
+    pre = f"r{k}_"
+    nph, t0d, vox = _le_incidence(ref, rec, lut, n_out)
+    _le_put_records(out, pre, rec)
+    if lut_key is None:
+        _le_put_lut(out, pre, lut)
+    else:
+        out[pre + "lut"] = np.array(lut_key)
+    n_ticks, start = _le_nticks(ref, nph, t0d)
+    out.update({pre + "n_out": np.int64(n_out), pre + "n_photons_det": nph, pre + "t0_det": t0d, pre + "voxel": vox,
+                pre + "n_ticks": np.int64(n_ticks), pre + "start_time": np.float64(start)})
+    out["n_runs"] = np.int64(k + 1)
+    return nph, t0d, vox
+
+
+def _le_face_points(b, a, n):
+    """coordinates on axis a of a TPC with borders b for a LUT of n voxels along it: both borders, border -+ 1.9e-2 (inside
+    get_voxel's 2e-2 margin), every interior voxel face min + k (max - min) / n in f64 with its two neighbours, and a point a
+    voxel and a half beyond either end (clamped)"""
+    lo, hi = b[a][0] - 2e-2, b[a][1] + 2e-2
+    pts = [b[a][0], b[a][1], b[a][0] - 1.9e-2, b[a][0] + 1.9e-2, b[a][1] - 1.9e-2, b[a][1] + 1.9e-2,
+           lo - 1.5 * (hi - lo) / n, hi + 1.5 * (hi - lo) / n]
+    for k in range(1, n):
+        face = lo + k * (hi - lo) / n
+        pts += [face, np.nextafter(face, -np.inf), np.nextafter(face, np.inf)]
+    return [float(p) for p in pts]
+
+
+def _gen_le_faces(case, cfg, tpcs):
+    ref = _le_ref(cfg, {})
+    det = ref.detector
+    n_out = ref.light.N_OP_CHANNEL
+    out = {}
+    reach = {f"reach_clamped_{s}_{ax}": 0 for s in ("low", "high") for ax in "xyz"}
+    reach.update(reach_on_face=0, reach_untouched=0)
+    k = 0
+    for si, shape in enumerate(((1, 1, 1), (3, 5, 2), (14, 26, 8))):
+        lut = _le_lut(shape, 4, 1, salt=si)
+        _le_put_lut(out, f"s{si}_", lut)
+        for itpc in tpcs:
+            b = det.TPC_BORDERS[itpc]
+            pts = [_le_face_points(b, a, shape[a]) for a in range(3)]
+            total = max(len(p) for p in pts)
+            for c0 in range(0, total, 60):
+                ms = list(range(c0, min(c0 + 60, total)))
+                rec = _le_records(len(ms) + 2)
+                for q, m in enumerate(ms):
+                    rec['x'][q], rec['y'][q], rec['z'][q] = (pts[a][m % len(pts[a])] for a in range(3))
+                    rec['pixel_plane'][q] = itpc
+                # two segments outside every TPC, at positions inside this one
+                for q in (len(ms), len(ms) + 1):
+                    rec['x'][q], rec['y'][q], rec['z'][q] = _le_inside(det, itpc, q, 64)
+                    rec['pixel_plane'][q] = det.DEFAULT_PLANE_INDEX
+                rec[[3, len(ms)]] = rec[[len(ms), 3]]           # (one of them inside the tile, not at its end)
+                rec['n_photons'] = f4(1000.5 + 3 * np.arange(len(rec)))
+                rec['t0'] = f4(0.25 + np.arange(len(rec)) / 64)
+                nph, t0d, vox = _le_incidence_run(ref, out, k, rec, lut, n_out, lut_key=f"s{si}_")
+                k += 1
+                rows, idx, fr = _le_voxel_unclamped(ref, rec, shape)
+                for a, ax in enumerate("xyz"):
+                    reach[f"reach_clamped_low_{ax}"] += int((idx[:, a] < 0).sum())
+                    reach[f"reach_clamped_high_{ax}"] += int((idx[:, a] > shape[a] - 1).sum())
+                    inner = (fr[:, a] > 0.5) & (fr[:, a] < shape[a] - 0.5)
+                    reach["reach_on_face"] += int((inner & (fr[:, a] == np.floor(fr[:, a]))).sum())
+                reach["reach_untouched"] += int(((vox == LE_SENT_VOX).all(axis=1) & (nph == LE_SENT_NPH).all(axis=1) &
+                                                 (t0d == LE_SENT_T0).all(axis=1)).sum())
+    out.update(reach)
+    _le_save(case, cfg, {}, out)
+
+
+def _le_plain_records(ref, tpcs, n, n_default=1):
+    """n records at interior points of the TPCs in turn, the last n_default of them outside every TPC"""
+    det = ref.detector
+    rec = _le_records(n)
+    for m in range(n):
+        itpc = tpcs[m % len(tpcs)]
+        rec['x'][m], rec['y'][m], rec['z'][m] = _le_inside(det, itpc, m, n)
+        rec['pixel_plane'][m] = itpc if m < n - n_default else det.DEFAULT_PLANE_INDEX
+    rec['n_photons'] = f4(200.25 + 17 * np.arange(n))
+    rec['t0'] = f4(0.125 + np.arange(n) / 32)
+    return rec
+
+
+def _gen_le_incidence_cases():
+    _gen_le_faces("faces_module0", "module0", (0, 1))
+    _gen_le_faces("faces_2x2", "2x2_no_modvar", (1, 4))
+
+    # a LUT of 6 detectors (lut_index = o % 6; not a multiple of 4: the one-channel kernel) and its twin of 48
+    ref = _le_ref("module0", {})
+    rec = _le_plain_records(ref, (0, 1), 21)
+    out = {}
+    for k, ndet in enumerate((6, 48)):
+        nph, _, _ = _le_incidence_run(ref, out, k, rec, _le_lut((3, 5, 2), ndet, 1, salt=2), ref.light.N_OP_CHANNEL)
+        out[f"reach_lit_{ndet}"] = int(((nph > 0) & (nph != LE_SENT_NPH)).sum())
+    _le_save("lut_6_detectors", "module0", {}, out)
+
+    # one module's slice of the channels: the tables' offset follows the segment's module (lightLUT.py:120-123)
+    ref = _le_ref("2x2_no_modvar", {})
+    n_out = ref.light.N_OP_CHANNEL // 4
+    rec = _le_plain_records(ref, (0, 1, 2, 5, 7), 26)
+    out = {}
+    nph, _, _ = _le_incidence_run(ref, out, 0, rec, _le_lut((3, 5, 2), 48, 1, salt=3), n_out)
+    mods = np.unique(rec['pixel_plane'][rec['pixel_plane'] != ref.detector.DEFAULT_PLANE_INDEX] // 2)
+    out["reach_modules"] = len(mods)
+    out["reach_lit"] = int(((nph > 0) & (nph != LE_SENT_NPH)).sum())
+    assert len(mods) == 4 and n_out < ref.light.N_OP_CHANNEL
+    _le_save("module_slice_2x2", "2x2_no_modvar", {}, out, bounds=dict(reach_modules=4))
+
+    # trigger mode 1: t0_det is not written, get_nticks returns the fixed window
+    over = dict(LIGHT_TRIG_MODE=1)
+    ref = _le_ref("module0", over)
+    rec = _le_plain_records(ref, (0, 1), 19)
+    out = {}
+    nph, t0d, _ = _le_incidence_run(ref, out, 0, rec, _le_lut((3, 5, 2), 48, 1, salt=4), ref.light.N_OP_CHANNEL)
+    assert (t0d == LE_SENT_T0).all()
+    lw = ref.light.LIGHT_WINDOW
+    assert int(out["r0_n_ticks"]) == int((lw[1] + lw[0]) / ref.light.LIGHT_TICK_SIZE) and float(out["r0_start_time"]) == 0.0
+    out["reach_t0_untouched"] = int((t0d == LE_SENT_T0).sum())
+    out["reach_lit"] = int(((nph > 0) & (nph != LE_SENT_NPH)).sum())
+    _le_save("trig_mode_1", "module0", over, out)
+
+    # efficiencies that are zero, negative and NaN: the reference writes NaN and -0.0 into the channels of other TPCs
+    ref = _le_ref("module0", {})
+    eff = np.asarray(ref.light.OP_CHANNEL_EFFICIENCY, dtype=float).copy()
+    eff[[2, 49]] = 0.0
+    eff[[4, 50]] = -0.25
+    eff[[9, 60]] = np.nan
+    over = dict(OP_CHANNEL_EFFICIENCY=[float(v) for v in eff])
+    ref = _le_ref("module0", over)
+    rec = _le_plain_records(ref, (0, 1), 23)
+    rec['n_photons'][5] = 0.0
+    out = {}
+    nph, _, _ = _le_incidence_run(ref, out, 0, rec, _le_lut((3, 5, 2), 48, 1, salt=5), ref.light.N_OP_CHANNEL)
+    out["reach_nan"] = int(np.isnan(nph).sum())
+    out["reach_negative_zero"] = int(((nph == 0) & np.signbit(nph)).sum())
+    out["reach_negative"] = int((nph < 0).sum())
+    _le_save("efficiency_fallback", "module0", over, out)
+
+    # no light: records without photons and voxels without visibility
+    ref = _le_ref("module0", {})
+    rec = _le_plain_records(ref, (0, 1), 22)
+    rec['n_photons'][::3] = 0.0
+    lut = _le_lut((3, 5, 2), 48, 1, salt=6)
+    lut['vis'][1] = 0.0
+    lut['vis'][:, :, :, ::5] = 0.0
+    out = {}
+    nph, _, vox = _le_incidence_run(ref, out, 0, rec, lut, ref.light.N_OP_CHANNEL)
+    out["reach_no_photons"] = int((rec['n_photons'] == 0).sum())
+    out["reach_dark_voxel"] = int((vox[:, 0] == 1).sum())
+    out["reach_lit"] = int(((nph > 0) & (nph != LE_SENT_NPH)).sum())
+    # ... and a run in which nothing is lit at all: get_nticks falls back to the fixed window
+    rec2 = rec[rec['pixel_plane'] != ref.detector.DEFAULT_PLANE_INDEX].copy()
+    rec2['n_photons'] = 0.0
+    nph2, _, _ = _le_incidence_run(ref, out, 1, rec2, lut, ref.light.N_OP_CHANNEL)
+    assert not (nph2 > 0).any() and float(out["r1_start_time"]) == 0.0
+    _le_save("dark", "module0", {}, out)
+
+
+# ---- photon sum ------------------------------------------------------------------------------------------------------------------------
+LE_SUM_CHANNELS = (0, 1, 5, 47, 48, 50, 95, 7)          # detector rows of the photon-sum cases: both TPCs of module0, not in order
+
+
+def _le_dyadic_eff(n):
+    return [float(2.0 ** -(1 + c % 2)) for c in range(n)]
+
+
+def _le_sum_records(ref, t0):
+    """one record per entry of t0, alternating TPCs, distinct odd photon counts: with dyadic efficiencies and visibilities no two
+    records give a detector the same photons"""
+    n = len(t0)
+    assert n <= 32
+    rec = _le_records(n)
+    for m in range(n):
+        itpc = m % 2
+        rec['x'][m], rec['y'][m], rec['z'][m] = _le_inside(ref.detector, itpc, m, n)
+        rec['pixel_plane'][m] = itpc
+    rec['n_photons'] = 2 * ((np.arange(n) * 5) % n) + 1
+    rec['t0'] = t0
+    return rec
+
+
+def _le_deposits(ref, rec, nph, vox, lut, op_channel, order, start, n_ticks):
+    """Every arrival of the photon sum by the reference's own expressions (light_sim.py:81-82, 90-93, 101-103, 116-121), in visiting
+    order: rows (idet, visit rank, itrk, bin, arrival time, photons, ticks that admit it, ticks that would but for the pre-filter)
+    and the deposits (idet, itick, visit rank, itrk, bin, photons)."""
+    light, units = ref.light, ref.consts.units
+    tick = light.LIGHT_TICK_SIZE
+    n_prof = lut['time_dist'].shape[-1]
+    st = np.arange(n_ticks) * tick + start
+    en = st + tick
+    lut8 = _le_lut8(lut)
+    arrivals, deposits = [], []
+    for idet, ch in enumerate(op_channel):
+        for q, itrk in enumerate(order[idet]):
+            ph = float(nph[itrk, ch])
+            if not ph > 0:
+                continue
+            tt = float(rec['t0'][itrk])
+            te = tt + n_prof * units.ns / units.mus
+            keep = ~((te < st) | (tt > en))
+            cell = lut8[vox[itrk, 0], vox[itrk, 1], vox[itrk, 2], ch % lut.shape[3]]
+            if light.ENABLE_LUT_SMEARING:
+                bins = [(ip, tt + ip * units.ns / units.mus, ph * float(cell['time_dist'][ip]) / tick) for ip in range(n_prof)]
+            else:
+                bins = [(0, tt + float(cell['t0_avg']) * units.ns / units.mus, ph / tick)]
+            for ip, pt, photons in bins:
+                inwin = (pt < en) & (pt > st)
+                hit = np.flatnonzero(inwin & keep)
+                arrivals.append((idet, q, itrk, ip, pt, photons, len(hit), int((inwin & ~keep).sum())))
+                deposits += [(idet, int(it), q, itrk, ip, photons) for it in hit]
+    return arrivals, deposits, st, en
+
+
+def _le_sum_run(ref, rec, vox, track_id, nph, op_channel, lut, start, n_ticks, M, order, init=None, out_dtype='f4'):
+    """The reference's sum_light_signals into zero / -1 arrays, or into copies of `init`: (light_sample_inc, ids i8, photons f8)"""
+    n_det = len(op_channel)
+    n_prof = lut['time_dist'].shape[-1]
+    inc8 = np.zeros(nph.shape, dtype=LE_INC8)
+    inc8['n_photons_det'] = nph
+    if init is None:
+        out = np.zeros((n_det, n_ticks), dtype=out_dtype)
+        tid = np.full((n_det, n_ticks, M), -1, dtype='i8')
+        tph = np.zeros((n_det, n_ticks, M))
+    else:
+        out, tid, tph = init[0].astype(out_dtype), init[1].copy(), init[2].copy()
+    ref.light_sim.sum_light_signals[(n_det, -(-n_ticks // 64)), (1, 64)](
+        rec, vox, track_id, inc8, op_channel, _le_lut8(lut), float(start), out, tid, tph, order, n_prof)
+    return out, tid, tph
+
+
+def _le_descending(nph, op_channel):
+    """visiting order of the driver and of the resident sum: descending photons per detector, ties by descending index"""
+    return np.ascontiguousarray(np.stack([np.argsort(nph[:, c], kind="stable")[::-1] for c in op_channel]), dtype=np.int32)
+
+
+def _le_sum_fixture(case, over, rec, lut, track_id, runs, order=None, bounds=None, extra=None, want_resident=None):
+    """One photon-sum fixture of module0.  runs: dicts (start: None = get_nticks' own, n_ticks, max_truth, init: None or a
+    function of (deposits, n_det, n_ticks, M) that returns the arrays the sum adds into).  Returns what extra() needs."""
+    ref = _le_ref("module0", over)
+    op_channel = np.array(LE_SUM_CHANNELS, dtype=np.int32)
+    n_out = ref.light.N_OP_CHANNEL
+    nph, t0d, vox = _le_incidence(ref, rec, lut, n_out)
+    assert not (vox == LE_SENT_VOX).any()
+    own_ticks, own_start = _le_nticks(ref, nph, t0d)
+    descending = _le_descending(nph, op_channel)
+    order = descending if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    no_ties = all(len(np.unique(nph[:, c][nph[:, c] > 0])) == (nph[:, c] > 0).sum() for c in op_channel)
+    out = {}
+    _le_put_records(out, "", rec)
+    _le_put_lut(out, "", lut)
+    out.update(op_channel=op_channel, sorted_indices=order, track_id=np.asarray(track_id, dtype='i8'), n_photons_det=nph,
+               t0_det=t0d, voxel=vox, n_prof=np.int64(lut['time_dist'].shape[-1]), own_start_time=np.float64(own_start),
+               own_n_ticks=np.int64(own_ticks), n_runs=np.int64(len(runs)))
+    reach = {}
+    for k, run in enumerate(runs):
+        start = own_start if run.get("start") is None else float(run["start"])
+        n_ticks, M = int(run["n_ticks"]), int(run["max_truth"])
+        arrivals, deposits, st, en = _le_deposits(ref, rec, nph, vox, lut, op_channel, order, start, n_ticks)
+        init = run["init"](ref, deposits, track_id, len(op_channel), n_ticks, M) if run.get("init") else None
+        res = _le_sum_run(ref, rec, vox, track_id, nph, op_channel, lut, start, n_ticks, M, order, init)
+        # dyadic inputs: the same sum with an f8 array gives the same values, so no f4 addition rounded (24 bits held everything)
+        res8 = _le_sum_run(ref, rec, vox, track_id, nph, op_channel, lut, start, n_ticks, M, order, init, out_dtype='f8')
+        assert np.array_equal(res[0].astype('f8'), res8[0]) and np.array_equal(res[2], res8[2]), (case, k, "a sum left 24 bits")
+        for _, _, _, _, _, photons, _, _ in arrivals:
+            assert photons == float(np.float32(photons)), (case, photons)
+        # every deposit the expressions admit is in the sum, and nothing else (the arrays a test compares are the reference's own)
+        cells = np.zeros((len(op_channel), n_ticks))
+        for idet, it, _, _, _, photons in deposits:
+            cells[idet, it] += photons
+        assert np.array_equal(cells + (0 if init is None else init[0].astype('f8')), res8[0]), (case, k)
+        pre = f"r{k}_"
+        out.update({pre + "start_time": np.float64(start), pre + "n_ticks": np.int64(n_ticks), pre + "max_truth": np.int64(M),
+                    pre + "light_sample_inc": res[0], pre + "true_id": res[1], pre + "true_photons": res[2],
+                    pre + "has_init": np.int64(init is not None)})
+        if init is not None:
+            out.update({pre + "init_inc": init[0], pre + "init_true_id": init[1], pre + "init_true_photons": init[2]})
+        if k == 0:
+            resident = int(run.get("start") is None and init is None and no_ties and np.array_equal(order, descending))
+            out["resident"] = np.int64(resident)
+            assert want_resident is None or resident == want_resident, (case, resident)
+        arr = np.array([(a[6], a[7], a[4]) for a in arrivals], dtype=float).reshape(-1, 3)
+        on_axis = (arr[:, 2] > st[0]) & (arr[:, 2] < en[-1])
+        per_pair = {}
+        for a in arrivals:
+            per_pair[(a[0], a[2])] = per_pair.get((a[0], a[2]), 0) + a[6]
+        r = dict(two_ticks=int((arr[:, 0] == 2).sum()), one_tick=int((arr[:, 0] == 1).sum()),
+                 no_tick=int(((arr[:, 0] == 0) & (arr[:, 1] == 0) & on_axis).sum()), prefiltered=int((arr[:, 1] > 0).sum()),
+                 before_axis=int((arr[:, 2] <= st[0]).sum()), past_axis=int((arr[:, 2] >= en[-1]).sum()),
+                 records_per_pair_max=max(per_pair.values()) if per_pair else 0)
+        assert (arr[:, 0] <= 2).all() and r["records_per_pair_max"] <= lut['time_dist'].shape[-1] + 2, (case, k, r)
+        out[pre + "records_per_pair_max"] = np.int64(r["records_per_pair_max"])
+        for name, v in r.items():
+            reach[name] = reach.get(name, 0) + v if name != "records_per_pair_max" else max(reach.get(name, 0), v)
+        if extra:
+            for name, v in extra(ref, run, k, arrivals, deposits, init, res, st, en).items():
+                reach[name] = reach.get(name, 0) + v
+    wanted = set(bounds or {}) | {"records_per_pair_max"}
+    out.update({"reach_" + name: v for name, v in reach.items() if name in wanted})
+    _le_save(case, "module0", over, out, bounds={"reach_" + k: v for k, v in (bounds or {}).items()})
+
+
+def _le_cells(deposits, thr):
+    """deposits above the truth threshold per (idet, itick) cell, in the reference's visiting order (rank, then bin)"""
+    cells = {}
+    for idet, it, q, itrk, ip, photons in sorted(deposits, key=lambda d: (d[0], d[1], d[2], d[4])):
+        if photons > thr:
+            cells.setdefault((idet, it), []).append((itrk, photons))
+    return cells
+
+
+def _gen_le_sum_cases():
+    n_prof = 16
+    base = dict(LIGHT_TICK_SIZE=0.001, OP_CHANNEL_EFFICIENCY=_le_dyadic_eff(96))
+    lut = _le_lut((2, 3, 2), 48, n_prof, salt=1)
+
+    # on-grid times under LUT smearing: start_time = -1.0 from get_nticks itself, t0 = k / 1000 in f64
+    over = dict(base, ENABLE_LUT_SMEARING=True)
+    k_grid = [0] + [(m * 482) // 31 for m in range(1, 32)]
+    rec = _le_sum_records(_le_ref("module0", over), np.array(k_grid) / 1000)
+    lut_g = lut.copy()
+    lut_g['t0'][tuple(_le_incidence(_le_ref("module0", over), rec[:1], lut, 96)[2][0])] = 0     # record 0 sees t0_det = 0
+    ids = np.arange(len(rec)) // 2 * 3 + 1
+    grid_bounds = dict(two_ticks=8, no_tick=8, one_tick=8)
+    _le_sum_fixture("grid_smear", over, rec, lut_g, ids, [dict(n_ticks=1536, max_truth=2)], bounds=grid_bounds, want_resident=1)
+    out = np.load(os.path.join(GOLD, "light_edge_grid_smear.npz"))
+    assert float(out["r0_start_time"]) == -1.0 and int(out["own_n_ticks"]) > 1536
+
+    # the same records from start times get_nticks would not give
+    starts = (-0.75, 0.0, float(np.float32(-0.9)))
+    _le_sum_fixture("grid_smear_free_start", over, rec, lut_g, ids, [dict(start=s, n_ticks=1536, max_truth=2) for s in starts],
+                    bounds=dict(one_tick=8, no_tick=8, two_ticks=1), want_resident=0)
+
+    # without smearing: one arrival per pair at t0 + t0_avg (whole ns); one t0_avg beyond the profile length is pre-filtered
+    over_ns = dict(base, ENABLE_LUT_SMEARING=False)
+    ref = _le_ref("module0", over_ns)
+    lut_n = lut_g.copy()
+    vox = _le_incidence(ref, rec, lut_n, 96)[2]
+    for m in (2, 3):                                   # a record of either TPC, for the detector rows of its TPC
+        lut_n['t0_avg'][vox[m, 0], vox[m, 1], vox[m, 2]] = n_prof + 4
+    _le_sum_fixture("grid_no_smear", over_ns, rec, lut_n, ids, [dict(n_ticks=1536, max_truth=2)],
+                    bounds=dict(prefiltered=1, one_tick=8, no_tick=1), want_resident=1)
+
+    # the ends of the axis: arrivals before tick 0 and past the last tick, a record whose whole profile precedes the start,
+    # axes of two ticks and of one
+    t_half = float(rec['t0'][9]) - 0.0005
+
+    def ends_extra(ref, run, k, arrivals, deposits, init, res, st, en):
+        te = rec['t0'] + n_prof * ref.consts.units.ns / ref.consts.units.mus
+        return dict(whole_profile_before=int((te < st[0]).sum()), short_axis_lit=int(run["n_ticks"] <= 2 and len(deposits) > 0))
+    _le_sum_fixture("axis_ends", over, rec, lut_g, ids,
+                    [dict(start=0.1005, n_ticks=200, max_truth=2), dict(start=0.1, n_ticks=200, max_truth=2),
+                     dict(start=t_half, n_ticks=2, max_truth=2), dict(start=t_half, n_ticks=1, max_truth=2)],
+                    bounds=dict(before_axis=8, past_axis=8, whole_profile_before=2, short_axis_lit=2, one_tick=8), extra=ends_extra,
+                    want_resident=0)
+
+    # truth slots: 2 slots, tracks shared by segments, more tracks than slots, an id of -1, photons at the threshold and a step
+    # above, a visiting order that is not descending, arrays that already hold sums and a slot 0 owned by a later track
+    thr = 187.5                                         # = 3 * 2^-4 / LIGHT_TICK_SIZE: photons of a record can equal it exactly
+    over_t = dict(base, ENABLE_LUT_SMEARING=True, MC_TRUTH_THRESHOLD=thr)
+    t0s = np.array([0.0105, 0.0105, 0.0105, 0.0105, 0.012, 0.012, 0.0105, 0.0105, 0.02, 0.02, 0.0125, 0.0125,
+                    0.0105, 0.0105, 0.021, 0.021, 0.0105, 0.0105, 0.012, 0.012, 0.0305, 0.0305, 0.0105, 0.0105])
+    rec_t = _le_sum_records(_le_ref("module0", over_t), t0s)
+    rec_t['n_photons'] = [3, 4, 6, 12, 5, 7, 24, 3, 9, 11, 13, 6, 48, 10, 3, 4, 14, 20, 15, 17, 3, 4, 28, 22]
+    ids_t = np.array([7, 7, 3, -1, 9, 3, 12, 12, -1, 9, 7, 5, 21, -1, 30, 30, 40, 41, 3, 9, 50, 51, 60, 61], dtype='i8')
+    lut_t = lut.copy()
+    lut_t['vis'] = 0.5
+    order_t = np.stack([np.arange(len(rec_t)) if d % 2 == 0 else (np.arange(len(rec_t)) * 7 + 3) % len(rec_t)
+                        for d in range(len(LE_SUM_CHANNELS))])
+
+    def preowned(ref, deposits, track_id, n_det, n_ticks, M):
+        """a non-zero sum in some cells, slot 0 owned by the track that comes last among those a cell meets, slot 1 by a stranger"""
+        out = np.zeros((n_det, n_ticks), dtype='f4')
+        tid = np.full((n_det, n_ticks, M), -1, dtype='i8')
+        tph = np.zeros((n_det, n_ticks, M))
+        cells = _le_cells(deposits, thr)
+        picked = 0
+        for (idet, it), recs in sorted(cells.items()):
+            tracks = [int(track_id[r]) for r, _ in recs if track_id[r] != -1]
+            if len(set(tracks)) >= 2 and tracks[0] != tracks[-1]:
+                out[idet, it] = 250.0
+                tid[idet, it, 0] = tracks[-1]
+                tph[idet, it, 0] = 500.0
+                if picked % 2:
+                    tid[idet, it, 1] = 99
+                    tph[idet, it, 1] = 125.0
+                picked += 1
+        out[0, 0] = 62.5                              # (a cell nothing arrives in keeps what it holds)
+        return out, tid, tph
+
+    def truth_extra(ref, run, k, arrivals, deposits, init, res, st, en):
+        cells = _le_cells(deposits, thr)
+        full = minus_one = pre = 0
+        for (idet, it), recs in cells.items():
+            tracks = [int(ids_t[r]) for r, _ in recs]
+            full += len(set(t for t in tracks if t != -1)) > run["max_truth"]
+            minus_one += any(t == -1 and any(u != -1 for u in tracks[i + 1:]) for i, t in enumerate(tracks))
+            if init is not None and init[1][idet, it, 0] != -1:
+                pre += tracks[0] != init[1][idet, it, 0] and int(init[1][idet, it, 0]) in tracks
+        at = sum(1 for d in deposits if d[5] == thr)
+        above = sum(1 for d in deposits if d[5] == thr * 4 / 3)
+        return dict(full_cells=full, minus_one_taken_over=minus_one, preowned=pre, at_threshold=min(at, above))
+    _le_sum_fixture("truth_slots", over_t, rec_t, lut_t, ids_t,
+                    [dict(start=0.0, n_ticks=64, max_truth=2), dict(start=0.0, n_ticks=64, max_truth=2, init=preowned)],
+                    order=order_t, bounds=dict(full_cells=1, minus_one_taken_over=1, at_threshold=1, preowned=1), extra=truth_extra,
+                    want_resident=0)
+
+
+def gen_light_edges():
+    """The reference's calculate_light_incidence, get_nticks and sum_light_signals at their edges:
+    tests/golden/light_edge_<case>.npz with the overridden constants by name and `reach_*` counts, computed from the reference's
+    expressions on the inputs, of what each case is there for (asserted here and again by the tests)."""
+    _gen_le_incidence_cases()
+    _gen_le_sum_cases()
+
+
 def gen_light_export():
     """light_sim.export_to_hdf5 / export_light_trig_to_hdf5 / export_light_wvfm_to_hdf5 / zero_suppress_waveform_truth
     (light_sim.py:621-757) with h5py.File replaced by an in-memory sink: what lands in light_trig, light_wvfm and
@@ -2156,7 +2697,7 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     for s in a.sets.split(","):
         {"consts": gen_consts, "qd": gen_qd, "pixels": gen_pixels, "light": gen_light, "light_response": gen_light_response,
-         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_wvfm_edges": gen_light_wvfm_edges, "light_export": gen_light_export, "fee": gen_fee,
+         "sampled": lambda: gen_sampled(a.jobs), "chain": lambda: gen_chain(a.jobs), "packets": gen_packets, "light_wvfm": gen_light_wvfm, "light_wvfm_edges": gen_light_wvfm_edges, "light_edges": gen_light_edges, "light_export": gen_light_export, "fee": gen_fee,
          "pixels_wide": lambda: gen_pixels_wide(a.jobs), "mc": lambda: gen_mc(a.jobs)}[s]()
     return 0
 

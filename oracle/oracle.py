@@ -322,7 +322,9 @@ def digitize(integral, gain=None):
     return out
 
 
-def light_incidence(tracks, lut, n_out=None):
+def light_incidence(tracks, lut, n_out=None, init=None):
+    """``init``: (n_photons_det, t0_det, voxel) the call writes into, like the reference into its caller's arrays (rows of
+    segments outside every TPC, and t0_det in trigger mode 1, keep what they hold); default zeros."""
     o = to_oracle(tracks)
     c = _consts()
     n = len(o)
@@ -334,13 +336,18 @@ def light_incidence(tracks, lut, n_out=None):
     c2t = np.ascontiguousarray(consts.light.OP_CHANNEL_TO_TPC, dtype=np.int32)
     nph = np.zeros((n, n_out), dtype=np.float32); t0d = np.zeros((n, n_out), dtype=np.float32)
     vox = np.zeros((n, 3), dtype=np.int32)
+    if init is not None:
+        nph, t0d, vox = (np.array(a, dtype=d, order='C') for a, d in zip(init, (np.float32, np.float32, np.int32)))
+        assert nph.shape == (n, n_out) and t0d.shape == (n, n_out) and vox.shape == (n, 3)
     lib().o_light_incidence(_p(o), C.c_int64(n), _p(vis), _p(t0), C.c_int(nx), C.c_int(ny), C.c_int(nz),
                             C.c_int(ndet), _p(eff), _p(c2t), C.c_int(n_out), _p(nph), _p(t0d), _p(vox), C.byref(c))
     return nph, t0d, vox
 
 
 def sum_light_signals(tracks, voxel, track_id, n_photons_det, op_channel, lut, start_time, n_ticks,
-                      sorted_indices, max_truth=0):
+                      sorted_indices, max_truth=0, init=None):
+    """``init``: (light_sample_inc, true ids, true photons) the sum adds into, like the reference into its caller's arrays;
+    default zeros and -1."""
     o = to_oracle(tracks)
     c = _consts()
     n = len(o)
@@ -352,6 +359,12 @@ def sum_light_signals(tracks, voxel, track_id, n_photons_det, op_channel, lut, s
     out = np.zeros((n_det, n_ticks), dtype=np.float32)
     tid = np.full((n_det, n_ticks, max(max_truth, 1)), -1, dtype=np.int64)
     tph = np.zeros((n_det, n_ticks, max(max_truth, 1)))
+    if init is not None:
+        out = np.array(init[0], dtype=np.float32, order='C')
+        assert out.shape == (n_det, n_ticks)
+        if max_truth:
+            tid, tph = np.array(init[1], dtype=np.int64, order='C'), np.array(init[2], dtype=np.float64, order='C')
+            assert tid.shape == tph.shape == (n_det, n_ticks, max_truth)
     lib().o_sum_light_signals(_p(o), C.c_int64(n), _p(np.ascontiguousarray(voxel, dtype=np.int32)),
                               _p(np.ascontiguousarray(track_id, dtype=np.int64)),
                               _p(np.ascontiguousarray(n_photons_det, dtype=np.float32)),

@@ -223,6 +223,83 @@ def load_light_wvfm_edge_case(name):
     return g
 
 
+LIGHT_EDGE_INCIDENCE_CASES = ("faces_module0", "faces_2x2", "lut_6_detectors", "module_slice_2x2", "trig_mode_1",
+                              "efficiency_fallback", "dark")
+LIGHT_EDGE_SUM_CASES = ("grid_smear", "grid_smear_free_start", "grid_no_smear", "axis_ends", "truth_slots")
+LIGHT_EDGE_CASES = LIGHT_EDGE_INCIDENCE_CASES + LIGHT_EDGE_SUM_CASES
+# what the incidence outputs hold before the call (oracle/gen_golden.py LE_SENT_*)
+LIGHT_EDGE_SENTINELS = (123.0, -7.0, -5)
+# lower bounds of the `reach_*` counts that have one (all others: non-zero)
+LIGHT_EDGE_REACH_BOUNDS = {"grid_smear": dict(reach_two_ticks=8, reach_no_tick=8, reach_one_tick=8),
+                           "grid_smear_free_start": dict(reach_no_tick=8, reach_one_tick=8),
+                           "grid_no_smear": dict(reach_one_tick=8), "axis_ends": dict(reach_before_axis=8, reach_past_axis=8, reach_one_tick=8),
+                           "module_slice_2x2": dict(reach_modules=4)}
+LIGHT_EDGE_INC_DTYPE = np.dtype([('segment_id', 'u4'), ('n_photons_det', 'f4'), ('t0_det', 'f4')])
+
+
+def load_light_edge_case(name):
+    """Constants of a tests/golden/light_edge_<name>.npz case (oracle/gen_golden.py gen_light_edges): the configuration the
+    fixture names with every constant it records set on ``consts`` (MC_TRUTH_THRESHOLD on sim, the others on light; a list of
+    efficiencies becomes an array).  Every ``reach_*`` count of the fixture must be non-zero, or at least its bound in
+    LIGHT_EDGE_REACH_BOUNDS; a photon-sum pair never needs more records than its profile bins + 2.  Returns the arrays as a dict.
+    Undo with ``load_cfg("module0")``."""
+    import json
+    assert name in LIGHT_EDGE_CASES
+    z = gold(f"light_edge_{name}.npz")
+    g = {k: z[k] for k in z.files}
+    load_cfg(str(g["cfg"]))
+    for k, v in json.loads(str(g["const_json"])).items():
+        if k == "OP_CHANNEL_EFFICIENCY":
+            v = np.array(v, dtype=np.float64)
+        setattr(consts.sim if k == "MC_TRUTH_THRESHOLD" else consts.light, k, tuple(v) if isinstance(v, list) else v)
+    reach = {k: int(g[k]) for k in g if k.startswith("reach_")}
+    bounds = LIGHT_EDGE_REACH_BOUNDS.get(name, {})
+    assert reach and all(v >= bounds.get(k, 1) for k, v in reach.items()), (name, reach)
+    assert set(bounds) <= set(reach), (name, reach)
+    if name in LIGHT_EDGE_SUM_CASES:
+        assert reach["reach_records_per_pair_max"] <= int(g["n_prof"]) + 2
+    return g
+
+
+def light_edge_records(g, pre=""):
+    """the records of a light-edge fixture (of run ``pre``) in the reference-run layout: f8 fields, i4 pixel_plane"""
+    r = np.zeros(g[pre + "x"].shape[0], dtype=REF_DTYPE)
+    for f in ("x", "y", "z", "t0", "n_photons", "pixel_plane"):
+        r[f] = g[pre + f]
+    return r
+
+
+def light_edge_lut(g, pre=""):
+    """the LUT of a light-edge fixture (of run ``pre``: its own, or the fixture-wide one its key names) as the structured array"""
+    if pre + "lut" in g:
+        pre = str(g[pre + "lut"])
+    td = g[pre + "lut_time_dist"]
+    lut = np.zeros(td.shape[:-1], dtype=[('vis', 'f4'), ('t0', 'f4'), ('t0_avg', 'f4'), ('time_dist', 'f4', (td.shape[-1],))])
+    for f in lut.dtype.names:
+        lut[f] = g[pre + "lut_" + f]
+    return lut
+
+
+def assert_same_floats(got, ref, what=""):
+    """bit for bit as values: NaN where the reference has NaN, elsewhere equal with the same sign (a -0.0 is not a 0.0)"""
+    got, ref = np.asarray(got), np.asarray(ref)
+    assert got.shape == ref.shape and got.dtype == ref.dtype, (what, got.shape, ref.shape, got.dtype, ref.dtype)
+    nan = np.isnan(ref)
+    bad = (np.isnan(got) != nan) | (~nan & ((got != ref) | (np.signbit(got) != np.signbit(ref))))
+    if bad.any():
+        i = tuple(np.argwhere(bad)[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} values differ; first at {i}: got {got[i]!r} ref {ref[i]!r}")
+
+
+def light_edge_sum_init(g, k):
+    """(light_sample_inc, true ids, true photons) run k of a photon-sum fixture adds into: what it recorded, else zeros and -1"""
+    pre = f"r{k}_"
+    if int(g[pre + "has_init"]):
+        return g[pre + "init_inc"].copy(), g[pre + "init_true_id"].copy(), g[pre + "init_true_photons"].copy()
+    shape = g[pre + "true_id"].shape
+    return np.zeros(shape[:2], dtype='f4'), np.full(shape, -1, dtype='i8'), np.zeros(shape)
+
+
 def light_wvfm_edge_phases(g, iset=0):
     """(phases_signal, phases_missing) of the two noise calls sim_triggers makes for trigger set `iset` of a digitiser fixture
     that records phase seeds: [rows, padded length // 2 + 1] each"""

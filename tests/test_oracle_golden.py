@@ -307,6 +307,73 @@ def test_light_wvfm_edge_digitiser(name):
         H.load_cfg("module0")
 
 
+@pytest.mark.parametrize("name", H.LIGHT_EDGE_INCIDENCE_CASES)
+def test_light_edge_incidence(name):
+    """The oracle's light_incidence and get_nticks against the reference's own calculate_light_incidence and get_nticks
+    (lightLUT.py:15-136, light_sim.py:24-41; oracle/gen_golden.py gen_light_edges) on voxel faces, borders, the 2e-2 margin and
+    points beyond it in even and odd TPCs, LUTs of 1x1x1 to 14x26x8 voxels and of 6 and 48 detectors, a module's slice of the
+    channels, trigger mode 1, efficiencies that are zero, negative and NaN, and records and voxels without light -- written
+    into arrays that hold sentinels.  Voxels, n_photons_det and t0_det bit for bit (NaN where the reference has NaN, -0.0
+    where it has -0.0); rows of segments outside every TPC, and t0_det in trigger mode 1, keep the sentinels."""
+    from larndsim_amd import light_sim
+    try:
+        g = H.load_light_edge_case(name)
+        s_nph, s_t0, s_vox = H.LIGHT_EDGE_SENTINELS
+        for k in range(int(g["n_runs"])):
+            pre = f"r{k}_"
+            r, lut, n_out = H.light_edge_records(g, pre), H.light_edge_lut(g, pre), int(g[pre + "n_out"])
+            n = len(r)
+            init = (np.full((n, n_out), s_nph, dtype='f4'), np.full((n, n_out), s_t0, dtype='f4'), np.full((n, 3), s_vox, dtype='i4'))
+            nph, t0d, vox = O.light_incidence(r, lut, n_out=n_out, init=init)
+            assert np.array_equal(vox, g[pre + "voxel"]), (name, k)
+            H.assert_same_floats(nph, g[pre + "n_photons_det"], f"{name} run {k} n_photons_det")
+            H.assert_same_floats(t0d, g[pre + "t0_det"], f"{name} run {k} t0_det")
+            inc = np.zeros((n, n_out), dtype=H.LIGHT_EDGE_INC_DTYPE)
+            inc['n_photons_det'], inc['t0_det'] = nph, t0d
+            n_ticks, start = light_sim.get_nticks(inc)
+            assert n_ticks == int(g[pre + "n_ticks"]) and float(start) == float(g[pre + "start_time"]), (name, k)
+    finally:
+        H.load_cfg("module0")
+
+
+@pytest.mark.parametrize("name", H.LIGHT_EDGE_SUM_CASES)
+def test_light_edge_photon_sum(name):
+    """The oracle's light_incidence, get_nticks and sum_light_signals against the reference's own (light_sim.py:58-129) on
+    arrival times that lie on the tick grid (most of them in no tick, some in two: reproduced, not repaired), start times
+    get_nticks gives and others, the pre-filter without smearing, the ends of the axis and axes of one and two ticks, and the
+    truth-slot rules (shared tracks, more tracks than slots, id -1, photons equal to the threshold, a visiting order that is not
+    descending, arrays and slots that hold something already).  Every value is dyadic, so sums, ids and slot photons are
+    compared bit for bit."""
+    from larndsim_amd import light_sim
+    try:
+        g = H.load_light_edge_case(name)
+        r, lut = H.light_edge_records(g), H.light_edge_lut(g)
+        n = len(r)
+        nph, t0d, vox = O.light_incidence(r, lut)
+        assert np.array_equal(vox, g["voxel"])
+        H.assert_same_floats(nph, g["n_photons_det"], name + " n_photons_det")
+        H.assert_same_floats(t0d, g["t0_det"], name + " t0_det")
+        inc = np.zeros(nph.shape, dtype=H.LIGHT_EDGE_INC_DTYPE)
+        inc['n_photons_det'], inc['t0_det'] = nph, t0d
+        n_ticks, start = light_sim.get_nticks(inc)
+        assert n_ticks == int(g["own_n_ticks"]) and float(start) == float(g["own_start_time"])
+        for k in range(int(g["n_runs"])):
+            pre = f"r{k}_"
+            T, M = int(g[pre + "n_ticks"]), int(g[pre + "max_truth"])
+            out, tid, tph = O.sum_light_signals(r, vox, g["track_id"], nph, g["op_channel"], lut, float(g[pre + "start_time"]), T,
+                                                g["sorted_indices"], max_truth=M, init=H.light_edge_sum_init(g, k))
+            H.assert_same_floats(out, g[pre + "light_sample_inc"], f"{name} run {k} sum")
+            assert np.array_equal(tid, g[pre + "true_id"]), (name, k)
+            H.assert_same_floats(tph, g[pre + "true_photons"], f"{name} run {k} truth photons")
+            assert g[pre + "light_sample_inc"].sum() > 0 and (g[pre + "true_id"] != -1).any()
+            # without truth slots: the same sums
+            out0, _, _ = O.sum_light_signals(r, vox, g["track_id"], nph, g["op_channel"], lut, float(g[pre + "start_time"]), T,
+                                             g["sorted_indices"], max_truth=0, init=H.light_edge_sum_init(g, k))
+            H.assert_same_floats(out0, g[pre + "light_sample_inc"], f"{name} run {k} sum without slots")
+    finally:
+        H.load_cfg("module0")
+
+
 @pytest.mark.parametrize("radius", H.WIDE_RADII)
 @pytest.mark.parametrize("cfg", H.WIDE_CFGS)
 def test_wide_neighbourhood_golden(cfg, radius):
