@@ -38,6 +38,7 @@ extern "C" {
 #define LDSIM_ESTATE (-4)   /* call order violated (e.g. no response table set) */
 #define LDSIM_ENODEV (-5)   /* no usable GPU */
 #define LDSIM_ENOMEM (-6)   /* a device allocation of the call failed (the context stays usable) */
+#define LDSIM_ENOCONV (-7)  /* an iterative solve missed its tolerance within its iteration limit (residual reported) */
 
 /* record field dtype codes */
 enum { LDSIM_F4 = 1, LDSIM_F8 = 2, LDSIM_I4 = 3, LDSIM_U4 = 4, LDSIM_I8 = 5, LDSIM_U8 = 6 };
@@ -941,6 +942,74 @@ typedef struct LdsimResponseBuildParams {   /* 56 bytes */
 } LdsimResponseBuildParams;
 int ldsim_response_build(ldsim_ctx* ctx, const LdsimResponseBuildParams* params, double* table);
 int ldsim_response_build_ms(ldsim_ctx* ctx, double* ms);
+
+/* ---- drift-field map builder: space charge by a Poisson solve, drift paths (csrc/kernels_fmapbuild.hip) ----------------------
+ * The producer of the maps ldsim_set_field_map loads (E, dx, dy, dz of one TPC); larndsim_amd/field_map_builder.py restates
+ * the model in numpy.
+ * Geometry and units.  One TPC is one box in the simulation frame (cm, z the drift coordinate).  Node grid (nx, ny, nz), every
+ * dimension >= 2, node (i, j, k) at origin + (i, j, k) * spacing (hx, hy, hz) and at linear index (i ny + j) nz + k; the first
+ * and last node of every axis lie on the box faces.  z_anode and z_cathode are the two z faces (TPC_BORDERS[tpc][2][0] and
+ * [2][1]); n = sign(z_cathode - z_anode); q = |z - z_anode| is the drift coordinate.  kV, kV/cm, source in kV/cm^2.
+ * Potential.  E = e0 n z^ - grad psi, e0 > 0 the nominal field, psi the perturbation: laplace psi = -s inside, s = rho / eps on
+ * the nodes, psi given on the six faces (Dirichlet; 0 = conducting anode and cathode and an ideally graded cage, anything else
+ * a cage defect).
+ * Discretisation.  7-point stencil on the interior nodes,
+ *   (A psi)(i, j, k) = sum over the axes a of (2 psi(c) - psi(c - e_a) - psi(c + e_a)) * (1 / h_a^2),
+ * the face values moved to the right: A psi = b, A symmetric positive definite.  ldsim_field_map_solve: on entry the face nodes
+ * of psi_inout hold the boundary values (its interior nodes are not read; the source's face nodes only have to be finite);
+ * conjugate gradients in f64 from psi = 0 inside, ended at the first iteration count at which |r|_2 <= tol |b|_2 for the recurrence's residual, the
+ * true residual b - A psi then formed and held to the same rule (missed: the iteration goes on from the true residual).
+ * *iterations = the iteration count, *residual = |b - A psi|_2 / |b|_2 of what is returned (0 when b = 0).  b = 0 -- no interior
+ * node included -- returns the boundary values and zeros inside with 0 iterations.  Every 2-norm is a sum over fixed chunks of
+ * 256 consecutive node indices (inside a chunk: lane l of wave w holds index 64 w + l, a wave's 64 values are folded by
+ * halves, 32, 16 .. 1, the four waves added in order) followed by the sum of the chunk partials (thread t adds partials t,
+ * t + 256, .. in rising order, then the same fold): one fixed order, so the bytes do not depend on the number of workgroups
+ * (option fmap_build_wgs; 0 = the default).  No floating-point atomics.  Missing tol within max_iters: LDSIM_ENOCONV, the
+ * message states the residual reached; psi_inout is not written then.
+ * Field at the nodes.  -grad psi by central differences inside; along an axis on whose face the node lies the second-order
+ * one-sided formula (4 (psi_1 - psi_0) - (psi_2 - psi_0)) / (2 h) (mirrored on the upper face), with 2 nodes the two-point
+ * difference.  Ex, Ey, En = e0 - n dpsi/dz,
+ * |E| = sqrt(Ex^2 + Ey^2 + En^2) (|En| where Ex = Ey = 0).
+ * Paths.  An electron moves with -mu(|E|, T) E,
+ *   mu(E, T) = (a0 + a1 E + a2 E sqrt(E) + a3 E^2 sqrt(E)) / (1 + (a1 / a0) E + a4 E^2 + a5 E^3) / (r sqrt(r)) * 1e-3, r = T / 89
+ * in cm^2 / kV / us (consts.electron_mobility), v_drift = e0 mu(e0, T).  With s = q_node - q running from 0 at the node to
+ * q_node on the anode plane:  dx/ds = -Ex / En,  dy/ds = -Ey / En,  dtau/ds = v_drift / (mu(|E|) En) - 1,  tau = v_drift t - s
+ * (so dx/dq = Ex / En, dt/dq = 1 / (mu En): a positive charge cloud pulls the electrons towards it).  The field at a point is the
+ * trilinear interpolation of the four node values (Ex, Ey, En, |E|) in fmap_eval's order and form: u = (p - origin) * (1 / h)
+ * clamped to [0, n - 1], cell min((int)u, n - 2), a + f (b - a) along z, then y, then x; z = z_anode + n q.  Classical RK4 in
+ * N = max(1, ceil(q_node / step)) equal steps q_node / N, stage m + c of step m at q = q_node - (m + c) (q_node / N); a node on
+ * the anode plane has a path of length 0.  En <= 0 (or not a number) at any stage: LDSIM_EINVAL "field reverses", naming the
+ * lowest such node.
+ * Channels, per node: E = |E| at the node; dx, dy = end point minus node; dz = n tau(q_node), so that |z + dz - z_anode| / v_drift
+ * is the path's drift time; flags (u8) = 1 where the end point lies outside [origin, origin + (n - 1) h] in x or y (charge that
+ * reaches the field cage; the values are kept).  s = 0 with zero boundary gives E == e0 and offsets == 0 bit for bit.
+ * ldsim_field_map_trace takes psi (host, [nx][ny][nz]) and fills the five host arrays; ldsim_field_map_build_ms fills ms[3]: the
+ * HIP-event times (ms) of the last solve (its kernels from the first to the last launch), of the field kernel and of the trace kernel.
+ * LDSIM_EINVAL (with a message naming the entry): spacing, e0, temperature, tol or step not finite and > 0, mobility[0] not
+ * finite and non-zero or another mobility parameter not finite, a dimension < 2, more than 2^31 - 1 nodes, z_anode or z_cathode
+ * not finite or equal, max_iters or check_every < 1, more than LDSIM_FIELD_MAP_BUILD_MAX_STEPS steps on the longest path, a
+ * non-finite source, boundary or psi value, a NULL array. */
+#define LDSIM_FIELD_MAP_BUILD_MAX_STEPS 1048576
+typedef struct LdsimFieldMapBuildParams {   /* 168 bytes */
+  double origin[3];              /* offset 0: node (0, 0, 0), cm */
+  double spacing[3];             /* 24: hx, hy, hz, cm */
+  double z_anode;                /* 48 */
+  double z_cathode;              /* 56 */
+  double e0;                     /* 64: nominal field, kV/cm */
+  double temperature;            /* 72: K */
+  double mobility[6];            /* 80: a0 .. a5 (ELECTRON_MOBILITY_PARAMS) */
+  double tol;                    /* 128: relative residual the solve ends at */
+  double step;                   /* 136: largest RK4 step in q, cm */
+  int32_t n[3];                  /* 144: nx, ny, nz */
+  int32_t max_iters;             /* 156 */
+  int32_t check_every;           /* 160: iterations between two reads of the residual by the host */
+  int32_t _pad;                  /* 164 */
+} LdsimFieldMapBuildParams;
+int ldsim_field_map_solve(ldsim_ctx* ctx, const LdsimFieldMapBuildParams* params, const double* source, double* psi_inout,
+                          int32_t* iterations, double* residual);
+int ldsim_field_map_trace(ldsim_ctx* ctx, const LdsimFieldMapBuildParams* params, const double* psi, double* E, double* dx,
+                          double* dy, double* dz, uint8_t* flags);
+int ldsim_field_map_build_ms(ldsim_ctx* ctx, double* ms);
 
 /* ---- multi-GPU: the one exchange step of the batch-sharded path, RCCL over xGMI -------------------------------
  * One process per GPU; (event, TPC-group) batches are sharded over the ranks and never share a pixel, so the only

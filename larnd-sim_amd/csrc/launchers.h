@@ -30,6 +30,12 @@ int lutbuild_trace(ldsim_ctx* ctx, const LdsimLutBuildParams* P, const LdsimLutD
 // ---- kernels_respbuild.hip ---------------------------------------------------------------------------------------------------
 int respbuild_build(ldsim_ctx* ctx, const LdsimResponseBuildParams* P, double* table);
 
+// ---- kernels_fmapbuild.hip ---------------------------------------------------------------------------------------------------
+int fmapbuild_solve(ldsim_ctx* ctx, const LdsimFieldMapBuildParams* P, const double* source, double* psi_inout, int32_t* iterations,
+                    double* residual);
+int fmapbuild_trace(ldsim_ctx* ctx, const LdsimFieldMapBuildParams* P, const double* psi, double* E, double* dx, double* dy,
+                    double* dz, uint8_t* flags);
+
 // ---- sort.hip ----------------------------------------------------------------------------------------------------------
 int sort_select_pairs(ldsim_ctx* ctx, const int32_t* neigh, const int32_t* nrad, int64_t seg_begin, int32_t batch0, int P,
                       int64_t n_entries, unsigned long long* keys_out, int32_t* vals_out, unsigned long long* d_count);

@@ -230,6 +230,10 @@ extern "C" int ldsim_set_option(ldsim_ctx* ctx, const char* name, double value) 
     if (!(value >= 64 && value <= 1048576 && value == (double)(int)value)) { ldsim_set_error("lut_build_group_photons must be an integer in [64, 1048576]"); return LDSIM_EINVAL; }
     ctx->lb_group = (int)value;
   }
+  else if (!strcmp(name, "fmap_build_wgs")) {
+    if (!(value >= 0 && value <= 65536 && value == (double)(int)value)) { ldsim_set_error("fmap_build_wgs must be an integer in [0, 65536] (0: the default)"); return LDSIM_EINVAL; }
+    ctx->fb_wgs = (int)value;
+  }
   else if (!strcmp(name, "lut_build_lds_tile")) {
     if (!(value == 0 || value == 1)) { ldsim_set_error("lut_build_lds_tile must be 0 or 1"); return LDSIM_EINVAL; }
     ctx->lb_tile = (int)value;
@@ -703,6 +707,28 @@ extern "C" int ldsim_response_build_ms(ldsim_ctx* ctx, double* ms) {
   LDSIM_ENTER(ctx);
   NEED(ctx && ms, "null argument");
   *ms = ctx->ms_rb;
+  return 0;
+}
+
+// ---- drift-field map builder (kernels_fmapbuild.hip) -------------------------------------------------------------------------
+extern "C" int ldsim_field_map_solve(ldsim_ctx* ctx, const LdsimFieldMapBuildParams* params, const double* source,
+                                     double* psi_inout, int32_t* iterations, double* residual) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return fmapbuild_solve(ctx, params, source, psi_inout, iterations, residual);
+}
+
+extern "C" int ldsim_field_map_trace(ldsim_ctx* ctx, const LdsimFieldMapBuildParams* params, const double* psi, double* E,
+                                     double* dx, double* dy, double* dz, uint8_t* flags) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return fmapbuild_trace(ctx, params, psi, E, dx, dy, dz, flags);
+}
+
+extern "C" int ldsim_field_map_build_ms(ldsim_ctx* ctx, double* ms) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && ms, "null argument");
+  for (int k = 0; k < 3; k++) ms[k] = ctx->ms_fb[k];
   return 0;
 }
 

@@ -419,6 +419,15 @@ struct ldsim_ctx {
   DevBuf rb_table;               // f64 [n_i][n_j][n_k]
   Event rb_ev[2];                // around response_build_kernel of the last build (ldsim_response_build_ms)
   double ms_rb = 0;
+  // drift-field map builder (ldsim_field_map_solve / _trace, kernels_fmapbuild.hip)
+  DevBuf fb_vec;                 // the solve's vectors, f64 [6][nodes]: source | psi | r | A p | p of even | p of odd iterations
+  DevBuf fb_part;                // chunk partials f64 [2][chunks]: |r|^2 | p . A p
+  DevBuf fb_state;               // FbState: the CG scalars, which stay on the device between the host's reads
+  DevBuf fb_field;               // the trace's node field, 32-byte (Ex, Ey, En, |E|) [nodes]; psi f64 [nodes] behind it
+  DevBuf fb_out;                 // the trace's results: E | dx | dy | dz f64 [4][nodes] | the reversal word u32 (+ pad) | flags u8 [nodes]
+  int fb_wgs = 0;                // option fmap_build_wgs: workgroups of the solve's kernels (0: one per chunk, 1024 at the most)
+  Event fb_ev[6];                // around the solve, the field kernel and the trace kernel of the last calls (ldsim_field_map_build_ms)
+  double ms_fb[3] = {0, 0, 0};
   // random streams (kernels_rng.hip): numba-style table of xoroshiro128p states, grown on demand
   DevBuf d_rng;
   int64_t rng_n = 0;

@@ -13,6 +13,7 @@ from .layout import LdsimTrackLayout, NFIELDS  # noqa: F401  (re-exported)
 LDSIM_MAX_TPC = 128
 
 LDSIM_OK, LDSIM_EINVAL, LDSIM_EHIP, LDSIM_ENOSPC, LDSIM_ESTATE, LDSIM_ENODEV = 0, -1, -2, -3, -4, -5
+LDSIM_ENOMEM, LDSIM_ENOCONV = -6, -7
 
 
 class LdsimConsts(C.Structure):
@@ -101,6 +102,15 @@ class LdsimResponseBuildParams(C.Structure):
                 ("_pad", C.c_int32)]
 
 
+class LdsimFieldMapBuildParams(C.Structure):
+    """include/ldsim.h LdsimFieldMapBuildParams (ldsim_field_map_solve / _trace): 168 bytes"""
+    _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("z_anode", C.c_double), ("z_cathode", C.c_double),
+                ("e0", C.c_double), ("temperature", C.c_double), ("mobility", C.c_double * 6), ("tol", C.c_double),
+                ("step", C.c_double), ("n", C.c_int32 * 3), ("max_iters", C.c_int32), ("check_every", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
+FIELD_MAP_BUILD_MAX_STEPS = 1048576   # include/ldsim.h LDSIM_FIELD_MAP_BUILD_MAX_STEPS
 RESPONSE_BUILD_MAX_K = 7679       # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_K
 RESPONSE_BUILD_MAX_NSUB = 16      # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_NSUB
 LUT_MAX_DETECTORS = 1024    # include/ldsim.h LDSIM_LUT_MAX_DETECTORS
