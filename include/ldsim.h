@@ -1011,6 +1011,105 @@ int ldsim_field_map_trace(ldsim_ctx* ctx, const LdsimFieldMapBuildParams* params
                           double* dy, double* dz, uint8_t* flags);
 int ldsim_field_map_build_ms(ldsim_ctx* ctx, double* ms);
 
+/* ---- track generator: keyed muon, pion and proton transport in LAr to segments (csrc/kernels_trackgen.hip) -------------------
+ * The producer of the edep-sim `segments` the driver starts from; larndsim_amd/track_generator.py restates the walk in numpy
+ * (generate_twin), makes the primaries (gun, cosmics) and turns the columns into segments / trajectories / vertices.
+ * Units and frame.  cm, MeV, us; positions in the input file's frame (drift axis in x), the medium uniform LAr inside the world
+ * box [world_lo, world_hi].  Particles: pdg +-13, +-211, 2212 with the masses LDSIM_TRACK_GEN_M_* and |charge| 1; a pion is a
+ * muon of another mass.  No decays, hadronic interactions, bremsstrahlung or separate delta-ray tracks.
+ * Kinematics at kinetic energy T of mass M (gen_kin): tau = T / M, (beta gamma)^2 = bg2 = tau (tau + 2), gamma = tau + 1,
+ * beta^2 = bg2 / gamma^2, r = me / M, Tmax = 2 me bg2 / (1 + 2 gamma r + r^2).  Density effect (gen_delta), x = log10(bg2) / 2:
+ * delta = 2 ln10 x - Cbar for x >= x1, + a (x1 - x)^k for x0 <= x < x1, delta0 10^(2 (x - x0)) below x0.  Rate in MeV / cm of the
+ * collisions below Tc (gen_rate):  S_r(T, Tc) = K (Z/A) rho / beta^2 [ 1/2 ln(2 me bg2 Tc / I^2) - (beta^2 / 2)(1 + Tc / Tmax)
+ * - delta / 2 ];  S(T) = S_r(T, Tmax) is the unrestricted Bethe mean.
+ * One step (gen_step) of a particle at p, unit direction d, kinetic energy T, time t:
+ *   h = max(min(step, max_loss_fraction T / S(T)), min_step); d_wall = the smallest distance to a wall along d (never negative;
+ *   on a tie the lowest axis); d_wall <= h: h = d_wall and the particle leaves.  With energy_loss: Tm = max(T - S(T) h / 2, t_min)
+ *   (the midpoint: the deterministic range converges with step^2); every quantity below is taken at Tm.  Tc' = min(t_cut, Tmax)
+ *   with straggling, Tmax without; mean loss dE = S_r(Tm, Tc') h.  With straggling, xi = (K / 2)(Z/A) rho h / beta^2:
+ *   soft: dE = max(dE + sqrt(xi Tc' (1 - beta^2 Tc' / (2 Tmax))) z0, 0);
+ *   hard, where Tmax > t_cut: the count n is Poisson of mean lambda = xi [(1 / t_cut - 1 / Tmax) - (beta^2 / Tmax) ln(Tmax / t_cut)]
+ *   by inversion of u' = u - 2^-25 (p = c = exp(-lambda); for k = 1 .. LDSIM_TRACK_GEN_HARD_CAP while u' > c: n = k,
+ *   p = p lambda / k, c = c + p -- the count is capped at LDSIM_TRACK_GEN_HARD_CAP = 8); collision j draws
+ *   T_h = 1 / (1 / t_cut - u_e (1 / t_cut - 1 / Tmax)) (the inverse of 1 / T^2 on [t_cut, Tmax]) and keeps it when
+ *   u_a > beta^2 T_h / Tmax, else draws again; the LDSIM_TRACK_GEN_HARD_TRIES = 4th draw is kept whatever u_a says.  dE += T_h: a
+ *   hard collision's energy is deposited in this segment.  The soft and hard means add up to S(Tm) h.
+ *   The walk ends stopped when dE >= T or T - dE < t_min: dE = T, h = min(h, T / S_r(Tm, Tc')); a stopped particle does not leave.
+ *   The end point is p + h d, on the wall's coordinate exactly when the particle leaves, clamped into the box always;
+ *   t += h / (beta c), c = 29979.2458 cm / us; T -= dE.  With mcs, and the walk going on: theta0 = 13.6 MeV / (beta^2 E)
+ *   sqrt(h / X0) max(1 + 0.038 ln(h / (X0 beta^2)), 0), E = Tm + M (beta p = beta^2 E), X0 = rad_length / density in cm; two
+ *   plane angles ax = theta0 z2, ay = theta0 z3; the local direction (ax, ay, 1) / nrm = (a, b, mu) is turned into d's frame by
+ *   the light LUT builder's rotation with (st cos phi, st sin phi) = (a, b) and renormalised.  Where |d_z| > 0.99999 that
+ *   builder replaces d by the local vector, which is right for a photon's wide angles and wrong for milliradians (a track along
+ *   z would forget every earlier deflection); here the same rotation is made about the x axis instead, on the cyclically
+ *   permuted components (d_y, d_z, d_x) -> (n_y, n_z, n_x).  No lateral displacement inside a step.  After max_steps steps the walk is truncated.  With energy_loss 0 (for
+ *   tests of the scattering alone) T stays, dE = 0 and a walk ends at a wall or truncated.
+ * Random numbers.  Uniforms are keyed_uniform values (csrc/rng.h; f32 in (0, 1], widened exactly) of the stream (seed, stage tag
+ * RNG_TAG_GEN = 7, key_mix(key_mix(RNG_KEY_ROOT, event_id), track_in_event)); the seed is the call's own argument, and a walk
+ * depends on nothing else in the call.  Normals take keyed_normal's pairing of two words, sqrt(-2 ln u_a) cos(2 pi u_b) and
+ * sqrt(-2 ln u_a) sin(2 pi u_b), evaluated in f64: an f32 libm differs between device and host by 1e-7, which a walk of some
+ * hundred steps would carry into its columns.  Step s owns the Philox blocks LDSIM_TRACK_GEN_STEP_BLOCKS s + 0 .. 31, i.e. the
+ * draw indices 128 s + i; an index whose branch is not taken stays unused.  In order: i = 0, 1: z0 (cos member); 2, 3: z2 (cos)
+ * and z3 (sin member); 4: the Poisson u; collision j, draw r = 0 .. 3: u_e, u_a = 8 + 8 j + 2 r, 9 + 8 j + 2 r.
+ * Output.  One segment per step, ordered by (primary index, step index): a count pass writes every primary's number of segments,
+ * an exclusive scan gives its offset, the write pass walks again and stores there.  f64 columns [LDSIM_TRACK_GEN_NF64][capacity]:
+ * x_start, y_start, z_start, x_end, y_end, z_end, x, y, z (midpoint), dx = h, dE, dEdx = dE / dx (0 where dx is 0), t_start,
+ * t_end, t (midpoint); i32 columns [LDSIM_TRACK_GEN_NI32][capacity]: primary index, step index, pdg, event_id.
+ * ldsim_track_gen_count: counts [n], end_state [n] (0 stopped, 1 left the box, 2 truncated) and end [n][6] = end point, end
+ * time, path length, remaining kinetic energy.  ldsim_track_gen: the columns; it reuses the counts of a count pass over the same
+ * (parameters, primaries, seed) when that was the context's last one, and counts itself otherwise.  *n_segments = segments
+ * written.  ldsim_track_gen_ms: HIP-event time of the last write pass.  Option track_gen_group_primaries (ldsim_set_option, 64 ..
+ * 2^20, or 0, the default: n / 2048 held to 64 .. 1024): primaries one workgroup walks; the bytes do not depend on it.
+ * LDSIM_EINVAL (with a message naming the entry): step, min_step, max_loss_fraction, t_cut, t_min, a medium constant or a primary's
+ * kinetic energy not finite and > 0, min_step > step, max_loss_fraction > 1, t_cut <= the mean excitation energy, a stopping
+ * power that is not positive at t_min, an empty or inverted world box, max_steps outside 1 .. LDSIM_TRACK_GEN_MAX_STEPS, a
+ * primary outside the world box, a zero direction, an unknown pdg, more than 2^31 - 1 primaries or segments, a capacity that is
+ * too small (the message says how many segments are needed), a NULL array. */
+#define LDSIM_TRACK_GEN_ME 0.51099895
+#define LDSIM_TRACK_GEN_M_MUON 105.6583755
+#define LDSIM_TRACK_GEN_M_PION 139.57039
+#define LDSIM_TRACK_GEN_M_PROTON 938.27208816
+#define LDSIM_TRACK_GEN_HARD_CAP 8
+#define LDSIM_TRACK_GEN_HARD_TRIES 4
+#define LDSIM_TRACK_GEN_STEP_BLOCKS 32
+#define LDSIM_TRACK_GEN_MAX_STEPS 16777216
+#define LDSIM_TRACK_GEN_NF64 15
+#define LDSIM_TRACK_GEN_NI32 4
+typedef struct LdsimTrackGenParams {   /* 192 bytes */
+  double world_lo[3];            /* offset 0: the world box, cm, file frame */
+  double world_hi[3];            /* 24 */
+  double step;                   /* 48: largest step, cm */
+  double min_step;               /* 56 */
+  double max_loss_fraction;      /* 64: largest mean loss of a step as a fraction of T, in (0, 1] */
+  double t_cut;                  /* 72: MeV; collisions above it are sampled one by one */
+  double t_min;                  /* 80: MeV; a walk ends below it */
+  double density;                /* 88: g / cm^3 */
+  double z_over_a;               /* 96: mol / g */
+  double mean_excitation;        /* 104: I, MeV */
+  double rad_length;             /* 112: X0, g / cm^2 */
+  double k_coeff;                /* 120: K = 4 pi N_A r_e^2 me c^2, MeV cm^2 / mol */
+  double sternheimer[6];         /* 128: a, k, x0, x1, Cbar, delta0 */
+  int32_t straggling;            /* 176 */
+  int32_t mcs;                   /* 180 */
+  int32_t energy_loss;           /* 184: 0 keeps T (tests of the scattering alone) */
+  int32_t max_steps;             /* 188 */
+} LdsimTrackGenParams;
+typedef struct LdsimTrackGenPrimary {  /* 80 bytes */
+  double pos[3];                 /* offset 0 */
+  double dir[3];                 /* 24: any length > 0, normalised by the walk */
+  double kinetic_energy;         /* 48: MeV */
+  double time;                   /* 56: us */
+  int32_t pdg;                   /* 64 */
+  int32_t event_id;              /* 68 */
+  int32_t track_in_event;        /* 72 */
+  int32_t _pad;                  /* 76 */
+} LdsimTrackGenPrimary;
+int ldsim_track_gen_count(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenPrimary* primaries, int64_t n,
+                          uint64_t seed, int32_t* counts, int32_t* end_state, double* end);
+int ldsim_track_gen(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenPrimary* primaries, int64_t n,
+                    uint64_t seed, int64_t capacity, double* f64_columns, int32_t* i32_columns, int64_t* n_segments);
+int ldsim_track_gen_ms(ldsim_ctx* ctx, double* ms);
+
 /* ---- multi-GPU: the one exchange step of the batch-sharded path, RCCL over xGMI -------------------------------
  * One process per GPU; (event, TPC-group) batches are sharded over the ranks and never share a pixel, so the only
  * collective reassembles the output: row counts (all-gather), then the 24-byte hit rows (all-gather-v). */

@@ -19,6 +19,12 @@ int seg_launch_get_pixels(ldsim_ctx* ctx, int64_t b, int64_t e, int radius, int3
                           int32_t* nrad, int P, double* n_list, const int32_t* radius_b, int32_t batch0);
 int seg_launch_time_intervals(ldsim_ctx* ctx, int64_t b, int64_t e, double* starts, int32_t* tmax);
 
+// ---- kernels_trackgen.hip (the entry points of ldsim_abi.hip hand their arguments through) ---------------------------------
+int trackgen_count(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrackGenPrimary* prim, int64_t n, uint64_t seed,
+                   int32_t* counts, int32_t* end_state, double* end);
+int trackgen_generate(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrackGenPrimary* prim, int64_t n, uint64_t seed,
+                      int64_t capacity, double* f64_columns, int32_t* i32_columns, int64_t* n_segments);
+
 // ---- kernels_lutbuild.hip (the entry points of ldsim_abi.hip hand their arguments through) ----------------------------------
 int lutbuild_build(ldsim_ctx* ctx, const LdsimLutBuildParams* P, const LdsimLutDetector* dets, int32_t ndet, int32_t nx,
                    int32_t ny, int32_t nz, int64_t voxel_begin, int64_t voxel_end, int64_t n_photons, uint64_t seed,

@@ -234,6 +234,10 @@ extern "C" int ldsim_set_option(ldsim_ctx* ctx, const char* name, double value) 
     if (!(value >= 0 && value <= 65536 && value == (double)(int)value)) { ldsim_set_error("fmap_build_wgs must be an integer in [0, 65536] (0: the default)"); return LDSIM_EINVAL; }
     ctx->fb_wgs = (int)value;
   }
+  else if (!strcmp(name, "track_gen_group_primaries")) {
+    if (!((value == 0 || value >= 64) && value <= 1048576 && value == (double)(int)value)) { ldsim_set_error("track_gen_group_primaries must be 0 (the default: chosen from the list's length) or an integer in [64, 1048576]"); return LDSIM_EINVAL; }
+    ctx->tg_group = (int)value;
+  }
   else if (!strcmp(name, "lut_build_lds_tile")) {
     if (!(value == 0 || value == 1)) { ldsim_set_error("lut_build_lds_tile must be 0 or 1"); return LDSIM_EINVAL; }
     ctx->lb_tile = (int)value;
@@ -729,6 +733,28 @@ extern "C" int ldsim_field_map_build_ms(ldsim_ctx* ctx, double* ms) {
   LDSIM_ENTER(ctx);
   NEED(ctx && ms, "null argument");
   for (int k = 0; k < 3; k++) ms[k] = ctx->ms_fb[k];
+  return 0;
+}
+
+// ---- track generator (kernels_trackgen.hip) -----------------------------------------------------------------------------------
+extern "C" int ldsim_track_gen_count(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenPrimary* primaries,
+                                     int64_t n, uint64_t seed, int32_t* counts, int32_t* end_state, double* end) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return trackgen_count(ctx, params, primaries, n, seed, counts, end_state, end);
+}
+
+extern "C" int ldsim_track_gen(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenPrimary* primaries, int64_t n,
+                               uint64_t seed, int64_t capacity, double* f64_columns, int32_t* i32_columns, int64_t* n_segments) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return trackgen_generate(ctx, params, primaries, n, seed, capacity, f64_columns, i32_columns, n_segments);
+}
+
+extern "C" int ldsim_track_gen_ms(ldsim_ctx* ctx, double* ms) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && ms, "null argument");
+  *ms = ctx->ms_tg;
   return 0;
 }
 

@@ -428,6 +428,18 @@ struct ldsim_ctx {
   int fb_wgs = 0;                // option fmap_build_wgs: workgroups of the solve's kernels (0: one per chunk, 1024 at the most)
   Event fb_ev[6];                // around the solve, the field kernel and the trace kernel of the last calls (ldsim_field_map_build_ms)
   double ms_fb[3] = {0, 0, 0};
+  // track generator (ldsim_track_gen_count / ldsim_track_gen, kernels_trackgen.hip): the primaries and per-primary results of the
+  // last count pass (kept for the write pass over the same input: tg_hash), the last write pass's columns
+  DevBuf tg_prim;                // LdsimTrackGenPrimary [n]
+  DevBuf tg_counts, tg_off;      // u64 [n] segments per primary | their exclusive scan
+  DevBuf tg_state, tg_end;       // i32 [n] end states | f64 [n][6] end point, end time, path, remaining T
+  DevBuf tg_f64, tg_i32;         // f64 [LDSIM_TRACK_GEN_NF64][total] | i32 [LDSIM_TRACK_GEN_NI32][total]
+  int tg_group = 0;              // option track_gen_group_primaries: primaries a workgroup walks (0: chosen from the list's length)
+  int tg_valid = 0;              // the count pass's results belong to (tg_hash, tg_n)
+  uint64_t tg_hash = 0;          // fold of (parameters, primaries, seed) of the last count pass
+  int64_t tg_n = 0, tg_total = 0;
+  Event tg_ev[2];                // around gen_kernel<true> of the last write pass (ldsim_track_gen_ms)
+  double ms_tg = 0;
   // random streams (kernels_rng.hip): numba-style table of xoroshiro128p states, grown on demand
   DevBuf d_rng;
   int64_t rng_n = 0;

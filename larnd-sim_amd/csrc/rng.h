@@ -36,7 +36,7 @@ __device__ inline float rng_normal_f32(RngState& st) {
 //   r23 = sqrtf(-2 logf(u(x2))), a23 = 2pi_f * u(x3):  draw 4m+2 = r23 * cosf(a23), draw 4m+3 = r23 * sinf(a23)
 // Uniform draw i is u(x_{i mod 4}) of block m = i / 4.  Stream keys are SplitMix64 folds (key_mix) of the identity of what is
 // simulated, never of its position in a launch: tests/test_cpu_keyed_rng.py restates all of this in numpy.
-enum : uint32_t { RNG_TAG_FEE = 1, RNG_TAG_LIGHT_FLUCT = 2, RNG_TAG_LIGHT_NOISE = 3, RNG_TAG_MC = 4, RNG_TAG_CHARGE = 5, RNG_TAG_LUT = 6 };
+enum : uint32_t { RNG_TAG_FEE = 1, RNG_TAG_LIGHT_FLUCT = 2, RNG_TAG_LIGHT_NOISE = 3, RNG_TAG_MC = 4, RNG_TAG_CHARGE = 5, RNG_TAG_LUT = 6, RNG_TAG_GEN = 7 };
 
 __host__ __device__ inline void philox_mulhilo(uint32_t a, uint32_t b, uint32_t& hi, uint32_t& lo) {
   const uint64_t p = (uint64_t)a * b;

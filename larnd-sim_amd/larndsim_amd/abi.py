@@ -110,6 +110,21 @@ class LdsimFieldMapBuildParams(C.Structure):
                 ("_pad", C.c_int32)]
 
 
+class LdsimTrackGenParams(C.Structure):
+    """include/ldsim.h LdsimTrackGenParams (ldsim_track_gen / _count): 192 bytes"""
+    _fields_ = [("world_lo", C.c_double * 3), ("world_hi", C.c_double * 3), ("step", C.c_double), ("min_step", C.c_double),
+                ("max_loss_fraction", C.c_double), ("t_cut", C.c_double), ("t_min", C.c_double), ("density", C.c_double),
+                ("z_over_a", C.c_double), ("mean_excitation", C.c_double), ("rad_length", C.c_double), ("k_coeff", C.c_double),
+                ("sternheimer", C.c_double * 6), ("straggling", C.c_int32), ("mcs", C.c_int32), ("energy_loss", C.c_int32),
+                ("max_steps", C.c_int32)]
+
+
+class LdsimTrackGenPrimary(C.Structure):
+    """include/ldsim.h LdsimTrackGenPrimary: 80 bytes (track_generator.primary_dtype is the same record in numpy)"""
+    _fields_ = [("pos", C.c_double * 3), ("dir", C.c_double * 3), ("kinetic_energy", C.c_double), ("time", C.c_double),
+                ("pdg", C.c_int32), ("event_id", C.c_int32), ("track_in_event", C.c_int32), ("_pad", C.c_int32)]
+
+
 FIELD_MAP_BUILD_MAX_STEPS = 1048576   # include/ldsim.h LDSIM_FIELD_MAP_BUILD_MAX_STEPS
 RESPONSE_BUILD_MAX_K = 7679       # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_K
 RESPONSE_BUILD_MAX_NSUB = 16      # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_NSUB

@@ -52,6 +52,7 @@ def maybe_create_rng_states(n, seed=0, rng_states=None, ctx=None):
 MASK64 = (1 << 64) - 1
 KEY_ROOT = 0x6A09E667F3BCC909
 TAG_FEE, TAG_LIGHT_FLUCT, TAG_LIGHT_NOISE, TAG_MC, TAG_CHARGE, TAG_LUT = 1, 2, 3, 4, 5, 6
+TAG_GEN = 7      # the track generator's walks and sources (track_generator.py)
 
 
 def philox4x32_10(ctr, key):
