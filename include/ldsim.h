@@ -1110,6 +1110,108 @@ int ldsim_track_gen(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const Lds
                     uint64_t seed, int64_t capacity, double* f64_columns, int32_t* i32_columns, int64_t* n_segments);
 int ldsim_track_gen_ms(ldsim_ctx* ctx, double* ms);
 
+/* ---- track cascade: delta rays, electrons and muon decays as tracks of their own (csrc/kernels_trackgen.hip) ------------------
+ * The walk above, with three additions: electrons are transported, a walk emits further particles, and those are walked in turn,
+ * one generation per call; larndsim_amd/track_cascade.py restates it in numpy (walk_generation_twin), loops over the generations
+ * (cascade, cascade_twin) and writes the file's parent links.  The entries above are untouched: pdg 11 stays unknown to them.
+ * Electrons, pdg +-11, mass LDSIM_TRACK_GEN_ME.  A positron is an electron of the other sign: no annihilation, no Bhabha
+ * scattering -- a parameter of the model, as the pion's.  tau = T / me, gamma = tau + 1, bg2 = tau (tau + 2), beta^2 = bg2 / gamma^2,
+ * e = I / me, g = (2 gamma - 1) / gamma^2, Tmax = T / 2 (Moller: the two electrons are indistinguishable).  Rate of the collisions
+ * below Tc (gen_rate_e), d = min(Tc, T / 2) / me:  S_r = (K / 2)(Z/A) rho / beta^2 [ ln(2 (tau + 2) / e^2) - 1 - beta^2
+ * + ln((tau - d) d) + tau / (tau - d) + (d^2 / 2 + (2 tau + 1) ln(1 - d / tau)) / gamma^2 - delta(bg2) ]; d = tau / 2 is the
+ * unrestricted ICRU-37 electron stopping power (with the default LAr constants 1.369, 1.473, 1.555 and 1.718 MeV cm^2 / g at 1, 5,
+ * 10 and 50 MeV).  Hard collisions above t_cut follow Moller: x = eps / T in [x0, x1] = [t_cut / T,
+ * 1/2], d sigma / d eps ~ (1 / T^2) [1 / x^2 + 1 / (1 - x)^2 + (1 - g) - g / (x (1 - x))] with the prefactor (K / 2)(Z/A) rho /
+ * beta^2 per cm; Poisson mean of a step (gen_lambda_e) lambda = (xi / T) [(x1 - x0)(1 - g + 1 / (x0 x1) + 1 / ((1 - x0)(1 - x1)))
+ * - g ln(x1 (1 - x0) / (x0 (1 - x1)))]; restricted loss plus the hard part's mean is the unrestricted loss identically.  The
+ * count is drawn as above (cap LDSIM_TRACK_GEN_HARD_CAP).  Collision j draws x from the proposal 1 / x^2 + 1 / (1 - x)^2 by
+ * inversion -- G(x) = (2 x - 1) / (x (1 - x)), c = G(x0)(1 - u_e), x = 2 / ((2 - c) + sqrt(4 + c^2)) -- and keeps it when
+ * u_a R <= r(x), r(x) = 1 + ((1 - g) y^2 - g y) / (1 - 2 y) with y = x (1 - x) the ratio of Moller's shape to the proposal and
+ * R = max(r(x0), r(1/2)) its largest value on the interval (dr/dy has the sign of 2 (1 - g) y (1 - y) - g, which rises in y: r
+ * falls, then rises).  T_h = x Tm.  Try LDSIM_TRACK_GEN_MOLLER_TRIES = 7 is kept whatever (it draws no u_a).  A try is refused
+ * with probability 1 - (integral of the shape) / (R integral of the proposal) <= 0.1775 for every g in (0, 1] and x0 in (0, 1/2)
+ * (the supremum, found numerically, is 0.17747 at g = 1, x0 = 0.178), so the forced try is reached with probability <= 0.1775^6
+ * = 3.13e-5 per collision.  The heavy particles' four-try sampler is the one above.  Soft Gaussian, midpoint rule, step rule, t_min,
+ * Highland scattering, walls and truncation are those above, evaluated with the electron's Tmax and S_r.
+ * Delta rays (delta_tracks, threshold t_track >= max(t_cut, t_min)), for heavy and electron parents alike.  An accepted hard
+ * collision with T_h >= t_track is not added to the segment's dE; the parent's T still falls by it, and an electron (pdg 11) of
+ * kinetic energy T_h is emitted.  Collisions between t_cut and t_track are deposited as above.  Direction: polar angle against
+ * the parent's direction at the step's start cos theta = T_h (E + me) / (p p_e) <= 1 (clamped), E and p the parent's total
+ * energy and momentum at Tm, p_e = sqrt(T_h (T_h + 2 me)); azimuth 2 pi u; turned into the parent's frame by the step's own
+ * rotation.  It starts at p + u' h d on the parent's segment as it ended (h after a stop's shortening; held inside the box), at
+ * t0 + u' (t1 - t0).  The parent's direction is not changed by the collision.  Stop rule: the walk ends stopped when dE + emitted
+ * >= T or T - dE - emitted < t_min, then dE = T - emitted.  A collision is emitted only while emitted + T_h < T, taken in the
+ * order j; one that would exhaust T is deposited instead, so dE stays positive.
+ * Decay of stopped muons (decays).  A walk of |pdg| 13 that ends in state 0 draws from the step index after its last.  mu+ always
+ * decays; mu- is captured where u_c <= capture_fraction (nothing is emitted, the rest energy is not tracked), else decays.  The
+ * electron has the muon's sign (13 -> 11, -13 -> -11), starts at the end point at t_end - lifetime ln u_t, isotropically (mu = 1 -
+ * 2 u, phi = 2 pi u), with total energy x W, W = (m_mu^2 + me^2) / (2 m_mu), x from the unpolarised Michel spectrum n(x) = 2 x^2
+ * (3 - 2 x) on (0, 1] by inversion: F(x) = 2 x^3 - x^4 = u_x solved by LDSIM_TRACK_GEN_MICHEL_NEWTON = 8 Newton steps from
+ * cbrt(u_x / 2) (F is convex and rising, so the iterates fall onto the root from the second on; 8 steps reach the last bit; no
+ * try is forced).  Nothing is emitted where x W <= me.  mu_plus_lifetime 2.1969811 us; mu_minus_lifetime (0.537 us)
+ * and capture_fraction (0.76) are PARAMETERS of the argon medium as recalled from the literature, not measurements of this
+ * project; they are consistent with each other (0.537 / 2.197 = 0.244 = 1 - 0.76).
+ * Out of scope: pion decay, capture products, bremsstrahlung, photons, annihilation, polarisation.  A Michel electron here loses
+ * energy by collisions only, so its track is longer than a real one (a 50 MeV electron's collision-only range is 22 cm).
+ * Draws of step s (indices 128 s + i) beyond those above: electron collision j, try r < 4: u_e, u_a = 8 + 8 j + 2 r, 9 + 8 j + 2 r
+ * (the heavy sampler's places); tries 4, 5: LDSIM_TRACK_GEN_DRAW_MOLLER + 5 j + 2 (r - 4) and the next; try 6: u_e =
+ * LDSIM_TRACK_GEN_DRAW_MOLLER + 5 j + 4; a delta ray of collision j: azimuth LDSIM_TRACK_GEN_DRAW_AZIMUTH + j, place
+ * LDSIM_TRACK_GEN_DRAW_PLACE + j.  Decay, at the step index after the last: 0 u_c, 1 u_t, 2 mu, 3 phi, 4 u_x.
+ * Generations.  Generation 0 is the caller's list (ldsim_track_cascade_particles fills key as the walk above derives it, parent
+ * -1, process 0); generation k + 1 is what generation k emitted, in the order (parent index, step, collision j; the decay
+ * product last).  A secondary's stream key is key_mix(key_mix(parent key, 1 + step), 1 + j), the decay's
+ * key_mix(key_mix(parent key, 1 + steps), LDSIM_TRACK_GEN_DECAY_KEY): a walk, and so its whole family, is a pure function of
+ * (parameters, ancestor record, seed).  The caller loops until nothing is emitted or to its cap, and walks the last generation
+ * with emit = 0: hard collisions are deposited and nothing decays, so energy is conserved whatever the cap.
+ * ldsim_track_cascade_count: counts [n], secondary_counts [n], end_state [n], end [n][6] as ldsim_track_gen_count.
+ * ldsim_track_cascade walks ONE generation: the segments in the columns above, ordered (particle, step), the column "primary"
+ * holding the particle's index; the emitted records at (exclusive scan of secondary_counts)[particle] + running index.  It reuses
+ * a count pass over the same (parameters, cascade parameters, particles, seed).  ldsim_track_cascade_ms: HIP-event time of the
+ * last write pass.  LDSIM_EINVAL, naming the entry: what the entries above refuse of the parameters and of a record (pdg: +-11,
+ * +-13, +-211, 2212), an electron stopping power that is not positive at t_min, t_track not finite or below t_cut or t_min,
+ * capture_fraction outside [0, 1], a lifetime not finite and > 0, a segment or secondary capacity that is too small (the message
+ * says how many are needed), more than 2^31 - 1 segments or secondaries, a NULL array. */
+#define LDSIM_TRACK_GEN_MOLLER_TRIES 7
+#define LDSIM_TRACK_GEN_MICHEL_NEWTON 8
+#define LDSIM_TRACK_GEN_DRAW_AZIMUTH 72
+#define LDSIM_TRACK_GEN_DRAW_PLACE 80
+#define LDSIM_TRACK_GEN_DRAW_MOLLER 88
+#define LDSIM_TRACK_GEN_DECAY_KEY 256
+typedef struct LdsimTrackGenParticle { /* 104 bytes */
+  double pos[3];                 /* offset 0: LdsimTrackGenPrimary's fields */
+  double dir[3];                 /* 24 */
+  double kinetic_energy;         /* 48 */
+  double time;                   /* 56 */
+  int32_t pdg;                   /* 64 */
+  int32_t event_id;              /* 68 */
+  int32_t track_in_event;        /* 72: the generation-0 ancestor's */
+  int32_t _pad;                  /* 76 */
+  uint64_t key;                  /* 80: the walk's stream key */
+  int32_t parent;                /* 88: index in the previous generation, -1 in generation 0 */
+  int32_t generation;            /* 92 */
+  int32_t process;               /* 96: 0 primary, 1 delta ray, 2 decay */
+  int32_t parent_step;           /* 100: the emitting step; a decay: the parent's number of steps; -1 in generation 0 */
+} LdsimTrackGenParticle;
+typedef struct LdsimTrackGenCascadeParams { /* 48 bytes */
+  double t_track;                /* offset 0: MeV; hard collisions from here on become tracks */
+  double mu_plus_lifetime;       /* 8: us */
+  double mu_minus_lifetime;      /* 16: us, in argon (a parameter) */
+  double capture_fraction;       /* 24: of stopped mu- in argon (a parameter) */
+  int32_t delta_tracks;          /* 32 */
+  int32_t decays;                /* 36 */
+  int32_t emit;                  /* 40: 0 = the last generation: nothing is emitted */
+  int32_t _pad;                  /* 44 */
+} LdsimTrackGenCascadeParams;
+int ldsim_track_cascade_particles(const LdsimTrackGenPrimary* primaries, int64_t n, LdsimTrackGenParticle* particles);
+int ldsim_track_cascade_count(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenCascadeParams* cascade,
+                              const LdsimTrackGenParticle* particles, int64_t n, uint64_t seed, int32_t* counts,
+                              int32_t* secondary_counts, int32_t* end_state, double* end);
+int ldsim_track_cascade(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenCascadeParams* cascade,
+                        const LdsimTrackGenParticle* particles, int64_t n, uint64_t seed, int64_t capacity, double* f64_columns,
+                        int32_t* i32_columns, int64_t* n_segments, int64_t secondary_capacity, LdsimTrackGenParticle* secondaries,
+                        int64_t* n_secondaries);
+int ldsim_track_cascade_ms(ldsim_ctx* ctx, double* ms);
+
 /* ---- multi-GPU: the one exchange step of the batch-sharded path, RCCL over xGMI -------------------------------
  * One process per GPU; (event, TPC-group) batches are sharded over the ranks and never share a pixel, so the only
  * collective reassembles the output: row counts (all-gather), then the 24-byte hit rows (all-gather-v). */

@@ -13,6 +13,12 @@
 // iteration, so a long walk does not idle the other lanes of its wave before the group runs out.  The count pass (WRITE = false)
 // writes every primary's number of segments and end state; after an exclusive scan the write pass walks again and stores segment
 // (primary, step) at offset[primary] + step: the output order is fixed whatever the scheduling.
+//
+// The cascade (ldsim_track_cascade_count, ldsim_track_cascade; larndsim_amd/track_cascade.py): gen_step<true> is the same step for
+// electrons too (Moller loss and collisions) and hands hard collisions above t_track to an emitter instead of the segment;
+// cas_kernel<WRITE> is gen_kernel's loop over LdsimTrackGenParticle records that also counts / stores the secondaries of every
+// walk (delta rays in the order (step, collision), the decay electron of a stopped muon last) at soffset[particle] + running
+// index.  One call walks one generation; the host loops.  gen_step<false> is the step gen_kernel has always made.
 #include <math.h>
 
 #include "launchers.h"
@@ -48,6 +54,20 @@ struct GenKin {
   double bg2, beta2, gamma, tmax;
 };
 
+// the cascade's switches (LdsimTrackGenCascadeParams; delta and decays are 0 in a last generation, emit = 0)
+struct CasConst {
+  double t_track, tau_plus, tau_minus, capture;
+  int32_t delta, decays;
+};
+
+// where a walk's secondaries go: out = the walk's first record (nullptr in the count pass), room = records that fit behind it
+struct GenEmit {
+  LdsimTrackGenParticle* out;
+  unsigned long long room;
+  unsigned n;                         // emitted so far
+  int32_t parent, generation, tie;    // the walking particle's index, generation and track_in_event
+};
+
 __host__ __device__ inline double gen_mass(int32_t pdg) {
   const int32_t a = pdg < 0 ? -pdg : pdg;
   return a == 13 ? LDSIM_TRACK_GEN_M_MUON : a == 211 ? LDSIM_TRACK_GEN_M_PION : LDSIM_TRACK_GEN_M_PROTON;
@@ -78,13 +98,100 @@ __host__ __device__ inline double gen_rate(const GenConst& g, const GenKin& k, d
          (0.5 * log(2.0 * LDSIM_TRACK_GEN_ME * k.bg2 * tc / g.i2) - 0.5 * k.beta2 * (1.0 + tc / k.tmax) - 0.5 * gen_delta(g, k.bg2));
 }
 
+// electrons (include/ldsim.h, "Electrons"): MeV / cm lost to Moller collisions below tc (tc = T / 2: the unrestricted ICRU-37 mean)
+__host__ __device__ inline double gen_rate_e(const GenConst& g, const GenKin& k, double T, double tc) {
+  const double tau = T / LDSIM_TRACK_GEN_ME, d = fmin(tc, 0.5 * T) / LDSIM_TRACK_GEN_ME;
+  const double e2 = g.i2 / (LDSIM_TRACK_GEN_ME * LDSIM_TRACK_GEN_ME);
+  return 0.5 * g.kzr / k.beta2 *
+         (log(2.0 * (tau + 2.0) / e2) - 1.0 - k.beta2 + log((tau - d) * d) + tau / (tau - d) +
+          (0.5 * d * d + (2.0 * tau + 1.0) * log(1.0 - d / tau)) / (k.gamma * k.gamma) - gen_delta(g, k.bg2));
+}
+
+// Moller collisions above t_cut per unit of xi = (K / 2)(Z/A) rho h / beta^2, at kinetic energy T > 2 t_cut
+__host__ __device__ inline double gen_lambda_e(const GenKin& k, double T, double t_cut) {
+  const double gm = (2.0 * k.gamma - 1.0) / (k.gamma * k.gamma), x0 = t_cut / T, x1 = 0.5;
+  return ((x1 - x0) * (1.0 - gm + 1.0 / (x0 * x1) + 1.0 / ((1.0 - x0) * (1.0 - x1))) - gm * log(x1 * (1.0 - x0) / (x0 * (1.0 - x1)))) / T;
+}
+
+// Moller's shape over the proposal 1 / x^2 + 1 / (1 - x)^2, as a function of x (1 - x): falls, then rises (largest at an end)
+__host__ __device__ inline double gen_moller_ratio(double gm, double x) {
+  const double y = x * (1.0 - x);
+  return 1.0 + ((1.0 - gm) * y * y - gm * y) / (1.0 - 2.0 * y);
+}
+
+__host__ __device__ inline double cas_mass(int32_t pdg) {
+  const int32_t a = pdg < 0 ? -pdg : pdg;
+  return a == 11 ? LDSIM_TRACK_GEN_ME : gen_mass(pdg);
+}
+
+// the local direction (a, b, mu) turned into the frame of the unit vector w and renormalised: the light LUT builder's rotation;
+// where w is within 0.99999 of the z axis its polar shortcut (which replaces w by the local vector: right for a photon's wide
+// angles, wrong for milliradians) gives way to the same rotation about the x axis, by a cyclic permutation of the components
+__host__ __device__ inline void gen_rotate(double wx, double wy, double wz, double a, double b, double mu, double& ox, double& oy,
+                                           double& oz) {
+  const bool polar = fabs(wz) > 0.99999;
+  const double dx = polar ? wy : wx, dy = polar ? wz : wy, dz = polar ? wx : wz;
+  const double den = sqrt(1.0 - dz * dz);
+  const double rx = (dx * dz * a - dy * b) / den + dx * mu;
+  const double ry = (dy * dz * a + dx * b) / den + dy * mu;
+  const double rz = -a * den + dz * mu;
+  const double nx = polar ? rz : rx, ny = polar ? rx : ry, nz = polar ? ry : rz;
+  const double nn = sqrt(nx * nx + ny * ny + nz * nz);
+  ox = nx / nn;
+  oy = ny / nn;
+  oz = nz / nn;
+}
+
 __device__ inline double gen_u(uint32_t x) { return (double)keyed_u01(x); }
 
+// draw i of the step whose first block is blk
+__device__ inline double cas_u(uint64_t seed, uint64_t key, uint32_t blk, int i) {
+  uint32_t x[4];
+  keyed_block(seed, RNG_TAG_GEN, key, blk + (uint32_t)(i >> 2), x);
+  const int q = i & 3;
+  return gen_u(q == 0 ? x[0] : q == 1 ? x[1] : q == 2 ? x[2] : x[3]);
+}
+
+// a delta ray of kinetic energy th from collision j of the step that starts at w (Tm: the parent's midpoint energy).  The
+// record's pos[0] holds the draw u of its place on the segment until gen_step knows the segment's final length.
+__device__ inline void cas_emit_delta(uint64_t seed, const GenWalk& w, double Tm, double th, int j, uint32_t blk, GenEmit& em) {
+  if (em.out && em.n < em.room) {
+    const double E = Tm + w.M, p = sqrt(Tm * (Tm + 2.0 * w.M)), pe = sqrt(th * (th + 2.0 * LDSIM_TRACK_GEN_ME));
+    const double ct = fmin(th * (E + LDSIM_TRACK_GEN_ME) / (p * pe), 1.0);
+    const double st = sqrt(1.0 - ct * ct), phi = GEN_TWO_PI * cas_u(seed, w.key, blk, LDSIM_TRACK_GEN_DRAW_AZIMUTH + j);
+    LdsimTrackGenParticle& r = em.out[em.n];
+    gen_rotate(w.dx, w.dy, w.dz, st * cos(phi), st * sin(phi), ct, r.dir[0], r.dir[1], r.dir[2]);
+    r.pos[0] = cas_u(seed, w.key, blk, LDSIM_TRACK_GEN_DRAW_PLACE + j);
+    r.kinetic_energy = th;
+    r.pdg = 11;
+    r.event_id = w.event;
+    r.track_in_event = em.tie;
+    r._pad = 0;
+    r.key = key_mix(key_mix(w.key, (uint64_t)(1 + w.step)), (uint64_t)(1 + j));
+    r.parent = em.parent;
+    r.generation = em.generation + 1;
+    r.process = 1;
+    r.parent_step = w.step;
+  }
+  em.n++;
+}
+
 // one step of the walk (include/ldsim.h, "One step"); sets w.state when the walk ends
-__device__ inline void gen_step(const GenConst& g, uint64_t seed, GenWalk& w, GenSeg& sg) {
+// CAS: electrons too, and hard collisions above cg->t_track leave as secondaries through em (cg, em: nullptr without CAS)
+template <bool CAS>
+__device__ inline void gen_step(const GenConst& g, const CasConst* cg, uint64_t seed, GenWalk& w, GenSeg& sg, GenEmit* em) {
   const uint32_t blk = (uint32_t)LDSIM_TRACK_GEN_STEP_BLOCKS * (uint32_t)w.step;
   GenKin k = gen_kin(w.T, w.M);
-  const double s_full = gen_rate(g, k, k.tmax);
+  bool el = false;
+  double eem = 0.0;                   // energy that left as secondaries
+  unsigned em0 = 0;
+  if constexpr (CAS) {
+    el = w.pdg == 11 || w.pdg == -11;
+    if (el) k.tmax = 0.5 * w.T;
+    em0 = em->n;
+  }
+  double s_full = gen_rate(g, k, k.tmax);
+  if constexpr (CAS) s_full = el ? gen_rate_e(g, k, w.T, k.tmax) : s_full;
   double h = fmax(fmin(g.step, g.frac * w.T / s_full), g.min_step);
   // distance to the walls along d (never negative; on a tie the lowest axis)
   double dw = INFINITY;
@@ -113,8 +220,10 @@ __device__ inline void gen_step(const GenConst& g, uint64_t seed, GenWalk& w, Ge
   if (g.eloss) {
     Tm = fmax(w.T - 0.5 * s_full * h, g.t_min);
     k = gen_kin(Tm, w.M);
+    if constexpr (CAS) if (el) k.tmax = 0.5 * Tm;
     const double tc = g.straggling ? fmin(g.t_cut, k.tmax) : k.tmax;
-    const double s_mean = gen_rate(g, k, tc);
+    double s_mean = gen_rate(g, k, tc);
+    if constexpr (CAS) s_mean = el ? gen_rate_e(g, k, Tm, tc) : s_mean;
     dE = s_mean * h;
     if (g.straggling) {
       const double xi = 0.5 * g.kzr * h / k.beta2;
@@ -124,7 +233,8 @@ __device__ inline void gen_step(const GenConst& g, uint64_t seed, GenWalk& w, Ge
       if (k.tmax > g.t_cut) {
         uint32_t x1[4];
         keyed_block(seed, RNG_TAG_GEN, w.key, blk + 1, x1);
-        const double lam = xi * ((1.0 / g.t_cut - 1.0 / k.tmax) - (k.beta2 / k.tmax) * log(k.tmax / g.t_cut));
+        double lam = xi * ((1.0 / g.t_cut - 1.0 / k.tmax) - (k.beta2 / k.tmax) * log(k.tmax / g.t_cut));
+        if constexpr (CAS) lam = el ? xi * gen_lambda_e(k, Tm, g.t_cut) : lam;
         const double up = gen_u(x1[0]) - 2.98023223876953125e-08;      // 2^-25
         double pk = exp(-lam), c = pk;
         int nh = 0;
@@ -137,19 +247,47 @@ __device__ inline void gen_step(const GenConst& g, uint64_t seed, GenWalk& w, Ge
         for (int j = 0; j < nh; j++) {
           uint32_t xj[4];
           double th = 0.0;
-          for (int r = 0; r < LDSIM_TRACK_GEN_HARD_TRIES; r++) {
-            if ((r & 1) == 0) keyed_block(seed, RNG_TAG_GEN, w.key, blk + 2 + 2 * j + (r >> 1), xj);
-            const double ue = gen_u((r & 1) ? xj[2] : xj[0]), ua = gen_u((r & 1) ? xj[3] : xj[1]);
-            th = 1.0 / (1.0 / g.t_cut - ue * (1.0 / g.t_cut - 1.0 / k.tmax));
-            if (ua > k.beta2 * th / k.tmax || r == LDSIM_TRACK_GEN_HARD_TRIES - 1) break;
+          if (CAS && el) {
+            // Moller: x = T_h / Tm on [x0, 1/2] from the proposal 1 / x^2 + 1 / (1 - x)^2 by its quadratic, kept with
+            // probability ratio / (the ratio's larger end value); the last try is kept whatever u_a says (and draws none)
+            const double gm = (2.0 * k.gamma - 1.0) / (k.gamma * k.gamma), xl = g.t_cut / Tm;
+            const double g0 = (2.0 * xl - 1.0) / (xl * (1.0 - xl));
+            const double top = fmax(gen_moller_ratio(gm, xl), gen_moller_ratio(gm, 0.5));
+            for (int r = 0; r < LDSIM_TRACK_GEN_MOLLER_TRIES; r++) {
+              const int i = r < LDSIM_TRACK_GEN_HARD_TRIES ? 8 + 8 * j + 2 * r
+                                                          : LDSIM_TRACK_GEN_DRAW_MOLLER + 5 * j + 2 * (r - LDSIM_TRACK_GEN_HARD_TRIES);
+              const double c = g0 * (1.0 - cas_u(seed, w.key, blk, i));
+              const double x = 2.0 / ((2.0 - c) + sqrt(4.0 + c * c));
+              th = x * Tm;
+              if (r == LDSIM_TRACK_GEN_MOLLER_TRIES - 1) break;
+              if (cas_u(seed, w.key, blk, i + 1) * top <= gen_moller_ratio(gm, x)) break;
+            }
+          } else {
+            for (int r = 0; r < LDSIM_TRACK_GEN_HARD_TRIES; r++) {
+              if ((r & 1) == 0) keyed_block(seed, RNG_TAG_GEN, w.key, blk + 2 + 2 * j + (r >> 1), xj);
+              const double ue = gen_u((r & 1) ? xj[2] : xj[0]), ua = gen_u((r & 1) ? xj[3] : xj[1]);
+              th = 1.0 / (1.0 / g.t_cut - ue * (1.0 / g.t_cut - 1.0 / k.tmax));
+              if (ua > k.beta2 * th / k.tmax || r == LDSIM_TRACK_GEN_HARD_TRIES - 1) break;
+            }
           }
-          dE = dE + th;
+          // a secondary of its own from t_track on, while what has left stays below T (else deposited, in the order j)
+          bool leaves_track = false;
+          if constexpr (CAS) leaves_track = cg->delta && th >= cg->t_track && eem + th < w.T;
+          if (leaves_track) {
+            eem = eem + th;
+            cas_emit_delta(seed, w, Tm, th, j, blk, *em);
+          } else {
+            dE = dE + th;
+          }
         }
       }
     }
-    stops = dE >= w.T || w.T - dE < g.t_min;
+    double spent = dE;
+    if constexpr (CAS) spent = dE + eem;
+    stops = spent >= w.T || w.T - spent < g.t_min;
     if (stops) {
       dE = w.T;
+      if constexpr (CAS) dE = w.T - eem;
       h = fmin(h, w.T / s_mean);
     }
   }
@@ -172,6 +310,18 @@ __device__ inline void gen_step(const GenConst& g, uint64_t seed, GenWalk& w, Ge
   sg.dE = dE;
   sg.t0 = w.t;
   sg.t1 = t1;
+  if constexpr (CAS) {
+    // the secondaries' places on the segment as it ended: p + u h d (held in the box), the time interpolated
+    if (em->out)
+      for (unsigned q = em0; q < em->n && q < em->room; q++) {
+        LdsimTrackGenParticle& r = em->out[q];
+        const double u = r.pos[0];
+        r.pos[0] = fmin(fmax(w.px + u * h * w.dx, g.lo[0]), g.hi[0]);
+        r.pos[1] = fmin(fmax(w.py + u * h * w.dy, g.lo[1]), g.hi[1]);
+        r.pos[2] = fmin(fmax(w.pz + u * h * w.dz, g.lo[2]), g.hi[2]);
+        r.time = w.t + u * (t1 - w.t);
+      }
+  }
   w.step++;
   if (stops) w.state = 0;
   else if (leaves) w.state = 1;
@@ -182,24 +332,12 @@ __device__ inline void gen_step(const GenConst& g, uint64_t seed, GenWalk& w, Ge
     const double ax = th0 * (rr * cos(aa)), ay = th0 * (rr * sin(aa));
     const double nrm = sqrt(1.0 + ax * ax + ay * ay);
     const double a = ax / nrm, b = ay / nrm, mu = 1.0 / nrm;
-    // the light LUT builder's rotation; where d is within 0.99999 of the z axis its polar shortcut (which replaces d by the local
-    // vector: right for a photon's wide angles, wrong for milliradians) gives way to the same rotation about the x axis, by a
-    // cyclic permutation of the components
-    const bool polar = fabs(w.dz) > 0.99999;
-    const double dx = polar ? w.dy : w.dx, dy = polar ? w.dz : w.dy, dz = polar ? w.dx : w.dz;
-    const double den = sqrt(1.0 - dz * dz);
-    const double rx = (dx * dz * a - dy * b) / den + dx * mu;
-    const double ry = (dy * dz * a + dx * b) / den + dy * mu;
-    const double rz = -a * den + dz * mu;
-    const double nx = polar ? rz : rx, ny = polar ? rx : ry, nz = polar ? ry : rz;
-    const double nn = sqrt(nx * nx + ny * ny + nz * nz);
-    w.dx = nx / nn;
-    w.dy = ny / nn;
-    w.dz = nz / nn;
+    gen_rotate(w.dx, w.dy, w.dz, a, b, mu, w.dx, w.dy, w.dz);
   }
   w.px = ex; w.py = ey; w.pz = ez;
   w.t = t1;
   w.T = w.T - dE;
+  if constexpr (CAS) w.T = stops ? 0.0 : w.T - eem;
   w.path = w.path + h;
 }
 
@@ -244,7 +382,7 @@ gen_kernel(const GenConst g, const LdsimTrackGenPrimary* __restrict__ prim, int6
       if (WRITE) off = offsets[idx];
       have = true;
     }
-    gen_step(g, seed, w, sg);
+    gen_step<false>(g, nullptr, seed, w, sg, nullptr);
     if (WRITE) {
       const unsigned long long o = off + (unsigned)(w.step - 1);
       if (o < (unsigned long long)cap) {
@@ -273,6 +411,129 @@ gen_kernel(const GenConst g, const LdsimTrackGenPrimary* __restrict__ prim, int6
   }
 }
 
+__device__ inline void cas_start(const LdsimTrackGenParticle& P, GenWalk& w) {
+  const double n = sqrt(P.dir[0] * P.dir[0] + P.dir[1] * P.dir[1] + P.dir[2] * P.dir[2]);
+  w.px = P.pos[0]; w.py = P.pos[1]; w.pz = P.pos[2];
+  w.dx = P.dir[0] / n; w.dy = P.dir[1] / n; w.dz = P.dir[2] / n;
+  w.T = P.kinetic_energy;
+  w.t = P.time;
+  w.path = 0.0;
+  w.M = cas_mass(P.pdg);
+  w.key = P.key;
+  w.step = 0;
+  w.state = GEN_WALKING;
+  w.pdg = P.pdg;
+  w.event = P.event_id;
+}
+
+// a muon that stopped (include/ldsim.h, "Decay"): draws of the step index after its last, w.step
+__device__ inline void cas_decay(const CasConst& cg, uint64_t seed, const GenWalk& w, GenEmit& em) {
+  const uint32_t blk = (uint32_t)LDSIM_TRACK_GEN_STEP_BLOCKS * (uint32_t)w.step;
+  uint32_t x0[4], xr[4];
+  keyed_block(seed, RNG_TAG_GEN, w.key, blk, x0);
+  const bool minus = w.pdg == 13;
+  if (minus && gen_u(x0[0]) <= cg.capture) return;
+  // the Michel x: F(x) = x^3 (2 - x) = u by Newton from cbrt(u / 2) (F is convex and rising: from the second iterate on the
+  // sequence falls onto the root)
+  keyed_block(seed, RNG_TAG_GEN, w.key, blk + 1, xr);
+  const double u = gen_u(xr[0]);
+  double x = cbrt(0.5 * u);
+  for (int r = 0; r < LDSIM_TRACK_GEN_MICHEL_NEWTON; r++) x = x - (x * x * x * (2.0 - x) - u) / (2.0 * x * x * (3.0 - 2.0 * x));
+  x = fmin(x, 1.0);
+  const double wmax = (LDSIM_TRACK_GEN_M_MUON * LDSIM_TRACK_GEN_M_MUON + LDSIM_TRACK_GEN_ME * LDSIM_TRACK_GEN_ME) / (2.0 * LDSIM_TRACK_GEN_M_MUON);
+  const double etot = x * wmax;
+  if (etot <= LDSIM_TRACK_GEN_ME) return;
+  if (em.out && em.n < em.room) {
+    const double mu = 1.0 - 2.0 * gen_u(x0[2]), phi = GEN_TWO_PI * gen_u(x0[3]);
+    const double st = sqrt(fmax(0.0, 1.0 - mu * mu));
+    LdsimTrackGenParticle& r = em.out[em.n];
+    r.pos[0] = w.px; r.pos[1] = w.py; r.pos[2] = w.pz;
+    r.dir[0] = st * cos(phi); r.dir[1] = st * sin(phi); r.dir[2] = mu;
+    r.kinetic_energy = etot - LDSIM_TRACK_GEN_ME;
+    r.time = w.t - (minus ? cg.tau_minus : cg.tau_plus) * log(gen_u(x0[1]));
+    r.pdg = minus ? 11 : -11;
+    r.event_id = w.event;
+    r.track_in_event = em.tie;
+    r._pad = 0;
+    r.key = key_mix(key_mix(w.key, (uint64_t)(1 + w.step)), (uint64_t)LDSIM_TRACK_GEN_DECAY_KEY);
+    r.parent = em.parent;
+    r.generation = em.generation + 1;
+    r.process = 2;
+    r.parent_step = w.step;
+  }
+  em.n++;
+}
+
+// gen_kernel's loop over one generation of a cascade.  WRITE = false: counts and scounts u64 [n] (segments, secondaries), state,
+// end as gen_kernel.  WRITE = true: segments as gen_kernel; secondary q of particle i into sec[soffsets[i] + q] (< scap, checked).
+template <bool WRITE>
+__global__ void __launch_bounds__(GEN_BLOCK)
+cas_kernel(const GenConst g, const CasConst cg, const LdsimTrackGenParticle* __restrict__ part, int64_t n, uint64_t seed, int32_t group,
+           unsigned long long* __restrict__ counts, unsigned long long* __restrict__ scounts, int32_t* __restrict__ state,
+           double* __restrict__ end, const unsigned long long* __restrict__ offsets, const unsigned long long* __restrict__ soffsets,
+           int64_t cap, int64_t scap, double* __restrict__ fcol, int32_t* __restrict__ icol, LdsimTrackGenParticle* __restrict__ sec) {
+  __shared__ unsigned next;
+  const int64_t first = (int64_t)blockIdx.x * group;
+  const unsigned mine = (unsigned)min((int64_t)group, n - first);
+  if (threadIdx.x == 0) next = 0;
+  __syncthreads();
+  GenWalk w;
+  GenSeg sg;
+  GenEmit em;
+  int64_t idx = 0;
+  unsigned long long off = 0;
+  bool have = false;
+  while (true) {
+    if (!have) {
+      const unsigned i = atomicAdd(&next, 1u);
+      if (i >= mine) break;
+      idx = first + i;
+      cas_start(part[idx], w);
+      em.out = nullptr;
+      em.room = 0;
+      em.n = 0;
+      em.parent = (int32_t)idx;
+      em.generation = part[idx].generation;
+      em.tie = part[idx].track_in_event;
+      if (WRITE) {
+        off = offsets[idx];
+        const unsigned long long so = soffsets[idx];
+        em.room = so < (unsigned long long)scap ? (unsigned long long)scap - so : 0;
+        em.out = sec + (so < (unsigned long long)scap ? so : 0);
+      }
+      have = true;
+    }
+    gen_step<true>(g, &cg, seed, w, sg, &em);
+    if (WRITE) {
+      const unsigned long long o = off + (unsigned)(w.step - 1);
+      if (o < (unsigned long long)cap) {
+        double* f = fcol + o;
+        const size_t c = (size_t)cap;
+        f[0 * c] = sg.xs; f[1 * c] = sg.ys; f[2 * c] = sg.zs;
+        f[3 * c] = sg.xe; f[4 * c] = sg.ye; f[5 * c] = sg.ze;
+        f[6 * c] = 0.5 * (sg.xs + sg.xe); f[7 * c] = 0.5 * (sg.ys + sg.ye); f[8 * c] = 0.5 * (sg.zs + sg.ze);
+        f[9 * c] = sg.h;
+        f[10 * c] = sg.dE;
+        f[11 * c] = sg.h > 0 ? sg.dE / sg.h : 0.0;
+        f[12 * c] = sg.t0; f[13 * c] = sg.t1; f[14 * c] = 0.5 * (sg.t0 + sg.t1);
+        int32_t* q = icol + o;
+        q[0 * c] = (int32_t)idx; q[1 * c] = w.step - 1; q[2 * c] = w.pdg; q[3 * c] = w.event;
+      }
+    }
+    if (w.state != GEN_WALKING) {
+      if (w.state == 0 && cg.decays && (w.pdg == 13 || w.pdg == -13)) cas_decay(cg, seed, w, em);
+      have = false;
+      if (!WRITE) {
+        counts[idx] = (unsigned long long)w.step;
+        scounts[idx] = (unsigned long long)em.n;
+        state[idx] = w.state;
+        double* e = end + 6 * idx;
+        e[0] = w.px; e[1] = w.py; e[2] = w.pz; e[3] = w.t; e[4] = w.path; e[5] = w.T;
+      }
+    }
+  }
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------
 #define GEN_NEED(cond, ...)               \
   do {                                    \
@@ -290,10 +551,8 @@ static uint64_t gen_hash(uint64_t h, const void* data, size_t bytes) {      // (
   return h;
 }
 
-// checks parameters and primaries, fills the kernel's constants
-static int gen_prepare(const char* who, const LdsimTrackGenParams* P, const LdsimTrackGenPrimary* prim, int64_t n, GenConst* g) {
-  GEN_NEED(P && (n == 0 || prim), "%s: null argument", who);
-  GEN_NEED(n >= 0 && n <= 2147483647LL, "%s: %lld primaries, need 0 .. 2^31 - 1", who, (long long)n);
+// checks the parameters, fills the kernel's constants; electrons: the cascade's entries, which walk them
+static int gen_prepare_params(const char* who, const LdsimTrackGenParams* P, GenConst* g, bool electrons) {
   GEN_NEED(gen_pos(P->step), "%s: step %g cm must be finite and > 0", who, P->step);
   GEN_NEED(gen_pos(P->min_step), "%s: min_step %g cm must be finite and > 0", who, P->min_step);
   GEN_NEED(P->min_step <= P->step, "%s: min_step %g exceeds step %g", who, P->min_step, P->step);
@@ -335,21 +594,43 @@ static int gen_prepare(const char* who, const LdsimTrackGenParams* P, const Ldsi
     GEN_NEED(gen_rate(*g, k, fmin(P->t_cut, k.tmax)) > 0, "%s: the stopping power of pdg %d is not positive at t_min %g MeV: raise "
              "t_min", who, pdg, P->t_min);
   }
+  if (electrons) {
+    GenKin k = gen_kin(P->t_min, LDSIM_TRACK_GEN_ME);
+    k.tmax = 0.5 * P->t_min;
+    GEN_NEED(gen_rate_e(*g, k, P->t_min, fmin(P->t_cut, k.tmax)) > 0, "%s: the stopping power of pdg 11 is not positive at t_min %g "
+             "MeV: raise t_min", who, P->t_min);
+  }
+  return 0;
+}
+
+// checks the records to walk (Rec: LdsimTrackGenPrimary, or LdsimTrackGenParticle with what = "particle" and electrons allowed)
+template <class Rec>
+static int gen_check_records(const char* who, const LdsimTrackGenParams* P, const Rec* prim, int64_t n, const char* what,
+                             bool electrons) {
   for (int64_t i = 0; i < n; i++) {
-    const LdsimTrackGenPrimary& r = prim[i];
-    GEN_NEED(r.pdg == 13 || r.pdg == -13 || r.pdg == 211 || r.pdg == -211 || r.pdg == 2212,
-             "%s: primary %lld has unknown pdg %d (13, -13, 211, -211 and 2212 are transported)", who, (long long)i, r.pdg);
-    GEN_NEED(gen_pos(r.kinetic_energy), "%s: primary %lld: kinetic energy %g MeV must be finite and > 0", who, (long long)i,
+    const Rec& r = prim[i];
+    GEN_NEED(r.pdg == 13 || r.pdg == -13 || r.pdg == 211 || r.pdg == -211 || r.pdg == 2212 || (electrons && (r.pdg == 11 || r.pdg == -11)),
+             "%s: %s %lld has unknown pdg %d (%s13, -13, 211, -211 and 2212 are transported)", who, what, (long long)i, r.pdg,
+             electrons ? "11, -11, " : "");
+    GEN_NEED(gen_pos(r.kinetic_energy), "%s: %s %lld: kinetic energy %g MeV must be finite and > 0", who, what, (long long)i,
              r.kinetic_energy);
     for (int k = 0; k < 3; k++)
       GEN_NEED(std::isfinite(r.pos[k]) && r.pos[k] >= P->world_lo[k] && r.pos[k] <= P->world_hi[k],
-               "%s: primary %lld starts outside the world box (coordinate %d = %g, box [%g, %g])", who, (long long)i, k, r.pos[k],
+               "%s: %s %lld starts outside the world box (coordinate %d = %g, box [%g, %g])", who, what, (long long)i, k, r.pos[k],
                P->world_lo[k], P->world_hi[k]);
     const double nn = sqrt(r.dir[0] * r.dir[0] + r.dir[1] * r.dir[1] + r.dir[2] * r.dir[2]);
-    GEN_NEED(std::isfinite(nn) && nn > 0, "%s: primary %lld has a zero direction", who, (long long)i);
-    GEN_NEED(std::isfinite(r.time), "%s: primary %lld: time is not finite", who, (long long)i);
+    GEN_NEED(std::isfinite(nn) && nn > 0, "%s: %s %lld has a zero direction", who, what, (long long)i);
+    GEN_NEED(std::isfinite(r.time), "%s: %s %lld: time is not finite", who, what, (long long)i);
   }
   return 0;
+}
+
+// checks parameters and primaries, fills the kernel's constants
+static int gen_prepare(const char* who, const LdsimTrackGenParams* P, const LdsimTrackGenPrimary* prim, int64_t n, GenConst* g) {
+  GEN_NEED(P && (n == 0 || prim), "%s: null argument", who);
+  GEN_NEED(n >= 0 && n <= 2147483647LL, "%s: %lld primaries, need 0 .. 2^31 - 1", who, (long long)n);
+  CK(gen_prepare_params(who, P, g, false));
+  return gen_check_records(who, P, prim, n, "primary", false);
 }
 
 // primaries per workgroup: the option, or by itself (0) enough groups to spread a short list over the device -- n / 2048, at
@@ -453,5 +734,172 @@ int trackgen_generate(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimT
   HIPCHK(hipEventElapsedTime(&ms, ctx->tg_ev[0], ctx->tg_ev[1]));
   ctx->ms_tg = ms;
   *n_segments = total;
+  return 0;
+}
+
+// ---- the cascade: one generation per call ----------------------------------------------------------------------------------------
+static int cas_prepare(const char* who, const LdsimTrackGenParams* P, const LdsimTrackGenCascadeParams* CP,
+                       const LdsimTrackGenParticle* part, int64_t n, GenConst* g, CasConst* cg) {
+  GEN_NEED(P && CP && (n == 0 || part), "%s: null argument", who);
+  GEN_NEED(n >= 0 && n <= 2147483647LL, "%s: %lld particles, need 0 .. 2^31 - 1", who, (long long)n);
+  CK(gen_prepare_params(who, P, g, true));
+  GEN_NEED(std::isfinite(CP->t_track) && CP->t_track >= P->t_cut && CP->t_track >= P->t_min,
+           "%s: t_track %g MeV must be finite and at least t_cut %g and t_min %g", who, CP->t_track, P->t_cut, P->t_min);
+  GEN_NEED(CP->capture_fraction >= 0 && CP->capture_fraction <= 1, "%s: capture_fraction %g must lie in [0, 1]", who,
+           CP->capture_fraction);
+  GEN_NEED(gen_pos(CP->mu_plus_lifetime), "%s: mu_plus_lifetime %g us must be finite and > 0", who, CP->mu_plus_lifetime);
+  GEN_NEED(gen_pos(CP->mu_minus_lifetime), "%s: mu_minus_lifetime %g us must be finite and > 0", who, CP->mu_minus_lifetime);
+  cg->t_track = CP->t_track;
+  cg->tau_plus = CP->mu_plus_lifetime;
+  cg->tau_minus = CP->mu_minus_lifetime;
+  cg->capture = CP->capture_fraction;
+  cg->delta = CP->emit != 0 && CP->delta_tracks != 0;
+  cg->decays = CP->emit != 0 && CP->decays != 0;
+  return gen_check_records(who, P, part, n, "particle", true);
+}
+
+// the count pass and its two scans; leaves the per-particle results in the ctx (tc_*), the totals in tc_total / tc_stotal.  Skipped
+// when the ctx holds them for the same (parameters, cascade parameters, particles, seed) already.
+static int cas_count_pass(ldsim_ctx* ctx, const GenConst& g, const CasConst& cg, const LdsimTrackGenParams* P,
+                          const LdsimTrackGenCascadeParams* CP, const LdsimTrackGenParticle* part, int64_t n, uint64_t seed) {
+  uint64_t h = gen_hash(0xCBF29CE484222325ULL ^ seed, P, sizeof(*P));
+  h = gen_hash(h, CP, sizeof(*CP));
+  h = gen_hash(h ^ (uint64_t)n, part, (size_t)n * sizeof(*part));
+  if (ctx->tc_valid && ctx->tc_hash == h && ctx->tc_n == n) return 0;
+  ctx->tc_valid = 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  CK(ctx->tc_part.ensure((size_t)n * sizeof(*part)));
+  CK(ctx->tc_counts.ensure((size_t)n * 16));
+  CK(ctx->tc_off.ensure((size_t)n * 16));
+  CK(ctx->tc_state.ensure((size_t)n * 4));
+  CK(ctx->tc_end.ensure((size_t)n * 48));
+  ctx->tc_total = ctx->tc_stotal = 0;
+  if (n) {
+    unsigned long long* cnt = ctx->tc_counts.as<unsigned long long>();
+    unsigned long long* off = ctx->tc_off.as<unsigned long long>();
+    HIPCHK(hipMemcpyAsync(ctx->tc_part.p, part, (size_t)n * sizeof(*part), hipMemcpyHostToDevice, st));
+    const int32_t group = gen_group(ctx, n);
+    const unsigned blocks = (unsigned)((n + group - 1) / group);
+    hipLaunchKernelGGL(cas_kernel<false>, dim3(blocks), dim3(GEN_BLOCK), 0, st, g, cg, ctx->tc_part.as<LdsimTrackGenParticle>(), n, seed,
+                       group, cnt, cnt + n, ctx->tc_state.as<int32_t>(), ctx->tc_end.as<double>(), (const unsigned long long*)nullptr,
+                       (const unsigned long long*)nullptr, (int64_t)0, (int64_t)0, (double*)nullptr, (int32_t*)nullptr,
+                       (LdsimTrackGenParticle*)nullptr);
+    HIPCHK(hipGetLastError());
+    CK(sort_exclusive_scan_u64(ctx, cnt, off, n));
+    CK(sort_exclusive_scan_u64(ctx, cnt + n, off + n, n));
+    unsigned long long last[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(&last[0], cnt + (n - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&last[1], off + (n - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&last[2], cnt + (2 * n - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&last[3], off + (2 * n - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ctx->tc_total = (int64_t)(last[0] + last[1]);
+    ctx->tc_stotal = (int64_t)(last[2] + last[3]);
+  }
+  ctx->tc_hash = h;
+  ctx->tc_n = n;
+  ctx->tc_valid = 1;
+  return 0;
+}
+
+int trackgen_cascade_count(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrackGenCascadeParams* CP,
+                           const LdsimTrackGenParticle* part, int64_t n, uint64_t seed, int32_t* counts, int32_t* secondary_counts,
+                           int32_t* end_state, double* end) {
+  static const char who[] = "ldsim_track_cascade_count";
+  GenConst g;
+  CasConst cg;
+  CK(cas_prepare(who, P, CP, part, n, &g, &cg));
+  if (n == 0) return 0;
+  GEN_NEED(counts && secondary_counts && end_state && end, "%s: null output array", who);
+  CK(cas_count_pass(ctx, g, cg, P, CP, part, n, seed));
+  std::vector<unsigned long long> c64((size_t)n * 2);
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(c64.data(), ctx->tc_counts.p, (size_t)n * 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(end_state, ctx->tc_state.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(end, ctx->tc_end.p, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < n; i++) {
+    counts[i] = (int32_t)c64[(size_t)i];                        // (<= LDSIM_TRACK_GEN_MAX_STEPS each)
+    secondary_counts[i] = (int32_t)c64[(size_t)(n + i)];        // (<= LDSIM_TRACK_GEN_HARD_CAP a step, + 1)
+  }
+  return 0;
+}
+
+int trackgen_cascade(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrackGenCascadeParams* CP,
+                     const LdsimTrackGenParticle* part, int64_t n, uint64_t seed, int64_t capacity, double* f64_columns,
+                     int32_t* i32_columns, int64_t* n_segments, int64_t secondary_capacity, LdsimTrackGenParticle* secondaries,
+                     int64_t* n_secondaries) {
+  static const char who[] = "ldsim_track_cascade";
+  GenConst g;
+  CasConst cg;
+  CK(cas_prepare(who, P, CP, part, n, &g, &cg));
+  GEN_NEED(n_segments && n_secondaries, "%s: null n_segments or n_secondaries", who);
+  GEN_NEED(capacity >= 0 && secondary_capacity >= 0, "%s: negative capacity", who);
+  *n_segments = *n_secondaries = 0;
+  ctx->ms_tc = 0;
+  if (n == 0) return 0;
+  CK(cas_count_pass(ctx, g, cg, P, CP, part, n, seed));
+  const int64_t total = ctx->tc_total, stotal = ctx->tc_stotal;
+  GEN_NEED(total <= 2147483647LL, "%s: %lld segments, more than 2^31 - 1: walk fewer particles per call", who, (long long)total);
+  GEN_NEED(stotal <= 2147483647LL, "%s: %lld secondaries, more than 2^31 - 1: walk fewer particles per call", who, (long long)stotal);
+  GEN_NEED(capacity >= total, "%s: capacity %lld is too small: %lld segments are needed", who, (long long)capacity, (long long)total);
+  GEN_NEED(secondary_capacity >= stotal, "%s: secondary capacity %lld is too small: %lld secondaries are needed", who,
+           (long long)secondary_capacity, (long long)stotal);
+  GEN_NEED(f64_columns && i32_columns && (stotal == 0 || secondaries), "%s: null output array", who);
+  hipStream_t st = ctx->stream;
+  CK(ctx->tc_f64.ensure((size_t)total * 8 * LDSIM_TRACK_GEN_NF64));
+  CK(ctx->tc_i32.ensure((size_t)total * 4 * LDSIM_TRACK_GEN_NI32));
+  CK(ctx->tc_sec.ensure((size_t)(stotal ? stotal : 1) * sizeof(LdsimTrackGenParticle)));
+  for (Event& e : ctx->tc_ev) CK(e.ensure());
+  const int32_t group = gen_group(ctx, n);
+  const unsigned blocks = (unsigned)((n + group - 1) / group);
+  const unsigned long long* off = ctx->tc_off.as<unsigned long long>();
+  HIPCHK(hipEventRecord(ctx->tc_ev[0], st));
+  hipLaunchKernelGGL(cas_kernel<true>, dim3(blocks), dim3(GEN_BLOCK), 0, st, g, cg, ctx->tc_part.as<LdsimTrackGenParticle>(), n, seed, group,
+                     (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, (double*)nullptr, off, off + n, total,
+                     stotal, ctx->tc_f64.as<double>(), ctx->tc_i32.as<int32_t>(), ctx->tc_sec.as<LdsimTrackGenParticle>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->tc_ev[1], st));
+  for (int c = 0; c < LDSIM_TRACK_GEN_NF64; c++)
+    HIPCHK(hipMemcpyAsync(f64_columns + (size_t)c * capacity, ctx->tc_f64.as<double>() + (size_t)c * total, (size_t)total * 8,
+                          hipMemcpyDeviceToHost, st));
+  for (int c = 0; c < LDSIM_TRACK_GEN_NI32; c++)
+    HIPCHK(hipMemcpyAsync(i32_columns + (size_t)c * capacity, ctx->tc_i32.as<int32_t>() + (size_t)c * total, (size_t)total * 4,
+                          hipMemcpyDeviceToHost, st));
+  if (stotal)
+    HIPCHK(hipMemcpyAsync(secondaries, ctx->tc_sec.p, (size_t)stotal * sizeof(LdsimTrackGenParticle), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->tc_ev[0], ctx->tc_ev[1]));
+  ctx->ms_tc = ms;
+  *n_segments = total;
+  *n_secondaries = stotal;
+  return 0;
+}
+
+// generation 0 of a cascade: the primaries with the stream keys gen_start gives them (host only)
+int trackgen_cascade_particles(const LdsimTrackGenPrimary* prim, int64_t n, LdsimTrackGenParticle* out) {
+  static const char who[] = "ldsim_track_cascade_particles";
+  GEN_NEED(n >= 0 && (n == 0 || (prim && out)), "%s: null argument or negative n", who);
+  for (int64_t i = 0; i < n; i++) {
+    const LdsimTrackGenPrimary& r = prim[i];
+    LdsimTrackGenParticle& o = out[i];
+    for (int k = 0; k < 3; k++) {
+      o.pos[k] = r.pos[k];
+      o.dir[k] = r.dir[k];
+    }
+    o.kinetic_energy = r.kinetic_energy;
+    o.time = r.time;
+    o.pdg = r.pdg;
+    o.event_id = r.event_id;
+    o.track_in_event = r.track_in_event;
+    o._pad = 0;
+    o.key = key_mix(key_mix(RNG_KEY_ROOT, (uint64_t)(int64_t)r.event_id), (uint64_t)(int64_t)r.track_in_event);
+    o.parent = -1;
+    o.generation = 0;
+    o.process = 0;
+    o.parent_step = -1;
+  }
   return 0;
 }

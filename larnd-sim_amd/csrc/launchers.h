@@ -24,6 +24,14 @@ int trackgen_count(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrac
                    int32_t* counts, int32_t* end_state, double* end);
 int trackgen_generate(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrackGenPrimary* prim, int64_t n, uint64_t seed,
                       int64_t capacity, double* f64_columns, int32_t* i32_columns, int64_t* n_segments);
+int trackgen_cascade_count(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrackGenCascadeParams* CP,
+                           const LdsimTrackGenParticle* part, int64_t n, uint64_t seed, int32_t* counts, int32_t* secondary_counts,
+                           int32_t* end_state, double* end);
+int trackgen_cascade(ldsim_ctx* ctx, const LdsimTrackGenParams* P, const LdsimTrackGenCascadeParams* CP,
+                     const LdsimTrackGenParticle* part, int64_t n, uint64_t seed, int64_t capacity, double* f64_columns,
+                     int32_t* i32_columns, int64_t* n_segments, int64_t secondary_capacity, LdsimTrackGenParticle* secondaries,
+                     int64_t* n_secondaries);
+int trackgen_cascade_particles(const LdsimTrackGenPrimary* prim, int64_t n, LdsimTrackGenParticle* out);
 
 // ---- kernels_lutbuild.hip (the entry points of ldsim_abi.hip hand their arguments through) ----------------------------------
 int lutbuild_build(ldsim_ctx* ctx, const LdsimLutBuildParams* P, const LdsimLutDetector* dets, int32_t ndet, int32_t nx,

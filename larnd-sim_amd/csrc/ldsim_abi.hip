@@ -758,6 +758,35 @@ extern "C" int ldsim_track_gen_ms(ldsim_ctx* ctx, double* ms) {
   return 0;
 }
 
+extern "C" int ldsim_track_cascade_particles(const LdsimTrackGenPrimary* primaries, int64_t n, LdsimTrackGenParticle* particles) {
+  return trackgen_cascade_particles(primaries, n, particles);
+}
+
+extern "C" int ldsim_track_cascade_count(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenCascadeParams* cascade,
+                                         const LdsimTrackGenParticle* particles, int64_t n, uint64_t seed, int32_t* counts,
+                                         int32_t* secondary_counts, int32_t* end_state, double* end) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return trackgen_cascade_count(ctx, params, cascade, particles, n, seed, counts, secondary_counts, end_state, end);
+}
+
+extern "C" int ldsim_track_cascade(ldsim_ctx* ctx, const LdsimTrackGenParams* params, const LdsimTrackGenCascadeParams* cascade,
+                                   const LdsimTrackGenParticle* particles, int64_t n, uint64_t seed, int64_t capacity,
+                                   double* f64_columns, int32_t* i32_columns, int64_t* n_segments, int64_t secondary_capacity,
+                                   LdsimTrackGenParticle* secondaries, int64_t* n_secondaries) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx, "null ctx");
+  return trackgen_cascade(ctx, params, cascade, particles, n, seed, capacity, f64_columns, i32_columns, n_segments, secondary_capacity,
+                          secondaries, n_secondaries);
+}
+
+extern "C" int ldsim_track_cascade_ms(ldsim_ctx* ctx, double* ms) {
+  LDSIM_ENTER(ctx);
+  NEED(ctx && ms, "null argument");
+  *ms = ctx->ms_tc;
+  return 0;
+}
+
 // ---- drift-field maps ----------------------------------------------------------------------------------------------------
 static int fmap_upload_desc(ldsim_ctx* ctx) {
   CK(ctx->d_fmap.ensure(sizeof(ctx->h_fmap)));

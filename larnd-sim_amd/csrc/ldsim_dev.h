@@ -440,6 +440,18 @@ struct ldsim_ctx {
   int64_t tg_n = 0, tg_total = 0;
   Event tg_ev[2];                // around gen_kernel<true> of the last write pass (ldsim_track_gen_ms)
   double ms_tg = 0;
+  // track cascade (ldsim_track_cascade_count / ldsim_track_cascade, kernels_trackgen.hip): one generation's particles and the
+  // per-particle results of the last count pass (kept for the write pass over the same input: tc_hash), the last write pass's output
+  DevBuf tc_part;                // LdsimTrackGenParticle [n]
+  DevBuf tc_counts, tc_off;      // u64 [2][n] segments | secondaries per particle, and the exclusive scan of each row
+  DevBuf tc_state, tc_end;       // i32 [n] end states | f64 [n][6] end point, end time, path, remaining T
+  DevBuf tc_f64, tc_i32;         // f64 [LDSIM_TRACK_GEN_NF64][total] | i32 [LDSIM_TRACK_GEN_NI32][total]
+  DevBuf tc_sec;                 // LdsimTrackGenParticle [secondaries]
+  int tc_valid = 0;              // the count pass's results belong to (tc_hash, tc_n)
+  uint64_t tc_hash = 0;          // fold of (parameters, cascade parameters, particles, seed) of the last count pass
+  int64_t tc_n = 0, tc_total = 0, tc_stotal = 0;
+  Event tc_ev[2];                // around cas_kernel<true> of the last write pass (ldsim_track_cascade_ms)
+  double ms_tc = 0;
   // random streams (kernels_rng.hip): numba-style table of xoroshiro128p states, grown on demand
   DevBuf d_rng;
   int64_t rng_n = 0;

@@ -125,6 +125,19 @@ class LdsimTrackGenPrimary(C.Structure):
                 ("pdg", C.c_int32), ("event_id", C.c_int32), ("track_in_event", C.c_int32), ("_pad", C.c_int32)]
 
 
+class LdsimTrackGenParticle(C.Structure):
+    """include/ldsim.h LdsimTrackGenParticle: 104 bytes (track_cascade.particle_dtype is the same record in numpy)"""
+    _fields_ = LdsimTrackGenPrimary._fields_ + [("key", C.c_uint64), ("parent", C.c_int32), ("generation", C.c_int32),
+                                                ("process", C.c_int32), ("parent_step", C.c_int32)]
+
+
+class LdsimTrackGenCascadeParams(C.Structure):
+    """include/ldsim.h LdsimTrackGenCascadeParams (ldsim_track_cascade / _count): 48 bytes"""
+    _fields_ = [("t_track", C.c_double), ("mu_plus_lifetime", C.c_double), ("mu_minus_lifetime", C.c_double),
+                ("capture_fraction", C.c_double), ("delta_tracks", C.c_int32), ("decays", C.c_int32), ("emit", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
 FIELD_MAP_BUILD_MAX_STEPS = 1048576   # include/ldsim.h LDSIM_FIELD_MAP_BUILD_MAX_STEPS
 RESPONSE_BUILD_MAX_K = 7679       # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_K
 RESPONSE_BUILD_MAX_NSUB = 16      # include/ldsim.h LDSIM_RESPONSE_BUILD_MAX_NSUB

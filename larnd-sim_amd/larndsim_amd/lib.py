@@ -60,6 +60,7 @@ EXPORTS = [
     "ldsim_response_build", "ldsim_response_build_ms",
     "ldsim_field_map_solve", "ldsim_field_map_trace", "ldsim_field_map_build_ms",
     "ldsim_track_gen_count", "ldsim_track_gen", "ldsim_track_gen_ms",
+    "ldsim_track_cascade_particles", "ldsim_track_cascade_count", "ldsim_track_cascade", "ldsim_track_cascade_ms",
     "ldsim_comm_unique_id", "ldsim_comm_init", "ldsim_comm_destroy", "ldsim_comm_count", "ldsim_comm_allreduce_f64", "ldsim_hits_accumulate",
     "ldsim_comm_allgather_hits", "ldsim_comm_gathered_download",
     "ldsim_compact_accumulate", "ldsim_comm_gather_compact", "ldsim_comm_gathered_compact_download", "ldsim_comm_gatherv_bytes",

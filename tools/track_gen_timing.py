@@ -36,7 +36,8 @@ def resource_usage():
     for line in r.stderr.splitlines():
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
-            name = "gen_kernel<true>" if "ILb1E" in m.group(1) else "gen_kernel<false>" if "ILb0E" in m.group(1) else m.group(1)
+            kernel = "cas_kernel" if "cas_kernel" in m.group(1) else "gen_kernel"
+            name = kernel + "<true>" if "ILb1E" in m.group(1) else kernel + "<false>" if "ILb0E" in m.group(1) else m.group(1)
             out[name] = {}
         m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|"
                       r"LDS Size \[bytes/block\]): (\d+)", line)
